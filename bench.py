@@ -1,6 +1,6 @@
 """Benchmark of the S-VolSDF volume-rendering hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
 
@@ -133,10 +133,18 @@ def main():
     ap.add_argument("--chamfer", action="store_true",
                     help="extra: short Chamfer optimisations per path on the analytic scene (tools/chamfer_parity.py; minutes)")
     ap.add_argument("--all-extras", action="store_true", help="all of the opt-in extras above")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (loss terms and model outputs) as "
+                         f"DIR/<name>.npy, float32 / float64, at most {DUMP_MAX_BYTES >> 20} MB in all.  So that the same "
+                         "arguments give that step the same inputs in every run, the settle phase is then exactly "
+                         f"{SETTLE_STEPS_DUMP} steps instead of --settle seconds, and in train mode the model's initial "
+                         "parameters are copied back in place (one device copy) right before the last timed step")
     ap.add_argument("--extras-file", default=None,
                     help="where the full record goes (default: gpurun_out/bench_extras.json when that directory exists, and "
                          "bench_extras.json next to this script)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.all_extras:
         args.other_precisions = args.inline_ab = args.volopt_loop = args.config4 = args.chamfer = True
 
@@ -233,14 +241,21 @@ def main():
         return t, (lambda: t(inp, gt, mvs=mvs))
 
     ts, step = make_step(model)
+    # --dump-outputs, train mode: the parameters the last timed step starts from.  Every step's weight gradients are float
+    # atomics, summed in a different order from run to run, and hundreds of Adam steps carry that into the weights; the
+    # initial parameters, put back before the last timed step, make its inputs the same in every run
+    p0 = ts.fp.flat.clone() if (args.dump_outputs and train) else None
 
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
     # steady state before the clock starts: a fresh process runs its first steps slower (module loads, allocator growth,
     # graph capture) and the chip needs load to settle its clocks; a timed region of a few ms would measure that
+    # (with --dump-outputs a fixed number of steps: the weights and optimiser state the last timed step starts from must not
+    # depend on how fast this build runs)
     settle_steps, t_settle = 0, time.perf_counter()
-    while time.perf_counter() - t_settle < args.settle and settle_steps < 5000:
+    while (settle_steps < SETTLE_STEPS_DUMP if args.dump_outputs else
+           time.perf_counter() - t_settle < args.settle and settle_steps < 5000):
         for _ in range(10):
             step()
         torch.cuda.synchronize()
@@ -249,7 +264,9 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for i in range(args.steps):
+        if p0 is not None and i == args.steps - 1:
+            ts.fp.flat.copy_(p0)
         out = step()
     torch.cuda.synchronize()
     if dist:
@@ -260,6 +277,8 @@ def main():
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
     del out
 
     # host side of a step: wall time the host thread needs to ENQUEUE a step (six steps into an empty queue, nothing
@@ -456,6 +475,40 @@ def main():
 
 class _Skip(Exception):
     pass
+
+
+SETTLE_STEPS_DUMP = 300            # settle steps under --dump-outputs (~1 s of the default step)
+DUMP_MAX_BYTES = 64 << 20          # all files of --dump-outputs together
+DUMP_SAMPLE = 1 << 20              # entries kept of an array that does not fit the budget in full
+
+
+def dump_outputs(dirname, out):
+    """Writes what a timed step returned -- train: (loss terms, model outputs), render: model outputs -- as
+    `dirname/<name>.npy`: loss terms as `loss_<term>`, outputs under their own keys.  Floating-point arrays keep float64 /
+    become float32, integer and boolean ones float64.  When the whole set exceeds DUMP_MAX_BYTES, each array larger than DUMP_SAMPLE entries is replaced by a fixed
+    sample of DUMP_SAMPLE entries of its flattened form (sorted indices, drawn by a generator seeded from the name)."""
+    import zlib
+    import numpy as np
+    import torch
+    losses, outputs = out if isinstance(out, tuple) else ({}, out)
+    arrays = {}
+    for prefix, d in (("loss_", losses), ("", outputs)):
+        for k in list(d.keys()):
+            v = d[k]
+            if not torch.is_tensor(v):
+                continue
+            a = v.detach().cpu().numpy()
+            arrays[prefix + k] = a.astype(np.float64 if a.dtype == np.float64 or not np.issubdtype(a.dtype, np.floating)
+                                          else np.float32)
+    if sum(a.nbytes for a in arrays.values()) > DUMP_MAX_BYTES:
+        for k, a in arrays.items():
+            if a.size > DUMP_SAMPLE:
+                rng = np.random.default_rng(zlib.crc32(k.encode()))
+                arrays[k] = a.reshape(-1)[np.sort(rng.choice(a.size, DUMP_SAMPLE, replace=False))]
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_MAX_BYTES, "dump over budget"
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
 
 
 MAX_LINE = 6144        # bytes of the final stdout line (the driver's record keeps a tail of ~8 KB)

@@ -533,7 +533,7 @@ def fx_forward_bg():
              **{k: v.detach().numpy() for k, v in out.items()}, **cap)
 
 
-def fx_cost_mapping():
+def fx_cost_mapping(suffix=""):
     from volsdf.vsdf import VolOpt
     rng = np.random.default_rng(21)
     R, S = 24, 98
@@ -554,8 +554,22 @@ def fx_cost_mapping():
                                  z_mvs={j: T(views[j]["z_mvs"])[None] for j in range(3)}, train_dataset=ds,
                                  hparams=SimpleNamespace(inverse_depth=inv), stg=0)
             pj, pi, valid = VolOpt.cost_mapping(me, z_vals=T(z), ts=torch.tensor([ids[vi]]), xyz_raw=T(xyz))
-            save(f"cost_mapping_inv{int(inv)}_v{vi}", xyz=xyz, view_index=vi, inverse_depth=inv, seed=5,
-                 pj=pj.numpy(), pi=pi.numpy(), valid=valid.numpy())
+            # the sgemm this run used: the rigid transforms of the look-up, (xyz - t) @ R per view, as the tests probe it
+            probe = dict(mm_out=np.stack([((T(xyz) - T(v["c2w"])[:3, 3]) @ T(v["c2w"])[:3, :3]).numpy() for v in views])) \
+                if suffix else {}
+            save(f"cost_mapping_inv{int(inv)}_v{vi}{suffix}", xyz=xyz, view_index=vi, inverse_depth=inv, seed=5,
+                 pj=pj.numpy(), pi=pi.numpy(), valid=valid.numpy(), **probe)
+
+
+def fx_cost_mapping_sgemm_nofma():
+    """The same outputs with MKL's sgemm on its pre-AVX2 code path (no FMA): what the reference computes on a host where
+    MKL does not take its AVX2 / AVX-512 kernels.  Made under MKL_CBWR=COMPATIBLE; started without it, it runs itself so (MKL reads the variable once, at its first call)."""
+    if os.environ.get("MKL_CBWR") != "COMPATIBLE":
+        import subprocess
+        subprocess.check_call([sys.executable, os.path.abspath(__file__), "cost_mapping_sgemm_nofma"],
+                              env=dict(os.environ, MKL_CBWR="COMPATIBLE"))
+        return
+    fx_cost_mapping("_sgemm_nofma")
 
 
 def fx_loss():
@@ -1049,7 +1063,7 @@ def fx_featurenet():
 
 
 ALL = dict(fusion=fx_fusion, filter_depth=fx_filter_depth, pfm=fx_pfm, chamfer=fx_chamfer, chamfer_mesh=fx_chamfer_mesh, featurenet=fx_featurenet, rays=fx_rays, sdf_mlp=fx_sdf_mlp, rgb_mlp=fx_rgb_mlp, density=fx_density, sampler=fx_sampler,
-           composite=fx_composite, forward=fx_forward, forward_bg=fx_forward_bg, cost_mapping=fx_cost_mapping, loss=fx_loss, casmvs=fx_casmvs, train_step=fx_train_step, train_step_r32=lambda: fx_train_step(32, 2, "train_step_r32"),
+           composite=fx_composite, forward=fx_forward, forward_bg=fx_forward_bg, cost_mapping=fx_cost_mapping, cost_mapping_sgemm_nofma=fx_cost_mapping_sgemm_nofma, loss=fx_loss, casmvs=fx_casmvs, train_step=fx_train_step, train_step_r32=lambda: fx_train_step(32, 2, "train_step_r32"),
            sdf_mlp_w1=lambda: fx_sdf_mlp("w1"), forward_w1=fx_forward_w1,
            train_step_w1=lambda: fx_train_step(16, 2, "train_step_w1", "w1"),
            train_step_bg=fx_train_step_bg,

@@ -255,6 +255,8 @@ def test_sharded_image_render():
 # generators continued from rank 0, the batch and the train-mode draws sharded the way TrainStep(shard_draws=True) does
 # --------------------------------------------------------------------------------------------------------------
 def _volopt_worker(rank, world, port, q):
+    # a CPU test: the ranks must not bind to a GPU of the host (init_data_parallel would, with one rank per device)
+    os.environ["HIP_VISIBLE_DEVICES"] = "-1"
     sys.path[:0] = [os.path.join(ROOT, "s-volsdf_amd")]
     import random
     from types import SimpleNamespace

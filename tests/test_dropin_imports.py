@@ -2,7 +2,8 @@
 reference's own import block (runner.py:18-40) and its dataset module import cleanly, the hot-path names resolve to
 this repository and everything else to the reference checkout.
 
-Build-container only: the reference never travels to the GPU box, so the test skips without /root/reference.  It runs
+The import-block test needs a checkout of the reference (SVOLSDF_REFERENCE_ROOT, default /root/reference) and skips
+without one; the others stand alone (the launcher's test builds a stand-in checkout of marker files).  It runs
 in a child interpreter (the package fall-through is decided when the mirror packages are first imported) with empty
 stub modules for the third-party packages this image lacks (tests/golden/ref_shim.py).
 """
@@ -17,8 +18,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "s-volsdf_amd")
 REFERENCE = os.environ.get("SVOLSDF_REFERENCE_ROOT", "/root/reference")
 
-pytestmark = pytest.mark.skipif(not os.path.isfile(os.path.join(REFERENCE, "runner.py")),
-                                reason="needs a checkout of the reference (build container only)")
+needs_reference = pytest.mark.skipif(not os.path.isfile(os.path.join(REFERENCE, "runner.py")),
+                                     reason=f"needs a checkout of the reference at {REFERENCE} (SVOLSDF_REFERENCE_ROOT)")
 
 CHILD = textwrap.dedent("""
     import os, sys, types
@@ -91,6 +92,7 @@ def _run(code, env_extra=None):
     return subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
 
 
+@needs_reference
 def test_runner_import_block_resolves():
     r = _run(CHILD.format(root=ROOT, ref=REFERENCE, pkg=PKG))
     assert r.returncode == 0 and "DROPIN-OK" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
@@ -123,16 +125,21 @@ def test_env_root_must_be_a_checkout(tmp_path):
 
 
 def test_launcher_runs_a_script_with_this_tree_first(tmp_path):
-    """svs_hip/launch.py: the script's directory must not shadow the drop-in modules, argv is the script's own."""
+    """svs_hip/launch.py: the script's directory must not shadow the drop-in modules, argv is the script's own.  The
+    checkout is a stand-in: the two files by which svs_hip.refpath recognises one, and an empty `models` package."""
+    ref = tmp_path / "reference"
+    for f in ("volsdf/vsdf.py", "models/CasMVSNet.py", "models/__init__.py"):
+        (ref / f).parent.mkdir(parents=True, exist_ok=True)
+        (ref / f).write_text("")
     probe = tmp_path / "probe.py"
     probe.write_text("import sys, models, volsdf.vsdf\n"
                      "print('ARGV', sys.argv[1:])\nprint('VSDF', volsdf.vsdf.__file__)\nprint('PATH', models.__path__)\n"
                      "assert __name__ == '__main__'\n")
-    env = dict(os.environ, SVOLSDF_REFERENCE_ROOT=REFERENCE)
+    env = dict(os.environ, SVOLSDF_REFERENCE_ROOT=str(ref))
     env.pop("PYTHONPATH", None)
     r = subprocess.run([sys.executable, os.path.join(PKG, "svs_hip", "launch.py"), str(probe), "testlist=scan106"],
                        cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     assert "ARGV ['testlist=scan106']" in r.stdout
     assert f"VSDF {os.path.join(PKG, 'volsdf', 'vsdf.py')}" in r.stdout
-    assert os.path.join(REFERENCE, "models") in r.stdout
+    assert os.path.join(str(ref), "models") in r.stdout

@@ -36,7 +36,7 @@ def test_chamfer_deterministic_run_repeats():
 
 def test_chamfer_parity_short():
     """600 steps per path WITH the synthetic MVS prior (the reference's regime: MVS term + annealed sparsity + rgb_smooth,
-    chamfer_parity.build_prior), four fixed seeds per path, all eight runs side by side: the reconstruction goes from the
+    chamfer_parity.build_prior), four fixed seeds per path, the eight runs four at a time side by side: the reconstruction goes from the
     geometric initialisation (a sphere of radius 120 mm, ~10 mm off the scene) to ~1 mm.  At 600 steps single runs of EITHER
     path scatter between 0.8 and 2.4 mm (the odd run is still converging), so this is a REGRESSION bound -- every run below
     5 mm, both means below 2 mm, the means within 0.6 mm of each other: a broken backward or prior look-up costs millimetres --

@@ -236,9 +236,12 @@ def child(path, seed, steps, rays, prior=False):
     print(json.dumps(info), flush=True)
 
 
+MAX_CHILDREN = 4        # concurrent child processes of measure(parallel=True)
+
+
 def measure(steps=3000, seeds=(0, 1), paths=("hip", "hip_f32", "torch_f32"), rays=512, timeout=3000, prior=False, parallel=False,
             seeds_by_path=None):
-    """seeds_by_path: {path: seeds} overriding `seeds` for a path (the HIP runs are cheap: more of them steady a median).  parallel: all (path, seed) runs as concurrent child processes on the one GPU (the plain-torch comparator is bound by its
+    """seeds_by_path: {path: seeds} overriding `seeds` for a path (the HIP runs are cheap: more of them steady a median).  parallel: the (path, seed) runs as concurrent child processes on the one GPU, MAX_CHILDREN at a time (the plain-torch comparator is bound by its
     host-side launches: three of them side by side take as long as one); train_s of a run is then not a timing of anything."""
     def start(path, s):
         env = dict(os.environ)
@@ -265,12 +268,26 @@ def measure(steps=3000, seeds=(0, 1), paths=("hip", "hip_f32", "torch_f32"), ray
 
     sb = lambda path: tuple((seeds_by_path or {}).get(path, seeds))
     # (keyed by position: a seed may be listed twice -- the repeatability check of the deterministic path)
-    procs = {(path, i): start(path, s) for path in paths for i, s in enumerate(sb(path))} if parallel else {}
+    # parallel: at most MAX_CHILDREN runs at a time (with the caller, which may hold the GPU itself, no more than six processes
+    # have the device open); a run starts as soon as the earliest running one has been collected
+    jobs = [(path, i, s) for path in paths for i, s in enumerate(sb(path))]
+    procs, waiting = {}, list(jobs) if parallel else []
+
+    def fill():
+        while waiting and len(procs) < MAX_CHILDREN:
+            path, i, s = waiting.pop(0)
+            procs[(path, i)] = start(path, s)
+
+    fill()
     res = {}
     for path in paths:
         runs = []
         for i, s in enumerate(sb(path)):
-            runs.append(finish(procs[(path, i)] if parallel else start(path, s), s))
+            if parallel:
+                runs.append(finish(procs.pop((path, i)), s))
+                fill()
+            else:
+                runs.append(finish(start(path, s), s))
         ok = [x for x in runs if "overall_mm" in x]
         res[path] = dict(runs=runs)
         if ok:
@@ -326,7 +343,7 @@ if __name__ == "__main__":
         ap.add_argument("--rays", type=int, default=512)
         ap.add_argument("--out", default=None)
         ap.add_argument("--prior", action="store_true", help="optimise with the synthetic MVS prior (the reference's stage-0 loss)")
-        ap.add_argument("--parallel", action="store_true", help="all (path, seed) runs side by side on the one GPU")
+        ap.add_argument("--parallel", action="store_true", help="the (path, seed) runs side by side on the one GPU (MAX_CHILDREN at a time)")
         a = ap.parse_args()
         out = measure(a.steps, tuple(int(s) for s in a.seeds.split(",")), tuple(a.paths.split(",")), a.rays, prior=a.prior,
                       parallel=a.parallel)
