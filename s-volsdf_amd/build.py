@@ -41,13 +41,7 @@ UNITS = {
     "svs_cloud.hip": ["-ffp-contract=off"],
     "svs_plan.hip": [],
 }
-# The two-waves-per-SIMD experiments of round 3 (svs_sdf_vals16 / svs_sdf_vals_pair, measured no faster
-# than the default kernel) are built on request, SVS_BUILD_EXPERIMENTS=1 (as __graft_entry__.build() does, for the tests).
-EXPERIMENTS = os.environ.get("SVS_BUILD_EXPERIMENTS", "0") == "1"
-if EXPERIMENTS:
-    UNITS.update({"svs_mlp_w16.hip": [], "svs_mlp_h2p.hip": []})
-BASE_FLAGS = (["-DSVS_EXPERIMENTAL_KERNELS"] if EXPERIMENTS else []) + ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
-              "-x", "hip"]
+BASE_FLAGS = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function", "-x", "hip"]
 
 
 def _hipcc():

@@ -9,17 +9,8 @@
 
 // Activation blocks are written once and read once by a later kernel: non-temporal stores keep them from evicting the
 // packed weight stream (2-4.6 MB per network, re-read by every workgroup) from the 4 MB L2 of an XCD.
-#ifdef SVS_NO_STREAM_HINTS
-#define SVS_STREAM_STORE(v, p) (*(p) = (v))
-#define SVS_STREAM_LOAD(p) (*(p))
-#else
 #define SVS_STREAM_STORE(v, p) __builtin_nontemporal_store((v), (p))
-#ifdef SVS_NO_STREAM_LOADS
-#define SVS_STREAM_LOAD(p) (*(p))
-#else
 #define SVS_STREAM_LOAD(p) __builtin_nontemporal_load(p)
-#endif
-#endif
 
 namespace svs {
 
@@ -46,11 +37,7 @@ inline int check_launch(const char* what) {
 // three stage sizes of config 3); measured neutral for conv2 / prob and harmful for the transposed-convolution GEMMs, whose
 // parity classes interleave in the output (conv7 0.025 -> 0.034 ms, conv9 0.049 -> 0.062): not applied there.
 __device__ __forceinline__ unsigned xcd_chunked(unsigned i, unsigned n) {
-#ifdef SVS_NO_XCD_REMAP
-  return i;
-#else
   return (n & 7u) ? i : (i & 7u) * (n >> 3) + (i >> 3);
-#endif
 }
 
 __host__ __device__ constexpr int rho(int r) { return (r & 3) + 8 * (r >> 2); }

@@ -371,9 +371,8 @@ int svs_featurenet_fpn2(const float* image, int H, int W, int base_channels, con
   SVS_FPN(10, ws + B.f1, nullptr, 0, stage2, 4 * b, 2 * b, H2, W2, 3, 1, 0);              // out2
   // inner2 + up(f1), then out3.  With out3 on the matrix cores (b = 8) the lateral step is formed while out3 converts its
   // input window and its 4b-channel full-resolution result never exists in memory (42 MB written and read back at 512 x 640:
-  // 22.7 + 30.8 us as two launches, NOTES/r06.md); SVS_FPN_FUSE_LATERAL=0: two launches
-  static const bool fuse_env = [] { const char* e = getenv("SVS_FPN_FUSE_LATERAL"); return !(e && e[0] == '0'); }();
-  if (fuse_env && b == 8 && wfrags && wfrags[12] && svs::conv2dmfma::supported(4 * b, b, 3, 1)) {
+  // 22.7 + 30.8 us as two launches, NOTES/r06.md)
+  if (b == 8 && wfrags && wfrags[12] && svs::conv2dmfma::supported(4 * b, b, 3, 1)) {
     if ((rc = svs::conv2dmfma::run_lateral(ws + B.c0, weights[11], biases[11], ws + B.f1, wfrags[12], biases[12], stage3, b, H, W, 0, s)) != SVS_OK)
       return rc;
   } else {

@@ -186,22 +186,14 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(Args a) {
   if (s0 < KS) {
     load_b(s0, xc);
 #pragma unroll
-#ifdef CONV_ABL_W0
-    for (int m = 0; m < MT; ++m) { ahc[m] = wf[0]; amc[m] = wf[64]; }
-#else
     for (int m = 0; m < MT; ++m) { ahc[m] = wf[((size_t)s0 * MT + m) * 128]; amc[m] = wf[((size_t)s0 * MT + m) * 128 + 64]; }
-#endif
   }
   for (int s = s0; s < KS; s += SS) {
     if (s + SS < KS) {
       load_b(s + SS, xn);
       const f16x8* wn = wf + (size_t)(s + SS) * MT * 128;
 #pragma unroll
-#ifdef CONV_ABL_W0
-      for (int m = 0; m < MT; ++m) { ahn[m] = wf[0]; amn[m] = wf[64]; }
-#else
       for (int m = 0; m < MT; ++m) { ahn[m] = wn[m * 128]; amn[m] = wn[m * 128 + 64]; }
-#endif
     }
     f16x8 bh, bm;
 #pragma unroll
@@ -321,11 +313,7 @@ __global__ __launch_bounds__(256) void deconv_cell_kernel(Args a) {
       if (dz > (m >> 1) || dy > (m & 1)) continue;                // the class does not reach these input rows
 #pragma unroll
       for (int mt = 0; mt < MTC; ++mt) {
-#ifdef CONV_ABL_W0      // diagnostic: every fragment is fragment 0 (no weight traffic beyond one line per lane)
-        const f16x8 ah = wf[0], am = wf[64];
-#else
         const f16x8 ah = wf[((m * KS + s) * MTC + mt) * 128], am = wf[((m * KS + s) * MTC + mt) * 128 + 64];
-#endif
         acc[m][mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(am, bh, acc[m][mt], 0, 0, 0);
         acc[m][mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bm, acc[m][mt], 0, 0, 0);
         acc[m][mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, acc[m][mt], 0, 0, 0);
@@ -444,10 +432,8 @@ constexpr long long kKsplitTiles = 2048;   // measured: pays below ~2 tiles per 
 
 template <int CIN, int MODE>
 static void launch_mt(const Args& a, int MT, long long tiles, hipStream_t s) {
-  // few tiles (the coarse levels): four waves per tile; SVS_GEMM_KSPLIT=0/1 forces the choice (measurements)
-  static const char* env = getenv("SVS_GEMM_KSPLIT");
-  const bool ksplit = (env && env[0]) ? env[0] == '1' : tiles <= kKsplitTiles;
-  if (ksplit) {
+  // few tiles (the coarse levels): four waves per tile
+  if (tiles <= kKsplitTiles) {
     const unsigned grid = (unsigned)tiles;
     if (MT == 1) conv_gemm_kernel<CIN, 1, MODE, true><<<grid, 256, 0, s>>>(a);
     else if (MT == 2) conv_gemm_kernel<CIN, 2, MODE, true><<<grid, 256, 0, s>>>(a);

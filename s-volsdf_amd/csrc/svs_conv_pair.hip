@@ -52,10 +52,6 @@ struct Args {
   int z_per_wg;
 };
 
-#ifndef CONVP_PD
-#define CONVP_PD 3
-#endif
-
 // KSPLIT = 2: eight waves, waves w and w + 4 share output row w and each takes half of the k-steps (and keeps only
 // that half of the weights: 144 registers instead of 288, so that two waves fit on a SIMD and nothing lives in AGPRs);
 // the upper half's partial sums cross through LDS at the end of the step.
@@ -68,7 +64,7 @@ __global__ __launch_bounds__(256 * KSPLIT, 1) void conv3d_pair_kernel(Args a) {
   constexpr int SLICE = UNITS * 16;
   constexpr int NW = 4 * KSPLIT;                  // waves
   constexpr int NDMA = (UNITS + 64 * NW - 1) / (64 * NW);   // copy instructions per wave and slice
-  constexpr int PD = CONVP_PD;                    // k-steps the B fragments are read ahead of their MFMAs
+  constexpr int PD = 3;                           // k-steps the B fragments are read ahead of their MFMAs
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   f32x4v* xchg = reinterpret_cast<f32x4v*>(smem + 4 * SLICE);     // [step parity][row][lane] partial sums (KSPLIT = 2)
   const int tid = threadIdx.x, lane = tid & 63;
@@ -153,9 +149,7 @@ __global__ __launch_bounds__(256 * KSPLIT, 1) void conv3d_pair_kernel(Args a) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();                 // everyone's part of slice z+1 has landed; nobody reads slice z-2 any more
     const int r0 = (z - z_begin) & 3;
-#ifndef CONVP_NODMA
     if (z + 2 <= z_end) copy_slice(z + 2, (r0 + 3) & 3);
-#endif
     if (z > z_begin) finish(z - 1);
     const unsigned char* base[3];
 #pragma unroll
@@ -170,9 +164,6 @@ __global__ __launch_bounds__(256 * KSPLIT, 1) void conv3d_pair_kernel(Args a) {
         const int s = S0 + i;
         const int row9 = s / G, kd = row9 / 3, kh = row9 % 3;
         const int t_s = (s % G) * (4 / G);
-#ifdef CONVP_NOLDS
-        if (i >= PD) return piece ? bm[i - PD] : bh[i - PD];
-#endif
         return *reinterpret_cast<const f16x8*>(base[kd] + (((kh * 2 + piece) * G) * kRS + t_s) * 16);
       };
 #pragma unroll
@@ -433,12 +424,9 @@ int svs_conv3d_pair(const void* split, const void* wfrag, const float* bias, flo
   }
   a.z_per_wg = (D + best - 1) / best;
   hipStream_t s = (hipStream_t)hip_stream;
-#ifndef CONVP_SPLIT32
-#define CONVP_SPLIT32 2
-#endif
   if (Cin == 8) return convpair::launch<8, 1>(a, s);
   if (Cin == 16) return convpair::launch<16, 1>(a, s);
-  return convpair::launch<32, CONVP_SPLIT32>(a, s);
+  return convpair::launch<32, 2>(a, s);
 }
 
 // bytes of the packed A fragments of svs_conv3d_rows: [ceil(27 Cin / 32)][2][64][16 B]

@@ -203,15 +203,7 @@ __global__ __launch_bounds__(256, NS <= 2 ? 4 : 2) void warp_variance_kernel(War
 // the depth loop is the INNER loop (passes over x outside), the corner tables of all planes of the workgroup are computed up
 // front.  Output: split volume only (direct stores; the float32 form needs a plane's whole tile at once and stays on the
 // kernel above).
-#ifndef SVS_WARP_DZ
-#define SVS_WARP_DZ 4
-#endif
-// Diagnostic builds (tools/dev/ablate_warp.sh; results are then wrong by construction): -DSVS_WARP_ABL=<mask>, 1: no stores of
-// the volume, 2: no gathers (a voxel's corners are never re-fetched), 4: no projection arithmetic (constant corner tables).
-#ifndef SVS_WARP_ABL
-#define SVS_WARP_ABL 0
-#endif
-constexpr int kWarpDz = SVS_WARP_DZ;
+constexpr int kWarpDz = 4;
 
 // depth: the hypothesis of voxel (d, y, x), loaded by the caller (all of a thread's loads are requested before the first
 // projection: a load per loop iteration in front of its ~100 dependent instructions was a latency chain, round 5)
@@ -221,23 +213,14 @@ __device__ __forceinline__ void warp_taps(const WarpArgs& a, int v, int x, int y
   w4 = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
   o4 = i32x4{0, 0, 0, 0};
   if (x >= W || d >= a.D) return;
-#if SVS_WARP_ABL & 16
-  depth = 500.0f + (float)d;
-#endif
   const float fx = (float)x, fy = (float)y;
   const float* R = a.rot[v];
   // rot @ [x,y,1] * depth + trans   (CasMVSNet.py:300-303); same operations, same order as warp_variance_kernel
   const float qx = ((R[0] * fx + R[1] * fy) + R[2]) * depth + a.trans[v][0];
   const float qy = ((R[3] * fx + R[4] * fy) + R[5]) * depth + a.trans[v][1];
   const float qz = ((R[6] * fx + R[7] * fy) + R[8]) * depth + a.trans[v][2];
-#if SVS_WARP_ABL & 8
-  const float rz = __builtin_amdgcn_rcpf(qz);
-  const float px = qx * rz, py = qy * rz;
-  const float gx = px * __builtin_amdgcn_rcpf((float)(W - 1) / 2.0f) - 1.0f, gy = py * __builtin_amdgcn_rcpf((float)(H - 1) / 2.0f) - 1.0f;
-#else
   const float px = qx / qz, py = qy / qz;
   const float gx = px / ((float)(W - 1) / 2.0f) - 1.0f, gy = py / ((float)(H - 1) / 2.0f) - 1.0f;
-#endif
   const float ix = ((gx + 1.0f) * (float)W - 1.0f) / 2.0f, iy = ((gy + 1.0f) * (float)H - 1.0f) / 2.0f;
   const float x0 = __builtin_floorf(ix), y0 = __builtin_floorf(iy);
   const float tx = ix - x0, ty = iy - y0;
@@ -287,11 +270,7 @@ __global__ __launch_bounds__(256, NS <= 2 ? 4 : 2) void warp_variance_reuse_kern
     const int dz = i / (NS * TW), r = i - dz * (NS * TW);
     const int v = r / TW, vx = r - v * TW;
     f32x4 w4; i32x4 o4;
-#if SVS_WARP_ABL & 4
-    w4 = f32x4{0.25f, 0.25f, 0.25f, 0.25f}; o4 = i32x4{0, C * 4, C * 4 * W, C * 4 * (W + 1)};
-#else
     warp_taps<C>(a, v, xt + vx, y, d0 + dz, dep[k], w4, o4);
-#endif
     tapw[dz][v][vx] = w4;
     tapo[dz][v][vx] = o4;
   }
@@ -352,22 +331,16 @@ __global__ __launch_bounds__(256, NS <= 2 ? 4 : 2) void warp_variance_reuse_kern
           const i32x4 o4 = tapo[dz + 1][v][vx];
           const char* __restrict__ src = reinterpret_cast<const char*>(a.src_hwc[v]);
           // (a voxel's LPV lanes take the same branch; a corner outside the image has offset 0 and weight 0)
-#if SVS_WARP_ABL & 32          // diagnostic: every plane gathers again (no reuse along depth; static load / store counts)
-#pragma unroll
-          for (int k = 0; k < 4; ++k) f[v][k] = *reinterpret_cast<const f32x4*>(src + ((unsigned)o4[k] + 16u * cg));
-#else
-          if (!(SVS_WARP_ABL & 2) &&
-              (o4[0] != held[v][0] || o4[1] != held[v][1] || o4[2] != held[v][2] || o4[3] != held[v][3])) {
+          if (o4[0] != held[v][0] || o4[1] != held[v][1] || o4[2] != held[v][2] || o4[3] != held[v][3]) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) f[v][k] = *reinterpret_cast<const f32x4*>(src + ((unsigned)o4[k] + 16u * cg));
             held[v] = o4;
           }
-#endif
         }
       } else if (p + 1 < kPasses) {
         first_gathers(p + 1);
       }
-      if (x < W && d < a.D && !((SVS_WARP_ABL & 1) && res[0] != 1.2345e-30f)) {
+      if (x < W && d < a.D) {
         uint2* u = reinterpret_cast<uint2*>(a.split + splitvol::unit(d, y, 0, cg >> 1, x, C / 8, Hp, Wp)) + (cg & 1);
         u[0] = __builtin_bit_cast(uint2, h);
         u[(size_t)(C / 8) * Wp * 2] = __builtin_bit_cast(uint2, lo);
@@ -388,11 +361,11 @@ __global__ __launch_bounds__(256, NS <= 2 ? 4 : 2) void warp_variance_reuse_kern
 //   * corner tables source-major (a wave's entries belong to one source: its camera block comes from SGPRs), the four corners
 //     without branches, the four IEEE divisions as the compiler's own sequence without its scaling / fix-up instructions where
 //     no operand needs them, the refined reciprocal shared (bit-identical quotients);
-//   * CPL channels per lane: 4 (default: round 5's shape, 16 waves per CU) or 8 (one 16-byte unit per lane, half the per-lane
-//     overhead, but 176-190 VGPRs: one 5-wave workgroup per CU -- measured slower, SVS_WARP_KERNEL=8).
-// ~1060 lane-instructions per (voxel, plane) at CPL = 4.  Measured (NOTES/r06.md): -4 % / -11 % / -6 % at the three stage
+//   * CPL = 4 channels per lane (round 5's shape, 16 waves per CU; eight per lane halved the per-lane overhead but needed
+//     176-190 VGPRs, one 5-wave workgroup per CU, and measured slower: NOTES/r06.md).
+// ~1060 lane-instructions per (voxel, plane).  Measured (NOTES/r06.md): -4 % / -11 % / -6 % at the three stage
 // shapes against round 5's kernel -- a third fewer instructions buy a twentieth of the time, so the kernel is NOT bound by
-// instruction issue (this round's hypothesis), nor by where its gathers hit (XCD experiment below).
+// instruction issue (this round's hypothesis), nor by where its gathers hit (below).
 // Same arithmetic per channel in the same order as warp_variance_kernel: the values are the float32 kernel's bit for bit
 // (tests/test_gpu_costvol.py::test_warp_variance_split_volume).
 // IEEE float32 quotients n0 / d and n1 / d as the compiler's own division sequence computes them (v_div_scale, v_rcp, the
@@ -468,23 +441,14 @@ __device__ __forceinline__ void warp_taps8(const WarpArgs& a, int v, int x, int 
 }
 
 // Geometry of the producer for CPL channels per lane: T threads, P passes over x per workgroup (TW = P * T / (C / CPL) voxels).
-//   CPL = 4 (default): 256 threads, TW = 160 / 128 / 128 at C = 32 / 16 / 8 -- round 5's shape: 16 waves per CU;
-//   CPL = 8: 320 / 320 / 128 threads, TW = 160 / 160 / 128 -- half the per-lane overhead, but 176-190 VGPRs (64 of them
-//            corners): one 5-wave workgroup per CU instead of four 4-wave ones, and the kernel turns latency-bound (measured
-//            0.267 against 0.226 ms at stage 1, NOTES/r06.md): kept selectable (SVS_WARP_KERNEL=8), not the default.
+//   CPL = 4: 256 threads, TW = 160 / 128 / 128 at C = 32 / 16 / 8 -- round 5's shape: 16 waves per CU.
 template <int C, int CPL> struct WarpCfg {};
 template <> struct WarpCfg<32, 4> { static constexpr int T = 256, P = 5; };
 template <> struct WarpCfg<16, 4> { static constexpr int T = 256, P = 2; };
 template <> struct WarpCfg<8, 4>  { static constexpr int T = 256, P = 1; };
-template <> struct WarpCfg<32, 8> { static constexpr int T = 320, P = 2; };
-template <> struct WarpCfg<16, 8> { static constexpr int T = 320, P = 1; };
-template <> struct WarpCfg<8, 8>  { static constexpr int T = 128, P = 1; };
 
 __device__ __forceinline__ void gload128(f32x4& v, unsigned off, const void* base) {
   asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(v) : "v"(off), "s"(base) : "memory");
-}
-__device__ __forceinline__ void gload128_16(f32x4& v, unsigned off, const void* base) {
-  asm volatile("global_load_dwordx4 %0, %1, %2 offset:16" : "=v"(v) : "v"(off), "s"(base) : "memory");
 }
 __device__ __forceinline__ void gload32(float& v, unsigned off, const void* base) {
   asm volatile("global_load_dword %0, %1, %2" : "=v"(v) : "v"(off), "s"(base) : "memory");
@@ -494,44 +458,12 @@ __device__ __forceinline__ void gstore128(unsigned off, const i32x4& v, void* ba
 }
 typedef int i32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void gstore64(unsigned off, const i32x2& v, void* base) {
-#if defined(SVS_WARP_NT_STORES) && SVS_WARP_NT_STORES == 1        // experiments: streaming / system-coherent store hints
-  asm volatile("global_store_dwordx2 %0, %1, %2 nt" :: "v"(off), "v"(v), "s"(base) : "memory");
-#elif defined(SVS_WARP_NT_STORES) && SVS_WARP_NT_STORES == 2
-  asm volatile("global_store_dwordx2 %0, %1, %2 sc0 sc1" :: "v"(off), "v"(v), "s"(base) : "memory");
-#elif defined(SVS_WARP_NT_STORES) && SVS_WARP_NT_STORES == 3
-  asm volatile("global_store_dwordx2 %0, %1, %2 sc1 nt" :: "v"(off), "v"(v), "s"(base) : "memory");
-#else
   asm volatile("global_store_dwordx2 %0, %1, %2" :: "v"(off), "v"(v), "s"(base) : "memory");
-#endif
 }
 // The conditional re-gather of one source's four corners (2 x 16 bytes each) for the lanes of `mask`: exec is narrowed INSIDE
 // the statement and the corner registers are tied operands of straight-line code.  (As `if (moved) f = load(...)` in C++ the
 // merge of old and new corners becomes a copy of all eight registers in front of the branch -- 72 v_mov per plane -- and, with
 // loads the compiler can see, a vmcnt(0) in front of each copy.)  No lane moved: the loads are skipped, nothing is counted.
-__device__ __forceinline__ void regather(f32x4 (&f)[4][2], const i32x4& o4, unsigned lane_off, const void* base,
-                                         unsigned long long mask) {
-  unsigned long long saved;
-  const unsigned o0 = (unsigned)o4[0] + lane_off, o1 = (unsigned)o4[1] + lane_off, o2 = (unsigned)o4[2] + lane_off,
-                 o3 = (unsigned)o4[3] + lane_off;
-  asm volatile(
-      "s_and_saveexec_b64 %[sv], %[mask]\n\t"
-      "s_cbranch_execz 1f\n\t"
-      "global_load_dwordx4 %[a0], %[o0], %[base]\n\t"
-      "global_load_dwordx4 %[a1], %[o0], %[base] offset:16\n\t"
-      "global_load_dwordx4 %[b0], %[o1], %[base]\n\t"
-      "global_load_dwordx4 %[b1], %[o1], %[base] offset:16\n\t"
-      "global_load_dwordx4 %[c0], %[o2], %[base]\n\t"
-      "global_load_dwordx4 %[c1], %[o2], %[base] offset:16\n\t"
-      "global_load_dwordx4 %[d0], %[o3], %[base]\n\t"
-      "global_load_dwordx4 %[d1], %[o3], %[base] offset:16\n"
-      "1:\n\t"
-      "s_mov_b64 exec, %[sv]"
-      : [a0] "+v"(f[0][0]), [a1] "+v"(f[0][1]), [b0] "+v"(f[1][0]), [b1] "+v"(f[1][1]), [c0] "+v"(f[2][0]), [c1] "+v"(f[2][1]),
-        [d0] "+v"(f[3][0]), [d1] "+v"(f[3][1]), [sv] "=&s"(saved)
-      : [o0] "v"(o0), [o1] "v"(o1), [o2] "v"(o2), [o3] "v"(o3), [base] "s"(base), [mask] "s"(mask)
-      : "memory");
-}
-
 __device__ __forceinline__ void regather(f32x4 (&f)[4][1], const i32x4& o4, unsigned lane_off, const void* base,
                                          unsigned long long mask) {
   unsigned long long saved;
@@ -563,7 +495,7 @@ __device__ __forceinline__ void wait_loads() {
 }
 
 template <int C, int NS, int CPL>
-__global__ __launch_bounds__((WarpCfg<C, CPL>::T), (CPL == 4 ? (NS <= 2 ? 4 : 2) : 1)) void warp_variance_reuse2_kernel(WarpArgs a) {
+__global__ __launch_bounds__((WarpCfg<C, CPL>::T), NS <= 2 ? 4 : 2) void warp_variance_reuse2_kernel(WarpArgs a) {
   constexpr int T = WarpCfg<C, CPL>::T, P = WarpCfg<C, CPL>::P;
   constexpr int LPV = C / CPL, VPP = T / LPV, TW = P * VPP, G = C / 8, Q = CPL / 4;
   constexpr int kSlice = kWarpDz * TW;              // table entries of one source
@@ -572,19 +504,11 @@ __global__ __launch_bounds__((WarpCfg<C, CPL>::T), (CPL == 4 ? (NS <= 2 ? 4 : 2)
   __shared__ __attribute__((aligned(16))) i32x4 tapo[kWarpDz][NS][TW];
   const int tid = threadIdx.x;
   const int H = a.H, W = a.W;
-  // (Experiment, -DSVS_WARP_XCD_ROWS: workgroups are dealt to the 8 XCDs round-robin in launch order, so every XCD sees every
-  // row and gathers from the WHOLE source feature maps; re-dealing the launch index (xcd_chunked) row-slowest gives XCD k
-  // the rows [k H/8, (k+1) H/8).  Measured on one box, three alternations: 0.216-0.222 against 0.213-0.220 ms at stage 1,
-  // 0.085 / 0.085 at stage 2, 0.057 against 0.061 at stage 3: the gathers are not what the kernel waits for.  Off.)
-#ifndef SVS_WARP_XCD_ROWS
+  // (Workgroups are dealt to the 8 XCDs round-robin in launch order, so every XCD sees every row and gathers from the WHOLE
+  // source feature maps.  Re-dealing the launch index row-slowest (xcd_chunked) was measured on one box, three alternations:
+  // 0.216-0.222 against 0.213-0.220 ms at stage 1, 0.085 / 0.085 at stage 2, 0.057 against 0.061 at stage 3: the gathers are
+  // not what the kernel waits for.  Not applied.)
   const int y = blockIdx.y, xb = blockIdx.x, zb = blockIdx.z;
-#else
-  const unsigned gx = gridDim.x, gz = gridDim.z;
-  const unsigned lin = xcd_chunked(blockIdx.x + gx * (blockIdx.y + gridDim.y * blockIdx.z), gx * gridDim.y * gz);
-  const int y = (int)(lin / (gx * gz));
-  const unsigned rem = lin - (unsigned)y * (gx * gz);
-  const int zb = (int)(rem / gx), xb = (int)(rem - (unsigned)zb * gx);
-#endif
   const int xt = xb * TW, d0 = zb * kWarpDz;
   const float inv_nv = 1.0f / (float)(NS + 1);
   // ---- corner tables, one (source, plane, voxel) per thread and round, source-major: a wave's entries of a round belong to
@@ -607,14 +531,7 @@ __global__ __launch_bounds__((WarpCfg<C, CPL>::T), (CPL == 4 ? (NS <= 2 ? 4 : 2)
       const int v = __builtin_amdgcn_readfirstlane(i / kSlice);
       const int r = i - v * kSlice, dz = r / TW, vx = r - dz * TW;
       f32x4 w4; i32x4 o4;
-#ifdef SVS_WARP8_PLAIN_TAPS
-      warp_taps<C>(a, v, xt + vx, y, d0 + dz, dep[k], w4, o4);
-#else
       warp_taps8<C>(a, v, xt + vx, y, d0 + dz, dep[k], hw, rhw, hh, rhh, w4, o4);
-#endif
-#if SVS_WARP_ABL & 4            // diagnostic: constant corner tables (the projection arithmetic is dead code)
-      w4 = f32x4{0.25f, 0.25f, 0.25f, 0.25f}; o4 = i32x4{0, C * 4, C * 4 * W, C * 4 * (W + 1)};
-#endif
       tapw[dz][v][vx] = w4;
       tapo[dz][v][vx] = o4;
     }
@@ -651,7 +568,6 @@ __global__ __launch_bounds__((WarpCfg<C, CPL>::T), (CPL == 4 ? (NS <= 2 ? 4 : 2)
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         gload128(f[v][k][0], (unsigned)o4[k] + lane_off, a.src_hwc[v]);
-        if (Q == 2) gload128_16(f[v][k][Q - 1], (unsigned)o4[k] + lane_off, a.src_hwc[v]);
       }
       held[v] = o4;
     }
@@ -665,16 +581,12 @@ __global__ __launch_bounds__((WarpCfg<C, CPL>::T), (CPL == 4 ? (NS <= 2 ? 4 : 2)
     const int vx = p * VPP + vl, x = xt + vx;
     // waves without a voxel inside the image leave here (x grows with p: they were not active before either)
     if (__builtin_amdgcn_readfirstlane(xt + p * VPP + (tid & ~63) / LPV) >= W) break;
-    // CPL = 8: the lane owns unit g; CPL = 4: half (g & 1) of unit g >> 1 (`so` = the unit's hi piece)
-    unsigned so = (unsigned)(splitvol::unit(d0, y, 0, CPL == 8 ? g : g >> 1, x < W ? x : W - 1, G, Hp, Wp) * 16);
+    // the lane owns half (g & 1) of unit g >> 1 (`so` = the unit's hi piece)
+    unsigned so = (unsigned)(splitvol::unit(d0, y, 0, g >> 1, x < W ? x : W - 1, G, Hp, Wp) * 16);
 #pragma unroll
     for (int dz = 0; dz < kWarpDz; ++dz) {
       const int d = d0 + dz;
-#if defined(SVS_WARP_STORE128)
-      constexpr int kStores = CPL == 8 ? 2 : 1;
-#else
       constexpr int kStores = 2;                         // vector-memory stores an active wave issues per stored plane
-#endif
       if (prev_stored) wait_loads<kStores>(); else wait_loads<0>();
       f32x4 res[Q];
 #pragma unroll
@@ -709,39 +621,17 @@ __global__ __launch_bounds__((WarpCfg<C, CPL>::T), (CPL == 4 ? (NS <= 2 ? 4 : 2)
           w4s[v] = tapw[dz + 1][v][vx];
           const i32x4 o4 = tapo[dz + 1][v][vx];
           // (a voxel's LPV lanes decide alike; a corner outside the image has offset 0 and weight 0)
-          const bool moved = !(SVS_WARP_ABL & 2) &&       // (diagnostic 2: a voxel's corners are never fetched again)
-                             (o4[0] != held[v][0] || o4[1] != held[v][1] || o4[2] != held[v][2] || o4[3] != held[v][3]);
+          const bool moved = o4[0] != held[v][0] || o4[1] != held[v][1] || o4[2] != held[v][2] || o4[3] != held[v][3];
           regather(f[v], o4, lane_off, a.src_hwc[v], __builtin_amdgcn_ballot_w64(moved));
           held[v] = o4;
         }
       } else if (p + 1 < P) {
         first_loads((p + 1) * VPP + vl);
       }
-#if SVS_WARP_ABL & 1            // diagnostic: no stores of the volume (the guard keeps the values alive)
-      const int stored = d < a.D && res[0][0] == 1.2345e-30f;
-#else
       const int stored = d < a.D;                                        // uniform
-#endif
       if (stored && x < W) {
-        if (CPL == 8) {
-          gstore128(so, __builtin_bit_cast(i32x4, __builtin_shufflevector(h[0], h[Q - 1], 0, 1, 2, 3, 4, 5, 6, 7)), a.split);
-          gstore128(so + mid_b, __builtin_bit_cast(i32x4, __builtin_shufflevector(lo[0], lo[Q - 1], 0, 1, 2, 3, 4, 5, 6, 7)), a.split);
-        } else {
-#ifndef SVS_WARP_STORE128
-          gstore64(so + 8u * (g & 1), __builtin_bit_cast(i32x2, h[0]), a.split);
-          gstore64(so + 8u * (g & 1) + mid_b, __builtin_bit_cast(i32x2, lo[0]), a.split);
-#else
-          // (experiment, -DSVS_WARP_STORE128: the two lanes of a unit swap halves (DPP quad_perm [1,0,3,2]), the even lane stores
-          // the whole hi unit, the odd lane the whole mid unit -- ONE 16-byte store per lane and plane instead of two 8-byte
-          // ones.  Measured on one box, three alternations: 0.228-0.240 against 0.225-0.239 ms at stage 1, 0.090 / 0.088,
-          // 0.063 / 0.062: the number of store instructions is not what the kernel waits for either.)
-          const i32x2 hv = __builtin_bit_cast(i32x2, h[0]), lv = __builtin_bit_cast(i32x2, lo[0]);
-          const i32x2 ph = {__builtin_amdgcn_mov_dpp(hv[0], 0xB1, 0xF, 0xF, true), __builtin_amdgcn_mov_dpp(hv[1], 0xB1, 0xF, 0xF, true)};
-          const i32x2 pl = {__builtin_amdgcn_mov_dpp(lv[0], 0xB1, 0xF, 0xF, true), __builtin_amdgcn_mov_dpp(lv[1], 0xB1, 0xF, 0xF, true)};
-          const i32x4 u = (g & 1) ? i32x4{pl[0], pl[1], lv[0], lv[1]} : i32x4{hv[0], hv[1], ph[0], ph[1]};
-          gstore128(so + ((g & 1) ? mid_b : 0u), u, a.split);
-#endif
-        }
+        gstore64(so + 8u * (g & 1), __builtin_bit_cast(i32x2, h[0]), a.split);
+        gstore64(so + 8u * (g & 1) + mid_b, __builtin_bit_cast(i32x2, lo[0]), a.split);
       }
       prev_stored = stored;
       so += plane_b;
@@ -749,19 +639,13 @@ __global__ __launch_bounds__((WarpCfg<C, CPL>::T), (CPL == 4 ? (NS <= 2 ? 4 : 2)
   }
 }
 
-template <int C, int CPL>
+template <int C>
 static bool launch_warp_reuse2(const WarpArgs& a, hipStream_t s) {
   // 32-bit byte offsets into the split volume and the feature maps
   const size_t vol = (size_t)(a.D + 2) * splitvol::padded_h(a.H) * 2 * (C / 8) * splitvol::padded_w(a.W) * 16;
   if (vol >= (1ull << 32) || (size_t)a.H * a.W * C * 4 >= (1ull << 31)) return false;
-  constexpr int T = WarpCfg<C, CPL>::T, tw = WarpCfg<C, CPL>::P * (T / (C / CPL));
+  constexpr int T = WarpCfg<C, 4>::T, tw = WarpCfg<C, 4>::P * (T / (C / 4));
   dim3 grid((a.W + tw - 1) / tw, a.H, (a.D + kWarpDz - 1) / kWarpDz), block(T);
-  if (CPL == 8) {
-    if (a.n_src == 1) warp_variance_reuse2_kernel<C, 1, CPL><<<grid, block, 0, s>>>(a);
-    else if (a.n_src == 2) warp_variance_reuse2_kernel<C, 2, CPL><<<grid, block, 0, s>>>(a);
-    else return false;
-    return true;
-  }
   switch (a.n_src) {
     case 1: warp_variance_reuse2_kernel<C, 1, 4><<<grid, block, 0, s>>>(a); break;
     case 2: warp_variance_reuse2_kernel<C, 2, 4><<<grid, block, 0, s>>>(a); break;
@@ -769,10 +653,6 @@ static bool launch_warp_reuse2(const WarpArgs& a, hipStream_t s) {
     default: warp_variance_reuse2_kernel<C, 4, 4><<<grid, block, 0, s>>>(a); break;
   }
   return true;
-}
-template <int CPL>
-static bool launch_warp_reuse2_any(int C, const WarpArgs& a, hipStream_t s) {
-  return C == 8 ? launch_warp_reuse2<8, CPL>(a, s) : (C == 16 ? launch_warp_reuse2<16, CPL>(a, s) : launch_warp_reuse2<32, CPL>(a, s));
 }
 
 template <int C>
@@ -965,10 +845,7 @@ struct C1Args {
   float* out;          // (D, H, W)
   int Cin, D, H, W, relu;
 };
-#ifndef SVS_C1_VZ
-#define SVS_C1_VZ 4
-#endif
-constexpr int kC1VX = 4, kC1VZ = SVS_C1_VZ, kC1TX = 8, kC1TY = 32;
+constexpr int kC1VX = 4, kC1VZ = 4, kC1TX = 8, kC1TY = 32;
 
 // A thread marches along z over kC1VZ output slices of its 4 x-positions with three accumulator sets in flight: input
 // slice zi adds its kd = 2 / 1 / 0 taps to the outputs zi-1 / zi / zi+1, the oldest set is then complete.  Loads are
@@ -1401,15 +1278,10 @@ static int warp_variance_any(const float* ref_feature, const float* const* src_f
   }
   if (C != 8 && C != 16 && C != 32) { set_error("svs_warp_variance: C must be 8, 16 or 32 (FeatureNet outputs)"); return SVS_ESHAPE; }
   hipStream_t s = (hipStream_t)hip_stream;
-  static const char* no_reuse = getenv("SVS_WARP_REUSE_OFF");
-  static const char* which = getenv("SVS_WARP_KERNEL");            // A/B: "8" | "5" (below)
-  if (a.split && !raw_warp && !(no_reuse && no_reuse[0] == '1')) {
-    // default: the round-6 producer at four channels per lane; "8": eight channels per lane; "5": round 5's kernel
-    if (!(which && which[0] == '5')) {
-      // (eight channels per lane only with up to two sources: 64 corner registers per source pair)
-      const bool ok = (which && which[0] == '8' && n_src <= 2) ? launch_warp_reuse2_any<8>(C, a, s) : launch_warp_reuse2_any<4>(C, a, s);
-      if (ok) return check_launch("svs_warp_variance_split");
-    }
+  if (a.split && !raw_warp) {
+    // the round-6 producer; round 5's kernel where its 32-bit offsets do not fit
+    const bool ok = C == 8 ? launch_warp_reuse2<8>(a, s) : (C == 16 ? launch_warp_reuse2<16>(a, s) : launch_warp_reuse2<32>(a, s));
+    if (ok) return check_launch("svs_warp_variance_split");
     if (C == 8) launch_warp_reuse<8>(a, s);
     else if (C == 16) launch_warp_reuse<16>(a, s);
     else launch_warp_reuse<32>(a, s);

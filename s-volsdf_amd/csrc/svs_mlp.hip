@@ -328,23 +328,6 @@ int svs_sdf_vals(const float* points, int n_points, const float* cam, int cam_st
   return check_launch("svs_sdf_vals");
 }
 
-#ifdef SVS_EXPERIMENTAL_KERNELS
-// svs_sdf_vals by the K-split-pair kernel (two waves per SIMD on the same 32 points, csrc/svs_mlp_h2p.hip): same stream
-// (fp16x2), same arguments.  An experiment kept for A/B runs; measured slower than svs_sdf_vals.
-int svs_sdf_vals_pair(const float* points, int n_points, const float* cam, int cam_stride, const float* dirs, const float* z,
-                      int S, int n_rays, const float* stream, float sphere_radius, float sphere_scale, int clamp_n, float* sdf,
-                      const int* gate, int gate_points, int gate_stride, void* hip_stream) {
-  SdfOnlyArgs a;
-  if (int rc = fill_src(a.src, points, n_points, cam, cam_stride, dirs, z, S, n_rays, "svs_sdf_vals_pair")) return rc;
-  if (!stream || !sdf) { set_error("svs_sdf_vals_pair: null stream/sdf"); return SVS_EINVAL; }
-  a.stream = reinterpret_cast<const f32x4*>(stream); a.sdf = sdf;
-  a.sphere_radius = sphere_radius; a.sphere_scale = sphere_scale; a.gate = gate;
-  a.gate_points = gate_points > 0 ? gate_points : 0x7fffff80; a.gate_stride = gate_stride;
-  if (gate && a.gate_points % kWgPts) { set_error("svs_sdf_vals_pair: gate_points must be a multiple of %d", kWgPts); return SVS_EINVAL; }
-  a.clamp_n = clamp_n < 0 ? a.src.P : clamp_n;
-  return launch_sdf_only_kp(a, (hipStream_t)hip_stream);
-}
-#endif
 
 size_t svs_sdf_hbuf_bytes(int n_points) { return (size_t)wave_tiles(n_points) * 8 * 128 * 64 * sizeof(float); }
 size_t svs_feat_tiles_bytes(int n_points) { return (size_t)wave_tiles(n_points) * 128 * 64 * sizeof(float); }

@@ -4,10 +4,6 @@
 #include "svs_common.h"
 #include "svs_mlp_layout.h"
 
-#ifndef SVS_DMA_ASM
-#define SVS_DMA_ASM 1
-#endif
-
 namespace svs {
 namespace mlp {
 
@@ -25,7 +21,6 @@ __device__ __forceinline__ void chunk_issue_piece(const f32x4* __restrict__ g, f
   const int idx = i * kThreads + wave_base;  // wave-uniform (wave_base_f4(), read once per kernel: Stream::wb)
   const unsigned lane_bytes = (threadIdx.x & 63u) * 16u;
   if ((i + 1) * kThreads <= N16 || idx < N16) {   // i is a constant after unrolling: whole rounds carry no branch
-#if SVS_DMA_ASM
     // Inline assembly, so that hipcc does not know the ring is written by vector-memory instructions.  The ring is
     // ordered by hand (Stream::advance / advance_keep<N>: counted vmcnt + barrier, inline assembly as well, hence
     // invisible to the waitcnt pass), and a DMA the pass can see makes it put `s_waitcnt vmcnt(0)` in front of the first
@@ -40,21 +35,8 @@ __device__ __forceinline__ void chunk_issue_piece(const f32x4* __restrict__ g, f
     // "may lead to undefined behaviour".  No other M0 user exists in the translation units that contain this asm: no
     // s_movrel / sendmsg / builtin LDS-DMA.)
     const unsigned lds_base = (unsigned)(unsigned long long)(__attribute__((address_space(3))) void*)(lds + idx);
-#if defined(SVS_ABL) && (SVS_ABL & 131072)      // diagnostic: a quarter of the lanes only (same instruction count, a quarter of the data)
-    asm volatile("s_mov_b64 s[96:97], exec\n\ts_mov_b64 exec, 0xffff\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1\n\t"
-                 "s_mov_b64 exec, s[96:97]" :: "v"(lane_bytes), "s"(g + idx), "s"(lds_base) : "memory", "s96", "s97");
-#elif defined(SVS_ABL) && (SVS_ABL & 262144)    // diagnostic: every lane fetches the SAME 16 bytes (same LDS write, one line of L2 traffic)
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
-                 :: "v"(0u), "s"(g + idx), "s"(lds_base) : "memory");
-#else
     asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
                  :: "v"(lane_bytes), "s"(g + idx), "s"(lds_base) : "memory");
-#endif
-#else
-    __builtin_amdgcn_global_load_lds(
-        (const __attribute__((address_space(1))) void*)(reinterpret_cast<const char*>(g + idx) + lane_bytes),
-        (__attribute__((address_space(3))) void*)(lds + idx), 16, 0, 0);
-#endif
   }
 }
 template <int N16>
@@ -76,9 +58,7 @@ struct StreamT {
   __device__ __forceinline__ const f32x4* cur_buf() const { return buf + cur * BUF; }
   template <int N16>
   __device__ __forceinline__ void prefetch() {
-#if !(defined(SVS_ABL) && (SVS_ABL & 64))
     chunk_issue<N16>(g, buf + (cur ^ 1) * BUF, wb);
-#endif
     g += N16;
   }
   // prefetch() in pieces: ceil(pieces / KS) of them at each of the first steps of a KS-step tile, then prefetch_done().
@@ -86,20 +66,16 @@ struct StreamT {
   // run under the matrix core instead of in front of it, and still land long before the tile ends.
   template <int N16, int KS>
   __device__ __forceinline__ void prefetch_step(int s) {
-#if !(defined(SVS_ABL) && (SVS_ABL & 64))
     constexpr int np = chunk_pieces<N16>(), per = (np + KS - 1) / KS;
 #pragma unroll
     for (int i = per * s; i < per * (s + 1) && i < np; ++i) chunk_issue_piece<N16>(g, buf + (cur ^ 1) * BUF, i, wb);
-#endif
   }
   template <int N16>
   __device__ __forceinline__ void prefetch_done() { g += N16; }
   // the chunk fetched by prefetch() becomes current: own loads landed, then everyone's
   __device__ __forceinline__ void advance() {
-#if !(defined(SVS_ABL) && (SVS_ABL & 8))
     __builtin_amdgcn_s_waitcnt(0);  // vmcnt(0) lgkmcnt(0) expcnt(0)
     __syncthreads();
-#endif
     cur ^= 1;
   }
   // The same, but the N youngest vector-memory operations of the wave -- float32 activation stores that the epilogue
@@ -109,9 +85,7 @@ struct StreamT {
   // of vector-memory instructions the wave really issued after prefetch().
   template <int N>
   __device__ __forceinline__ void advance_keep() {
-#if !(defined(SVS_ABL) && (SVS_ABL & 8))
     asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory");
-#endif
     cur ^= 1;
   }
 };

@@ -23,9 +23,6 @@ __global__ __launch_bounds__(kThreads, 1) void sdf_only_h2_kernel(SdfOnlyArgs a)
   st.cur = 1;
   const int lane = threadIdx.x & 63, half = lane >> 5, wave = threadIdx.x >> 6;
   const int p = (blockIdx.x * kWaves + wave) * kTilePts + (lane & 31);
-#if SVS_ABL & 16   // diagnostic: cycle stamps of wave 0 replace the first outputs of the workgroup
-  const uint64_t c0 = __builtin_amdgcn_s_memtime(), r0 = __builtin_amdgcn_s_memrealtime();
-#endif
 
   st.prefetch<kChunk0F4>();   // chunk 0 -> buffer 0 (overlaps the positional encoding below)
   float x0, x1, x2;
@@ -33,18 +30,10 @@ __global__ __launch_bounds__(kThreads, 1) void sdf_only_h2_kernel(SdfOnlyArgs a)
   const float r2 = x0 * x0 + x1 * x1 + x2 * x2;   // for the sphere clamp at the end: one live value instead of three
   PosEnc pe;
   pe.compute(x0, x1, x2);
-#if SVS_ABL & 16
-  asm volatile("" : "+v"(pe.v[38]));
-  const uint64_t c1 = __builtin_amdgcn_s_memtime();
-#endif
 
   Pieces2 x, xn;
   f32x16 y8[8];
   forward_trunk_h2<false>(st, x, xn, y8, pe, lane, half, nullptr);
-#if SVS_ABL & 16
-  asm volatile("" : "+v"(y8[7][15]));
-  const uint64_t c2 = __builtin_amdgcn_s_memtime();
-#endif
   // the VEC chunk was prefetched by the last tile of layer 7
   float sdf = sdf_head(st.cur_buf(), y8, lane);
   if (a.sphere_radius > 0.0f && p < a.clamp_n) {
@@ -52,16 +41,6 @@ __global__ __launch_bounds__(kThreads, 1) void sdf_only_h2_kernel(SdfOnlyArgs a)
     sdf = __builtin_fminf(sdf, a.sphere_scale * (a.sphere_radius - nrm));
   }
   if (half == 0 && p < a.src.P) a.sdf[p] = sdf;
-#if SVS_ABL & 16
-  asm volatile("" : "+v"(sdf));
-  const uint64_t c3 = __builtin_amdgcn_s_memtime(), r3 = __builtin_amdgcn_s_memrealtime();
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float* o = a.sdf + (size_t)blockIdx.x * kWgPts;
-    o[0] = (float)(c1 - c0); o[1] = (float)(c2 - c1); o[2] = (float)(c3 - c2); o[3] = (float)(c3 - c0);
-    o[4] = (float)(r3 - r0); o[5] = (float)(r0 & 0xffffff);
-  }
-#endif
 }
 
 // --------------------------------------------------------------------------------------------------------------
@@ -86,11 +65,7 @@ struct RevEpi {
 
   // three slices, one per MFMA gap of a k-step: exp2 | 1 - e and the product | masks, split
   __device__ __forceinline__ void a(int r) {
-#if SVS_ABL & 512      // diagnostic: no softplus' arithmetic in the reverse epilogue
-    d = 0.5f;
-#else
     d = __builtin_amdgcn_exp2f(grad_times<true>(h, r, -100.0f * 1.44269504088896341f));
-#endif
     pin(d);
   }
   __device__ __forceinline__ void a2(int r) {
@@ -124,7 +99,7 @@ struct RevEpi {
   }
   // the gbuf stores issued during tile t (see TrunkEpi::late_store): the pieces of k-steps 2(t-1) and 2(t-2)+1
   __device__ __forceinline__ void st(int t, int s) {
-    if (!GBUF || (SVS_ABL & 256)) return;         // (256: diagnostic, no gbuf stores)
+    if (!GBUF) return;
     if (s == 9) store_piece(gblk, 2 * (t - 1), lane, out->h[2 * (t - 1)], 0);
     if (t >= 2 && s == 11) store_piece(gblk, 2 * (t - 2) + 1, lane, out->h[2 * (t - 2) + 1], 0);
     if (GP && s == 13) store_piece(gblk, 2 * (t - 1), lane, out->m[2 * (t - 1)], 1);
@@ -160,7 +135,7 @@ __device__ __forceinline__ void reverse_layer_h2(Stream& st, const Pieces2& in, 
     if (t >= 1) pin(ep.h.h[0], ep.h.h[1]), pin(ep.h.m[0], ep.h.m[1]);
     const TilePieces hcur = hnext;
     auto hload = [&](int s) {
-      if (t == 7 || (SVS_ABL & 128)) return;      // (128: diagnostic, no h loads)
+      if (t == 7) return;
       if (s == 10) hnext.h[0] = load_piece(hblk, 2 * (t + 1), lane, 0);
       if (s == 12) hnext.h[1] = load_piece(hblk, 2 * (t + 1) + 1, lane, 0);
       if (s == 14) hnext.m[0] = load_piece(hblk, 2 * (t + 1), lane, 1);
@@ -203,21 +178,12 @@ __global__ __launch_bounds__(kThreads, 1) void sdf_full_h2_kernel(SdfFullArgs a)
   const int lane = threadIdx.x & 63, half = lane >> 5, wave = threadIdx.x >> 6;
   const int wtile = blockIdx.x * kWaves + wave;
   const int p = wtile * kTilePts + (lane & 31);
-#if SVS_ABL & 16   // diagnostic: cycle stamps of wave 0 replace the workgroup's first gradient outputs
-  uint64_t cs[8];
-  cs[0] = __builtin_amdgcn_s_memtime();
-  const uint64_t r0 = __builtin_amdgcn_s_memrealtime();
-#define SVS_STAMP(i, var) { asm volatile("" : "+v"(var)); cs[i] = __builtin_amdgcn_s_memtime(); }
-#else
-#define SVS_STAMP(i, var)
-#endif
 
   st.prefetch<kChunk0F4>();
   float x0, x1, x2;
   load_point(a.src, p, x0, x1, x2);
   PosEnc pe;
   pe.compute(x0, x1, x2);
-  SVS_STAMP(1, pe.v[38])
 
   float* hb = a.hbuf + (size_t)wtile * kBlockF;                        // block l of this tile: + l * block_stride()
   float* gb = GBUF ? a.gbuf + (size_t)wtile * kBlockF : nullptr;
@@ -230,7 +196,6 @@ __global__ __launch_bounds__(kThreads, 1) void sdf_full_h2_kernel(SdfFullArgs a)
   {
     f32x16 y8[8];
     forward_trunk_h2<true>(st, x, xn, y8, pe, lane, half, hb);
-    SVS_STAMP(2, y8[7][15])
     // ---- head: current chunk = VEC (W8 row 0 in C-layout order as float32, b8[0])
     st.prefetch<kChunkF4>();                       // FEAT tile 0
     sdf = sdf_head(st.cur_buf(), y8, lane);
@@ -261,7 +226,6 @@ __global__ __launch_bounds__(kThreads, 1) void sdf_full_h2_kernel(SdfFullArgs a)
     if (GBUF) store_record(grec0 + 7 * rec_stride, lane, 1.0f, __builtin_fmaxf(gm7, __shfl_xor(gm7, 32)));
     st.advance();
   }
-  SVS_STAMP(3, sdf)
   // ---- feature vector = rows 1..256 of lin8 (no activation), stored as a PAIR block (the radiance network's operand
   // and the B operand of its first weight gradient); tile t-1 is split and stored while tile t's MFMAs run
   float* ft = a.feat_tiles ? a.feat_tiles + (size_t)wtile * kBlockF : nullptr;
@@ -289,7 +253,6 @@ __global__ __launch_bounds__(kThreads, 1) void sdf_full_h2_kernel(SdfFullArgs a)
 #pragma unroll
     for (int r = 0; r < 16; ++r) slice(7, r);
   }
-  SVS_STAMP(4, sdf)
   // ---- reverse layers 7..1, operands ping-pong between xn and x
   f32x16 skip7 = (f32x16)(0.0f);   // g(PE[0..31]) from the skip connection (tile 7 of g(h_4 spliced))
   f32x16 skip6 = (f32x16)(0.0f);   // tile 6; only local rows 25..31 are PE[32..38]
@@ -297,7 +260,6 @@ __global__ __launch_bounds__(kThreads, 1) void sdf_full_h2_kernel(SdfFullArgs a)
     reverse_layer_h2<GBUF, GP>(st, xn, x, l, hb, gb, grec0, rec_stride, skip6, skip7, lane, half);
     if (l > 1) reverse_layer_h2<GBUF, GP>(st, x, xn, l - 1, hb, gb, grec0, rec_stride, skip6, skip7, lane, half);
   }
-  SVS_STAMP(5, skip7[0])
   // ---- reverse layer 0: g(PE) = W0^T g(a_0) (+ skip), 2 tiles; g(a_0) is in x
   st.prefetch<kChunkF4>();
   f32x16 gpe0 = tile_mma_h2<16>(st.cur_buf(), x, lane);
@@ -357,16 +319,6 @@ __global__ __launch_bounds__(kThreads, 1) void sdf_full_h2_kernel(SdfFullArgs a)
     a.sdf[p] = sdf;
     a.grad[3 * p + 0] = dx0; a.grad[3 * p + 1] = dx1; a.grad[3 * p + 2] = dx2;
   }
-#if SVS_ABL & 16
-  SVS_STAMP(6, dx0)
-  const uint64_t r1 = __builtin_amdgcn_s_memrealtime();
-  __syncthreads();
-  if (threadIdx.x == 0) {   // pe, trunk, head, features, reverse 7..1, reverse 0 + Jacobian, total, real time
-    float* o = a.grad + (size_t)blockIdx.x * kWgPts * 3;
-    for (int i = 0; i < 6; ++i) o[i] = (float)(cs[i + 1] - cs[i]);
-    o[6] = (float)(cs[6] - cs[0]); o[7] = (float)(r1 - r0);
-  }
-#endif
 }
 
 // --------------------------------------------------------------------------------------------------------------
@@ -486,23 +438,21 @@ using namespace svs::mlp;
 
 namespace svs {
 namespace mlp {
-// diagnostic builds with fewer registers must not become two workgroups per CU: pad the LDS request
-constexpr int kLdsAbl = (SVS_ABL & 32) ? 0 : (SVS_ABL ? 20480 : 0);
 int launch_sdf_only_h2(const SdfOnlyArgs& a, hipStream_t s) {
-  static int once = set_lds(sdf_only_h2_kernel, kLdsBytes + kLdsAbl, "svs_sdf_vals");
+  static int once = set_lds(sdf_only_h2_kernel, kLdsBytes, "svs_sdf_vals");
   if (once) return once;
-  sdf_only_h2_kernel<<<(a.src.P + kWgPts - 1) / kWgPts, kThreads, kLdsBytes + kLdsAbl, s>>>(a);
+  sdf_only_h2_kernel<<<(a.src.P + kWgPts - 1) / kWgPts, kThreads, kLdsBytes, s>>>(a);
   return check_launch("svs_sdf_vals");
 }
 int launch_sdf_full_h2(const SdfFullArgs& a, bool grad_pair, hipStream_t s) {
-  static int once = set_lds(sdf_full_h2_kernel<true, true>, kLdsBytes + kLdsAbl, "svs_sdf_outputs") |
-                    set_lds(sdf_full_h2_kernel<true, false>, kLdsBytes + kLdsAbl, "svs_sdf_outputs") |
-                    set_lds(sdf_full_h2_kernel<false, false>, kLdsBytes + kLdsAbl, "svs_sdf_outputs");
+  static int once = set_lds(sdf_full_h2_kernel<true, true>, kLdsBytes, "svs_sdf_outputs") |
+                    set_lds(sdf_full_h2_kernel<true, false>, kLdsBytes, "svs_sdf_outputs") |
+                    set_lds(sdf_full_h2_kernel<false, false>, kLdsBytes, "svs_sdf_outputs");
   if (once) return once;
   const int grid = (a.src.P + kWgPts - 1) / kWgPts;
-  if (!a.gbuf) sdf_full_h2_kernel<false, false><<<grid, kThreads, kLdsBytes + kLdsAbl, s>>>(a);
-  else if (grad_pair) sdf_full_h2_kernel<true, true><<<grid, kThreads, kLdsBytes + kLdsAbl, s>>>(a);     // training: ghat blocks stored
-  else sdf_full_h2_kernel<true, false><<<grid, kThreads, kLdsBytes + kLdsAbl, s>>>(a);
+  if (!a.gbuf) sdf_full_h2_kernel<false, false><<<grid, kThreads, kLdsBytes, s>>>(a);
+  else if (grad_pair) sdf_full_h2_kernel<true, true><<<grid, kThreads, kLdsBytes, s>>>(a);     // training: ghat blocks stored
+  else sdf_full_h2_kernel<true, false><<<grid, kThreads, kLdsBytes, s>>>(a);
   return check_launch("svs_sdf_outputs");
 }
 int launch_rgb_h2(const RgbArgs& a, bool grad_pair, hipStream_t s) {

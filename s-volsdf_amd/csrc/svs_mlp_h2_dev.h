@@ -80,23 +80,6 @@ __device__ __forceinline__ f32x16 tile_bias(const f32x4* __restrict__ chunk, int
   return acc;
 }
 
-// Diagnostic builds (tools/ablate_fwd.sh): -DSVS_ABL=<mask> compiles parts of the forward kernels out to time the rest
-// (results are then wrong by construction).  1: identity instead of softplus, 2: no operand split, 4: no MFMAs,
-// 8: no chunk wait / barrier, 16: cycle stamps instead of results (sdf_only), 32: let the slimmer variants run two
-// workgroups per CU (otherwise their LDS request is padded to keep one), 64: no weight fetch; reverse pass of sdf_full:
-// 128: no h loads, 256: no gbuf stores, 512: no softplus' arithmetic; pass A (svs_mlp_bwd_h2.hip): 1024 no side-tile loads,
-// 2048 no u stores; pass B: 4096 no side-tile loads, 8192 no abar stores, 16384 no second-order / sbar terms, 32768 no softplus'
-// arithmetic, 65536 per-tile cycle stamps into sbar_out (tools/bench_kernels.py BK_STAMPS=1); the weight fetch (svs_mlp_dev.h):
-// 131072 a quarter of the lanes per LDS-DMA instruction, 262144 every lane the same address.  Never defined in the product build.
-#ifndef SVS_ABL
-#define SVS_ABL 0
-#endif
-#if SVS_ABL & 4
-#define SVS_ABL_MFMA(x)
-#else
-#define SVS_ABL_MFMA(x) x
-#endif
-
 struct NoEpi { __device__ __forceinline__ void operator()(int) const {} };
 struct NoPre { __device__ __forceinline__ void operator()() const {} };
 
@@ -120,16 +103,16 @@ __device__ __forceinline__ f32x16 tile_mma_h2(const f32x4* __restrict__ chunk, c
   for (int s = 0; s < KS; ++s) {
     f16x8 nh, nm;
     __builtin_amdgcn_sched_barrier(0);
-    SVS_ABL_MFMA(acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(am, x.h[first_step + s], acc, 0, 0, 0));
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(am, x.h[first_step + s], acc, 0, 0, 0);
     __builtin_amdgcn_sched_barrier(0);
     if (s + 1 < KS) { nh = a_ptr[(2 * s + 2) * 64]; nm = a_ptr[(2 * s + 3) * 64]; }
     ea(s);
     __builtin_amdgcn_sched_barrier(0);
-    SVS_ABL_MFMA(acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, x.m[first_step + s], acc, 0, 0, 0));
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, x.m[first_step + s], acc, 0, 0, 0);
     __builtin_amdgcn_sched_barrier(0);
     eb(s);
     __builtin_amdgcn_sched_barrier(0);
-    SVS_ABL_MFMA(acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, x.h[first_step + s], acc, 0, 0, 0));
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, x.h[first_step + s], acc, 0, 0, 0);
     __builtin_amdgcn_sched_barrier(0);
     ec(s);
     dma(s);

@@ -64,22 +64,14 @@ struct TrunkEpi {
   // softplus of element r in three slices, one per MFMA gap of a k-step (a gap hides about 24 cycles of vector issue,
   // an exp2 or log2 costs 8): a = exp2, a2 = max + log2, b = the final fma and the element's share of emit()
   __device__ __forceinline__ void a(int r) {
-#if SVS_ABL & 1
-    sa.lg = 0.0f;
-#else
     sa.lg = __builtin_amdgcn_exp2f(__builtin_fabsf(prev[r]) * (-100.0f * 1.44269504088896341f));
-#endif
     pin(sa.lg);
   }
   __device__ __forceinline__ void a2(int r) {
-#if SVS_ABL & 1
-    sa.mx = prev[r];
-#else
     // max(a, 0) without the canonicalising v_max hipcc puts in front of fmaxf in IEEE mode (a is an MFMA result)
     // (volatile + first: hipcc pads an inline-asm instruction that directly precedes an MFMA with an s_nop)
     asm volatile("v_max_f32 %0, 0, %1" : "=v"(sa.mx) : "v"(prev[r]));
     sa.lg = __builtin_amdgcn_logf(1.0f + sa.lg);
-#endif
     pin(sa.lg);
   }
   template <bool DEFER = false>
@@ -105,7 +97,7 @@ struct TrunkEpi {
   template <bool DEFER = false>
   __device__ __forceinline__ void emit(int tp, int r, float v) {
     if (LAST) y8[tp][r] = v;
-    if (kSplit && !(SVS_ABL & 2)) {
+    if (kSplit) {
       v8[r & 7] = v;
       if ((r & 7) == 7 && !(DEFER && r == 15)) {
         const int k = 2 * tp + (r >> 3);
@@ -117,7 +109,7 @@ struct TrunkEpi {
   }
   template <bool STORE = false>
   __device__ __forceinline__ void finish(int tp) {
-    if (kSplit && !(SVS_ABL & 2)) {
+    if (kSplit) {
       const int k = 2 * tp + 1;
       split8(v8, xn->h[k], xn->m[k]);
       pin(xn->h[k], xn->m[k]);

@@ -433,20 +433,16 @@ __global__ __launch_bounds__(kThreadsW, 1) void wgrad_h2_multi_kernel(MultiArgs 
       touched = false;
       if (touching && item + kAhead + 1 < n_items) { touch(item + kAhead + 1); touched = true; }
     };
-#ifdef SVS_WGRAD_A_SERIAL
-    issue_next();
-#endif
     const unsigned la = lds_addr(ring + (item % kRing) * kSlotAll);
     const unsigned lb = la + kB;
     const unsigned ftab = la + kSlot + kRecBytes + wave * 64;
     const unsigned nimg = lb + kNarrowImg;
     const bool want_bias = has_db && p0;
     const bool two = narrow;             // only the narrow float32 tile is split into two pieces
-#ifndef SVS_WGRAD_A_SERIAL
     // The A fragments of BOTH contraction k-steps (hi and mid pieces, their factors) are requested together, the next item's
     // copies are issued behind the requests, and the fragments are waited for once: the item period is the multiply phase plus
-    // what precedes it serially in every wave (section 3f of NOTES/r06.md), and the form before (-DSVS_WGRAD_A_SERIAL: copies
-    // first, then per k-step hi then mid, a full LDS round trip each) put four round trips there.
+    // what precedes it serially in every wave (section 3f of NOTES/r06.md), and the form before (copies first, then per k-step
+    // hi then mid, a full LDS round trip each) put four round trips there.
     Frag fa2[2], fam2[2];
     f32x4 fraw2[2];
 #pragma unroll
@@ -457,27 +453,10 @@ __global__ __launch_bounds__(kThreadsW, 1) void wgrad_h2_multi_kernel(MultiArgs 
     }
     issue_next();        // (the next item's copies are issued while these reads are on their way)
     lds_wait();
-#endif
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
-#ifndef SVS_WGRAD_A_SERIAL
       const f16x8 ah = frag_of(fa2[ks]) * __builtin_bit_cast(f16x8, fraw2[ks]);
       const f16x8 am = GP ? frag_of(fam2[ks]) * __builtin_bit_cast(f16x8, fraw2[ks]) : ah;
-#else
-      Frag fa;
-      f32x4 fraw;
-      tr_issue(fa, la + 512 * ks + a_rd, la + 512 * ks + (a_rd ^ 128));
-      lds_read128(fraw, ftab + 32 * ks + 16 * rh);
-      lds_wait();
-      const f16x8 ah = frag_of(fa) * __builtin_bit_cast(f16x8, fraw);
-      f16x8 am = ah;
-      if (GP) {
-        Frag fam;
-        tr_issue(fam, la + kPlane + 512 * ks + a_rd, la + kPlane + 512 * ks + (a_rd ^ 128));
-        lds_wait();
-        am = frag_of(fam) * __builtin_bit_cast(f16x8, fraw);
-      }
-#endif
       if (want_bias) {
         // row sums of A: the fragment holds 8 points of row lane & 31 (the other lane half holds the other 8)
 #pragma unroll
@@ -495,10 +474,6 @@ __global__ __launch_bounds__(kThreadsW, 1) void wgrad_h2_multi_kernel(MultiArgs 
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         if (i > 0 && narrow) break;
-#if defined(SVS_WGRAD_DIAG) && (SVS_WGRAD_DIAG & 8)   // diagnostic build: the copies and the barriers only (no B fragment reads, no MFMAs)
-        asm volatile("" :: "v"(ah), "v"(am));
-        continue;
-#endif
         Frag fh, fm;
         if (!narrow) {
           const unsigned rd = lb + 2048 * i + 512 * ks + rd0;
@@ -509,13 +484,9 @@ __global__ __launch_bounds__(kThreadsW, 1) void wgrad_h2_multi_kernel(MultiArgs 
           tr_issue(fm, nimg + kExtraPiece + ks * 1024 + rx0, nimg + kExtraPiece + ks * 1024 + rx1);
         }
         lds_wait();
-#if defined(SVS_WGRAD_DIAG) && (SVS_WGRAD_DIAG & 4)   // diagnostic build: the fragments are read, nothing is multiplied
-        asm volatile("" :: "v"(fh.lo), "v"(fh.hi), "v"(fm.lo), "v"(fm.hi));
-#else
         if (two || GP) acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, frag_of(fm), acc[i], 0, 0, 0);
         if (GP) acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(am, frag_of(fh), acc[i], 0, 0, 0);
         acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, frag_of(fh), acc[i], 0, 0, 0);
-#endif
       }
     }
   }
@@ -530,15 +501,7 @@ __global__ __launch_bounds__(kThreadsW, 1) void wgrad_h2_multi_kernel(MultiArgs 
     for (int r = 0; r < 16; ++r) {
       const int row = 32 * wave + rho(r) + 4 * half;
       const int c = a.col0 + 32 * i + col;
-      // (-DSVS_WGRAD_DIAG=<mask>, tools/dev/ab_defs.sh + tools/dev/time_wgrad.py: 1 no flush, 2 plain stores, 4 fragments read but
-      // nothing multiplied, 8 copies and barriers only; never defined in the product build)
-#if defined(SVS_WGRAD_DIAG) && (SVS_WGRAD_DIAG & 1)   // diagnostic build: no flush (the guard keeps the accumulators alive)
-      if (c < a.ldw && acc[i][r] == 1.2345e-31f) a.dW[(size_t)row * a.ldw + c] = acc[i][r];
-#elif defined(SVS_WGRAD_DIAG) && (SVS_WGRAD_DIAG & 2) // diagnostic build: plain stores instead of atomics (wrong sums)
-      if (c < a.ldw) a.dW[(size_t)row * a.ldw + c] = acc[i][r] * inv_s;
-#else
       if (c < a.ldw) atomicAdd(&a.dW[(size_t)row * a.ldw + c], acc[i][r] * inv_s);
-#endif
     }
   }
   if (a.db) {
@@ -613,8 +576,7 @@ int svs_wgrad_multi(const svs_wgrad_job* jobs, int n_jobs, int precision, void* 
         // (a narrow item copies 36 of a wide item's 64 KiB and multiplies one B tile of eight, but an item's time is mostly
         // the latency of its copy: priced at 4 / 10 of a wide item, as until round 6, its workgroups were the radiance launch's
         // longest -- 0.33 ms alone; 5 ... 7: 0.29-0.30; 8, 10: 0.30-0.31 (profiles/r06_wgrad_what_bounds_it.txt))
-        static const int narrow_work = [] { const char* e = getenv("SVS_WGRAD_NARROW_WORK"); return e ? atoi(e) : 6; }();
-        work[n] = (long long)X.n_tiles * narrow_work;
+        work[n] = (long long)X.n_tiles * 6;
         total += work[n++];
       }
     }

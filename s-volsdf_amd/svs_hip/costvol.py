@@ -160,7 +160,7 @@ class SplitVolume:
 
 
 def pair_supported(C, Cout):
-    return C in (8, 16, 32) and Cout <= 8 and not os.environ.get("SVS_CONV_PAIR_OFF")
+    return C in (8, 16, 32) and Cout <= 8
 
 
 def warp_variance(features, proj_matrices, depth_values, split=False):
@@ -498,7 +498,7 @@ def gemm_weight_fragments(weight, transposed):
 
 
 def rows_supported(Cin, Cout):
-    return Cin == 16 and Cout <= 16 and not os.environ.get("SVS_CONV_ROWS_OFF")
+    return Cin == 16 and Cout <= 16
 
 
 def conv3d(x, weight, bias=None, skip=None, stride=1, transposed=False, relu=True, split_out=False):
@@ -520,16 +520,16 @@ def conv3d(x, weight, bias=None, skip=None, stride=1, transposed=False, relu=Tru
                 _lib.check(L.svs_conv3d_pair(_ptr(x.buf), _ptr(pair_weight_fragments(weight)), _ptr(bias), _ptr(out), x.C, Cout,
                                              x.D, x.H, x.W, int(relu), _stream()), "svs_conv3d_pair")
             return out
-        x = x.float()                # no fused form for this layer (or switched off): back to the float32 volume
+        x = x.float()                # no fused form for this layer: back to the float32 volume
     x = _f32(x)
     Cin, D, H, W = x.shape
     Cout = weight.shape[2]
-    if not transposed and stride == 1 and Cout == 1 and not os.environ.get("SVS_CONV_C1_OFF"):
+    if not transposed and stride == 1 and Cout == 1:
         out = torch.empty((1, D, H, W), device=x.device)
         _lib.check(L.svs_conv3d_c1(_ptr(x), _ptr(_f32(weight)), _ptr(bias), _ptr(skip), _ptr(out), Cin, D, H, W, int(relu),
                                    _stream()), "svs_conv3d_c1")
         return out
-    if not transposed and stride == 1 and Cin in (8, 16, 32) and Cout <= 16 and not os.environ.get("SVS_CONV_RING_OFF"):
+    if not transposed and stride == 1 and Cin in (8, 16, 32) and Cout <= 16:
         frag = mfma_weight_fragments(weight)
         out = torch.empty((Cout, D, H, W), device=x.device)
         _lib.check(L.svs_conv3d_mfma(_ptr(x), _ptr(frag), _ptr(bias), _ptr(skip), _ptr(out), Cin, Cout, D, H, W,
@@ -540,7 +540,7 @@ def conv3d(x, weight, bias=None, skip=None, stride=1, transposed=False, relu=Tru
     else:
         shp = (Cout, (D - 1) // stride + 1, (H - 1) // stride + 1, (W - 1) // stride + 1)
     out = torch.empty(shp, device=x.device)
-    if not transposed and stride == 2 and Cin == 8 and Cout <= 16 and W % 2 == 0 and not os.environ.get("SVS_CONV_S2C8_OFF"):
+    if not transposed and stride == 2 and Cin == 8 and Cout <= 16 and W % 2 == 0:
         frag = s2c8_weight_fragments(weight)
         if split_out and Cout == 16 and skip is None:
             sv = SplitVolume(Cout, *shp[1:], x.device)

@@ -165,15 +165,6 @@ SIGNATURES.update({
     "svs_plan_destroy": (c_int, [_P]),
 })
 
-# entry points of the experimental kernels: present only in a library built with SVS_BUILD_EXPERIMENTS=1
-EXPERIMENTAL_SIGNATURES = {
-    "svs_sdf_vals16": (c_int, [_P, c_int, _P, c_int, _P, _P, c_int, c_int, _P, c_float, c_float, c_int, _P, _P,
-                               c_int, c_int, _P]),
-    "svs_sdf_vals_pair": (c_int, [_P, c_int, _P, c_int, _P, _P, c_int, c_int, _P, c_float, c_float, c_int, _P, _P,
-                                  c_int, c_int, _P]),
-}
-
-
 ABI_VERSION = 101          # svs_version() of the library this binding was written against (include/svolsdf_hip.h)
 
 
@@ -190,11 +181,6 @@ def load():
         fn = getattr(lib, name)          # AttributeError if the header and the library disagree
         fn.restype = res
         fn.argtypes = args
-    for name, (res, args) in EXPERIMENTAL_SIGNATURES.items():
-        fn = getattr(lib, name, None)
-        if fn is not None:
-            fn.restype = res
-            fn.argtypes = args
     have = lib.svs_version()
     if have != ABI_VERSION:
         raise SvsError(f"{LIB_PATH} has ABI version {have}, this binding was written against {ABI_VERSION}: "

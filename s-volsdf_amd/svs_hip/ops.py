@@ -86,26 +86,12 @@ def default_precision():
 class PackedMlp:
     """Packed weight streams of one ImplicitNetwork / RenderingNetwork pair (rebuilt after every optimiser step)."""
 
-    def __init__(self, device, precision=None, sdf_kernel=None):
+    def __init__(self, device, precision=None):
         L = _lib.load()
         self.device = device
         self.precision = default_precision() if precision is None else int(precision)
         self.sdf_stream = torch.empty(L.svs_stream_bytes(1) // 4, device=device)
         self.rgb_stream = torch.empty(L.svs_stream_bytes(3) // 4, device=device)
-        # sdf_kernel / SVS_SDF_KERNEL: which kernel runs the sampler's sdf-only evaluations -- "32" (default: one wave per SIMD,
-        # 32 points per wave), "16" (two waves per SIMD, 16-point waves, csrc/svs_mlp_w16.hip: its own encoding of the forward
-        # stream) or "pair" (two waves per SIMD on the same 32 points, csrc/svs_mlp_h2p.hip).  The two-wave variants are
-        # experiments kept for A/B runs: same speed / slower (DESIGN.md section 4)
-        import os
-        self.sdf_kernel = (sdf_kernel or os.environ.get("SVS_SDF_KERNEL", "32")) if is_h2(self.precision) else "32"
-        if self.sdf_kernel not in ("32", "16", "pair"):
-            raise ValueError(f"SVS_SDF_KERNEL must be 32, 16 or pair, not {self.sdf_kernel!r}")
-        if self.sdf_kernel != "32" and not hasattr(L, "svs_sdf_vals_pair"):
-            raise _lib.SvsError(f"SVS_SDF_KERNEL={self.sdf_kernel}: the experimental two-waves-per-SIMD kernels are not in this "
-                                "library; rebuild with SVS_BUILD_EXPERIMENTS=1 python s-volsdf_amd/build.py --force")
-        self.w16 = self.sdf_kernel == "16"
-        self.sdf_stream16 = torch.empty(L.svs_stream_bytes(9) // 4, device=device) if self.w16 else None
-        self._ws16 = torch.empty(L.svs_pack_workspace_bytes() // 4, device=device) if self.w16 else None
         # one row-norm workspace per stream: the fused train step packs the two on different HIP streams at the same time
         self._ws = torch.empty(L.svs_pack_workspace_bytes() // 4, device=device)
         self._ws_rgb = torch.empty(L.svs_pack_workspace_bytes() // 4, device=device)
@@ -119,9 +105,6 @@ class PackedMlp:
         self._keep = (v, b, g)
         _lib.check(L.svs_pack_stream(1, self.precision, _ptr_array(v), _ptr_array(g) if g else None, _ptr_array(b),
                                      _ptr(self._ws), _ptr(self.sdf_stream), _stream()), "svs_pack_stream(sdf)")
-        if self.w16:
-            _lib.check(L.svs_pack_stream(9, self.precision, _ptr_array(v), _ptr_array(g) if g else None, _ptr_array(b),
-                                         _ptr(self._ws16), _ptr(self.sdf_stream16), _stream()), "svs_pack_stream(sdf w16)")
 
     def pack_rgb(self, weight_v, weight_g, bias):
         L = _lib.load()
@@ -164,16 +147,6 @@ def sdf_vals(packed, src, sphere_radius, sphere_scale, out=None, gate=None, clam
     per group of gate_points points (0: one group), gate_stride ints apart: groups whose flag is 0 are skipped."""
     L = _lib.load()
     sdf = out if out is not None else torch.empty(src.n, 1, device=src.device)
-    if getattr(packed, "sdf_kernel", "32") == "pair":
-        _lib.check(L.svs_sdf_vals_pair(*src.args(), _ptr(packed.sdf_stream), float(sphere_radius), float(sphere_scale),
-                                       int(clamp_n), _ptr(sdf), ctypes.c_void_p(gate) if gate else None, int(gate_points),
-                                       int(gate_stride), _stream()), "svs_sdf_vals_pair")
-        return sdf
-    if getattr(packed, "w16", False):
-        _lib.check(L.svs_sdf_vals16(*src.args(), _ptr(packed.sdf_stream16), float(sphere_radius), float(sphere_scale),
-                                    int(clamp_n), _ptr(sdf), ctypes.c_void_p(gate) if gate else None, int(gate_points),
-                                    int(gate_stride), _stream()), "svs_sdf_vals16")
-        return sdf
     _lib.check(L.svs_sdf_vals(*src.args(), _ptr(packed.sdf_stream), packed.precision, float(sphere_radius), float(sphere_scale),
                               int(clamp_n), _ptr(sdf), ctypes.c_void_p(gate) if gate else None, int(gate_points),
                               int(gate_stride), _stream()), "svs_sdf_vals")
@@ -341,14 +314,11 @@ def composite_bg(z, z_max, sdf, rgb, depth_scale, beta_param, beta_min, z_bg, bg
                 depth_values=depth_values, depth_values_all=depth_all, depth_vals=depth_vals, normal_map=normal_map)
 
 
-_STAGE_IN = os.environ.get("SVS_STAGE_IN", "1") != "0"      # A/B switch: 0 = hipMemcpyAsync (tensor.copy_)
-
-
 def stage_in(dev_tensor, pinned_tensor):
     """pinned host tensor -> device tensor of the same byte size, by a kernel on the current stream (svs_stage_in); falls back to
     a non-blocking copy_ for buffers the kernel does not take (alignment, sizes that are not a multiple of 4 bytes)."""
     nbytes = pinned_tensor.numel() * pinned_tensor.element_size()
-    ok = (_STAGE_IN and pinned_tensor.is_pinned() and pinned_tensor.is_contiguous() and dev_tensor.is_contiguous()
+    ok = (pinned_tensor.is_pinned() and pinned_tensor.is_contiguous() and dev_tensor.is_contiguous()
           and nbytes == dev_tensor.numel() * dev_tensor.element_size() and nbytes % 4 == 0
           and pinned_tensor.data_ptr() % 16 == 0 and dev_tensor.data_ptr() % 16 == 0 and nbytes > 0)
     if not ok:

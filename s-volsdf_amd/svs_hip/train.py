@@ -41,15 +41,6 @@ def record_off(n_points, n_blocks, block):
     return n_blocks * T * KBLOCK + block * T * KREC
 
 
-# Experiment, OFF by default: in captured sequences the prior look-up as a branch beside the fused SDF / radiance launches and
-# lin8's first-row gradient beside the SDF weight-gradient launch (51 us of small launches off a 256-ray step's critical
-# chain).  Measured with launch plans, A/B twice on one box: 1.315 / 1.311 against 1.319 / 1.311 ms (DTU model, 256 rays), 1.55
-# against 1.495 with the background model -- the branches' stream crossings and the fifth busy stream cost what they save.
-_PLAN_BRANCHES = os.environ.get("SVS_PLAN_BRANCHES", "0") == "1"
-_RGB_MERGE = os.environ.get("SVS_RGB_WGRAD_MERGE", "0")       # 0 (default) | 1 | auto (MlpBackward.accumulate: an experiment)
-_WGRAD_SPLIT = os.environ.get("SVS_WGRAD_SPLIT", "0")         # 0 (default) | 1 | auto (MlpBackward.accumulate: an experiment)
-
-
 def _off(t, n_floats):
     """device pointer `n_floats` floats into tensor t"""
     return t.data_ptr() + 4 * n_floats
@@ -217,11 +208,10 @@ class MlpBackward:
         def addr(x):
             return x.value if isinstance(x, ctypes.c_void_p) else x
 
-        def job(slot, n_pts, amax, a0, sa0, b0, sb0, a1=None, sa1=0, b1=None, sb1=0, extra=None, sx=0, rec0=None, rec1=None,
-                bias=True):
+        def job(slot, n_pts, amax, a0, sa0, b0, sb0, a1=None, sa1=0, b1=None, sb1=0, extra=None, sx=0, rec0=None, rec1=None):
             return _lib.WGradJob(addr(a0), addr(b0), sa0, sb0, addr(a1), addr(b1), sa1, sb1,
                                  addr(extra), sx, n_pts, LDW, addr(_off(acc.dWk, slot * 256 * LDW)),
-                                 addr(_off(acc.dbk, slot * 256)) if bias else None, addr(_off(acc.absmax, amax)) if h2 else None,
+                                 addr(_off(acc.dbk, slot * 256)), addr(_off(acc.absmax, amax)) if h2 else None,
                                  addr(rec0) if h2 else None, addr(rec1) if h2 else None)
 
         def wgrad_multi(cached):
@@ -287,36 +277,10 @@ class MlpBackward:
                                 rec0=zrec(l)))
             return jobs
 
-        # Experiment (SVS_WGRAD_SPLIT = 1 | auto: up to 40 960 points; OFF by default).  Small batches (config 4's 256 rays per
-        # GPU): the step is the SUM of its kernels' latencies, the sweeps' workgroups do not fill the chip and HBM idles under
-        # them.  The second-order half of the SDF weight gradients -- ghat_l x u_l^T, complete once pass A is -- rides with
-        # the radiance weight gradients in ONE launch beside pass B, and the launch that ends the step is the first-order
-        # half (abar_l x h_l^T, bias gradients) only.  Same sums, same accumulators (gradient tests pass).  Round 4 had the
-        # second-order launch queued BEHIND the radiance launch (it started when pass B was half done): 1.46 against 1.42 ms.
-        # Round 5, merged, A/B three times on one box: 1.186 against 1.194 ms at 256 rays (DTU), 1.358 against 1.324 with the
-        # background model, 1.94 / 1.94 at 512 rays -- the launch that ends the step is not HBM-bound at this size (26 items
-        # per workgroup: ring fill, atomic flush and the spread of the workgroups' finishing times), halving its bytes takes
-        # 15 % off it, and pass B runs slower beside 0.7 GB of streaming.  Off.
-        split = h2 and side and not defer_wgrad and extra is None and \
-            (_WGRAD_SPLIT == "1" or (_WGRAD_SPLIT == "auto" and n_total <= 40960))
-        # Experiment (SVS_RGB_WGRAD_MERGE = 1 | auto: up to 40 960 points; OFF by default): the radiance network's weight
-        # gradients ride in the SDF network's launch at the end of the step instead of running beside pass A on a stream of
-        # their own.  One workgroup of the GEMM takes a whole CU (8 waves, 136 KB of LDS), and so does one of a sweep (one
-        # 512-register wave per SIMD): beside pass A the radiance launch's 256 workgroups take turns with the sweep's ~200 -- at
-        # 256 rays pass A lasts 122 us (195 with the background networks' launches beside it as well), pass B 226.  Merged, the
-        # sweeps run alone and the last launch grows -- A/B three times on one box: 1.215 against 1.208 ms (DTU model), 1.39
-        # against 1.363 with the background model, 2.02 / 2.01 at 512 rays: what the concurrent launch costs the sweeps is less
-        # than its own duration.  Off.
-        merge_rgb = h2 and side and not defer_wgrad and extra is None and not split and \
-            (_RGB_MERGE == "1" or (_RGB_MERGE == "auto" and n_total <= 40960))
         deferred = None
         if defer_wgrad:
             ev_rgb = torch.cuda.Event(); ev_rgb.record(main)
             deferred = dict(rgb=dict(jobs=job_list(rkey, rgb_jobs), key=rkey), ev_rgb=ev_rgb)
-            join = None
-        elif split:
-            join = None
-        elif merge_rgb:
             join = None
         else:
             fork = torch.cuda.Event(); fork.record(main)
@@ -332,18 +296,6 @@ class MlpBackward:
         _lib.check(L.svs_sdf_bwd_a(*src.args(), _ptr(d_grad), _ptr(mask), _ptr(hbuf), _ptr(gbuf), _ptr(S.sdf), prec,
                                    _ptr(self.ubuf), _ptr(self.a2buf), _ptr(self.pebuf),
                                    _ptr(acc.absmax) if h2 else None, st), "svs_sdf_bwd_a")
-        join2 = None
-        if split:
-            k2 = ("sdf2", n_total, prec, self.ubuf.data_ptr(), gbuf.data_ptr(), acc.dWk.data_ptr())
-            urec = lambda l: _off(self.ubuf, record_off(n_total, 9, l))
-            second = lambda: [job(l, n_total, 0, _off(gbuf, l * LS), KBLOCK, _off(self.ubuf, l * LS), KBLOCK,
-                                  rec0=urec(l), bias=False) for l in range(8)]
-            after_a = torch.cuda.Event(); after_a.record(main)
-            with torch.cuda.stream(side_stream):
-                side_stream.wait_event(after_a)
-                # one launch: the radiance network's five layers + the eight second-order products of the SDF network
-                wgrad_multi(job_array(rkey + k2, job_list(rkey, rgb_jobs), dict(jobs=job_list(k2, second), key=k2)))
-                join2 = torch.cuda.Event(); join2.record(side_stream)
         _lib.check(L.svs_sdf_bwd_b(n_total, _ptr(d_sdf_full), _ptr(mask), _ptr(self.feat_bar), n_main, _ptr(hbuf),
                                    _ptr(gbuf), _ptr(self.a2buf), _ptr(self.ubuf), _ptr(S.sdf), prec, _ptr(self.abuf),
                                    _ptr(self.sbar), _ptr(acc.absmax) if h2 else None, st),
@@ -351,29 +303,18 @@ class MlpBackward:
         # the first row of lin8's weight gradient: a 257-vector reduction over two blocks (0.04 ms alone).  On the side stream,
         # beside the weight-gradient launch, it was starved to the length of that launch (one workgroup of the GEMM per CU
         # leaves it a quarter of the register file): it runs in front of it on this stream
-        # (experiment, SVS_PLAN_BRANCHES=1: in a captured sequence on the radiance weight gradients' stream after all)
-        row0_aside = side and not defer_wgrad and _PLAN_BRANCHES and torch.cuda.is_current_stream_capturing()
-        if row0_aside:
-            after_b = torch.cuda.Event(); after_b.record(main)
-            with torch.cuda.stream(side_stream):
-                side_stream.wait_event(after_b)
-                _lib.check(L.svs_lin8_row0_grad(_ptr(hbuf), _ptr(self.ubuf), _ptr(self.sbar), n_total, prec, _ptr(acc.row0),
-                                                _stream()), "svs_lin8_row0_grad")
-                join = torch.cuda.Event(); join.record(side_stream)
-        else:
-            _lib.check(L.svs_lin8_row0_grad(_ptr(hbuf), _ptr(self.ubuf), _ptr(self.sbar), n_total, prec, _ptr(acc.row0),
-                                            _stream()), "svs_lin8_row0_grad")
+        _lib.check(L.svs_lin8_row0_grad(_ptr(hbuf), _ptr(self.ubuf), _ptr(self.sbar), n_total, prec, _ptr(acc.row0),
+                                        _stream()), "svs_lin8_row0_grad")
         ev = self.timer_events = ([torch.cuda.Event(enable_timing=True) for _ in range(2)] if self.time_wgrad else None)
         if ev:
             ev[0].record()
-        skey = ("sdf1" if split else "sdf", n_total, n_main, prec, self.abuf.data_ptr(), self.ubuf.data_ptr(), self.pebuf.data_ptr(),
+        skey = ("sdf", n_total, n_main, prec, self.abuf.data_ptr(), self.ubuf.data_ptr(), self.pebuf.data_ptr(),
                 hbuf.data_ptr(), gbuf.data_ptr(), self.feat_bar.data_ptr(), acc.dWk.data_ptr())
 
         def sdf_jobs():
             arec = lambda l: _off(self.abuf, record_off(n_total, 8, l))
             urec = lambda l: _off(self.ubuf, record_off(n_total, 9, l))
-            second = (lambda l: dict(a1=_off(gbuf, l * LS), sa1=KBLOCK, b1=_off(self.ubuf, l * LS), sb1=KBLOCK, rec1=urec(l))) \
-                if not split else (lambda l: {})
+            second = lambda l: dict(a1=_off(gbuf, l * LS), sa1=KBLOCK, b1=_off(self.ubuf, l * LS), sb1=KBLOCK, rec1=urec(l))
             jobs = [job(0, n_total, 0, _off(self.abuf, 0), KBLOCK, _ptr(self.pebuf), KBLOCK, rec0=arec(0), **second(0))]
             for l in range(1, 8):
                 jobs.append(job(l, n_total, 0, _off(self.abuf, l * LS), KBLOCK, _off(hbuf, (l - 1) * LS), KBLOCK, rec0=arec(l),
@@ -389,15 +330,9 @@ class MlpBackward:
             return deferred
         if extra is not None:
             main.wait_event(extra["ev_all"])
-        if merge_rgb:
-            wgrad_multi(job_array(skey + rkey, job_list(skey, sdf_jobs), dict(jobs=job_list(rkey, rgb_jobs), key=rkey)))
-            join = torch.cuda.Event(); join.record(main)
-        else:
-            wgrad_multi(job_array(skey, job_list(skey, sdf_jobs), extra["sdf"] if extra else None))
+        wgrad_multi(job_array(skey, job_list(skey, sdf_jobs), extra["sdf"] if extra else None))
         if ev:
             ev[1].record()
-        if join2 is not None and not row0_aside:
-            join = join2                      # (recorded on the same side stream, after the radiance launch's event)
         if wait and side:
             main.wait_event(join)
         self._hold = (d_grad, d_sdf_full, d_normals, d_rgb)      # keep inputs alive until the streams are joined

@@ -119,16 +119,6 @@ def allreduce_range(flat_grad, lo, hi, async_op=False):
     return dist.all_reduce(flat_grad[lo:hi], op=dist.ReduceOp.SUM, async_op=async_op)
 
 
-# Experiment, OFF by default: in captured sequences the prior look-up as a branch beside the fused SDF / radiance launches and
-# lin8's first-row gradient beside the SDF weight-gradient launch (51 us of small launches off a 256-ray step's critical
-# chain).  Measured with launch plans, A/B twice on one box: 1.315 / 1.311 against 1.319 / 1.311 ms (DTU model, 256 rays), 1.55
-# against 1.495 with the background model -- the branches' stream crossings and the fifth busy stream cost what they save.
-_PLAN_BRANCHES = os.environ.get("SVS_PLAN_BRANCHES", "0") == "1"
-_SMALL_GROUP_INLINE = os.environ.get("SVS_SMALL_GROUP_INLINE", "0") == "1"     # A/B: the small ray group's radiance weight gradients in line
-# Two ray groups: the second (small) group only runs its sweeps; its weight-gradient jobs ride along in the first group's two
-# launches (train.MlpBackward.accumulate, defer_wgrad / extra).  The small group's own launches cost a ring fill and a
-# workgroup per CU each for 5 % of the points: 0.46 + 0.2 ms of kernel time per step beside the large group's (round 4).
-_FOLD_WGRAD = os.environ.get("SVS_FOLD_WGRAD", "1") == "1"
 _DP_BUCKETS = os.environ.get("SVS_DP_BUCKETS", "1") == "1"        # A/B: 0 = one all-reduce of the whole flat gradient at the end
 
 
@@ -233,12 +223,6 @@ class _Scratch:
         self.d_beta = torch.zeros(8, device=dev)
         self.bg_bwd = BgBackward(dev) if is_bg else None
         self._bg_streams = {}
-
-    def lookup_stream(self):
-        """stream of the prior look-up when it runs as a branch of a captured sequence"""
-        if getattr(self, "_lookup", None) is None:
-            self._lookup = torch.cuda.Stream(device=self.dev)
-        return self._lookup
 
     def bg_stream(self, gi):
         """stream of ray group gi's background-network backward (runs beside the fg backward)"""
@@ -689,7 +673,11 @@ class TrainStep:
         results, joins, holds = [None] * len(groups), [], [None] * len(groups)     # (in group order whatever the enqueue order)
         # d loss / d beta of a group: one group writes it straight into the flat gradient, several into slots that are summed
         beta_out = (lambda gi: self.beta_grad.view(1)) if len(groups) == 1 else (lambda gi: sc.d_beta[gi:gi + 1])
-        fold = _FOLD_WGRAD and len(groups) == 2 and not serial
+        # Two ray groups: the second (small) group only runs its sweeps; its weight-gradient jobs ride along in the first
+        # group's two launches (train.MlpBackward.accumulate, defer_wgrad / extra).  The small group's own launches cost a ring
+        # fill and a workgroup per CU each for 5 % of the points: 0.46 + 0.2 ms of kernel time per step beside the large
+        # group's (round 4).
+        fold = len(groups) == 2 and not serial
         folded = None
         # (folded: the small group is enqueued FIRST, on its side stream, so that the events the large group's weight-gradient
         # launches wait for exist when those launches are enqueued)
@@ -707,27 +695,9 @@ class TrainStep:
                 keep = {}
                 # (a capture tolerates the background forward's side stream only below the ORIGIN stream: the note above)
                 m._side_ok_in_capture = gi == 0 and not serial
-                # (experiment, SVS_PLAN_BRANCHES=1: the prior look-up -- it needs the sample depths only -- as a branch of a
-                # captured sequence; the model calls the hook right after its sampler)
-                looked_up = {}
-                if mvs is not None and dyn is not None and m._side_ok_in_capture and _PLAN_BRANCHES:
-                    def after_sampling(cam_loc, ray_dirs, z_vals, stream=stream):
-                        ev = torch.cuda.Event(); ev.record(stream)
-                        ls = sc.lookup_stream()
-                        with torch.cuda.stream(ls):
-                            ls.wait_event(ev)
-                            looked_up["res"] = ops.cost_lookup(mvs["views"], mvs["same_view"], mvs["img_res"], cam=cam_loc,
-                                                               dirs=ray_dirs, z=z_vals,
-                                                               inverse_depth=mvs.get("inverse_depth", False),
-                                                               same_view_dev=dyn["same_view"])
-                            looked_up["join"] = torch.cuda.Event(); looked_up["join"].record(ls)
-                    inp["_after_sampling"] = after_sampling
                 out = m._forward_impl(inp, fast, keep, rng=m.slice_rng(rng, lo, hi))
                 m._side_ok_in_capture = False
-                if looked_up:
-                    stream.wait_event(looked_up["join"])
-                    out['pj'], out['pi'], _ = looked_up["res"]
-                elif mvs is not None:
+                if mvs is not None:
                     out['pj'], out['pi'], _ = ops.cost_lookup(mvs["views"], mvs["same_view"], mvs["img_res"],
                                                               cam=keep["cam_loc"], dirs=keep["ray_dirs"], z=keep["z_vals"],
                                                               inverse_depth=mvs.get("inverse_depth", False),
@@ -780,7 +750,7 @@ class TrainStep:
                     folded = sc.bwd[gi].accumulate(keep, d_rgb, d_sdf, g["grad_theta"], wait=False, side=False, defer_wgrad=True)
                 else:
                     joins.append(sc.bwd[gi].accumulate(keep, d_rgb, d_sdf, g["grad_theta"], wait=False,
-                                                       side=not serial and not (gi and _SMALL_GROUP_INLINE),
+                                                       side=not serial,
                                                        extra=folded if (fold and gi == 0) else None))
                 results[gi] = (lo_out, out)
                 holds[gi] = (keep, g, d_sdf, d_rgb, inp, g_gt, folded)

@@ -188,9 +188,6 @@ class VolSDFNetworkBG(nn.Module):
         z_bg, bg_pts, bg_depth = self.ray_sampler._bg_last
         z_vals, z_max = ops.split_last(z_all)
         S, Nb = z_vals.shape[1], z_bg.shape[1]
-        hook = input.get("_after_sampling")          # (trainer: work that depends on the sample depths only)
-        if hook is not None:
-            hook(cam_loc, ray_dirs, z_vals)
         n_main = R * S
         eikonal_points = None
         if self.training:

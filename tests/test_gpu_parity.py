@@ -202,38 +202,6 @@ def test_sdf_mlp_ragged(dev, ops, packed, P):
     np.testing.assert_allclose(grad.cpu().numpy(), g_ref, atol=2e-4, rtol=1e-4)
 
 
-@pytest.mark.parametrize("kernel", ["16", "pair"])
-def test_sdf_vals_two_wave_variants(dev, ops, kernel):
-    """The two experimental two-waves-per-SIMD sdf-only kernels (SVS_SDF_KERNEL=16 / pair) against the oracle and against the
-    default kernel: ragged sizes, ray mode with the sphere clamp, and a gated launch.  (Opt-in build: SVS_BUILD_EXPERIMENTS=1.)"""
-    from svs_hip import lib
-    if not hasattr(lib.load(), "svs_sdf_vals_pair"):
-        pytest.skip("library built without the experimental kernels (SVS_BUILD_EXPERIMENTS=1 python s-volsdf_amd/build.py --force)")
-    params = synth.make_params(0)
-    layers = orc.effective_weights(params, "implicit_network", 9)
-    v, g, b = ([params[f"implicit_network.lin{l}.{n}"] for l in range(9)] for n in ("weight_v", "weight_g", "bias"))
-    pk0, pk1 = ops.PackedMlp(dev), ops.PackedMlp(dev, sdf_kernel=kernel)
-    for pk in (pk0, pk1):
-        pk.pack_sdf([G(t, dev) for t in v], [G(t, dev) for t in g], [G(t, dev) for t in b])
-    for P in (1, 31, 128, 1000, 4099):
-        x = np.random.default_rng(P).uniform(-2.5, 2.5, (P, 3)).astype(F32)
-        src = ops.PointSource(points=G(x, dev))
-        got = ops.sdf_vals(pk1, src, 3.0, 20.0).cpu().numpy()
-        np.testing.assert_allclose(got, orc.sdf_vals(layers, x), atol=1e-4)
-        np.testing.assert_allclose(got, ops.sdf_vals(pk0, src, 3.0, 20.0).cpu().numpy(), atol=5e-6)
-    K, pose = synth.make_camera()
-    dirs, cam, _ = orc.rays_from_uv(synth.make_uv(256, seed=5), pose, K)
-    z = np.sort(np.random.default_rng(1).uniform(0.5, 5.0, (256, 128)), -1).astype(F32)
-    src = ops.PointSource(cam=G(cam, dev), dirs=G(dirs, dev), z=G(z, dev))
-    a, c = ops.sdf_vals(pk1, src, 3.0, 20.0), ops.sdf_vals(pk0, src, 3.0, 20.0)
-    np.testing.assert_allclose(a.cpu().numpy(), c.cpu().numpy(), atol=5e-6)
-    # gate: two groups of 128 rays, the second switched off -> its outputs stay untouched
-    flags = torch.tensor([1, 0], dtype=torch.int32, device=dev)
-    out = torch.full((256 * 128, 1), -7.0, device=dev)
-    ops.sdf_vals(pk1, src, 3.0, 20.0, out=out, gate=flags.data_ptr(), gate_points=128 * 128, gate_stride=1)
-    assert torch.equal(out[:128 * 128], a[:128 * 128]) and bool((out[128 * 128:] == -7.0).all())
-
-
 def test_sdf_ray_mode(dev, ops, packed):
     pk, params = packed
     layers = orc.effective_weights(params, "implicit_network", 9)

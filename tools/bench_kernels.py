@@ -1,6 +1,5 @@
 """Per-kernel timings at bench sizes (1024 rays): isolates each hot kernel with events on the launch stream.
-Development aid for the roofline work; prints one JSON object.  BK_RAYS=<n>: another batch size (default 1024); BK_STAMPS=1 with a
--DSVS_ABL=65536 build of svs_mlp_bwd_h2.hip (tools/dev/ab_defs.sh + SVS_LIB_PATH): pass B's per-tile cycle stamps and clock."""
+Development aid for the roofline work; prints one JSON object.  BK_RAYS=<n>: another batch size (default 1024)."""
 import ctypes
 import json
 import os
@@ -9,7 +8,6 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (os.path.join(ROOT, "tests", "golden"), os.path.join(ROOT, "s-volsdf_amd")):
     sys.path.insert(0, p)
-import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import synth  # noqa: E402
 from volsdf.utils.conf import dtu_model_conf  # noqa: E402
@@ -95,14 +93,6 @@ def main():
     t = timeit(lambda: lib.check(L.svs_sdf_bwd_b(n_total, P(dsf), P(mask), P(bw.feat_bar), n_main, P(hbuf), P(gbuf), P(bw.a2buf), P(bw.ubuf),
                                                  P(bw.streams.sdf), prec, P(bw.abuf), P(bw.sbar), N(am), st())))
     res["sdf_bwd_b"] = dict(ms=t, tflops=n_total * F_SDF / t / 1e9)
-    if os.environ.get("BK_STAMPS"):      # a -DSVS_ABL=65536 build: cycle stamps of wave 0 of every workgroup in sbar_out
-        torch.cuda.synchronize()
-        o = bw.sbar[: (n_total // 128) * 128].reshape(-1, 128)[:, :19].double().cpu().numpy()
-        np.set_printoptions(linewidth=200, suppress=True)
-        print("workgroups", o.shape[0], "shader MHz during the kernel %.0f" % (o[:, 17] / o[:, 18] * 100).mean(), file=sys.stderr)
-        print("per tile index, cycles summed over 8 stages: MFMA part", o[:, :8].mean(0).round(0), file=sys.stderr)
-        print("                                    wait + barrier part", o[:, 8:16].mean(0).round(0), file=sys.stderr)
-        print("last epilogues %.0f  total %.0f  (sum of parts %.0f)" % (o[:, 16].mean(), o[:, 17].mean(), o[:, :17].sum(1).mean()), file=sys.stderr)
     from svs_hip.train import block_stride, record_off
     LS = block_stride(n_total)
     R = lambda buf, n, nb, l: _off(buf, record_off(n, nb, l)) if h2 else None
