@@ -1,6 +1,6 @@
 """Benchmark of the S-VolSDF volume-rendering hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
 
@@ -17,6 +17,11 @@ Timed region: W warm-up steps (with --graph the step's launch sequence is captur
 steps until `--settle` seconds of steady state have passed (clocks, allocator), then barrier + synchronize, EXACTLY K
 steps, synchronize + barrier; the maximum over ranks is reported.
 
+A plain run does only that, writes --dump-outputs and prints the line: `value` and `ms_per_step`, with
+`host_enqueue_ms_per_step` and `roofline` null.  `--full` adds the secondary measurements below, all run after the timed
+region: the host's enqueue time, `roofline`, `cpu_baseline`, `gpu_torch_baseline`, `costvol` / `render_eval` and, with
+N > 1, `other_scaling`.
+
 Rank 0 prints ONE compact JSON line LAST (<= 6 KB: `compact_line`, self-tested by `check_line`); the full record -- every
 roofline row, the baselines' details, the secondary measurements -- goes to `bench_extras.json` next to this script (and to
 gpurun_out/ when that directory exists).  `roofline` prices the kernel with the largest time per step; the per-launch
@@ -25,7 +30,7 @@ region in the same process -- an event pair per launch would perturb the timed r
 be bracketed at all; the line carries that row and the five largest.  `cpu_baseline` times the CPU port on a bounded sample of
 the same workload; `gpu_torch_baseline` the reference's step -- the sampler under no_grad, then plain PyTorch float32 autograd
 + clip + Adam -- on the same GPU.  Opt-in extras (never part of the default command): --other-precisions, --inline-ab,
---volopt-loop, --config4, --chamfer, --all-extras.
+--volopt-loop, --config4, --chamfer, --all-extras; each implies --full.
 
 Precision.  The default (SVS_MLP_PRECISION=f16x2) evaluates every layer product, forward AND backward, as three fp16 MFMA
 products of two-piece operands with float32 accumulation, and every activation block kept for the backward holds both pieces:
@@ -79,15 +84,7 @@ def block_bytes():
     return train.algorithmic_bytes_per_point()
 
 
-def main():
-    if len(sys.argv) == 3 and sys.argv[1] == "--volopt-child":
-        rays, warm, steps, variants = sys.argv[2].split(":")[:4]
-        model = (sys.argv[2].split(":") + ["dtu"])[4]
-        print(json.dumps(_volopt_loop(int(rays), int(warm), int(steps), tuple(variants.split(",")), model=model)))
-        return
-    if len(sys.argv) == 3 and sys.argv[1] == "--allreduce-child":
-        print(json.dumps(_allreduce_one_rank(int(sys.argv[2]))))
-        return
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
@@ -109,6 +106,11 @@ def main():
                          "captured sequence enqueued as plain launches by one library call (svs_plan_run); auto (default, also "
                          "VolOpt's): plan for batches of less than two rounds of workgroups (< 656 rays per GPU of the DTU model, "
                          "one or two ray groups: the host-bound sizes), eager otherwise; on / linear: hipGraphLaunch of the capture (with its stream topology / as one chain)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the secondary measurements: the host's enqueue time, the per-kernel "
+                         "roofline, the CPU and PyTorch-eager baselines, the cost-volume / eval-render extras and, with N > 1, "
+                         "the other scaling mode (each can be skipped by its --no-* option below).  Without it a run does only "
+                         "what `value` and `ms_per_step` need.  Every opt-in extra implies --full")
     ap.add_argument("--no-kernel-timing", action="store_true", help="skip the per-kernel event timing (roofline = null)")
     ap.add_argument("--no-host-timing", action="store_true",
                     help="skip the 18 extra steps that time the host's enqueueing (`host_enqueue_ms_per_step`): counter passes "
@@ -142,11 +144,30 @@ def main():
     ap.add_argument("--extras-file", default=None,
                     help="where the full record goes (default: gpurun_out/bench_extras.json when that directory exists, and "
                          "bench_extras.json next to this script)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
     if args.all_extras:
         args.other_precisions = args.inline_ab = args.volopt_loop = args.config4 = args.chamfer = True
+    # a plain run measures the headline alone (set-up, warm-up, settle, timed steps, --dump-outputs): the measurements after
+    # the timed region are --full's, and every opt-in extra runs on top of them
+    args.full = args.full or args.other_precisions or args.inline_ab or args.volopt_loop or args.config4 or args.chamfer
+    if not args.full:
+        args.no_host_timing = args.no_kernel_timing = args.no_cpu_baseline = args.no_gpu_torch = args.no_extras = True
+        args.no_other_scaling = True
+    return args
+
+
+def main():
+    if len(sys.argv) == 3 and sys.argv[1] == "--volopt-child":
+        rays, warm, steps, variants = sys.argv[2].split(":")[:4]
+        model = (sys.argv[2].split(":") + ["dtu"])[4]
+        print(json.dumps(_volopt_loop(int(rays), int(warm), int(steps), tuple(variants.split(",")), model=model)))
+        return
+    if len(sys.argv) == 3 and sys.argv[1] == "--allreduce-child":
+        print(json.dumps(_allreduce_one_rank(int(sys.argv[2]))))
+        return
+    args = parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # started as a plain `python bench.py --gpus N`: this process has not touched a GPU; it starts the N ranks as

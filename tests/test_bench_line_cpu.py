@@ -88,3 +88,22 @@ def test_check_line_rejects_nan():
     b = _bench()
     with pytest.raises(ValueError):
         b.check_line('{"metric": "m", "value": NaN, "roofline": null}')
+
+
+SECONDARY = ("no_host_timing", "no_kernel_timing", "no_cpu_baseline", "no_gpu_torch", "no_extras", "no_other_scaling")
+
+
+def test_plain_run_measures_the_headline_alone():
+    """without --full a run skips every measurement after the timed region; --full runs them unless a --no-* option skips
+    one, and every opt-in extra implies --full"""
+    b = _bench()
+    plain = b.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert not plain.full and all(getattr(plain, k) for k in SECONDARY)
+    assert not any((plain.other_precisions, plain.inline_ab, plain.volopt_loop, plain.config4, plain.chamfer))
+    full = b.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full"])
+    assert full.full and not any(getattr(full, k) for k in SECONDARY)
+    some = b.parse_args(["--full", "--no-cpu-baseline", "--no-kernel-timing"])
+    assert [getattr(some, k) for k in SECONDARY] == [False, True, True, False, False, False]
+    for extra in ("--other-precisions", "--inline-ab", "--volopt-loop", "--config4", "--chamfer", "--all-extras"):
+        a = b.parse_args([extra])
+        assert a.full and not any(getattr(a, k) for k in SECONDARY), extra

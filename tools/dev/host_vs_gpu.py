@@ -11,7 +11,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 CASES = sys.argv[1:] or ["--rays 256", "--rays 256 --model bmvs", "--rays 128", "--rays 128 --model bmvs", "--rays 1024",
                          "--rays 2048 --model bmvs"]
-BASE = [sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-exact-f32", "--no-gpu-torch",
+BASE = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--no-exact-f32", "--no-gpu-torch",
         "--no-kernel-timing", "--no-volopt-loop", "--no-extras", "--steps", "100"]
 for case in CASES:
     for g in os.environ.get("MODES", "off plan").split():

@@ -4,7 +4,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/plan_trace
 rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-B="python3 $R/bench.py --no-cpu-baseline --no-exact-f32 --no-gpu-torch --no-volopt-loop --no-extras --no-kernel-timing --steps 50 --warmup 10 ${ARGS}"
+B="python3 $R/bench.py --full --no-cpu-baseline --no-exact-f32 --no-gpu-torch --no-volopt-loop --no-extras --no-kernel-timing --steps 50 --warmup 10 ${ARGS}"
 timeout 300 rocprofv3 --kernel-trace --stats -d $O/eager --output-format csv -- $B --graph off > $O/eager.log 2>&1
 timeout 300 rocprofv3 --kernel-trace --stats -d $O/plan --output-format csv -- $B --graph plan > $O/plan.log 2>&1
 cd $R
