@@ -62,10 +62,21 @@ def rgb_mlp(p, x, n, d, feat):
     return torch.sigmoid(h)
 
 
-def composite(z, sdf, rgb, beta_param, ds, beta_min=1e-4):
+def laplace_density(sdf, beta, stable=False):
+    """density.py:21-26.  stable: the same function as 0.5 exp(-s / beta) / beta for s > 0 and (1 - 0.5 exp(s / beta)) /
+    beta otherwise, without the cancellation of 0.5 + 0.5 * expm1(-s / beta) (whose absolute floor, eps / beta, the last
+    interval of 1e10 turns into a visible error of the float64 gradients once sdf / beta exceeds ~20).  Its gradient w.r.t.
+    sdf at sdf = 0 is 0, as sign(0) = 0 gives the reference's."""
+    if not stable:
+        return (1 / beta) * (0.5 + 0.5 * sdf.sign() * torch.expm1(-sdf.abs() / beta))
+    e = torch.exp(-sdf.abs() / beta)
+    return torch.where(sdf > 0, 0.5 * e, torch.where(sdf < 0, 1 - 0.5 * e, 0.5 + 0 * e)) / beta
+
+
+def composite(z, sdf, rgb, beta_param, ds, beta_min=1e-4, stable=False):
     """network.py:281-295 + :237-243 -> weights, rgb_values, depth_values"""
     beta = beta_param.abs() + beta_min
-    sigma = (1 / beta) * (0.5 + 0.5 * sdf.sign() * torch.expm1(-sdf.abs() / beta))
+    sigma = laplace_density(sdf, beta, stable)
     dists = torch.cat([z[:, 1:] - z[:, :-1], torch.full_like(z[:, :1], 1e10)], -1)
     fe = dists * sigma
     sfe = torch.cat([torch.zeros_like(fe[:, :1]), fe[:, :-1]], -1)
@@ -76,26 +87,38 @@ def composite(z, sdf, rgb, beta_param, ds, beta_min=1e-4):
 
 
 def loss_fn(out, rgb, rgb_smooth, it, *, eikonal_weight=0.1, rgb_weight=1.0, mvs_weight=1.0, sparse_weight=1.0,
-            gce=0.5, confi=1e-3, anneal_rgb=200, norm=None):
-    """VolSDFLoss.forward (loss.py:80-114) -> total.  norm = (n_rays, n_eik): denominators of the means when `out` holds
-    only a shard of a larger batch (the shards' totals then add up to the batch's total); None: the sizes of `out`."""
-    n_rays, n_eik = norm if norm is not None else (out["rgb_values"].shape[0], out["grad_theta"].shape[0])
+            gce=0.5, confi=1e-3, anneal_rgb=200, norm=None, terms=False):
+    """VolSDFLoss.forward (loss.py:80-114) -> total, or (terms=True) the dict of its five outputs rgb_loss, eikonal_loss,
+    mvs_loss, sparse_loss, loss.  norm = (n_rays, n_eik): denominators of the means when `out` holds only a shard of a
+    larger batch (the shards' totals then add up to the batch's total); None: the sizes of `out`.  Without "grad_theta"
+    the eikonal term is 0, without "pi" the MVS and sparsity terms are (the reference rejects the annealed phase then)."""
+    n_eik_out = out["grad_theta"].shape[0] if "grad_theta" in out else 0
+    n_rays, n_eik = norm if norm is not None else (out["rgb_values"].shape[0], n_eik_out)
     over_rays = lambda per_ray: per_ray.sum() / n_rays
+    zero = out["rgb_values"].new_zeros(())
     rgb_loss = over_rays((out["rgb_values"] - rgb).abs().mean(-1))
-    eik = ((out["grad_theta"].norm(2, dim=1) - 1) ** 2).sum() / n_eik
-    total = eikonal_weight * eik
+    eik = ((out["grad_theta"].norm(2, dim=1) - 1) ** 2).sum() / n_eik if n_eik_out else zero
+    mvs, sparse, anneal = zero, zero, 0.0
     on = sparse_weight > 0 and anneal_rgb > 0 and it < anneal_rgb
     if "pi" in out:
         pw = out["pi"] * out["pj"]
-        w = out["weights"]
-        l = (-pw * w.detach() ** gce * torch.log(w + 1e-8)).sum(1)
-        total = total + mvs_weight * over_rays(1. * (pw.sum(1) > confi) * l)
+        if mvs_weight > 0:
+            w = out["weights"]
+            # loss.py:60-65: gce == 1 is the plain weighted sum, not the gce -> 1 limit of the general form
+            l = (-pw * w).sum(1) if gce == 1 else (-pw * w.detach() ** gce * torch.log(w + 1e-8)).sum(1)
+            mvs = over_rays(1. * (pw.sum(1) > confi) * l)
         if on:
             conf = pw.sum(-1)
-            sparse = over_rays((1. / (out["depth_values"].squeeze() + 1e-3)) * (conf < confi))
-            total = total + sparse_weight * (1.0 - it / anneal_rgb) * sparse
+            sparse = over_rays((1. / (out["depth_values"].reshape(-1) + 1e-3)) * (conf < confi))
+            anneal = 1.0 - it / anneal_rgb
             rgb_loss = over_rays((out["rgb_values"] - rgb_smooth).abs().mean(-1) * (conf < 1e-8))
-    return total + rgb_weight * rgb_loss
+    total = eikonal_weight * eik
+    total = total + mvs_weight * mvs
+    total = total + sparse_weight * anneal * sparse
+    total = total + rgb_weight * rgb_loss
+    if terms:
+        return dict(rgb_loss=rgb_loss, eikonal_loss=eik, mvs_loss=mvs, sparse_loss=sparse, loss=total)
+    return total
 
 
 def forward_differentiable(p, cam, dirs, z, eik_points, depth_scale, radius=3.0, scale=20.0, device=None):
@@ -138,11 +161,11 @@ def bg_rgb_mlp(p, d, feat):
     return torch.sigmoid(h @ p["bg_rendering_network.lin1.weight"].T + p["bg_rendering_network.lin1.bias"])
 
 
-def composite_bg(z, z_max, sdf, rgb, beta_param, ds, z_bg, bg_out0, bg_rgb, beta_min=1e-4, bg_depth=None):
+def composite_bg(z, z_max, sdf, rgb, beta_param, ds, z_bg, bg_out0, bg_rgb, beta_min=1e-4, bg_depth=None, stable=False):
     """network_bg.py:76-125,147-180 -> weights, bg_transmittance, rgb_values, depth_values[, depth_values_all when the
-    background samples' conventional depths bg_depth (R,Nb) are given: network_bg.py:105-107]"""
+    background samples' conventional depths bg_depth (R,Nb) are given: network_bg.py:105-107].  stable: laplace_density"""
     beta = beta_param.abs() + beta_min
-    sigma = (1 / beta) * (0.5 + 0.5 * sdf.sign() * torch.expm1(-sdf.abs() / beta))
+    sigma = laplace_density(sdf, beta, stable)
     dists = torch.cat([z[:, 1:] - z[:, :-1], z_max.unsqueeze(-1) - z[:, -1:]], -1)
     fe = dists * sigma
     sfe = torch.cat([torch.zeros_like(fe[:, :1]), fe], -1)

@@ -114,6 +114,9 @@ int svs_clip_guard_adam(float* params, float* grads, float* exp_avg, float* exp_
   if (!params || !grads || !exp_avg || !exp_avg_sq || !workspace || n <= 0 || (!step_counter && step < 1)) {
     set_error("svs_clip_guard_adam: bad argument"); return SVS_EINVAL;
   }
+  // every check before the first launch: a rejected call must leave step_counter and the workspace untouched
+  const bool aligned = (((uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) == 0;
+  if (!aligned) { set_error("svs_clip_guard_adam: the four buffers must be 16-byte aligned"); return SVS_EINVAL; }
   double* part = (double*)workspace;
   int* bad = (int*)(part + kBlocks);
   hipStream_t s = (hipStream_t)hip_stream;
@@ -121,8 +124,6 @@ int svs_clip_guard_adam(float* params, float* grads, float* exp_avg, float* exp_
   AdamScalars sc;
   sc.max_norm = (float)max_norm; sc.beta1 = (float)beta1; sc.omb1 = (float)(1.0 - beta1); sc.beta2 = (float)beta2;
   sc.omb2 = (float)(1.0 - beta2); sc.eps = (float)eps; sc.lr = lr; sc.beta1_d = beta1; sc.beta2_d = beta2;
-  const bool aligned = (((uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) == 0;
-  if (!aligned) { set_error("svs_clip_guard_adam: the four buffers must be 16-byte aligned"); return SVS_EINVAL; }
   long long blocks = ((n >> 2) + 255) / 256;
   blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
   adam_kernel<<<(int)blocks, 256, 0, s>>>(params, grads, exp_avg, exp_avg_sq, n, part, bad, kBlocks, sc, step, step_counter, info);

@@ -125,9 +125,27 @@ __device__ __forceinline__ double wave_cumsum_incl(const double* in, double* out
   }
   double acc = scan - tot;
   for (int j = lo; j < hi; ++j) { acc += in[j]; out[j] = acc; }
-  // the total is returned as the very value stored in out[m - 1]: callers form suffix sums as total - out[i], which must be
-  // exactly zero for the last element (its free energy carries dist = 1e10)
   return __shfl(acc, (m - 1) / c);
+}
+// out[j] = sum_{i > j} in[i] (in place allowed), summed from the top down.  Not total - prefix: that difference carries
+// eps times the whole ray's sum, which swamps a suffix behind an opaque surface at beta_min (test_composite_backward_edges
+// [1e-12-2] and test_composite_bg_backward_edges[0.0-2]: d_sdf 5.6x and 2.1x its largest value off).  The last element's
+// suffix is exactly 0 (its interval is 1e10).
+__device__ __forceinline__ void wave_suffix_excl(const double* in, double* out, int m, int lane) {
+  const int c = (m + 63) >> 6;
+  const int lo = lane * c;
+  const int hi = (lo + c < m) ? lo + c : m;
+  double tot = 0.0;
+  for (int j = hi - 1; j >= lo; --j) tot += in[j];
+  double scan = tot;                    // -> sum of the chunks of lanes >= lane
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const double o = __shfl_down(scan, d);
+    if (lane + d < 64) scan += o;
+  }
+  double acc = __shfl_down(scan, 1);    // the chunks of lanes > lane
+  if (lane == 63) acc = 0.0;
+  for (int j = hi - 1; j >= lo; --j) { const double v = in[j]; out[j] = acc; acc += v; }
 }
 // Laplace density and its derivatives in double (density.py:21-30)
 struct DensityD {
@@ -136,7 +154,10 @@ struct DensityD {
     const double as = s < 0.0 ? -s : s;
     const double e = dexp(-as / beta);
     const double sgn = s > 0.0 ? 1.0 : (s < 0.0 ? -1.0 : 0.0);
-    sigma = (1.0 / beta) * (0.5 + 0.5 * sgn * (e - 1.0));
+    // 0.5 + 0.5 * sgn * (e - 1) without its cancellation: formed as written, sigma for sdf / beta > 20 kept only
+    // 1e-16 / e of its relative accuracy, which the last interval (1e10) carries into d_sdf and d beta
+    // (test_composite_backward_edges[0.02-2/63/64/98/256]: d_sdf up to 130x its largest value off, d beta 4x its bound)
+    sigma = (1.0 / beta) * (s > 0.0 ? 0.5 * e : 1.0 - 0.5 * e);
     // sign(0) = 0 in the reference's density: its gradient w.r.t. sdf vanishes there as well
     dsig_dsdf = s != 0.0 ? -0.5 * e / (beta * beta) : 0.0;
     dsig_dbeta = -sigma / beta + 0.5 * sgn * e * as / (beta * beta * beta);
@@ -258,12 +279,12 @@ __global__ __launch_bounds__(64) void composite_bwd_kernel(CompositeBwdArgs a) {
     pre[i] = d * w;                     // summand of the suffix sums
   }
   __syncthreads();
-  const double tot = wave_cumsum_incl(pre, pre, S, lane);   // inclusive prefix of dw_i * w_i
+  wave_suffix_excl(pre, pre, S, lane);
   __syncthreads();
   double dbeta = 0.0;
   for (int i = lane; i < S; i += 64) {
     const size_t p = (size_t)r * S + i;
-    const double suffix = tot - pre[i];                          // sum_{j>i} dw_j w_j
+    const double suffix = pre[i];                                // sum_{j>i} dw_j w_j
     const double dfe = dw[i] * tr[i] * dexp(-fe[i]) - suffix;
     const double dist = i < S - 1 ? (double)(float)(zs[i + 1] - zs[i]) : 1e10;
     const double dsig = dfe * dist;
@@ -783,14 +804,14 @@ __global__ __launch_bounds__(64) void composite_bg_bwd_kernel(CompositeBgBwdArgs
     pre[i] = d * w;
   }
   __syncthreads();
-  const double tot = wave_cumsum_incl(pre, pre, S, lane);
+  wave_suffix_excl(pre, pre, S, lane);
   __syncthreads();
-  const double btot = wave_cumsum_incl(bpre, bpre, Nb, lane);
+  wave_suffix_excl(bpre, bpre, Nb, lane);
   __syncthreads();
   double dbeta = 0.0;
   for (int i = lane; i < S; i += 64) {
     const size_t p = (size_t)r * S + i;
-    const double suffix = tot - pre[i];
+    const double suffix = pre[i];
     // every free energy also attenuates the background term: d (tbg * B) / d fe_i = -tbg * B
     const double dfe = (dw[i] * tr[i] * dexp(-fe[i]) - suffix) - tbg * bdot;
     const double dsig = dfe * fg_dist(i);
@@ -800,7 +821,7 @@ __global__ __launch_bounds__(64) void composite_bg_bwd_kernel(CompositeBgBwdArgs
   }
   for (int i = lane; i < Nb; i += 64) {
     const size_t p = (size_t)r * Nb + i;
-    const double suffix = btot - bpre[i];
+    const double suffix = bpre[i];
     const double dfe = bdw[i] * btr[i] * dexp(-bfe[i]) - suffix;
     const float o = a.bg_out0[p];
     const double sg = o > 0.0f ? 1.0 : (o < 0.0f ? -1.0 : 0.0);

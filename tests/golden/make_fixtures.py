@@ -592,6 +592,65 @@ def fx_loss():
     save("loss", **arr)
 
 
+# shapes (R, S, n_eik; 0 = no grad_theta) and settings (gce, mvs_weight, pi/pj given, iter_step, sparse_weight) of
+# fx_loss_grid; anneal_rgb = 200, confi = 1e-3.  The annealed phase without pi is left out: the reference raises there.
+LOSS_GRID_SHAPES = [(1, 1, 0), (7, 63, 7), (33, 64, 65), (130, 65, 128), (64, 256, 128)]
+LOSS_GRID_SETTINGS = [(0.5, 1.0, 1, 50, 1.0), (0.0, 1.0, 1, 250, 1.0), (1.0, 1.0, 1, 50, 1.0), (0.5, 0.0, 1, 50, 1.0),
+                      (0.0, 1.0, 1, 50, 0.0), (1.0, 1.0, 0, 250, 1.0), (0.5, 1.0, 0, 50, 0.0)]
+LOSS_GRID_CASES = [(k, j) for k in range(5) for j in (range(7) if k < 3 else (0, 1, 5))]
+
+
+def fx_loss_grid():
+    """VolSDFLoss in float64 with autograd over LOSS_GRID_CASES: the five loss terms and the gradients w.r.t. rgb_values,
+    grad_theta, weights and depth_values.  Per shape one input set: rays cycle through sum(pi * pj) < 1e-8, in
+    (1e-8, confi) and > confi (each at least 1e-6 relative from a threshold), some weights are exactly 0, one grad_theta row
+    is 0 and one has norm exactly 1."""
+    from volsdf.model.loss import VolSDFLoss
+    rng = np.random.default_rng(47)
+    confi = 1e-3
+    arr = dict(shapes=np.asarray(LOSS_GRID_SHAPES, np.int64), settings=np.asarray(LOSS_GRID_SETTINGS, np.float64),
+               cases=np.asarray(LOSS_GRID_CASES, np.int64), confi=np.float64(confi), anneal_rgb=np.int64(200))
+    for k, (R, S, n_eik) in enumerate(LOSS_GRID_SHAPES):
+        w = (rng.uniform(0, 1, (R, S)) ** 4).astype(F32)
+        w[rng.uniform(0, 1, (R, S)) < 0.1] = 0.0
+        pi = (rng.uniform(0, 0.2, (R, S)) ** 2).astype(F32)
+        pj = (rng.uniform(0, 0.3, (R, S)) ** 2).astype(F32) + F32(1e-3)
+        target = np.array([3e-9, 2e-5, 5e-2])[(np.arange(R) + 2) % 3]
+        pi = (pi * (target / (pi.astype(np.float64) * pj).sum(1))[:, None]).astype(F32)
+        if R > 3:
+            pi[3] = 0.0
+        conf = (pi.astype(np.float64) * pj).sum(1)
+        for t in (1e-8, confi):
+            assert (np.abs(conf - t) > 1e-6 * t).all()
+        inp = dict(rgb_values=rng.uniform(0, 1, (R, 3)).astype(F32), weights=w, pi=pi, pj=pj,
+                   depth_values=rng.uniform(0.5, 4, (R, 1)).astype(F32), rgb=rng.uniform(0, 1, (1, R, 3)).astype(F32),
+                   rgb_smooth=rng.uniform(0, 1, (1, R, 3)).astype(F32))
+        if n_eik:
+            gt = rng.normal(0, 1, (n_eik, 3)).astype(F32)
+            gt[0] = 0.0
+            gt[1] = (0.0, -1.0, 0.0)
+            inp["grad_theta"] = gt
+        arr.update({f"s{k}_{n}": v for n, v in inp.items()})
+    for c, (k, j) in enumerate(LOSS_GRID_CASES):
+        gce, mvs_w, has_pi, it, sp_w = LOSS_GRID_SETTINGS[j]
+        loss = VolSDFLoss(rgb_loss="torch.nn.L1Loss", eikonal_weight=0.1, rgb_weight=1.0, mvs_weight=mvs_w,
+                          sparse_weight=sp_w, anneal_rgb=200, gce=gce, confi=confi)
+        loss.iter_step = it
+        names = ["rgb_values", "weights", "depth_values"] + (["grad_theta"] if f"s{k}_grad_theta" in arr else [])
+        out = {n: torch.tensor(arr[f"s{k}_{n}"], dtype=torch.float64, requires_grad=True) for n in names}
+        if has_pi:
+            out.update({n: torch.tensor(arr[f"s{k}_{n}"], dtype=torch.float64) for n in ("pi", "pj")})
+        gt = {n: torch.tensor(arr[f"s{k}_{n}"], dtype=torch.float64) for n in ("rgb", "rgb_smooth")}
+        res = loss(out, gt)
+        res["loss"].backward()
+        for n, v in res.items():
+            arr[f"c{c}_{n}"] = np.float64(v.item())
+        for n in names:
+            g = out[n].grad
+            arr[f"c{c}_d_{n}"] = g.numpy() if g is not None else np.zeros(out[n].shape)
+    save("loss_grid", **arr)
+
+
 def _load_costreg(model, stage, params):
     sd = {k: T(v) for k, v in params.items()}
     model.cost_regularization[stage].load_state_dict(sd, strict=True)
@@ -1063,7 +1122,7 @@ def fx_featurenet():
 
 
 ALL = dict(fusion=fx_fusion, filter_depth=fx_filter_depth, pfm=fx_pfm, chamfer=fx_chamfer, chamfer_mesh=fx_chamfer_mesh, featurenet=fx_featurenet, rays=fx_rays, sdf_mlp=fx_sdf_mlp, rgb_mlp=fx_rgb_mlp, density=fx_density, sampler=fx_sampler,
-           composite=fx_composite, forward=fx_forward, forward_bg=fx_forward_bg, cost_mapping=fx_cost_mapping, cost_mapping_sgemm_nofma=fx_cost_mapping_sgemm_nofma, loss=fx_loss, casmvs=fx_casmvs, train_step=fx_train_step, train_step_r32=lambda: fx_train_step(32, 2, "train_step_r32"),
+           composite=fx_composite, forward=fx_forward, forward_bg=fx_forward_bg, cost_mapping=fx_cost_mapping, cost_mapping_sgemm_nofma=fx_cost_mapping_sgemm_nofma, loss=fx_loss, loss_grid=fx_loss_grid, casmvs=fx_casmvs, train_step=fx_train_step, train_step_r32=lambda: fx_train_step(32, 2, "train_step_r32"),
            sdf_mlp_w1=lambda: fx_sdf_mlp("w1"), forward_w1=fx_forward_w1,
            train_step_w1=lambda: fx_train_step(16, 2, "train_step_w1", "w1"),
            train_step_bg=fx_train_step_bg,

@@ -240,3 +240,148 @@ def test_mlp_backward_vs_autograd(dev, ops, precision):
             worst = max(worst, e)
             assert e < bound, (f"implicit lin{l}.{name}", e)
     print(precision, "worst relative gradient error", worst)
+
+
+# ------------------------------------------------------------------------------------------------------
+# compositing backward down to beta = beta_min, at odd sample counts and degenerate scenes
+# ------------------------------------------------------------------------------------------------------
+def edge_scene(R, S, seed, beta_param, beta_min=1e-4):
+    """Rays cycling through five kinds: 0 an opaque surface (sdf from +0.5 to -0.5 within three samples: transmittance
+    underflows behind it at small beta), 1 never reaching a surface, 2 smooth with entries of sdf exactly 0, 3 duplicate z
+    values (zero-length intervals), 4 sdf through +-5 beta along the ray (where the 1 / beta^2 and 1 / beta^3 factors of
+    the gradients are largest)."""
+    rs = np.random.default_rng(seed)
+    z = np.sort(rs.uniform(0.5, 5.5, (R, S)), -1)
+    sdf = np.empty((R, S))
+    beta = abs(beta_param) + beta_min
+    for r in range(R):
+        kind = r % 5
+        if kind == 0:
+            c = rs.integers(0, S)
+            sdf[r] = np.clip(0.5 - (np.arange(S) - c) / 3.0, -0.5, 0.5) + rs.normal(0, 1e-3, S)
+        elif kind == 1:
+            sdf[r] = rs.uniform(0.3, 1.0, S)
+        elif kind == 4:
+            sdf[r] = beta * np.linspace(5.0, -5.0, S)
+        else:
+            sdf[r] = rs.normal(0.2, 0.4, S) - np.linspace(0, 0.8, S)
+            if kind == 2:
+                sdf[r, rs.uniform(0, 1, S) < 0.25] = 0.0
+            elif S > 1:
+                dup = rs.uniform(0, 1, S - 1) < 0.3
+                z[r, 1:][dup] = z[r, :-1][dup]
+                z[r] = np.maximum.accumulate(z[r])
+    return (z.astype(F32), sdf.astype(F32), rs.uniform(0, 1, (R, S, 3)).astype(F32), rs.uniform(0.8, 1.0, (R, 1)).astype(F32))
+
+
+def beta_condition(make_loss, beta_param, shape):
+    """d loss / d beta_param as the sum of its per-sample summands (float64 autograd with one beta per sample): returns
+    the sum and the sum of the summands' magnitudes, whose ratio is the condition of the sum."""
+    bp = torch.full(shape, float(beta_param), dtype=torch.float64, requires_grad=True)
+    make_loss(bp).backward()
+    g = bp.grad.numpy()
+    return float(g.sum()), float(np.abs(g).sum())
+
+
+def fe_floor(z, sdf, beta_param, eps, beta_min=1e-4):
+    """Absolute error floor of the free energies fe = dist * sigma in precision eps, per sample.  For sdf > 0 the Laplace
+    density (0.5 + 0.5 * sign * expm1(-x)) / beta, x = |sdf| / beta, is a cancellation: expm1(-x) near -1 carries an
+    absolute rounding of eps, so sigma is off by up to min(eps / beta, sigma) -- times the interval (1e10 for the last
+    sample).  Returns (dist, floor) in float64."""
+    z = z.astype(np.float64)
+    dist = np.concatenate([z[:, 1:] - z[:, :-1], np.full((z.shape[0], 1), 1e10)], 1)
+    beta = abs(beta_param) + beta_min
+    sigma = 0.5 * np.exp(-np.abs(sdf.astype(np.float64)) / beta) / beta
+    return dist, np.where(sdf > 0, dist * np.minimum(eps / beta, sigma), 0.0)
+
+
+def transmittance(w):
+    return np.concatenate([np.ones((w.shape[0], 1)), 1.0 - np.cumsum(w, 1)[:, :-1]], 1).clip(0.0, 1.0)
+
+
+def weights_bound(z, sdf, beta_param, w64):
+    """|w32 - w64| per sample: 1e-6, plus T_i times the float32 floor of the free energies up to and including sample i
+    (dw_i / dfe_j is bounded by T_i for every j <= i), and which samples are checked at all: not the last sample of a ray
+    whose last sdf is > 0, whose float32 free energy (interval 1e10 times a density below the float32 floor) the
+    reference's own formula leaves undetermined."""
+    _, floor = fe_floor(z, sdf, beta_param, 2.0 ** -24)
+    checked = np.ones(sdf.shape, bool)
+    checked[:, -1] = sdf[:, -1] <= 0
+    floor[:, -1] = 0.0
+    return 1e-6 + transmittance(w64) * np.cumsum(floor, 1), checked
+
+
+# 0: beta = beta_min with d beta exactly 0 (sign(0) = 0); 1e-12: beta_min again, with its d beta
+BETAS = [0.0, 1e-12, 1e-3, -1e-3, 0.02, 0.1]
+
+
+@pytest.mark.parametrize("S", [2, 63, 64, 65, 98, 256])
+@pytest.mark.parametrize("beta_param", BETAS)
+def test_composite_backward_edges(dev, ops, beta_param, S):
+    import torch_ref as tref
+    R = 37
+    idx = BETAS.index(beta_param) + S
+    z, sdf, rgb, ds = edge_scene(R, S, idx, beta_param)
+    rs = np.random.default_rng(idx + 100)
+    g_rgb = rs.normal(0, 1, (R, 3)).astype(F32)
+    with_wd = idx % 2 == 0                                  # d_weights and d_depth_values both given, or both absent
+    g_w = rs.normal(0, 1, (R, S)).astype(F32) if with_wd else None
+    g_d = rs.normal(0, 1, (R, 1)).astype(F32) if with_wd else None
+    T = lambda a, rg=False: torch.tensor(a, dtype=torch.float64, requires_grad=rg)
+    tz, tds = T(z), T(ds)
+
+    def make_loss(bp, tsdf=None, trgb=None, with_w=False):
+        w, rv, dv = tref.composite(tz, T(sdf) if tsdf is None else tsdf, T(rgb) if trgb is None else trgb, bp, tds,
+                                   stable=True)
+        loss = (rv * T(g_rgb)).sum()
+        if with_wd:
+            loss = loss + (w * T(g_w)).sum() + (dv * T(g_d)).sum()
+        return (loss, w) if with_w else loss
+
+    tsdf, trgb, tb = T(sdf, True), T(rgb, True), T(np.asarray(beta_param), True)
+    loss, w = make_loss(tb, tsdf, trgb, with_w=True)
+    loss.backward()
+    w64 = w.detach().numpy()
+    # the forward on the same inputs: float32 weights finite, non-negative and within 1e-6 of float64 -- wider only by
+    # the float32 cancellation floor of the density where sdf > 0 (weights_bound, which also names the samples left
+    # out); the kernel follows the reference's float32 evaluation, which tests/test_gpu_render.py holds bit for bit
+    fw = ops.composite(G(z, dev), G(sdf.reshape(-1, 1), dev), G(rgb.reshape(-1, 3), dev), G(ds, dev),
+                       torch.tensor(beta_param, device=dev), 1e-4)["weights"].cpu().numpy()
+    assert np.isfinite(fw).all() and (fw >= 0).all()
+    wb, checked = weights_bound(z, sdf, beta_param, w64)
+    assert (np.abs(fw - w64) <= wb)[checked].all()
+    at = checked & (wb <= 1e-6 * (1 + 1e-9))
+    err_w = np.abs(fw - w64)[checked]
+    print(f"weights: {(~checked).sum()} samples left out, {at.mean():.1%} at the 1e-6 bound (max err there "
+          f"{np.abs(fw - w64)[at].max():.1e}), max err {err_w.max():.1e} "
+          f"(bound there {wb[checked][err_w.argmax()]:.1e})")
+    d_sdf, d_rgb, d_beta = ops.composite_bwd(G(z, dev), G(sdf.reshape(-1, 1), dev), G(rgb.reshape(-1, 3), dev), G(ds, dev),
+                                             torch.tensor(beta_param, device=dev), 1e-4, G(g_rgb, dev),
+                                             G(g_w, dev) if with_wd else None, G(g_d, dev) if with_wd else None)
+    d_sdf, d_rgb, d_beta = d_sdf.cpu().numpy().reshape(R, S), d_rgb.cpu().numpy().reshape(R, S, 3), float(d_beta)
+    assert np.isfinite(d_sdf).all() and np.isfinite(d_rgb).all() and np.isfinite(d_beta)
+    e_rgb = rel_err(d_rgb, trgb.grad.numpy())
+    assert e_rgb < 2e-5, e_rgb
+    e_sdf = rel_err(d_sdf, tsdf.grad.numpy())
+    assert e_sdf < 2e-5, e_sdf
+    if beta_param == 0.0:
+        assert d_beta == 0.0 and float(tb.grad) == 0.0       # d|b|/db = sign(0) = 0
+        return
+    ref, mag = beta_condition(make_loss, beta_param, (R, S))
+    assert abs(ref - float(tb.grad)) <= 1e-9 * mag
+    # 5e-5 relative; where the sum cancels, 1e-6 of the summands' magnitudes (float32 per-ray partials and the forward's
+    # float32 interval lengths perturb each summand by a few float32 ulps)
+    tol = max(5e-5 * abs(ref), 1e-6 * mag)
+    print(f"beta_param={beta_param} S={S}: d_beta {d_beta:.6e} ref {ref:.6e} cond {mag / max(abs(ref), 1e-300):.1e} "
+          f"rel {abs(d_beta - ref) / abs(ref):.1e}; d_sdf {e_sdf:.1e} d_rgb {e_rgb:.1e} w {err_w.max():.1e}")
+    assert abs(d_beta - ref) <= tol
+
+
+def test_composite_rejects_one_sample(dev, ops):
+    """S = 1 is outside the kernels' contract (they need S >= 2): an error, not a result."""
+    z = torch.ones(4, 1, device=dev)
+    with pytest.raises(Exception):
+        ops.composite_bwd(z, z.reshape(-1, 1), torch.ones(4, 3, device=dev), z, torch.tensor(0.1, device=dev), 1e-4,
+                          torch.ones(4, 3, device=dev))
+    with pytest.raises(Exception):
+        ops.composite(z, z.reshape(-1, 1), torch.ones(4, 3, device=dev), z, torch.tensor(0.1, device=dev), 1e-4)

@@ -501,3 +501,58 @@ def test_deterministic_mode_repeats_bit_for_bit(dev, model_kind, R):
     assert float(ga[0].abs().max()) > 0 and torch.isfinite(pa).all()
     gd, pd = run(False)                                    # default mode: same sums in another order
     assert float((ga[0] - gd[0]).abs().max()) <= 1e-4 * float(ga[0].abs().max())
+
+
+@pytest.mark.parametrize("S", [2, 65, 255])
+@pytest.mark.parametrize("beta_param", [0.0, 1e-12, 1e-3, -1e-3, 0.02, 0.1])
+def test_composite_bg_backward_edges(dev, beta_param, S):
+    """svs_composite_bg_bwd down to beta = beta_min on the scenes of test_gpu_backward.edge_scene (opaque surfaces,
+    empty rays, sdf exactly 0, duplicate z, sdf through +-5 beta), R not a multiple of 4, against float64 autograd of
+    torch_ref.composite_bg."""
+    import torch_ref as tref
+    from svs_hip import ops
+    from test_gpu_backward import beta_condition, edge_scene
+    R, Nb = 37, 32
+    idx = 10 * S + [0.0, 1e-12, 1e-3, -1e-3, 0.02, 0.1].index(beta_param)
+    z, sdf, rgb, ds = edge_scene(R, S, idx, beta_param)
+    rs = np.random.default_rng(idx + 7)
+    z_max = (z[:, -1] + rs.uniform(0.05, 0.5, R)).astype(F32)
+    z_bg = np.sort(rs.uniform(0, 1 / 3, (R, Nb)), -1)[:, ::-1].astype(F32).copy()
+    bo = rs.normal(0, 2.0, (R, Nb)).astype(F32)
+    brgb = rs.uniform(0, 1, (R, Nb, 3)).astype(F32)
+    with_wd = S != 65                                       # d_weights and d_depth_values both given, or both absent
+    g_rgb = rs.normal(0, 1, (R, 3)).astype(F32)
+    g_w = rs.normal(0, 0.1, (R, S)).astype(F32) if with_wd else None
+    g_d = rs.normal(0, 0.5, (R, 1)).astype(F32) if with_wd else None
+    D = lambda a, rg=False: torch.tensor(a, dtype=torch.float64, requires_grad=rg)
+    tsdf, trgb, tbo, tbrgb, tb = D(sdf, True), D(rgb, True), D(bo, True), D(brgb, True), D(np.asarray(beta_param), True)
+
+    def make_loss(bp, a=None, b=None, c=None, d=None):
+        w, _, rv, dv = tref.composite_bg(D(z), D(z_max), D(sdf) if a is None else a, D(rgb) if b is None else b, bp, D(ds),
+                                         D(z_bg), D(bo) if c is None else c, D(brgb) if d is None else d, stable=True)
+        loss = (rv * D(g_rgb)).sum()
+        if with_wd:
+            loss = loss + (w * D(g_w)).sum() + (dv * D(g_d)).sum()
+        return loss
+
+    make_loss(tb, tsdf, trgb, tbo, tbrgb).backward()
+    out = ops.composite_bg_bwd(G(z, dev), G(z_max, dev), G(sdf.reshape(-1, 1), dev), G(rgb.reshape(-1, 3), dev), G(ds, dev),
+                               torch.tensor(beta_param, device=dev), 1e-4, G(z_bg, dev), G(bo.reshape(-1, 1), dev),
+                               G(brgb.reshape(-1, 3), dev), G(g_rgb, dev), G(g_w, dev) if with_wd else None,
+                               G(g_d, dev) if with_wd else None)
+    d_sdf, d_rgb, d_bo, d_brgb, d_beta = [t.cpu().numpy() for t in out]
+    for a in (d_sdf, d_rgb, d_bo, d_brgb, d_beta):
+        assert np.isfinite(a).all()
+    errs = [_rel(d_sdf.reshape(R, S), tsdf.grad.numpy()), _rel(d_rgb.reshape(R, S, 3), trgb.grad.numpy()),
+            _rel(d_bo.reshape(R, Nb), tbo.grad.numpy()), _rel(d_brgb.reshape(R, Nb, 3), tbrgb.grad.numpy())]
+    assert max(errs) < 2e-5, errs
+    d_beta = float(d_beta[0])
+    if beta_param == 0.0:
+        assert d_beta == 0.0 and float(tb.grad) == 0.0
+        return
+    ref, mag = beta_condition(make_loss, beta_param, (R, S))
+    assert abs(ref - float(tb.grad)) <= 1e-9 * mag
+    tol = max(5e-5 * abs(ref), 1e-6 * mag)                 # as test_composite_backward_edges
+    print(f"bg beta_param={beta_param} S={S}: d_beta rel {abs(d_beta - ref) / abs(ref):.1e} cond "
+          f"{mag / max(abs(ref), 1e-300):.1e}; grads {max(errs):.1e}")
+    assert abs(d_beta - ref) <= tol

@@ -540,27 +540,6 @@ def test_cost_lookup_ray_mode_full_size(dev, ops):
     assert np.abs(pj.cpu().numpy()[agree] - pj_r[agree]).mean() < 1e-7
 
 
-def _torch_loss(out, rgb, rgb_smooth, it, **kw):
-    """plain torch float32 restatement of loss.py:80-114 (autograd reference for the fused loss kernel)."""
-    eik_w, rgb_w, mvs_w, sp_w = kw["eikonal_weight"], kw["rgb_weight"], kw["mvs_weight"], kw["sparse_weight"]
-    gce, confi, anneal_rgb = kw["gce"], kw["confi"], kw["anneal_rgb"]
-    rgb_loss = (out["rgb_values"] - rgb).abs().mean()
-    eik = ((out["grad_theta"].norm(2, dim=1) - 1) ** 2).mean()
-    pw = out["pi"] * out["pj"]
-    w = out["weights"]
-    l = (-pw * w.detach() ** gce * torch.log(w + 1e-8)).sum(1)
-    mvs = (1. * (pw.sum(1) > confi) * l).mean()
-    on = sp_w > 0 and anneal_rgb > 0 and it < anneal_rgb
-    sparse = torch.zeros(())
-    anneal = 0.0
-    if on:
-        conf = pw.sum(-1)
-        sparse = ((1. / (out["depth_values"].squeeze() + 1e-3)) * (conf < confi)).mean()
-        anneal = 1.0 - it / anneal_rgb
-        rgb_loss = ((out["rgb_values"] - rgb_smooth).abs().mean(-1) * (conf < 1e-8)).mean()
-    return rgb_w * rgb_loss + eik_w * eik + mvs_w * mvs + sp_w * anneal * sparse
-
-
 @pytest.mark.parametrize("it", [0, 100, 250])
 def test_loss_kernel(dev, ops, golden_dir, it):
     g = dict(np.load(os.path.join(golden_dir, "loss.npz")))
@@ -575,9 +554,12 @@ def test_loss_kernel(dev, ops, golden_dir, it):
     l = losses.cpu().numpy()
     for i, k in enumerate(("rgb_loss", "eikonal_loss", "mvs_loss", "sparse_loss", "loss")):
         np.testing.assert_allclose(l[i], g[f"it{it}_{k}"], rtol=3e-6, atol=1e-7, err_msg=k)
-    t = {k: torch.tensor(g[k], requires_grad=k in ("rgb_values", "grad_theta", "weights", "depth_values"))
+    # gradients: float64 autograd of oracle/torch_ref.loss_fn (pinned to the reference by test_torch_ref_loss_grid)
+    import torch_ref as tref
+    t = {k: torch.tensor(g[k], dtype=torch.float64, requires_grad=k in ("rgb_values", "grad_theta", "weights", "depth_values"))
          for k in ("rgb_values", "grad_theta", "weights", "pi", "pj", "depth_values")}
-    _torch_loss(t, torch.tensor(g["rgb"]).reshape(-1, 3), torch.tensor(g["rgb_smooth"]).reshape(-1, 3), it, **kw).backward()
+    T = lambda a: torch.tensor(a, dtype=torch.float64).reshape(-1, 3)
+    tref.loss_fn(t, T(g["rgb"]), T(g["rgb_smooth"]), it, **kw).backward()
     for k in ("rgb_values", "grad_theta", "weights", "depth_values"):
         ref = t[k].grad.numpy() if t[k].grad is not None else np.zeros_like(g[k])
         np.testing.assert_allclose(grads[k].cpu().numpy().reshape(ref.shape), ref, rtol=2e-5, atol=1e-8, err_msg=k)

@@ -641,3 +641,41 @@ def test_feature_net(golden_dir):
         assert out[k].shape == g[k].shape
         np.testing.assert_allclose(out[k], g[k], atol=2e-6)
     assert g["stage1"].shape == (32, 9, 13) and g["stage3"].shape == (8, 36, 52)
+
+
+def loss_grid_case(g, c):
+    """Inputs and settings of case c of loss_grid.npz (make_fixtures.fx_loss_grid)."""
+    k, j = (int(x) for x in g["cases"][c])
+    R, S, n_eik = (int(x) for x in g["shapes"][k])
+    gce, mvs_w, has_pi, it, sp_w = g["settings"][j]
+    names = ["rgb_values", "weights", "depth_values"] + (["grad_theta"] if n_eik else []) + (["pi", "pj"] if has_pi else [])
+    inp = {n: g[f"s{k}_{n}"] for n in names}
+    kw = dict(eikonal_weight=0.1, rgb_weight=1.0, mvs_weight=float(mvs_w), sparse_weight=float(sp_w), gce=float(gce),
+              confi=float(g["confi"]), anneal_rgb=int(g["anneal_rgb"]))
+    return inp, g[f"s{k}_rgb"], g[f"s{k}_rgb_smooth"], int(it), kw
+
+
+@pytest.mark.parametrize("c", range(27))
+def test_torch_ref_loss_grid(golden_dir, c):
+    """oracle/torch_ref.loss_fn (the autograd reference of the fused loss kernel) == the reference's VolSDFLoss in float64:
+    the five terms and the gradients w.r.t. the four differentiable outputs, across gce, the MVS / sparsity switches, the
+    annealing phase, the three confidence classes and shapes from one ray and sample to S = 256."""
+    import torch
+    import torch_ref as tref
+    g = load(golden_dir, "loss_grid")
+    assert len(g["cases"]) == 27
+    inp, rgb, rgb_smooth, it, kw = loss_grid_case(g, c)
+    t = {n: torch.tensor(v, dtype=torch.float64, requires_grad=n not in ("pi", "pj")) for n, v in inp.items()}
+    T = lambda a: torch.tensor(a.reshape(-1, 3), dtype=torch.float64)
+    res = tref.loss_fn(t, T(rgb), T(rgb_smooth), it, terms=True, **kw)
+    for n in ("rgb_loss", "eikonal_loss", "mvs_loss", "sparse_loss", "loss"):
+        np.testing.assert_allclose(res[n].item(), float(g[f"c{c}_{n}"]), rtol=1e-12, atol=1e-300, err_msg=n)
+    res["loss"].backward()
+    for n in t:
+        if n in ("pi", "pj"):
+            continue
+        got = t[n].grad.numpy() if t[n].grad is not None else np.zeros(t[n].shape)
+        ref = g[f"c{c}_d_{n}"]
+        np.testing.assert_allclose(got, ref, rtol=1e-12, atol=1e-12 * np.abs(ref).max() + 1e-300, err_msg=n)
+    # the total without terms=True is the same number, for the callers that want only the total
+    assert float(tref.loss_fn({n: v.detach() for n, v in t.items()}, T(rgb), T(rgb_smooth), it, **kw)) == float(res["loss"])
