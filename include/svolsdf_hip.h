@@ -502,6 +502,29 @@ int svs_fuse_view(const float* ref_depth, const float* confidence, const float* 
 int svs_fuse_points(const double* depth_avg, const uint8_t* final_mask, const float* ref_img, const double* mats, int H, int W,
                     int* offset_ws, float* xyz, uint8_t* rgb, int* count, void* hip_stream);
 
+/* ---- f5  image-based rendering of an evaluation view (simple_ibr.py:116-235) -----------------------------------------
+ * One reference (evaluation) view, n_src in 1..16 source (training) views, H and W positive multiples of 8 (the
+ * reference's pyrUp(g_i) must match g_(i-1)'s shape).  float32 throughout; workspace: svs_ibr_workspace_bytes(), shared
+ * by both entries (stream-ordered).  Both entries check every argument before their first launch: a rejected call
+ * (SVS_EINVAL: null pointer or n_src out of range; SVS_ESHAPE: H or W) writes nothing.
+ * svs_ibr_weights: simple_ibr.py:171-214 -- per source, cv2.remap(INTER_CUBIC, BORDER_CONSTANT 0) of the image and of
+ *   the direction field at map_x / map_y (5-bit fixed point, OpenCV's A = -0.75 cubic), the sampled direction
+ *   normalised, cos_dir = dot with ref_dir, nan_to_num, times geo_mask; the constant 0.2 of the render appended;
+ *   softmax(20 w) over the n_src+1 entries; fill_j = img_j w_j + pred (1 - w_j) (entry n_src: the render itself);
+ *   masks_j = erode(w_j > 0.2, 5x5) w_j for the sources, w_last + 1e-2 for the render, divided by their sum.
+ *   src_imgs / src_dirs: HOST arrays of n_src DEVICE pointers to (H,W,3); ref_dir, pred_img (H,W,3); geo_mask (uint8),
+ *   map_x, map_y (n_src,H,W): the per-source outputs of svs_fuse_view.  -> fill (n_src+1,H,W,3), masks (n_src+1,H,W):
+ *   one mask value per pixel (the reference's three channels are identical).
+ * svs_ibr_laplacian_blend: Laplacian_Blending(fill, masks, num_levels=4) (simple_ibr.py:80-136): Gaussian pyramids by
+ *   cv2.pyrDown (levels 1..3), per level sum_j m_jl (g_jl - pyrUp(g_j,l+1)) (the coarsest: sum_j m_j3 g_j3),
+ *   reconstruction out_l = pyrUp(out_l+1) + LS_l, clip(0, 1).  -> out (H,W,3). */
+size_t svs_ibr_workspace_bytes(int n_src, int H, int W);
+int svs_ibr_weights(const float* const* src_imgs, const float* const* src_dirs, const float* ref_dir, const float* pred_img,
+                    const uint8_t* geo_mask, const float* map_x, const float* map_y, int n_src, int H, int W,
+                    void* workspace, float* fill, float* masks, void* hip_stream);
+int svs_ibr_laplacian_blend(const float* fill, const float* masks, int n_src, int H, int W, void* workspace, float* out,
+                            void* hip_stream);
+
 /* ---- f4  Chamfer evaluator on point clouds (evals/eval_dtu.py:100-176) ---------------------------------------------
  * All clouds are (n,3) float64 (what open3d hands the reference).  One structure serves both neighbour problems:
  * points sorted by uniform-grid cell + a hash from cell to its run; grid_ws: svs_cloud_grid_bytes(n_points of the

@@ -39,6 +39,7 @@ UNITS = {
     "svs_optim.hip": ["-ffp-contract=off"],
     "svs_fusion.hip": ["-ffp-contract=off"],
     "svs_cloud.hip": ["-ffp-contract=off"],
+    "svs_ibr.hip": ["-ffp-contract=off"],
     "svs_plan.hip": [],
 }
 BASE_FLAGS = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function", "-x", "hip"]

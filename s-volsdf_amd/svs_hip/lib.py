@@ -126,6 +126,9 @@ SIGNATURES = {
     "svs_fuse_view": (c_int, [_P, _P, _PP, _P, c_int, c_int, c_int, c_float, c_double, c_float, c_int, _P, _P, _P, _P, _P,
                               _P, _P, _P, _P, _P]),
     "svs_fuse_points": (c_int, [_P, _P, _P, _P, c_int, c_int, _P, _P, _P, _P, _P]),
+    "svs_ibr_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "svs_ibr_weights": (c_int, [_PP, _PP, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P, _P]),
+    "svs_ibr_laplacian_blend": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P]),
     "svs_warp_variance": (c_int, [_P, _PP, POINTER(c_float), c_int, c_int, c_int, c_int, c_int, _P, _P, c_int, _P]),
     "svs_conv3d": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "svs_conv3d_mfma_wfrag_bytes": (c_size_t, [c_int]),
