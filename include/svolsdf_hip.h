@@ -525,6 +525,21 @@ int svs_ibr_weights(const float* const* src_imgs, const float* const* src_dirs, 
 int svs_ibr_laplacian_blend(const float* fill, const float* masks, int n_src, int H, int W, void* workspace, float* out,
                             void* hip_stream);
 
+/* ---- f5  novel-view scores (eval_vsdf.py:186-212, --result_from blend|default) --------------------------------------
+ * V evaluation views of one size (H, W >= 7: the SSIM window) in one call and two launches.  pred, gt, mask: device
+ * (V,H,W,3) uint8 -- the rendered PNG codes, the 8-bit ground-truth codes (load_rgb = code / 255), the mask per channel
+ * (nonzero: inside).  -> out: device double (V,3) per view: the masked sum of squared code differences over the whole
+ * image, the masked element count (psnr = -10 log10(sse / 255^2 / count) on the host: +inf for a perfect match, NaN for
+ * an empty mask, as torch.mean gives them), and structural_similarity(pred_fg, gt_fg, multichannel=True) of
+ * scikit-image 0.17.2 on the white-composited images x m + (1 - m): win 7, cov_norm 49/48, data_range = 2 (float32's
+ * dtype_range (-1, 1); the reference passes none), S cropped by 3 pixels, the three channel means averaged.  Exact
+ * integer window moments, float64 S, fixed-order sums: bit-identical run to run.  workspace: svs_nvs_workspace_bytes().
+ * Every argument is checked before the first launch: a rejected call (SVS_EINVAL: null pointer or V < 1; SVS_ESHAPE:
+ * H or W < 7, or too large) writes nothing. */
+size_t svs_nvs_workspace_bytes(int V, int H, int W);
+int svs_nvs_score(const uint8_t* pred, const uint8_t* gt, const uint8_t* mask, int V, int H, int W, void* workspace,
+                  double* out, void* hip_stream);
+
 /* ---- f4  Chamfer evaluator on point clouds (evals/eval_dtu.py:100-176) ---------------------------------------------
  * All clouds are (n,3) float64 (what open3d hands the reference).  One structure serves both neighbour problems:
  * points sorted by uniform-grid cell + a hash from cell to its run; grid_ws: svs_cloud_grid_bytes(n_points of the

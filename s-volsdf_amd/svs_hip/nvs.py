@@ -1,0 +1,201 @@
+"""Novel-view scores on the HIP path (eval_vsdf.py:186-212, `--result_from blend|default`; csrc/svs_nvs.hip).
+
+`score_views` is the reference's masked PSNR and scikit-image 0.17.2 SSIM for a stack of evaluation views in one
+`svs_nvs_score` call.  `load_gt` reads the ground truth and masks the reference's SceneDataset reads for those views, and
+`score_scan` scores the eval_blend_XXX.png (or eval_XXX.png) files of one scan.  The view ids are explicit: the
+reference's id tables stay in its dataset module.  LPIPS, the reference's third metric, needs VGG weights and
+TensorFlow and is not computed.
+
+    python -m svs_hip.nvs --data-dir-root data_s_volsdf --dataset DTU --scan 106 \\
+        --rendering-dir exps_result/ours_106/rendering_1562 --views 1 2 9 --result-from blend [--json scores.json]
+"""
+import argparse
+import glob
+import json
+import os
+
+import numpy as np
+import torch
+
+from . import lib as _lib
+from .fusion import _dev
+from .ops import _ptr, _stream
+
+IMG_RES = (576, 768)                                   # dataset.img_res of config/confs/dtu.conf and bmvs.conf
+DATASETS = ("DTU", "BlendedMVS")
+DTU_UNMASKED_SCANS = (1, 4, 11, 13, 48)                # scene_dataset.py:172: scored without eval masks
+
+
+def _u8_dev(a, what):
+    if torch.is_tensor(a):
+        if a.dtype != torch.uint8:
+            raise TypeError(f"{what} must be uint8, got {a.dtype}")
+        return a.detach().to(device=_dev()).contiguous()
+    a = np.asarray(a)
+    if a.dtype != np.uint8:
+        raise TypeError(f"{what} must be uint8, got {a.dtype}")
+    return torch.from_numpy(np.ascontiguousarray(a)).to(_dev())
+
+
+def score_views(pred, gt, mask):
+    """pred, gt: (V,H,W,3) uint8 codes (the rendered PNGs, the 8-bit ground truth); mask: (V,H,W,3) uint8, nonzero
+    inside.  Arrays or tensors, host or device.  -> psnr[V], ssim[V] float64 numpy: the reference's masked PSNR over the
+    whole image (+inf for a perfect match, NaN for an empty mask) and SSIM of the white-composited images."""
+    shape = tuple(pred.shape)
+    if len(shape) != 4 or shape[3] != 3:
+        raise ValueError(f"expected (V,H,W,3) images, got {shape}")
+    if tuple(gt.shape) != shape or tuple(mask.shape) != shape:
+        raise ValueError(f"pred {shape}, gt {tuple(gt.shape)} and mask {tuple(mask.shape)} differ")
+    V, H, W, _ = shape
+    if V < 1 or H < 7 or W < 7:
+        raise ValueError(f"need at least one view of at least 7x7 pixels (the SSIM window), got {shape}")
+    L = _lib.load()
+    p, g, m = _u8_dev(pred, "pred"), _u8_dev(gt, "gt"), _u8_dev(mask, "mask")
+    ws = torch.empty(int(L.svs_nvs_workspace_bytes(V, H, W)), dtype=torch.uint8, device=p.device)
+    out = torch.empty(V, 3, dtype=torch.float64, device=p.device)
+    _lib.check(L.svs_nvs_score(_ptr(p), _ptr(g), _ptr(m), V, H, W, _ptr(ws), _ptr(out), _stream()), "svs_nvs_score")
+    res = out.cpu().numpy()
+    with np.errstate(divide="ignore", invalid="ignore"):
+        psnr = -10.0 * np.log10(res[:, 0] / (255.0 * 255.0) / res[:, 1])
+    return psnr, res[:, 2].copy()
+
+
+def _read_png(path):
+    from PIL import Image
+    with Image.open(path) as im:
+        return np.array(im)
+
+
+def _check_size(a, img_res, path):
+    if tuple(a.shape[:2]) != tuple(img_res):
+        raise NotImplementedError(f"{path}: {a.shape[:2]} differs from img_res {tuple(img_res)}; the reference resizes it "
+                                  f"with cv2.resize, which is not ported")
+
+
+def _image_paths(image_dir):
+    """sorted(glob_imgs(image_dir)) (volsdf/utils/general.py:18-22)"""
+    paths = []
+    for ext in ("*.png", "*.jpg", "*.JPEG", "*.JPG"):
+        paths.extend(glob.glob(os.path.join(image_dir, ext)))
+    return sorted(paths)
+
+
+def load_gt(data_dir_root, dataset, scan, views, img_res=IMG_RES, mask=None):
+    """The ground truth and masks SceneDataset (scene_dataset.py:113-206) holds for the given views of one scan.
+    -> gt (V,H,W,3) uint8 codes (load_rgb's values are code / 255), mask (V,H,W,3) uint8 0/1.
+
+    Image v is file number v of sorted(glob_imgs({root}/{dataset}/scan{scan}/image)), 8-bit RGB.  Masks: DTU reads
+    eval_mask/scan{S}/mask/{v:03d}.png (or eval_mask/scan{S}/{v:03d}.png when mask/000.png does not exist, decided once
+    for the scan), inside where a channel is 255; BlendedMVS reads eval_mask/scan{S}/mask/{v:08d}.png (RGBA), inside
+    where alpha / 255 > 0.5, for all three channels.  mask=None follows the reference: masked, except the DTU scans
+    1, 4, 11, 13 and 48 (all ones); True / False force it.  The views are the scored (evaluation) views: the reference
+    reads DTU masks only for its evaluation ids and BlendedMVS masks for its evaluation and training ids."""
+    if dataset not in DATASETS:
+        raise NotImplementedError(f"dataset {dataset!r}: only {DATASETS}")
+    scan = int(scan)
+    inst = os.path.join(data_dir_root, dataset, f"scan{scan}")
+    paths = _image_paths(os.path.join(inst, "image"))
+    if mask is None:
+        mask = not (dataset == "DTU" and scan in DTU_UNMASKED_SCANS)
+    mask_dir = os.path.join(data_dir_root, dataset, "eval_mask", f"scan{scan}")
+    if dataset == "DTU" and not os.path.exists(os.path.join(mask_dir, "mask", "000.png")):
+        mask_fn = lambda v: os.path.join(mask_dir, f"{v:03d}.png")             # noqa: E731
+    elif dataset == "DTU":
+        mask_fn = lambda v: os.path.join(mask_dir, "mask", f"{v:03d}.png")     # noqa: E731
+    else:
+        mask_fn = lambda v: os.path.join(mask_dir, "mask", f"{v:08d}.png")     # noqa: E731
+    H, W = img_res
+    gts, masks = [], []
+    for v in views:
+        v = int(v)
+        if not 0 <= v < len(paths):
+            raise IndexError(f"view {v}: {inst}/image holds {len(paths)} images")
+        img = _read_png(paths[v])
+        if img.dtype != np.uint8:
+            raise ValueError(f"{paths[v]}: {img.dtype} image; only 8-bit images are supported")
+        if img.ndim != 3 or img.shape[2] != 3:
+            raise ValueError(f"{paths[v]}: expected an RGB image, got shape {img.shape}")
+        _check_size(img, img_res, paths[v])
+        gts.append(img)
+        if not mask:
+            masks.append(np.ones((H, W, 3), np.uint8))
+            continue
+        fn = mask_fn(v)
+        m = _read_png(fn)
+        if dataset == "DTU":
+            if m.ndim != 3 or m.shape[2] < 3 or m.dtype != np.uint8:
+                raise ValueError(f"{fn}: expected an 8-bit RGB(A) mask, got {m.dtype} {m.shape}")
+            _check_size(m, img_res, fn)
+            masks.append((m[:, :, :3] == 255).astype(np.uint8))                # (png / 255.) == 1
+        else:
+            if m.ndim != 3 or m.shape[2] != 4 or m.dtype != np.uint8:
+                raise AssertionError(f"{fn}: expected an 8-bit RGBA mask, got {m.dtype} {m.shape}")
+            _check_size(m, img_res, fn)
+            inside = m[:, :, 3].astype(np.float32) / np.float32(255.0) > 0.5          # alpha * 1. / 255. > 0.5
+            masks.append(np.repeat(inside[:, :, None], 3, axis=2).astype(np.uint8))
+    return np.stack(gts), np.stack(masks)
+
+
+def prediction_path(rendering_dir, view, result_from="blend"):
+    """eval_blend_{v:03d}.png for 'blend', eval_{v:03d}.png for 'default' (eval_vsdf.py:191-194)"""
+    if result_from == "blend":
+        return os.path.join(rendering_dir, f"eval_blend_{int(view):03d}.png")
+    if result_from == "default":
+        return os.path.join(rendering_dir, f"eval_{int(view):03d}.png")
+    raise NotImplementedError(f"result_from {result_from!r}: 'blend' or 'default'")
+
+
+def score_scan(rendering_dir, data_dir_root, dataset, scan, views, result_from="blend", img_res=IMG_RES, mask=None):
+    """Scores the rendered views of one scan against its ground truth (eval_vsdf.py:186-212 for explicit view ids).
+    -> dict(views, psnr, ssim): float64 arrays in view order."""
+    views = [int(v) for v in views]
+    if not views:
+        raise ValueError("no views to score")
+    preds = []
+    for v in views:
+        fn = prediction_path(rendering_dir, v, result_from)
+        p = _read_png(fn)
+        if p.dtype != np.uint8 or p.ndim != 3 or p.shape[2] != 3:
+            raise ValueError(f"{fn}: expected an 8-bit RGB image, got {p.dtype} {p.shape}")
+        _check_size(p, img_res, fn)
+        preds.append(p)
+    gt, m = load_gt(data_dir_root, dataset, scan, views, img_res=img_res, mask=mask)
+    psnr, ssim = score_views(np.stack(preds), gt, m)
+    return dict(views=np.asarray(views), psnr=psnr, ssim=ssim)
+
+
+def scan_lines(scan, psnr, ssim):
+    """The reference's per-scan block (eval_vsdf.py:273-276) without its LPIPS line."""
+    psnr, ssim = np.asarray(psnr, np.float64), np.asarray(ssim, np.float64)
+    return [f"SCAN {scan}:",
+            "    psnr mean = {0}, std {1}".format("%.4f" % psnr.mean(), "%.4f" % psnr.std()),
+            "    ssim mean = {0}, std {1}".format("%.4f" % ssim.mean(), "%.4f" % ssim.std())]
+
+
+def main(argv=None):
+    p = argparse.ArgumentParser(description="GPU novel-view scores (the reference's eval_vsdf.py --result_from): masked "
+                                            "PSNR and SSIM of the rendered evaluation views of one scan.")
+    p.add_argument("--data-dir-root", required=True, help="holds {DTU|BlendedMVS}/scanN/image and .../eval_mask")
+    p.add_argument("--dataset", required=True, choices=DATASETS)
+    p.add_argument("--scan", type=int, required=True)
+    p.add_argument("--rendering-dir", required=True, help="holds eval_blend_{:03d}.png / eval_{:03d}.png")
+    p.add_argument("--views", type=int, nargs="+", required=True, help="evaluation view ids (training views excluded)")
+    p.add_argument("--result-from", default="blend", choices=("blend", "default"))
+    p.add_argument("--img-res", type=int, nargs=2, default=IMG_RES, metavar=("H", "W"))
+    p.add_argument("--mask", choices=("auto", "on", "off"), default="auto",
+                   help="auto: the reference's rule (DTU scans 1, 4, 11, 13, 48 unmasked)")
+    p.add_argument("--json", help="write the per-view values here")
+    a = p.parse_args(argv)
+    mask = {"auto": None, "on": True, "off": False}[a.mask]
+    r = score_scan(a.rendering_dir, a.data_dir_root, a.dataset, a.scan, a.views, result_from=a.result_from,
+                   img_res=tuple(a.img_res), mask=mask)
+    for line in scan_lines(a.scan, r["psnr"], r["ssim"]):
+        print(line)
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(dict(scan=a.scan, dataset=a.dataset, result_from=a.result_from, views=r["views"].tolist(),
+                           psnr=[float(x) for x in r["psnr"]], ssim=[float(x) for x in r["ssim"]]), f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
