@@ -540,6 +540,31 @@ size_t svs_nvs_workspace_bytes(int V, int H, int W);
 int svs_nvs_score(const uint8_t* pred, const uint8_t* gt, const uint8_t* mask, int V, int H, int W, void* workspace,
                   double* out, void* hip_stream);
 
+/* ---- f6  scene loading: the image work of SceneDataset (volsdf/datasets/scene_dataset.py:163-206) --------------------
+ * V views of one source size (Hs,Ws) to one destination size (H,W) per call; H, W >= 16 (the 31-tap smoothing reflects
+ * once), V >= 1.  Every argument is checked before the first launch: a rejected call (SVS_EINVAL: null pointer, V < 1,
+ * divisor <= 0; SVS_ESHAPE: a size) writes nothing.  The per-axis tables are DEVICE arrays the host builds
+ * (svs_hip/scene.py::cubic_table / linear_table, as OpenCV builds its own): xofs (W) / yofs (H) int32, the index of the
+ * first tap (it may lie outside the image: every tap index is clamped on its own), xcoef / ycoef float32 (W,taps) /
+ * (H,taps).  The coordinate is fx = (float)((d + 0.5) * scale - 0.5), scale = 1 / (dst / src) in double; s = floor(fx),
+ * t = fx - s; cubic: first tap s - 1, Keys' weights with A = -0.75 at t; linear: first tap s, weights (1 - t, t).
+ * svs_scene_resize_cubic: scene_dataset.py:163-169 -- load_rgb's code * (1/255) (float32 multiply) and
+ *   cv2.resize(img, (W,H), interpolation=cv2.INTER_CUBIC), no prefilter.  codes: (V,Hs,Ws,3) uint8 -> out (V,H,W,3)
+ *   float32.  Hs == H and Ws == W: code * (1/255) alone (the reference skips the resize; the tables may be null).
+ * svs_scene_smooth: scene_dataset.py:172 -- cv2.GaussianBlur(img, (31,31), 90): separable, float32 weights of
+ *   exp(-(i-15)^2 / (2 90^2)) normalised in float64, BORDER_REFLECT_101, rows then columns.  img, out: (V,H,W,3) float32
+ *   (out may not alias img); workspace: svs_scene_workspace_bytes() (the float32 intermediate).
+ * svs_scene_mask: scene_dataset.py:178-206 -- cv2.resize(mask, (W,H), cv2.INTER_NEAREST) and > 0.5.  The third
+ *   positional parameter of cv2.resize is dst, so the default INTER_LINEAR is what runs (UNPINNED):
+ *   2 taps per axis.  mask: (V,Hs,Ws) uint8, read as code / divisor in float32 (1 for a 0/1 mask, 255 for an alpha
+ *   channel) -> out (V,H,W,3) float32 0/1, the three channels equal. */
+size_t svs_scene_workspace_bytes(int V, int H, int W);
+int svs_scene_resize_cubic(const uint8_t* codes, int V, int Hs, int Ws, int H, int W, const int* xofs, const float* xcoef,
+                           const int* yofs, const float* ycoef, float* out, void* hip_stream);
+int svs_scene_smooth(const float* img, int V, int H, int W, void* workspace, float* out, void* hip_stream);
+int svs_scene_mask(const uint8_t* mask, float divisor, int V, int Hs, int Ws, int H, int W, const int* xofs,
+                   const float* xcoef, const int* yofs, const float* ycoef, float* out, void* hip_stream);
+
 /* ---- f4  Chamfer evaluator on point clouds (evals/eval_dtu.py:100-176) ---------------------------------------------
  * All clouds are (n,3) float64 (what open3d hands the reference).  One structure serves both neighbour problems:
  * points sorted by uniform-grid cell + a hash from cell to its run; grid_ws: svs_cloud_grid_bytes(n_points of the
