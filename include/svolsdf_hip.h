@@ -565,6 +565,32 @@ int svs_scene_smooth(const float* img, int V, int H, int W, void* workspace, flo
 int svs_scene_mask(const uint8_t* mask, float divisor, int V, int Hs, int Ws, int H, int W, const int* xofs,
                    const float* xcoef, const int* yofs, const float* ycoef, float* out, void* hip_stream);
 
+/* ---- f7  the finish of an evaluation view (eval_vsdf.py:230-262, volsdf/utils/plots.py:392-468) ----------------------
+ * What the reference does in numpy on the host after merge_output, on the render's device tensors.  Every argument is
+ * checked before the launch: a rejected call (SVS_EINVAL: null pointer; SVS_ESHAPE: a size) writes nothing.
+ * svs_view_finish: one pass over weights (n_pixels,n_samples) float32.  rgb_values, normal_map (n_pixels,3),
+ *   depth_values (n_pixels) float32 ->
+ *   rgb_codes (n_pixels,3) uint8 = (rgb * 255).astype(np.uint8) (eval_vsdf.py:245): float32 multiply, then x86 numpy's
+ *     cast: truncation toward zero to int32, low 8 bits kept (outside the int32 range and for NaN: 0);
+ *   normal_codes (n_pixels,3) uint8 = (((n + 1) / 2) * 255).astype(np.uint8), float32 in that order (:251-254), the same
+ *     cast (normal_map is not bounded by 1: -1.5 -> 255, 300.7 -> 44);
+ *   depth_est (n_pixels) float32 = depth_values * scale_factor, one float32 multiply (:240);
+ *   acc (n_pixels) float32 = the row sums of weights (:258) in one fixed order (it depends on n_samples and the row
+ *     index modulo 4 only): bit-identical run to run, within (S-1) 2^-24 sum|w| of the exact sum.
+ *   n_pixels in 1..2^26, n_samples in 1..16384.  weights is read with 16-byte loads when it is 16-byte aligned.
+ * svs_view_depth_colors: the colour step of visualize_depth / visualize_cmap / matte (plots.py:392-468) for an image of
+ *   `width` columns (n_pixels a multiple of it).  depth (n_pixels) float32: the UNSCALED depth_values; acc (n_pixels);
+ *   lo, hi: the two bounds in depth units (weighted percentile -/+ float32 eps, found by the caller);
+ *   table (table_len,3) float64 DEVICE: the colour table (matplotlib's turbo: 256 rows) -> codes (n_pixels,3) uint8:
+ *   v = nan_to_num(clip((c(depth) - min(c(lo),c(hi))) / |c(hi) - c(lo)|, 0, 1)) with c(x) = -log(x + eps_f32), row
+ *   int(v * table_len) of the table (v = 1: the last row), times acc plus the 8-pixel checker (0.8 / 1.0) times the
+ *   float32 (1 - acc), times 255, the cast above.  Evaluated in float64, as numpy evaluates it. */
+int svs_view_finish(const float* rgb_values, const float* normal_map, const float* depth_values, const float* weights,
+                    int n_pixels, int n_samples, float scale_factor, uint8_t* rgb_codes, uint8_t* normal_codes,
+                    float* depth_est, float* acc, void* hip_stream);
+int svs_view_depth_colors(const float* depth, const float* acc, int n_pixels, int width, double lo, double hi,
+                          const double* table, int table_len, uint8_t* codes, void* hip_stream);
+
 /* ---- f4  Chamfer evaluator on point clouds (evals/eval_dtu.py:100-176) ---------------------------------------------
  * All clouds are (n,3) float64 (what open3d hands the reference).  One structure serves both neighbour problems:
  * points sorted by uniform-grid cell + a hash from cell to its run; grid_ws: svs_cloud_grid_bytes(n_points of the

@@ -135,6 +135,8 @@ SIGNATURES = {
     "svs_scene_resize_cubic": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P]),
     "svs_scene_smooth": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P]),
     "svs_scene_mask": (c_int, [_P, c_float, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P]),
+    "svs_view_finish": (c_int, [_P, _P, _P, _P, c_int, c_int, c_float, _P, _P, _P, _P, _P]),
+    "svs_view_depth_colors": (c_int, [_P, _P, c_int, c_int, c_double, c_double, _P, c_int, _P, _P]),
     "svs_warp_variance": (c_int, [_P, _PP, POINTER(c_float), c_int, c_int, c_int, c_int, c_int, _P, _P, c_int, _P]),
     "svs_conv3d": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "svs_conv3d_mfma_wfrag_bytes": (c_size_t, [c_int]),

@@ -80,7 +80,27 @@ def _image_paths(image_dir):
     return sorted(paths)
 
 
-def load_gt(data_dir_root, dataset, scan, views, img_res=IMG_RES, mask=None):
+def _gt_from_scene(scene, views, img_res, mask):
+    """gt codes and masks of `views` from a loaded svs_hip.scene.SceneDataset (its images are float32 (H*W,3) in the
+    reference's units; a native-size image is code * (1/255), so rint(rgb * 255) is the file's code exactly)."""
+    H, W = int(img_res[0]), int(img_res[1])
+    if (int(scene.img_res[0]), int(scene.img_res[1])) != (H, W):
+        raise ValueError(f"the dataset was loaded at {tuple(scene.img_res)}, img_res is {(H, W)}")
+    gts, masks = [], []
+    for v in views:
+        v = int(v)
+        if not 0 <= v < scene.n_images:
+            raise IndexError(f"view {v}: the scan holds {scene.n_images} images")
+        rgb = scene.rgb_images[v].numpy().astype(np.float64).reshape(H, W, 3)
+        gts.append(np.clip(np.rint(rgb * 255.0), 0, 255).astype(np.uint8))
+        if mask:
+            masks.append((scene.masks[v].numpy().reshape(H, W, 3) == 1.0).astype(np.uint8))
+        else:
+            masks.append(np.ones((H, W, 3), np.uint8))
+    return np.stack(gts), np.stack(masks)
+
+
+def load_gt(data_dir_root, dataset, scan, views, img_res=IMG_RES, mask=None, scene=None):
     """The ground truth and masks SceneDataset (scene_dataset.py:113-206) holds for the given views of one scan.
     -> gt (V,H,W,3) uint8 codes (load_rgb's values are code / 255), mask (V,H,W,3) uint8 0/1.
 
@@ -89,10 +109,19 @@ def load_gt(data_dir_root, dataset, scan, views, img_res=IMG_RES, mask=None):
     for the scan), inside where a channel is 255; BlendedMVS reads eval_mask/scan{S}/mask/{v:08d}.png (RGBA), inside
     where alpha / 255 > 0.5, for all three channels.  mask=None follows the reference: masked, except the DTU scans
     1, 4, 11, 13 and 48 (all ones); True / False force it.  The views are the scored (evaluation) views: the reference
-    reads DTU masks only for its evaluation ids and BlendedMVS masks for its evaluation and training ids."""
+    reads DTU masks only for its evaluation ids and BlendedMVS masks for its evaluation and training ids.
+
+    scene: a svs_hip.scene.SceneDataset of that scan loaded at img_res.  Images and masks are then taken from it instead
+    of the files, which covers ground truth that is not stored at img_res (the dataset resizes it as the reference does).
+    The scorer works on 8-bit codes: a resized image is rounded to the nearest code (at most 0.5 / 255 from the float
+    ground truth the reference scores against); a native-size image gives the file's codes exactly."""
     if dataset not in DATASETS:
         raise NotImplementedError(f"dataset {dataset!r}: only {DATASETS}")
     scan = int(scan)
+    if scene is not None:
+        if mask is None:
+            mask = not (dataset == "DTU" and scan in DTU_UNMASKED_SCANS)
+        return _gt_from_scene(scene, views, img_res, mask)
     inst = os.path.join(data_dir_root, dataset, f"scan{scan}")
     paths = _image_paths(os.path.join(inst, "image"))
     if mask is None:
@@ -145,9 +174,10 @@ def prediction_path(rendering_dir, view, result_from="blend"):
     raise NotImplementedError(f"result_from {result_from!r}: 'blend' or 'default'")
 
 
-def score_scan(rendering_dir, data_dir_root, dataset, scan, views, result_from="blend", img_res=IMG_RES, mask=None):
+def score_scan(rendering_dir, data_dir_root, dataset, scan, views, result_from="blend", img_res=IMG_RES, mask=None,
+               scene=None):
     """Scores the rendered views of one scan against its ground truth (eval_vsdf.py:186-212 for explicit view ids).
-    -> dict(views, psnr, ssim): float64 arrays in view order."""
+    scene: see load_gt.  -> dict(views, psnr, ssim): float64 arrays in view order."""
     views = [int(v) for v in views]
     if not views:
         raise ValueError("no views to score")
@@ -159,7 +189,7 @@ def score_scan(rendering_dir, data_dir_root, dataset, scan, views, result_from="
             raise ValueError(f"{fn}: expected an 8-bit RGB image, got {p.dtype} {p.shape}")
         _check_size(p, img_res, fn)
         preds.append(p)
-    gt, m = load_gt(data_dir_root, dataset, scan, views, img_res=img_res, mask=mask)
+    gt, m = load_gt(data_dir_root, dataset, scan, views, img_res=img_res, mask=mask, scene=scene)
     psnr, ssim = score_views(np.stack(preds), gt, m)
     return dict(views=np.asarray(views), psnr=psnr, ssim=ssim)
 
