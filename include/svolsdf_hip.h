@@ -565,6 +565,37 @@ int svs_scene_smooth(const float* img, int V, int H, int W, void* workspace, flo
 int svs_scene_mask(const uint8_t* mask, float divisor, int V, int Hs, int Ws, int H, int W, const int* xofs,
                    const float* xcoef, const int* yofs, const float* ycoef, float* out, void* hip_stream);
 
+/* ---- f8  from the MVS network's outputs to the default-config point cloud (runner.py:267-271, :362-368) --------------
+ * The evaluation mask of filter_depth (eval_mask: true in config/base.yaml) and the confidence map it thresholds, which
+ * the reference computes on the host with scikit-image and OpenCV.  Every argument is checked before the first launch: a
+ * rejected call (SVS_EINVAL: null pointer, misaligned workspace, V < 1 or > 65535, radius outside 0..32; SVS_ESHAPE: a
+ * size below 1, more than 65535 rows or more than 2^26 pixels) writes nothing.  Per-axis tables as in f6 (linear).
+ * svs_mask_dilate_disk: runner.py:365 -- skimage.morphology.binary_dilation(mask, disk(radius)) =
+ *   scipy.ndimage.binary_dilation(mask != 0, structure=disk(radius)), border value 0; disk(r) = x^2 + y^2 <= r^2 on the
+ *   integer grid (441 taps for r = 12).  mask (V,Hs,Ws) uint8, a pixel is set iff its code is non-zero -> out (V,Hs,Ws)
+ *   uint8 0/1 (out may alias mask); radius 0: out = mask != 0.  workspace: svs_mask_dilate_workspace_bytes(), 8-byte
+ *   aligned (the bit-packed rows and their dilation).  Bit-exact.
+ * svs_mask_resize_any: runner.py:366-368 -- cv2.resize(mask * 1., (W,H)) > 0. for a 0/1 mask (float64 INTER_LINEAR of
+ *   non-negative values with non-negative weights: no cancellation), i.e. a destination pixel is set iff one of its
+ *   2x2 taps is set and that tap's row and column weights are both non-zero.  mask (V,Hs,Ws) uint8 -> out (V,H,W) uint8
+ *   0/1.  Hs == H and Ws == W: out = mask != 0 (the tables may be null).  Bit-exact against that rule.
+ * svs_mvs_confidence: runner.py:267-271 -- conf_final = cv2.resize(conf_1, (W,H)) * cv2.resize(conf_2, (W,H)) *
+ *   cv2.resize(photometric_confidence, (W,H)).  conf_k (Hk,Wk) float32 with its own linear tables to (H,W) -> out (H,W)
+ *   float32 = (r1 * r2) * r3; r_k: the horizontal pass S[x0] a0 + S[x1] a1 on both source rows, then R0 b0 + R1 b1, each
+ *   product and sum rounded to float32 on its own (no fma); a map of size (H,W) is taken as it is (its tables may be
+ *   null).  One launch.  UNPINNED: whether OpenCV's own float32 path contracts to fma depends on its build
+ *   (INTEGRATION.md gives the call to check it against). */
+size_t svs_mask_dilate_workspace_bytes(int V, int Hs, int Ws);
+int svs_mask_dilate_disk(const uint8_t* mask, int V, int Hs, int Ws, int radius, void* workspace, uint8_t* out,
+                         void* hip_stream);
+int svs_mask_resize_any(const uint8_t* mask, int V, int Hs, int Ws, int H, int W, const int* xofs, const float* xcoef,
+                        const int* yofs, const float* ycoef, uint8_t* out, void* hip_stream);
+int svs_mvs_confidence(const float* conf1, int H1, int W1, const int* xofs1, const float* xcoef1, const int* yofs1,
+                       const float* ycoef1, const float* conf2, int H2, int W2, const int* xofs2, const float* xcoef2,
+                       const int* yofs2, const float* ycoef2, const float* conf3, int H3, int W3, const int* xofs3,
+                       const float* xcoef3, const int* yofs3, const float* ycoef3, int H, int W, float* out,
+                       void* hip_stream);
+
 /* ---- f7  the finish of an evaluation view (eval_vsdf.py:230-262, volsdf/utils/plots.py:392-468) ----------------------
  * What the reference does in numpy on the host after merge_output, on the render's device tensors.  Every argument is
  * checked before the launch: a rejected call (SVS_EINVAL: null pointer; SVS_ESHAPE: a size) writes nothing.

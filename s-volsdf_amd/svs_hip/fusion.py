@@ -214,7 +214,8 @@ def filter_depth(views, pairs, conf=0.0, filter_dist=1, filter_diff=0.01, thres_
                  mask_dir=None):
     """filter_depth (runner.py:301-401) on in-memory views.  views: {view_id: dict(K, E, img, depth, confidence)},
     pairs: [(ref_view, [src_view, ...]), ...] (runner.py:303-305 builds all-vs-all pairs of the training views),
-    eval_masks: optional {view_id: (H,W) mask} already dilated / resized (runner.py:349-368 is image preprocessing).
+    eval_masks: optional {view_id: (H,W) mask}, dilated and resized (runner.py:349-368): arrays, or the device tensors of
+    `svs_hip.mvsout.eval_mask`, which does both on the GPU.
     Returns (vertices (n,3) float32, colours (n,3) uint8, per-view stats); writes the PLY if plyfilename is given and
     the three masks per view under mask_dir."""
     from helpers.utils import save_mask
@@ -239,9 +240,12 @@ def filter_depth(views, pairs, conf=0.0, filter_dist=1, filter_diff=0.01, thres_
 
 
 def filter_depth_folder(scan_folder, out_folder, plyfilename, view_ids, conf=0.0, filter_dist=1, filter_diff=0.01,
-                        thres_view=1):
+                        thres_view=1, *, eval_mask_root=None, dataset=None, eval_mask_radius=12):
     """The file-level form (runner.py:301-332): cams/{id:08}_cam.txt and images/{id:08}.jpg under scan_folder,
-    depth_est/ and confidence/ PFMs under out_folder; all-vs-all pairs of view_ids."""
+    depth_est/ and confidence/ PFMs under out_folder; all-vs-all pairs of view_ids.  With eval_mask_root (the reference's
+    data_dir_root; `dataset` 'DTU' or 'BlendedMVS') every view's final mask is cut by its evaluation mask, as with the
+    reference's default eval_mask: true (runner.py:350-368): the file of `svs_hip.mvsout.eval_mask_path` for the scan
+    named by out_folder's last component, dilated by disk(eval_mask_radius) and resized to the depth map on the GPU."""
     from datasets.data_io import read_pfm
     from helpers.utils import read_camera_parameters, read_img
     views = {}
@@ -251,5 +255,11 @@ def filter_depth_folder(scan_folder, out_folder, plyfilename, view_ids, conf=0.0
                         depth=np.ascontiguousarray(read_pfm(os.path.join(out_folder, "depth_est/{:0>8}.pfm".format(v)))[0]),
                         confidence=np.ascontiguousarray(read_pfm(os.path.join(out_folder, "confidence/{:0>8}.pfm".format(v)))[0]))
     pairs = [(v, [x for x in view_ids if x != v]) for v in view_ids]
-    return filter_depth(views, pairs, conf, filter_dist, filter_diff, thres_view, plyfilename,
+    eval_masks = None
+    if eval_mask_root is not None:
+        from . import mvsout
+        scan_name = os.path.normpath(out_folder).split(os.sep)[-1]
+        eval_masks = mvsout.folder_eval_masks(eval_mask_root, dataset, scan_name, view_ids,
+                                              {v: views[v]["depth"].shape for v in view_ids}, radius=eval_mask_radius)
+    return filter_depth(views, pairs, conf, filter_dist, filter_diff, thres_view, plyfilename, eval_masks=eval_masks,
                         mask_dir=os.path.join(out_folder, "mask"))
