@@ -16,10 +16,12 @@
 //   blend:   pyrDown to levels 1..3 for every image and mask plane at once, then per level the blended Laplacian
 //            sum_j m_jl (g_jl - up(g_j,l+1)) plus up(out_l+1), with every up() formed on the fly.
 // Memory- and latency-bound gathers and stencils: no matrix cores.
-#include "svs_common.h"
+#include "svs_image.h"
 
 namespace svs {
 namespace ibr {
+
+using namespace svs::image;
 
 constexpr int kMaxSrc = 16;
 constexpr int kLevels = 4;            // Laplacian_Blending(num_levels=4): levels 0..3 are used
@@ -247,12 +249,7 @@ __global__ __launch_bounds__(kErodeTile * kErodeTile) void ibr_erode_kernel(Erod
   a.masks[ol] = ml / sum;
 }
 
-// ---- Gaussian pyramid: cv2.pyrDown, BORDER_REFLECT_101 ---------------------------------------------------------------
-__device__ __forceinline__ int reflect101(int p, int len) {
-  if (len == 1) return 0;
-  while ((unsigned)p >= (unsigned)len) p = p < 0 ? -p : 2 * len - 2 - p;
-  return p;
-}
+// ---- Gaussian pyramid: cv2.pyrDown, BORDER_REFLECT_101 (a level may be narrower than the 2-pixel halo) ------------------
 
 struct DownArgs {
   const float* img;                   // (nj,h,w,3)
@@ -275,8 +272,8 @@ __global__ __launch_bounds__(256) void ibr_pyr_down_kernel(DownArgs a) {
   int rows[5], cols[5];
 #pragma unroll
   for (int k = 0; k < 5; ++k) {
-    rows[k] = reflect101(2 * y - 2 + k, a.h);
-    cols[k] = reflect101(2 * x - 2 + k, a.w);
+    rows[k] = reflect101_any(2 * y - 2 + k, a.h);
+    cols[k] = reflect101_any(2 * x - 2 + k, a.w);
   }
   const size_t base = (size_t)j * a.h * a.w;
   float acc[4], r[5];
@@ -312,12 +309,12 @@ __device__ __forceinline__ void up_tap(int Y, int X, int h, int w, UpTap& t) {
   const int yy = Y >> 1, xx = X >> 1;
   t.odd_row = Y & 1;
   if (!t.odd_row) {
-    t.rows[0] = reflect101(2 * (yy - 1), 2 * h) >> 1;
+    t.rows[0] = reflect101_any(2 * (yy - 1), 2 * h) >> 1;
     t.rows[1] = yy;
-    t.rows[2] = reflect101(2 * (yy + 1), 2 * h) >> 1;
+    t.rows[2] = reflect101_any(2 * (yy + 1), 2 * h) >> 1;
   } else {
     t.rows[0] = yy;
-    t.rows[1] = reflect101(2 * (yy + 1), 2 * h) >> 1;
+    t.rows[1] = reflect101_any(2 * (yy + 1), 2 * h) >> 1;
     t.rows[2] = yy;
   }
   t.cols[0] = xx - 1; t.cols[1] = xx; t.cols[2] = xx + 1;
@@ -397,10 +394,9 @@ __global__ __launch_bounds__(256) void ibr_blend_level_kernel(BlendArgs a) {
 }
 
 inline int check_sizes(const char* what, int n_src, int H, int W) {
-  if (n_src < 1 || n_src > kMaxSrc) { set_error("%s: n_src must be 1..%d", what, kMaxSrc); return SVS_EINVAL; }
-  if (H < 8 || W < 8 || (H & 7) || (W & 7) || (long long)H * W > (1LL << 26)) {
-    set_error("%s: H and W must be positive multiples of 8 (H*W <= 2^26)", what); return SVS_ESHAPE;
-  }
+  int rc = check_count(what, "n_src", n_src, kMaxSrc);
+  if (rc || (rc = check_image(what, "H and W", H, W, 8))) return rc;
+  if ((H & 7) || (W & 7)) { set_error("%s: H and W must be multiples of 8", what); return SVS_ESHAPE; }
   return SVS_OK;
 }
 

@@ -13,7 +13,7 @@
 //   (one thread per word), unpack.  A pure boolean function of the input: bit-exact.
 // svs_mask_resize_any = cv2.resize(mask * 1., (W,H)) > 0. (runner.py:366-368; float64 INTER_LINEAR).  Inputs and weights
 //   are non-negative, so nothing cancels: a destination pixel is set iff one of its 2x2 taps is set and that tap's row
-//   weight and column weight are both non-zero.  Taps and weights: svs_hip/scene.py::linear_table (tap indices clamped one
+//   weight and column weight are both non-zero.  Taps and weights: svs_hip/images.py::linear_table (tap indices clamped one
 //   by one).  Equal sizes: mask != 0.
 // svs_mvs_confidence = conf_1 * conf_2 * photometric_confidence of the three maps resized to (H,W) with cv2.resize
 //   (INTER_LINEAR, float32; runner.py:267-271): per map the horizontal pass S[x0] a0 + S[x1] a1 on the two source rows,
@@ -22,18 +22,18 @@
 //   path may contract to fma depending on its build (INTEGRATION.md gives the cv2 call to check it against).
 //
 // All of it is bandwidth-trivial (2 MB per 1200x1600 mask; the packed rows of a mask are 240 KB and stay in L2).
-#include "svs_common.h"
+#include "svs_image.h"
 
 namespace svs {
 namespace mvsout {
+
+using namespace svs::image;
 
 constexpr int kThreads = 256;
 constexpr int kWave = 64;
 constexpr int kMaxRadius = 32;                          // < 64: a shifted word needs its direct neighbours only
 
 struct Disk { unsigned char h[kMaxRadius + 1]; };       // h[k] = isqrt(r^2 - k^2), k = 0..r
-
-__device__ __forceinline__ int clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 
 // one wave per word: lane l holds pixel 64 q + l.  grid: (ceil(Wq / 4), Hs, V)
 __global__ __launch_bounds__(kThreads) void pack_kernel(const uint8_t* __restrict__ mask, unsigned long long* __restrict__ bits,
@@ -87,8 +87,7 @@ __global__ __launch_bounds__(kThreads) void unpack_kernel(const unsigned long lo
 
 struct ResizeArgs {
   const uint8_t* src;                                   // (V,Hs,Ws)
-  const int* xofs; const float* xcoef;                  // (W), (W,2)
-  const int* yofs; const float* ycoef;                  // (H), (H,2)
+  Axis2 x, y;                                           // (W), (H)
   uint8_t* dst;                                         // (V,H,W)
   int Hs, Ws, H, W;
 };
@@ -97,15 +96,13 @@ struct ResizeArgs {
 __global__ __launch_bounds__(kThreads) void resize_any_kernel(ResizeArgs a) {
   const int x = blockIdx.x * kThreads + threadIdx.x, y = blockIdx.y, v = blockIdx.z;
   if (x >= a.W) return;
-  const int sx = a.xofs[x], sy = a.yofs[y];
-  const int x0 = clampi(sx, a.Ws - 1), x1 = clampi(sx + 1, a.Ws - 1);
+  const Taps2 tx = taps2(a.x, x, a.Ws), ty = taps2(a.y, y, a.Hs);
   const uint8_t* img = a.src + (size_t)v * a.Hs * a.Ws;
-  const uint8_t* r0 = img + (size_t)clampi(sy, a.Hs - 1) * a.Ws;
-  const uint8_t* r1 = img + (size_t)clampi(sy + 1, a.Hs - 1) * a.Ws;
-  const bool cx0 = a.xcoef[2 * x] != 0.0f, cx1 = a.xcoef[2 * x + 1] != 0.0f;
-  const bool cy0 = a.ycoef[2 * y] != 0.0f, cy1 = a.ycoef[2 * y + 1] != 0.0f;
-  const bool h0 = (cx0 && r0[x0] != 0) || (cx1 && r0[x1] != 0);
-  const bool h1 = (cx0 && r1[x0] != 0) || (cx1 && r1[x1] != 0);
+  const uint8_t* r0 = img + (size_t)ty.i0 * a.Ws;
+  const uint8_t* r1 = img + (size_t)ty.i1 * a.Ws;
+  const bool cx0 = tx.w0 != 0.0f, cx1 = tx.w1 != 0.0f, cy0 = ty.w0 != 0.0f, cy1 = ty.w1 != 0.0f;
+  const bool h0 = (cx0 && r0[tx.i0] != 0) || (cx1 && r0[tx.i1] != 0);
+  const bool h1 = (cx0 && r1[tx.i0] != 0) || (cx1 && r1[tx.i1] != 0);
   a.dst[((size_t)v * a.H + y) * a.W + x] = (uint8_t)((cy0 && h0) || (cy1 && h1));
 }
 
@@ -116,22 +113,19 @@ __global__ __launch_bounds__(kThreads) void nonzero_kernel(const uint8_t* __rest
 
 struct ConfMap {
   const float* src;                                     // (Hk,Wk)
-  const int* xofs; const float* xcoef;                  // (W), (W,2); unused when the map has the size (H,W)
-  const int* yofs; const float* ycoef;                  // (H), (H,2)
+  Axis2 x, y;                                           // (W), (H); unused when the map has the size (H,W)
   int Hk, Wk;
 };
 struct ConfArgs { ConfMap m[3]; float* dst; int H, W; };
 
 __device__ __forceinline__ float resized(const ConfMap& m, int x, int y, int H, int W) {
   if (m.Hk == H && m.Wk == W) return m.src[(size_t)y * W + x];
-  const int sx = m.xofs[x], sy = m.yofs[y];
-  const int x0 = clampi(sx, m.Wk - 1), x1 = clampi(sx + 1, m.Wk - 1);
-  const float* r0 = m.src + (size_t)clampi(sy, m.Hk - 1) * m.Wk;
-  const float* r1 = m.src + (size_t)clampi(sy + 1, m.Hk - 1) * m.Wk;
-  const float a0 = m.xcoef[2 * x], a1 = m.xcoef[2 * x + 1], b0 = m.ycoef[2 * y], b1 = m.ycoef[2 * y + 1];
-  const float h0 = __fadd_rn(__fmul_rn(r0[x0], a0), __fmul_rn(r0[x1], a1));
-  const float h1 = __fadd_rn(__fmul_rn(r1[x0], a0), __fmul_rn(r1[x1], a1));
-  return __fadd_rn(__fmul_rn(h0, b0), __fmul_rn(h1, b1));
+  const Taps2 tx = taps2(m.x, x, m.Wk), ty = taps2(m.y, y, m.Hk);
+  const float* r0 = m.src + (size_t)ty.i0 * m.Wk;
+  const float* r1 = m.src + (size_t)ty.i1 * m.Wk;
+  const float h0 = __fadd_rn(__fmul_rn(r0[tx.i0], tx.w0), __fmul_rn(r0[tx.i1], tx.w1));
+  const float h1 = __fadd_rn(__fmul_rn(r1[tx.i0], tx.w0), __fmul_rn(r1[tx.i1], tx.w1));
+  return __fadd_rn(__fmul_rn(h0, ty.w0), __fmul_rn(h1, ty.w1));
 }
 
 // grid: (ceil(W / kThreads), H)
@@ -149,16 +143,10 @@ inline int isqrt_int(int n) {
   return s;
 }
 
-inline int check_image(const char* what, const char* names, int H, int W) {
-  if (H < 1 || W < 1 || (long long)H * W > (1LL << 26) || H > 65535) {
-    set_error("%s: %s must be >= 1 with at most 65535 rows and 2^26 pixels", what, names); return SVS_ESHAPE;
-  }
-  return SVS_OK;
-}
-
-inline int check_views(const char* what, int V) {
-  if (V < 1 || V > 65535) { set_error("%s: V must be in 1..65535", what); return SVS_EINVAL; }
-  return SVS_OK;
+// an image whose rows are a launch-grid dimension
+inline int check_rows(const char* what, const char* names, int H, int W) {
+  const int rc = check_image(what, names, H, W);
+  return rc ? rc : check_grid_dim(what, "the number of rows", H);
 }
 
 inline size_t words_per_row(int Ws) { return ((size_t)Ws + kWave - 1) / kWave; }
@@ -182,8 +170,8 @@ int svs_mask_dilate_disk(const uint8_t* mask, int V, int Hs, int Ws, int radius,
   if (!mask || !workspace || !out) { set_error("%s: null argument", what); return SVS_EINVAL; }
   if (((uintptr_t)workspace & 7) != 0) { set_error("%s: workspace must be 8-byte aligned", what); return SVS_EINVAL; }
   if (radius < 0 || radius > kMaxRadius) { set_error("%s: radius must be in 0..%d", what, kMaxRadius); return SVS_EINVAL; }
-  int rc = check_views(what, V);
-  if (rc || (rc = check_image(what, "Hs and Ws", Hs, Ws))) return rc;
+  int rc = check_count(what, "V", V, kMaxGridDim);
+  if (rc || (rc = check_rows(what, "Hs and Ws", Hs, Ws))) return rc;
   hipStream_t s = (hipStream_t)hip_stream;
   const int Wq = (int)words_per_row(Ws);
   const size_t n_words = (size_t)V * Hs * Wq;
@@ -205,8 +193,8 @@ int svs_mask_resize_any(const uint8_t* mask, int V, int Hs, int Ws, int H, int W
                         const int* yofs, const float* ycoef, uint8_t* out, void* hip_stream) {
   const char* what = "svs_mask_resize_any";
   if (!mask || !out) { set_error("%s: null argument", what); return SVS_EINVAL; }
-  int rc = check_views(what, V);
-  if (rc || (rc = check_image(what, "Hs and Ws", Hs, Ws)) || (rc = check_image(what, "H and W", H, W))) return rc;
+  int rc = check_count(what, "V", V, kMaxGridDim);
+  if (rc || (rc = check_rows(what, "Hs and Ws", Hs, Ws)) || (rc = check_rows(what, "H and W", H, W))) return rc;
   hipStream_t s = (hipStream_t)hip_stream;
   if (Hs == H && Ws == W) {
     const size_t n = (size_t)V * H * W;
@@ -215,7 +203,7 @@ int svs_mask_resize_any(const uint8_t* mask, int V, int Hs, int Ws, int H, int W
     return check_launch(what);
   }
   if (!xofs || !xcoef || !yofs || !ycoef) { set_error("%s: null table", what); return SVS_EINVAL; }
-  ResizeArgs a{mask, xofs, xcoef, yofs, ycoef, out, Hs, Ws, H, W};
+  ResizeArgs a{mask, {xofs, xcoef}, {yofs, ycoef}, out, Hs, Ws, H, W};
   resize_any_kernel<<<dim3((W + kThreads - 1) / kThreads, H, V), kThreads, 0, s>>>(a);
   return check_launch(what);
 }
@@ -226,14 +214,14 @@ int svs_mvs_confidence(const float* conf1, int H1, int W1, const int* xofs1, con
                        const float* xcoef3, const int* yofs3, const float* ycoef3, int H, int W, float* out,
                        void* hip_stream) {
   const char* what = "svs_mvs_confidence";
-  ConfArgs a{{{conf1, xofs1, xcoef1, yofs1, ycoef1, H1, W1}, {conf2, xofs2, xcoef2, yofs2, ycoef2, H2, W2},
-              {conf3, xofs3, xcoef3, yofs3, ycoef3, H3, W3}}, out, H, W};
+  ConfArgs a{{{conf1, {xofs1, xcoef1}, {yofs1, ycoef1}, H1, W1}, {conf2, {xofs2, xcoef2}, {yofs2, ycoef2}, H2, W2},
+              {conf3, {xofs3, xcoef3}, {yofs3, ycoef3}, H3, W3}}, out, H, W};
   if (!conf1 || !conf2 || !conf3 || !out) { set_error("%s: null argument", what); return SVS_EINVAL; }
-  int rc = check_image(what, "H and W", H, W);
+  int rc = check_rows(what, "H and W", H, W);
   if (rc) return rc;
   for (const ConfMap& m : a.m) {
-    if ((rc = check_image(what, "every map's size", m.Hk, m.Wk))) return rc;
-    if ((m.Hk != H || m.Wk != W) && (!m.xofs || !m.xcoef || !m.yofs || !m.ycoef)) {
+    if ((rc = check_rows(what, "every map's size", m.Hk, m.Wk))) return rc;
+    if ((m.Hk != H || m.Wk != W) && (!m.x.ofs || !m.x.coef || !m.y.ofs || !m.y.coef)) {
       set_error("%s: null table of a map that is resized", what); return SVS_EINVAL;
     }
   }

@@ -5,7 +5,7 @@
 // svs_scene_resize_cubic = cv2.resize(code * (1/255), (W,H), interpolation=cv2.INTER_CUBIC) of 8-bit RGB codes: a
 //   separable 4-tap filter (Keys' cubic, A = -0.75), source coordinate (d + 0.5) * scale - 0.5, every tap index clamped
 //   to the image on its own, no prefilter when shrinking.  As OpenCV does, the HOST builds one table per axis (the
-//   first tap's index and four float32 coefficients per destination column / row: svs_hip/scene.py::cubic_table) and
+//   first tap's index and four float32 coefficients per destination column / row: svs_hip/images.py::cubic_table) and
 //   the kernel only gathers: rows first, h_r = ((p0 c0 + p1 c1) + p2 c2) + p3 c3 for the four source rows, then the
 //   same sum down the rows, float32, no fma contraction.  load_rgb's img_as_float32 MULTIPLIES the code by float32
 //   (1/255) (it does not divide; the two differ by one ulp at some codes): so does this.  Equal sizes: code * (1/255)
@@ -14,19 +14,21 @@
 //   normalised in float64, rounded to float32: 0.03197 .. 0.03242), BORDER_REFLECT_101 on both axes, rows first, then
 //   columns, float32 intermediate (the workspace).  Each pass sums as OpenCV's symmetric filters do: w15 x0 +
 //   sum_k w(15+k) (x(+k) + x(-k)), k = 1..15 in order.  One LDS tile with a 15-pixel halo per workgroup and axis.
-//   H, W >= 16: a single reflection covers the halo.
+//   H, W >= 16: a single reflection covers the halo (svs_image.h::reflect101_once).
 // svs_scene_mask = the reference's cv2.resize(mask, (W,H), cv2.INTER_NEAREST) followed by > 0.5.  The third POSITIONAL
 //   parameter of cv2.resize is dst, not interpolation, so the interpolation that runs is the default INTER_LINEAR
 //   (UNPINNED: no OpenCV at hand to confirm it): 2 taps per axis, the same coordinate rule, indices
-//   clamped, tables of the first index and two float32 weights from the host (svs_hip/scene.py::linear_table).  The
+//   clamped, tables of the first index and two float32 weights from the host (svs_hip/images.py::linear_table).  The
 //   8-bit single-channel input is divided by `divisor` in float32 first (1 for a 0/1 mask, 255 for the BlendedMVS alpha
 //   channel, which the reference interpolates before it thresholds); the 0/1 result goes to all three channels.
 //
 // All three are bandwidth-trivial (about 20 MB of traffic per 576x768 view); plain vector loads and stores.
-#include "svs_common.h"
+#include "svs_image.h"
 
 namespace svs {
 namespace scene {
+
+using namespace svs::image;
 
 constexpr int kThreads = 256;
 constexpr int kR = 15;                                  // Gaussian radius: ksize 31
@@ -38,9 +40,6 @@ constexpr int kRowW = 256, kRowH = 8, kRowHalo = 3 * kR;
 constexpr int kColW = 64, kColH = 64, kColPer = kColH / (kThreads / kColW);
 
 struct Weights { float w[kR + 1]; };                    // w[k]: the weight at distance k from the centre
-
-__device__ __forceinline__ int clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
-__device__ __forceinline__ int reflect101(int v, int n) { return v < 0 ? -v : (v >= n ? 2 * n - 2 - v : v); }
 
 struct CubicArgs {
   const uint8_t* src;                                   // (V,Hs,Ws,3)
@@ -90,8 +89,7 @@ __global__ __launch_bounds__(kThreads) void codes_to_float_kernel(const uint8_t*
 
 struct MaskArgs {
   const uint8_t* src;                                   // (V,Hs,Ws)
-  const int* xofs; const float* xcoef;                  // (W), (W,2)
-  const int* yofs; const float* ycoef;                  // (H), (H,2)
+  Axis2 x, y;                                           // (W), (H)
   float* dst;                                           // (V,H,W,3)
   int Hs, Ws, H, W;
   float divisor;
@@ -100,15 +98,13 @@ struct MaskArgs {
 __global__ __launch_bounds__(kThreads) void mask_kernel(MaskArgs a) {
   const int x = blockIdx.x * kThreads + threadIdx.x, y = blockIdx.y, v = blockIdx.z;
   if (x >= a.W) return;
-  const int sx = a.xofs[x], sy = a.yofs[y];
-  const int x0 = clampi(sx, a.Ws - 1), x1 = clampi(sx + 1, a.Ws - 1);
+  const Taps2 tx = taps2(a.x, x, a.Ws), ty = taps2(a.y, y, a.Hs);
   const uint8_t* img = a.src + (size_t)v * a.Hs * a.Ws;
-  const uint8_t* r0 = img + (size_t)clampi(sy, a.Hs - 1) * a.Ws;
-  const uint8_t* r1 = img + (size_t)clampi(sy + 1, a.Hs - 1) * a.Ws;
-  const float ax0 = a.xcoef[2 * x], ax1 = a.xcoef[2 * x + 1], ay0 = a.ycoef[2 * y], ay1 = a.ycoef[2 * y + 1];
-  const float h0 = ((float)r0[x0] / a.divisor) * ax0 + ((float)r0[x1] / a.divisor) * ax1;
-  const float h1 = ((float)r1[x0] / a.divisor) * ax0 + ((float)r1[x1] / a.divisor) * ax1;
-  const float m = (h0 * ay0 + h1 * ay1) > 0.5f ? 1.0f : 0.0f;
+  const uint8_t* r0 = img + (size_t)ty.i0 * a.Ws;
+  const uint8_t* r1 = img + (size_t)ty.i1 * a.Ws;
+  const float h0 = ((float)r0[tx.i0] / a.divisor) * tx.w0 + ((float)r0[tx.i1] / a.divisor) * tx.w1;
+  const float h1 = ((float)r1[tx.i0] / a.divisor) * tx.w0 + ((float)r1[tx.i1] / a.divisor) * tx.w1;
+  const float m = (h0 * ty.w0 + h1 * ty.w1) > 0.5f ? 1.0f : 0.0f;
   float* out = a.dst + (((size_t)v * a.H + y) * a.W + x) * 3;
   out[0] = m; out[1] = m; out[2] = m;
 }
@@ -127,7 +123,7 @@ __global__ __launch_bounds__(kThreads) void smooth_rows_kernel(const float* __re
     const int px = (e + 3 * kR) / 3 - kR, ch = e - 3 * px;
     const int y = y0 + r;
     float val = 0.0f;                                   // beyond what any pixel of the image reads
-    if (y < H && px < W + kR) val = src[img + (size_t)y * WF + reflect101(px, W) * 3 + ch];
+    if (y < H && px < W + kR) val = src[img + (size_t)y * WF + reflect101_once(px, W) * 3 + ch];
     tile[r][j] = val;
   }
   __syncthreads();
@@ -156,7 +152,7 @@ __global__ __launch_bounds__(kThreads) void smooth_cols_kernel(const float* __re
     const int r = i / kColW, c = i - r * kColW;
     const int y = y0 - kR + r, e = e0 + c;
     float val = 0.0f;
-    if (e < WF && y < H + kR) val = src[img + (size_t)reflect101(y, H) * WF + e];
+    if (e < WF && y < H + kR) val = src[img + (size_t)reflect101_once(y, H) * WF + e];
     tile[r][c] = val;
   }
   __syncthreads();
@@ -184,20 +180,12 @@ inline Weights gaussian_weights() {
   return w;
 }
 
+// V views of (H,W): H, W >= 16 (the 31-tap filter reflects once); V and H are launch-grid dimensions
 inline int check_dst(const char* what, int V, int H, int W) {
   if (V < 1) { set_error("%s: V must be >= 1", what); return SVS_EINVAL; }
-  if (H < kMinSize || W < kMinSize || (long long)H * W > (1LL << 26)) {
-    set_error("%s: H and W must be >= 16 (the 31-tap filter reflects once) with H*W <= 2^26", what); return SVS_ESHAPE;
-  }
-  if (V > 65535 || H > 65535) { set_error("%s: V and H must be <= 65535 (the launch grid)", what); return SVS_ESHAPE; }
-  return SVS_OK;
-}
-
-inline int check_src(const char* what, int Hs, int Ws) {
-  if (Hs < 1 || Ws < 1 || (long long)Hs * Ws > (1LL << 26)) {
-    set_error("%s: Hs and Ws must be >= 1 with Hs*Ws <= 2^26", what); return SVS_ESHAPE;
-  }
-  return SVS_OK;
+  int rc = check_image(what, "H and W", H, W, kMinSize);
+  if (rc || (rc = check_grid_dim(what, "V", V))) return rc;
+  return check_grid_dim(what, "H", H);
 }
 
 }  // namespace scene
@@ -218,7 +206,7 @@ int svs_scene_resize_cubic(const uint8_t* codes, int V, int Hs, int Ws, int H, i
   const char* what = "svs_scene_resize_cubic";
   if (!codes || !out) { set_error("%s: null argument", what); return SVS_EINVAL; }
   int rc = check_dst(what, V, H, W);
-  if (rc || (rc = check_src(what, Hs, Ws))) return rc;
+  if (rc || (rc = check_image(what, "Hs and Ws", Hs, Ws))) return rc;
   hipStream_t s = (hipStream_t)hip_stream;
   if (Hs == H && Ws == W) {
     const size_t n = (size_t)V * H * W * 3;
@@ -252,8 +240,8 @@ int svs_scene_mask(const uint8_t* mask, float divisor, int V, int Hs, int Ws, in
   if (!mask || !xofs || !xcoef || !yofs || !ycoef || !out) { set_error("%s: null argument", what); return SVS_EINVAL; }
   if (!(divisor > 0.0f)) { set_error("%s: divisor must be positive", what); return SVS_EINVAL; }
   int rc = check_dst(what, V, H, W);
-  if (rc || (rc = check_src(what, Hs, Ws))) return rc;
-  MaskArgs a{mask, xofs, xcoef, yofs, ycoef, out, Hs, Ws, H, W, divisor};
+  if (rc || (rc = check_image(what, "Hs and Ws", Hs, Ws))) return rc;
+  MaskArgs a{mask, {xofs, xcoef}, {yofs, ycoef}, out, Hs, Ws, H, W, divisor};
   mask_kernel<<<dim3((W + kThreads - 1) / kThreads, H, V), kThreads, 0, (hipStream_t)hip_stream>>>(a);
   return check_launch(what);
 }

@@ -26,7 +26,7 @@ import torch
 
 from . import lib as _lib
 from . import scene as _scene
-from .nvs import DATASETS, IMG_RES
+from .images import DATASETS, IMG_RES, device
 from .ops import _f32, _ptr, _stream
 from .renderer import render_image
 
@@ -272,9 +272,7 @@ def evaluate(ckpt, data_dir_root, dataset, scan, img_res=IMG_RES, evals_folder="
     views: explicit ids, or None for default_views().  ibr: the scan's MVS folder (cams/, images/): blends every view that
     is not a source from `src_views` (default: the training ids among the views) with svs_hip.ibr; score: svs_hip.nvs
     on those views ('blend' after ibr, 'default' otherwise).  -> dict(folder, epoch, views, written, seconds, scores)."""
-    if not torch.cuda.is_available():
-        raise _lib.SvsError("svs_hip.evalviews needs the GPU (there is no CPU fallback)")
-    dev = torch.device("cuda", torch.cuda.current_device())
+    dev = device("evalviews")
     sec = OrderedDict((k, 0.0) for k in ("load", "render", "finish", "write"))
     t0 = time.perf_counter()
     if views is None:

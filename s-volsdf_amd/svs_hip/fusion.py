@@ -13,17 +13,8 @@ import numpy as np
 import torch
 
 from . import lib as _lib
+from .images import device, to_device
 from .ops import _ptr, _ptr_array, _stream
-
-
-def _dev():
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def _to_dev(a, dtype):
-    if torch.is_tensor(a):
-        return a.detach().to(device=_dev(), dtype=dtype).contiguous()
-    return torch.from_numpy(np.ascontiguousarray(np.asarray(a), dtype=np.dtype(str(dtype).replace("torch.", "")))).to(_dev())
 
 
 def pair_matrices(K_ref, E_ref, K_src, E_src):
@@ -43,12 +34,12 @@ def fuse_view(ref, srcs, conf=0.0, filter_dist=1, filter_diff=0.01, thres_view=1
     and with points=True xyz (n,3) float32, rgb (n,3) uint8 (row-major order of the surviving pixels); with
     per_source=True also src_mask, src_depth_reproj, src_x, src_y (n_src,H,W)."""
     L = _lib.load()
-    dev = _dev()
-    depth = _to_dev(ref["depth"], torch.float32)
+    dev = device("fusion")
+    depth = to_device(ref["depth"], torch.float32, "fusion")
     H, W = depth.shape
-    confidence = _to_dev(ref["confidence"], torch.float32) if "confidence" in ref else torch.full((H, W), float("inf"), device=dev)
+    confidence = to_device(ref["confidence"], torch.float32, "fusion") if "confidence" in ref else torch.full((H, W), float("inf"), device=dev)
     n_src = len(srcs)
-    src_depths = [_to_dev(s["depth"], torch.float32) for s in srcs]
+    src_depths = [to_device(s["depth"], torch.float32, "fusion") for s in srcs]
     for d in src_depths:
         if tuple(d.shape) != (H, W):
             raise AssertionError("source depth map shape differs from the reference view's")     # runner.py:334
@@ -64,7 +55,7 @@ def fuse_view(ref, srcs, conf=0.0, filter_dist=1, filter_diff=0.01, thres_view=1
         out["src_mask"] = torch.empty(n_src, H, W, dtype=torch.uint8, device=dev)
         for k in ("src_depth_reproj", "src_x", "src_y"):
             out[k] = torch.empty(n_src, H, W, dtype=torch.float32, device=dev)
-    em = None if extra_mask is None else (_to_dev(extra_mask, torch.float32) > 0).to(torch.uint8).contiguous()
+    em = None if extra_mask is None else (to_device(extra_mask, torch.float32, "fusion") > 0).to(torch.uint8).contiguous()
     _lib.check(L.svs_fuse_view(_ptr(depth), _ptr(confidence), _ptr_array(src_depths), _ptr(mats_d), n_src, H, W,
                                float(conf), float(filter_dist), float(filter_diff), int(thres_view), _ptr(em),
                                _ptr(out["depth_avg"]), _ptr(out["photo_mask"]), _ptr(out["geo_mask"]), _ptr(out["final_mask"]),
@@ -74,7 +65,7 @@ def fuse_view(ref, srcs, conf=0.0, filter_dist=1, filter_diff=0.01, thres_view=1
         K, E = np.asarray(ref["K"]), np.asarray(ref["E"])
         pm = np.concatenate([np.asarray(np.linalg.inv(K), np.float64).reshape(-1), np.asarray(np.linalg.inv(E), np.float64).reshape(-1)])
         pm_d = torch.from_numpy(pm).to(dev)
-        img = _to_dev(ref["img"], torch.float32) if "img" in ref else None
+        img = to_device(ref["img"], torch.float32, "fusion") if "img" in ref else None
         if img is not None and tuple(img.shape) != (H, W, 3):
             raise AssertionError("reference image shape differs from its depth map's")            # runner.py:322
         ws = torch.empty(H * W, dtype=torch.int32, device=dev)

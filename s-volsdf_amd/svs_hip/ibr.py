@@ -16,7 +16,8 @@ import numpy as np
 import torch
 
 from . import lib as _lib
-from .fusion import fuse_view, _dev, _to_dev
+from .fusion import fuse_view
+from .images import device, to_device
 from .ops import _ptr, _ptr_array, _stream
 
 _UV = {}
@@ -31,7 +32,7 @@ def _uv_grid(H, W):
     key = (H, W, torch.cuda.current_device())
     if key not in _UV:
         y, x = np.mgrid[0:H, 0:W].astype(np.float32)
-        _UV[key] = torch.from_numpy(np.stack([x.ravel(), y.ravel()], 1)).to(_dev())
+        _UV[key] = torch.from_numpy(np.stack([x.ravel(), y.ravel()], 1)).to(device("ibr"))
     return _UV[key]
 
 
@@ -39,7 +40,7 @@ def ray_dirs(K, E, H, W):
     """get_dir_loc (simple_ibr.py:75-88): unit ray directions (H,W,3) float32 of the camera at every integer pixel.
     pose = inv(E) in float32 and the intrinsics in a 4x4, as the reference forms them."""
     L = _lib.load()
-    dev = _dev()
+    dev = device("ibr")
     intr = np.eye(4)
     intr[:3, :3] = np.asarray(K)
     pose = np.linalg.inv(np.asarray(E, np.float32))
@@ -78,13 +79,13 @@ def blend_view(ref, srcs, pred_img, return_stages=False):
     the fill images (n+1,H,W,3) and masks (n+1,H,W)."""
     H, W = check_shapes(ref, srcs, pred_img)
     L = _lib.load()
-    dev = _dev()
+    dev = device("ibr")
     n = len(srcs)
     geo = fuse_view(ref, srcs, filter_dist=2, per_source=True, points=False)
     ref_dir = ray_dirs(ref["K"], ref["E"], H, W)
     src_dirs = [ray_dirs(s["K"], s["E"], H, W) for s in srcs]
-    src_imgs = [_to_dev(s["img"], torch.float32) for s in srcs]
-    pred = _to_dev(pred_img, torch.float32)
+    src_imgs = [to_device(s["img"], torch.float32, "ibr") for s in srcs]
+    pred = to_device(pred_img, torch.float32, "ibr")
     ws = torch.empty(int(L.svs_ibr_workspace_bytes(n, H, W)), dtype=torch.uint8, device=dev)
     fill = torch.empty(n + 1, H, W, 3, dtype=torch.float32, device=dev)
     masks = torch.empty(n + 1, H, W, dtype=torch.float32, device=dev)

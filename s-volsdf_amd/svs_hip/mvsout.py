@@ -25,40 +25,28 @@ import numpy as np
 import torch
 
 from . import lib as _lib
+from .images import linear_table, tables_device, to_device
+from .images import view_mask_file as eval_mask_path       # the file rule of runner.py:351-360, decided per file
 from .ops import _ptr, _stream
-from .scene import linear_table
 
 MAX_RADIUS = 32
 LAUNCHES = {"dilate": 0, "resize": 0, "confidence": 0}      # entry-point calls made by this process (tests, bench_mvsout.py)
 KERNELS_PER_CALL = {"dilate": 3, "resize": 1, "confidence": 1}
 
 
-def _dev():
-    if not torch.cuda.is_available():
-        raise _lib.SvsError("svs_hip.mvsout needs the GPU (there is no CPU fallback)")
-    return torch.device("cuda", torch.cuda.current_device())
-
-
 def _mask_dev(mask, what):
     """(Hs,Ws) or (V,Hs,Ws) array / tensor of any numeric type -> uint8 device tensor (V,Hs,Ws) of its codes (a bool or
     float input: 1 where non-zero), and whether a view axis was added"""
-    dev = _dev()
-    t = mask if torch.is_tensor(mask) else torch.from_numpy(np.ascontiguousarray(np.asarray(mask)))
-    if t.dim() not in (2, 3):
-        raise ValueError(f"{what}: expected (Hs,Ws) or (V,Hs,Ws), got {tuple(t.shape)}")
-    if t.dtype != torch.uint8:
-        t = (t != 0).to(torch.uint8)
-    t = t.detach().to(dev, non_blocking=True)
+    t = mask if torch.is_tensor(mask) else np.asarray(mask)
+    if "uint8" not in str(t.dtype):
+        t = t != 0
+    t = to_device(t, torch.uint8, "mvsout", what, ndim=(2, 3), expect="(Hs,Ws) or (V,Hs,Ws)", non_blocking=True)
     single = t.dim() == 2
     return (t[None] if single else t).contiguous(), single
 
 
 def _tables(H, W, Hs, Ws, dev):
-    if (Hs, Ws) == (H, W):
-        return [None] * 4
-    xo, xc = linear_table(W, Ws)
-    yo, yc = linear_table(H, Hs)
-    return [torch.from_numpy(t).to(dev) for t in (xo, xc, yo, yc)]
+    return [None] * 4 if (Hs, Ws) == (H, W) else tables_device(linear_table, H, W, Hs, Ws, dev)
 
 
 def dilate_disk(mask, radius=12):
@@ -101,31 +89,11 @@ def eval_mask(image, H, W, radius=12):
     return resize_any(dilate_disk(a, radius), H, W)
 
 
-def eval_mask_path(data_dir_root, dataset, scan_name, view):
-    """The evaluation-mask file of a view (runner.py:351-360): BlendedMVS eval_mask/<scan>/mask/{view:08}.png; DTU
-    eval_mask/<scan>/mask/{view:03}.png, else eval_mask/<scan>/{view:03}.png."""
-    mask_dir = os.path.join(data_dir_root, dataset, "eval_mask", scan_name)
-    if dataset == "BlendedMVS":
-        path = os.path.join(mask_dir, "mask", "{:0>8}.png".format(view))
-    elif dataset == "DTU":
-        path = os.path.join(mask_dir, "mask", "{:0>3}.png".format(view))
-        if not os.path.exists(path):
-            path = os.path.join(mask_dir, "{:0>3}.png".format(view))
-    else:
-        raise NotImplementedError(f"dataset {dataset!r}: only DTU and BlendedMVS have evaluation masks")
-    if not os.path.exists(path):
-        raise FileNotFoundError(f"evaluation mask of view {view} not found: {path}")
-    return path
-
-
 def _map_dev(a, what):
-    dev = _dev()
-    t = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(np.asarray(a)))
-    if t.dim() == 3:
+    t = a if torch.is_tensor(a) else np.asarray(a)
+    if t.ndim == 3:
         t = t[0]                                                  # batch entry 0, like the loop at runner.py:261-262
-    if t.dim() != 2:
-        raise ValueError(f"{what}: expected (H,W) or (B,H,W), got {tuple(t.shape)}")
-    return t.detach().to(device=dev, dtype=torch.float32).contiguous()
+    return to_device(t, torch.float32, "mvsout", what, ndim=(2,), expect="(H,W) or (B,H,W)")
 
 
 def confidence_product(conf1, conf2, conf3, H, W):

@@ -10,7 +10,6 @@ TensorFlow and is not computed (INTEGRATION.md).
         --rendering-dir exps_result/ours_106/rendering_1562 --views 1 2 9 --result-from blend [--json scores.json]
 """
 import argparse
-import glob
 import json
 import os
 
@@ -18,24 +17,9 @@ import numpy as np
 import torch
 
 from . import lib as _lib
-from .fusion import _dev
+from .images import (DATASETS, DTU_UNMASKED_SCANS, IMG_RES, alpha_inside, glob_images, read_bmvs_alpha, read_dtu_mask,
+                     read_rgb8, scan_mask_files, to_device)
 from .ops import _ptr, _stream
-
-IMG_RES = (576, 768)                                   # dataset.img_res of config/confs/dtu.conf and bmvs.conf
-DATASETS = ("DTU", "BlendedMVS")
-DTU_UNMASKED_SCANS = (1, 4, 11, 13, 48)                # scene_dataset.py:172: scored without eval masks
-
-
-def _u8_dev(a, what):
-    if torch.is_tensor(a):
-        if a.dtype != torch.uint8:
-            raise TypeError(f"{what} must be uint8, got {a.dtype}")
-        return a.detach().to(device=_dev()).contiguous()
-    a = np.asarray(a)
-    if a.dtype != np.uint8:
-        raise TypeError(f"{what} must be uint8, got {a.dtype}")
-    return torch.from_numpy(np.ascontiguousarray(a)).to(_dev())
-
 
 def score_views(pred, gt, mask):
     """pred, gt: (V,H,W,3) uint8 codes (the rendered PNGs, the 8-bit ground truth); mask: (V,H,W,3) uint8, nonzero
@@ -50,7 +34,7 @@ def score_views(pred, gt, mask):
     if V < 1 or H < 7 or W < 7:
         raise ValueError(f"need at least one view of at least 7x7 pixels (the SSIM window), got {shape}")
     L = _lib.load()
-    p, g, m = _u8_dev(pred, "pred"), _u8_dev(gt, "gt"), _u8_dev(mask, "mask")
+    p, g, m = (to_device(a, torch.uint8, "nvs", what, cast=False) for a, what in ((pred, "pred"), (gt, "gt"), (mask, "mask")))
     ws = torch.empty(int(L.svs_nvs_workspace_bytes(V, H, W)), dtype=torch.uint8, device=p.device)
     out = torch.empty(V, 3, dtype=torch.float64, device=p.device)
     _lib.check(L.svs_nvs_score(_ptr(p), _ptr(g), _ptr(m), V, H, W, _ptr(ws), _ptr(out), _stream()), "svs_nvs_score")
@@ -60,24 +44,10 @@ def score_views(pred, gt, mask):
     return psnr, res[:, 2].copy()
 
 
-def _read_png(path):
-    from PIL import Image
-    with Image.open(path) as im:
-        return np.array(im)
-
-
 def _check_size(a, img_res, path):
     if tuple(a.shape[:2]) != tuple(img_res):
         raise NotImplementedError(f"{path}: {a.shape[:2]} differs from img_res {tuple(img_res)}; the reference resizes it "
                                   f"with cv2.resize, which is not ported")
-
-
-def _image_paths(image_dir):
-    """sorted(glob_imgs(image_dir)) (volsdf/utils/general.py:18-22)"""
-    paths = []
-    for ext in ("*.png", "*.jpg", "*.JPEG", "*.JPG"):
-        paths.extend(glob.glob(os.path.join(image_dir, ext)))
-    return sorted(paths)
 
 
 def _gt_from_scene(scene, views, img_res, mask):
@@ -123,45 +93,31 @@ def load_gt(data_dir_root, dataset, scan, views, img_res=IMG_RES, mask=None, sce
             mask = not (dataset == "DTU" and scan in DTU_UNMASKED_SCANS)
         return _gt_from_scene(scene, views, img_res, mask)
     inst = os.path.join(data_dir_root, dataset, f"scan{scan}")
-    paths = _image_paths(os.path.join(inst, "image"))
+    paths = glob_images(os.path.join(inst, "image"))
     if mask is None:
         mask = not (dataset == "DTU" and scan in DTU_UNMASKED_SCANS)
-    mask_dir = os.path.join(data_dir_root, dataset, "eval_mask", f"scan{scan}")
-    if dataset == "DTU" and not os.path.exists(os.path.join(mask_dir, "mask", "000.png")):
-        mask_fn = lambda v: os.path.join(mask_dir, f"{v:03d}.png")             # noqa: E731
-    elif dataset == "DTU":
-        mask_fn = lambda v: os.path.join(mask_dir, "mask", f"{v:03d}.png")     # noqa: E731
-    else:
-        mask_fn = lambda v: os.path.join(mask_dir, "mask", f"{v:08d}.png")     # noqa: E731
+    mask_fn = scan_mask_files(data_dir_root, dataset, scan)
     H, W = img_res
     gts, masks = [], []
     for v in views:
         v = int(v)
         if not 0 <= v < len(paths):
             raise IndexError(f"view {v}: {inst}/image holds {len(paths)} images")
-        img = _read_png(paths[v])
-        if img.dtype != np.uint8:
-            raise ValueError(f"{paths[v]}: {img.dtype} image; only 8-bit images are supported")
-        if img.ndim != 3 or img.shape[2] != 3:
-            raise ValueError(f"{paths[v]}: expected an RGB image, got shape {img.shape}")
+        img = read_rgb8(paths[v])
         _check_size(img, img_res, paths[v])
         gts.append(img)
         if not mask:
             masks.append(np.ones((H, W, 3), np.uint8))
             continue
         fn = mask_fn(v)
-        m = _read_png(fn)
         if dataset == "DTU":
-            if m.ndim != 3 or m.shape[2] < 3 or m.dtype != np.uint8:
-                raise ValueError(f"{fn}: expected an 8-bit RGB(A) mask, got {m.dtype} {m.shape}")
+            m = read_dtu_mask(fn)                                                # per channel: they need not agree here
             _check_size(m, img_res, fn)
-            masks.append((m[:, :, :3] == 255).astype(np.uint8))                # (png / 255.) == 1
+            masks.append(m.astype(np.uint8))
         else:
-            if m.ndim != 3 or m.shape[2] != 4 or m.dtype != np.uint8:
-                raise AssertionError(f"{fn}: expected an 8-bit RGBA mask, got {m.dtype} {m.shape}")
+            m = read_bmvs_alpha(fn)
             _check_size(m, img_res, fn)
-            inside = m[:, :, 3].astype(np.float32) / np.float32(255.0) > 0.5          # alpha * 1. / 255. > 0.5
-            masks.append(np.repeat(inside[:, :, None], 3, axis=2).astype(np.uint8))
+            masks.append(np.repeat(alpha_inside(m)[:, :, None], 3, axis=2).astype(np.uint8))
     return np.stack(gts), np.stack(masks)
 
 
@@ -184,9 +140,7 @@ def score_scan(rendering_dir, data_dir_root, dataset, scan, views, result_from="
     preds = []
     for v in views:
         fn = prediction_path(rendering_dir, v, result_from)
-        p = _read_png(fn)
-        if p.dtype != np.uint8 or p.ndim != 3 or p.shape[2] != 3:
-            raise ValueError(f"{fn}: expected an 8-bit RGB image, got {p.dtype} {p.shape}")
+        p = read_rgb8(fn)
         _check_size(p, img_res, fn)
         preds.append(p)
     gt, m = load_gt(data_dir_root, dataset, scan, views, img_res=img_res, mask=mask, scene=scene)

@@ -40,7 +40,8 @@ import torch
 
 from . import lib as _lib
 from . import refpath as _refpath
-from .nvs import DATASETS, DTU_UNMASKED_SCANS, IMG_RES, _image_paths
+from .images import (BMVS_ALPHA_DIVISOR, DATASETS, DTU_UNMASKED_SCANS, IMG_RES, cubic_table, device, glob_images, linear_table,
+                     read_bmvs_alpha, read_dtu_mask, read_rgb8, scan_mask_files, tables_device, to_device)
 from .ops import _ptr, _stream
 
 CHUNK = 8                      # views per kernel call: bounds device memory (8 x 1200x1600 codes + 3 float images of 576x768)
@@ -147,78 +148,20 @@ def get_near_id(data_dir, scan_id, idx):
     return ref(data_dir, int(scan_id), idx)
 
 
-# ---- the per-axis tables (host, no GPU) ------------------------------------------------------------------------------
-def source_coords(dst, src):
-    """OpenCV's split of the source coordinate: fx = (float)((d + 0.5) * scale - 0.5) with scale = 1 / (dst / src) in
-    double, s = floor(fx), t = fx - s (exact in float32).  -> s int32 (dst,), t float32 (dst,)"""
-    scale = 1.0 / (float(dst) / float(src))
-    fx = ((np.arange(dst, dtype=np.float64) + 0.5) * scale - 0.5).astype(np.float32)
-    s = np.floor(fx)
-    return s.astype(np.int32), (fx - s).astype(np.float32)
-
-
-def cubic_table(dst, src):
-    """-> first tap index (s - 1; taps are clamped by the kernel) int32 (dst,), Keys' cubic weights for A = -0.75 at t,
-    float32 (dst,4): evaluated in float64 from the float32 t and rounded once (OpenCV evaluates the same polynomials in
-    float32: up to ~1e-7 apart)."""
-    s, t = source_coords(dst, src)
-    t = t.astype(np.float64)
-    A = -0.75
-
-    def near(x):                                        # |x| <= 1
-        return ((A + 2.0) * x - (A + 3.0)) * x * x + 1.0
-
-    def far(x):                                         # 1 < |x| < 2
-        return ((A * x - 5.0 * A) * x + 8.0 * A) * x - 4.0 * A
-    coef = np.stack([far(t + 1.0), near(t), near(1.0 - t), far(2.0 - t)], -1)
-    return (s - 1).astype(np.int32), coef.astype(np.float32)
-
-
-def linear_table(dst, src):
-    """-> first tap index s int32 (dst,), weights (1 - t, t) float32 (dst,2)"""
-    s, t = source_coords(dst, src)
-    return s, np.stack([np.float32(1.0) - t, t], -1).astype(np.float32)
-
-
 # ---- the kernels -----------------------------------------------------------------------------------------------------
-def _dev():
-    if not torch.cuda.is_available():
-        raise _lib.SvsError("svs_hip.scene needs the GPU (there is no CPU fallback)")
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def _u8_dev(a, what, ndim):
-    if not torch.is_tensor(a):
-        a = np.asarray(a)
-        if a.dtype != np.uint8:
-            raise TypeError(f"{what} must be uint8, got {a.dtype}")
-        a = torch.from_numpy(np.ascontiguousarray(a))
-    if a.dtype != torch.uint8:
-        raise TypeError(f"{what} must be uint8, got {a.dtype}")
-    if a.dim() != ndim:
-        raise ValueError(f"{what}: expected {ndim} dimensions, got {tuple(a.shape)}")
-    return a.detach().to(_dev(), non_blocking=True).contiguous()
-
-
-def _tables_dev(builder, H, W, Hs, Ws, dev):
-    xo, xc = builder(W, Ws)
-    yo, yc = builder(H, Hs)
-    return [torch.from_numpy(t).to(dev) for t in (xo, xc, yo, yc)]
-
-
 def prepare_images(codes, img_res):
     """codes: (V,Hs,Ws,3) uint8 RGB codes, array or tensor, host or device.  -> rgb, rgb_smooth: float32 DEVICE tensors
     (V,H*W,3): cv2.resize(code * (1/255), (W,H), INTER_CUBIC) (code * (1/255) itself at equal sizes) and
     cv2.GaussianBlur(rgb, (31,31), 90) of it (scene_dataset.py:163-175)."""
     H, W = int(img_res[0]), int(img_res[1])
-    d = _u8_dev(codes, "codes", 4)
+    d = to_device(codes, torch.uint8, "scene", "codes", ndim=(4,), cast=False, non_blocking=True)
     V, Hs, Ws, C = d.shape
     if C != 3:
         raise ValueError(f"codes: expected (V,Hs,Ws,3), got {tuple(d.shape)}")
     L = _lib.load()
     rgb = torch.empty(V, H * W, 3, dtype=torch.float32, device=d.device)
     smooth = torch.empty_like(rgb)
-    tabs = [None] * 4 if (Hs, Ws) == (H, W) else _tables_dev(cubic_table, H, W, Hs, Ws, d.device)
+    tabs = [None] * 4 if (Hs, Ws) == (H, W) else tables_device(cubic_table, H, W, Hs, Ws, d.device)
     _lib.check(L.svs_scene_resize_cubic(_ptr(d), V, Hs, Ws, H, W, *[_ptr(t) for t in tabs], _ptr(rgb), _stream()),
                "svs_scene_resize_cubic")
     LAUNCHES["resize"] += 1
@@ -233,11 +176,11 @@ def prepare_masks(masks01, img_res, divisor=1.0):
     -> float32 DEVICE tensor (V,H*W,3) of 0/1: the reference's cv2.resize(mask, (W,H), cv2.INTER_NEAREST) -- which runs
     INTER_LINEAR, its third positional parameter being dst -- and > 0.5, in all three channels (scene_dataset.py:178-202)."""
     H, W = int(img_res[0]), int(img_res[1])
-    d = _u8_dev(masks01, "masks01", 3)
+    d = to_device(masks01, torch.uint8, "scene", "masks01", ndim=(3,), cast=False, non_blocking=True)
     V, Hs, Ws = d.shape
     L = _lib.load()
     out = torch.empty(V, H * W, 3, dtype=torch.float32, device=d.device)
-    tabs = _tables_dev(linear_table, H, W, Hs, Ws, d.device)
+    tabs = tables_device(linear_table, H, W, Hs, Ws, d.device)
     _lib.check(L.svs_scene_mask(_ptr(d), float(divisor), V, Hs, Ws, H, W, *[_ptr(t) for t in tabs], _ptr(out), _stream()),
                "svs_scene_mask")
     LAUNCHES["mask"] += 1
@@ -273,57 +216,27 @@ def load_K_Rt_from_P(P, P_=None):
 
 
 # ---- files -----------------------------------------------------------------------------------------------------------
-def _decode_rgb(path):
-    from PIL import Image
-    with Image.open(path) as im:
-        a = np.array(im)
-    if a.dtype != np.uint8:
-        raise ValueError(f"{path}: {a.dtype} image; only 8-bit images are supported")
-    if a.ndim != 3 or a.shape[2] != 3:
-        raise ValueError(f"{path}: expected an RGB image, got shape {a.shape}")
-    return a
-
-
 def _decode_dtu_mask(path):
-    """inside where the code is 255 ((png / 255.) == 1, scene_dataset.py:181-182); the three channels must agree"""
-    from PIL import Image
-    with Image.open(path) as im:
-        m = np.array(im)
-    if m.ndim != 3 or m.shape[2] < 3 or m.dtype != np.uint8:
-        raise ValueError(f"{path}: expected an 8-bit RGB(A) mask, got {m.dtype} {m.shape}")
-    inside = m[:, :, :3] == 255
+    """one 0/1 mask per pixel: the three channels must agree"""
+    inside = read_dtu_mask(path)
     if not (np.array_equal(inside[..., 0], inside[..., 1]) and np.array_equal(inside[..., 0], inside[..., 2])):
         raise ValueError(f"{path}: the mask's three channels differ; one mask per pixel is supported")
     return inside[..., 0].astype(np.uint8)
 
 
-def _decode_bmvs_mask(path):
-    """the alpha codes of an RGBA mask (scene_dataset.py:195-197); divided by 255 on the device"""
-    from PIL import Image
-    with Image.open(path) as im:
-        m = np.array(im)
-    if m.ndim != 3 or m.shape[2] != 4 or m.dtype != np.uint8:
-        raise AssertionError(f"{path}: expected an 8-bit RGBA mask, got {m.dtype} {m.shape}")
-    return np.ascontiguousarray(m[:, :, 3])
-
-
 def _mask_files(data_dir_root, data_dir, scan_id, n_images):
     """{view: mask file} for the views whose mask the reference reads (scene_dataset.py:130-138,178,190-191), and the
-    divisor of their codes."""
-    mask_dir = os.path.join(data_dir_root, data_dir, "eval_mask", f"scan{scan_id}")
+    divisor of their codes (the BlendedMVS alpha codes are divided by 255 on the device)."""
+    fn = scan_mask_files(data_dir_root, data_dir, scan_id)
     if data_dir == "DTU":
         if int(scan_id) in DTU_UNMASKED_SCANS:
             return {}, 1.0
-        if os.path.exists(os.path.join(mask_dir, "mask", "000.png")):
-            fn = lambda v: os.path.join(mask_dir, "mask", f"{v:03d}.png")        # noqa: E731
-        else:
-            fn = lambda v: os.path.join(mask_dir, f"{v:03d}.png")                # noqa: E731
         return {v: fn(v) for v in get_eval_ids("DTU") if v < n_images}, 1.0
     views = get_eval_ids("BlendedMVS", scan_id=scan_id) + get_trains_ids("BlendedMVS", scan=f"scan{scan_id}", num_views=3)
-    files = {v: os.path.join(mask_dir, "mask", f"{v:08d}.png") for v in views if v < n_images}
+    files = {v: fn(v) for v in views if v < n_images}
     for f in files.values():
         assert os.path.exists(f), f
-    return files, 255.0
+    return files, BMVS_ALPHA_DIVISOR
 
 
 class Phases:
@@ -352,7 +265,7 @@ def _to_host(dst, src, ph):
 def _upload(stack, ph):
     t = torch.from_numpy(stack)
     ph.bytes_up += t.numel()
-    return t.to(_dev(), non_blocking=True) if torch.cuda.is_available() else t
+    return t.to(device("scene"), non_blocking=True) if torch.cuda.is_available() else t
 
 
 def _host_tensor(*shape):
@@ -369,10 +282,10 @@ def load_images(image_paths, mask_files, mask_divisor, img_res, phases=None):
     size = None
     with ThreadPoolExecutor(max_workers=min(MAX_DECODERS, os.cpu_count() or 1)) as pool:
         chunks = _chunks(n, CHUNK)
-        ahead = [pool.submit(_decode_rgb, image_paths[i]) for i in chunks[0]] if chunks else []
+        ahead = [pool.submit(read_rgb8, image_paths[i]) for i in chunks[0]] if chunks else []
         for c, ids in enumerate(chunks):
             cur, t0 = ahead, time.perf_counter()
-            ahead = [pool.submit(_decode_rgb, image_paths[i]) for i in chunks[c + 1]] if c + 1 < len(chunks) else []
+            ahead = [pool.submit(read_rgb8, image_paths[i]) for i in chunks[c + 1]] if c + 1 < len(chunks) else []
             imgs = [f.result() for f in cur]
             size = size or imgs[0].shape[:2]
             for i, a in zip(ids, imgs):
@@ -395,7 +308,7 @@ def load_images(image_paths, mask_files, mask_divisor, img_res, phases=None):
         masks = [ones] * n
         views = sorted(mask_files)
         if views:
-            decode = _decode_dtu_mask if mask_divisor == 1.0 else _decode_bmvs_mask
+            decode = _decode_dtu_mask if mask_divisor == 1.0 else read_bmvs_alpha
             mhost = _host_tensor(len(views), H * W, 3)
             msize = None
             for ids in _chunks(len(views), CHUNK):
@@ -474,7 +387,7 @@ class SceneDataset(torch.utils.data.Dataset):
             self.cam_file = os.path.join(data_dir_root, data_dir, "scan114", "cameras.npz")
         assert os.path.exists(image_dir), "Data directory is empty"
         assert os.path.exists(self.cam_file), "Data directory is empty"
-        image_paths = _image_paths(image_dir)
+        image_paths = glob_images(image_dir)
         self.n_images = len(image_paths)
         assert self.n_images > 0, "Data directory is empty"
         cams = np.load(self.cam_file)
