@@ -1,6 +1,9 @@
 """GPU parity of the CasMVSNet cost-volume kernels against the oracle and
 the reference-generated fixtures.  Tolerances: 2e-4 abs on warped features / variance (bilinear sampling at
-|coordinate| ~ 1e2 px), 2e-3 abs / 5e-5 mean on the 11-layer 3-D U-Net output, exact regression index."""
+|coordinate| ~ 1e2 px), 2e-3 abs / 5e-5 mean on the 11-layer 3-D U-Net output, exact regression index.
+The tail of the cost volume (softmax / depth / confidence, the depth hypotheses) and the prior look-up it feeds are held to
+float64 references at their dispatch edges in tests/test_gpu_costvol_tail.py (references: tests/costvol_tail_ref.py, inputs:
+tests/costvol_tail_cases.py, their CPU-side checks: tests/test_costvol_tail_cpu.py)."""
 import os
 
 import numpy as np
@@ -86,6 +89,8 @@ def test_three_stage_forward_golden(dev, golden_dir):
         assert np.abs(reg - g[f"s{st}_reg"]).mean() < 5e-5
         # depth / confidence: continuous in reg except where the truncated index flips
         np.testing.assert_allclose(o["depth"][0].cpu().numpy(), g[f"s{st}_depth"], rtol=2e-5)
+        # (a fixture comparison through 11 conv layers; the tight check of the confidence -- 1e-6 wherever the index agrees,
+        # the index exact outside near-ties -- is tests/test_gpu_costvol_tail.py::test_tail_vs_float64)
         dconf = np.abs(o["photometric_confidence"][0].cpu().numpy() - g[f"s{st}_conf"])
         assert (dconf > 1e-4).mean() < 0.01
         # the probability volume -- what VolOpt.cost_mapping looks up -- at every stage
