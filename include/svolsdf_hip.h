@@ -565,6 +565,29 @@ int svs_scene_smooth(const float* img, int V, int H, int W, void* workspace, flo
 int svs_scene_mask(const uint8_t* mask, float divisor, int V, int Hs, int Ws, int H, int W, const int* xofs,
                    const float* xcoef, const int* yofs, const float* ycoef, float* out, void* hip_stream);
 
+/* ---- f9  the MVS loader's image work (datasets/general_eval.py:157-176, 220-232, 254, 267-268; runner.py:106) -------
+ * V views of one source size (Hs,Ws) with C = 3 or 4 channels to one destination size (H,W) per call.  src: (V,Hs,Ws,C),
+ * uint8 codes (src_is_float = 0) or float32 (src_is_float = 1: the second pass of the x2_mvsres chain).  A code's value
+ * is helpers/utils.py:27's np.float32(code) / 255. -- a float32 DIVISION, one ulp from f6's multiply at some codes --
+ * read from code_table, a DEVICE array of the 256 values the host computes (it may be null for a float32 source).  The
+ * per-axis tables are f6's cubic tables.  Every argument is checked before the launch: a rejected call (SVS_EINVAL: null
+ * pointer, V < 1, C not 3 or 4, src_is_float not 0 or 1; SVS_ESHAPE: a size below 1, H or V above 65535, more than 2^26
+ * pixels) writes nothing.  Neither synchronises nor allocates; one launch each.
+ * svs_mvs_resize_cubic: general_eval.py:174 -- cv2.resize(img, (W,H), interpolation=cv2.INTER_CUBIC) of the float32
+ *   image -> out (V,H,W,C) float32; coordinates, clamping, weights and order of operations as svs_scene_resize_cubic.
+ *   Hs == H and Ws == W: a copy of the values (the tables may be null).
+ * svs_mvs_resize_pack: the same resize fused with general_eval.py:254, 267-268 -> imgs (V,3,H,W), masks (V,1,H,W)
+ *   float32 planes; C = 4: rgb * alpha (the product after the resize) and alpha; C = 3: rgb and ones.
+ * svs_mvs_codes: runner.py:106 -- np.clip(img * 255, 0, 255).astype(np.uint8) of img (3,H,W) float32 planes ->
+ *   codes (H,W,3) uint8: float32 multiply, clip, truncation toward zero; NaN -> 0. */
+int svs_mvs_resize_cubic(const void* src, int src_is_float, const float* code_table, int V, int Hs, int Ws, int C, int H,
+                         int W, const int* xofs, const float* xcoef, const int* yofs, const float* ycoef, float* out,
+                         void* hip_stream);
+int svs_mvs_resize_pack(const void* src, int src_is_float, const float* code_table, int V, int Hs, int Ws, int C, int H,
+                        int W, const int* xofs, const float* xcoef, const int* yofs, const float* ycoef, float* imgs,
+                        float* masks, void* hip_stream);
+int svs_mvs_codes(const float* img, int H, int W, uint8_t* codes, void* hip_stream);
+
 /* ---- f8  from the MVS network's outputs to the default-config point cloud (runner.py:267-271, :362-368) --------------
  * The evaluation mask of filter_depth (eval_mask: true in config/base.yaml) and the confidence map it thresholds, which
  * the reference computes on the host with scikit-image and OpenCV.  Every argument is checked before the first launch: a

@@ -1,5 +1,5 @@
 // Image-index helpers and argument checks shared by the evaluation-side kernels (svs_scene.hip, svs_mvsout.hip,
-// svs_ibr.hip): only index computation and validation live here, every kernel keeps its own arithmetic.
+// svs_ibr.hip, svs_mvsdata.hip): only index computation and validation live here, every kernel keeps its own arithmetic.
 #pragma once
 #include "svs_common.h"
 
@@ -33,6 +33,26 @@ struct Taps2 { int i0, i1; float w0, w1; };
 __device__ __forceinline__ Taps2 taps2(const Axis2& t, int d, int len) {
   const int s = t.ofs[d];
   return {clampi(s, len - 1), clampi(s + 1, len - 1), t.coef[2 * d], t.coef[2 * d + 1]};
+}
+
+// One axis of a 4-tap (INTER_CUBIC) resize as the host builds it (svs_hip/images.py::cubic_table): the first tap's
+// index (s - 1, it may lie outside the source) and Keys' four float32 weights per destination coordinate.
+struct Axis4 {
+  const int* ofs;                                       // (dst)
+  const float* coef;                                    // (dst,4)
+};
+struct Taps4 { int i[4]; float w[4]; };
+
+// the four source indices of destination coordinate d, each clamped on its own to a source of `len`, and their weights
+__device__ __forceinline__ Taps4 taps4(const Axis4& t, int d, int len) {
+  const int s = t.ofs[d];
+  Taps4 r;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    r.i[k] = clampi(s + k, len - 1);
+    r.w[k] = t.coef[4 * d + k];
+  }
+  return r;
 }
 
 // ---- host-side argument checks: each sets the error string, prefixed with the entry point's name ------------------

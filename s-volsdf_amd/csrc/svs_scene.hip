@@ -43,8 +43,7 @@ struct Weights { float w[kR + 1]; };                    // w[k]: the weight at d
 
 struct CubicArgs {
   const uint8_t* src;                                   // (V,Hs,Ws,3)
-  const int* xofs; const float* xcoef;                  // (W), (W,4): first tap = xofs[x] (may lie outside: clamped)
-  const int* yofs; const float* ycoef;                  // (H), (H,4)
+  Axis4 x, y;                                           // (W), (H): first tap = ofs[d] (may lie outside: clamped)
   float* dst;                                           // (V,H,W,3)
   int Hs, Ws, H, W;
 };
@@ -54,20 +53,17 @@ __global__ __launch_bounds__(kThreads) void resize_cubic_kernel(CubicArgs a) {
   const int x = blockIdx.x * kThreads + threadIdx.x, y = blockIdx.y, v = blockIdx.z;
   if (x >= a.W) return;
   const float k255 = 1.0f / 255.0f;
-  const int sx = a.xofs[x], sy = a.yofs[y];
-  float cx[4], cy[4];
+  const Taps4 tx = taps4(a.x, x, a.Ws), ty = taps4(a.y, y, a.Hs);
+  const float* cx = tx.w;
+  const float* cy = ty.w;
   int ox[4];
 #pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    cx[k] = a.xcoef[4 * x + k];
-    cy[k] = a.ycoef[4 * y + k];
-    ox[k] = clampi(sx + k, a.Ws - 1) * 3;
-  }
+  for (int k = 0; k < 4; ++k) ox[k] = tx.i[k] * 3;
   const uint8_t* img = a.src + (size_t)v * a.Hs * a.Ws * 3;
   float h[4][3];
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    const uint8_t* row = img + (size_t)clampi(sy + r, a.Hs - 1) * a.Ws * 3;
+    const uint8_t* row = img + (size_t)ty.i[r] * a.Ws * 3;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       const float p0 = (float)row[ox[0] + c] * k255, p1 = (float)row[ox[1] + c] * k255;
@@ -214,7 +210,7 @@ int svs_scene_resize_cubic(const uint8_t* codes, int V, int Hs, int Ws, int H, i
     return check_launch(what);
   }
   if (!xofs || !xcoef || !yofs || !ycoef) { set_error("%s: null table", what); return SVS_EINVAL; }
-  CubicArgs a{codes, xofs, xcoef, yofs, ycoef, out, Hs, Ws, H, W};
+  CubicArgs a{codes, {xofs, xcoef}, {yofs, ycoef}, out, Hs, Ws, H, W};
   resize_cubic_kernel<<<dim3((W + kThreads - 1) / kThreads, H, V), kThreads, 0, s>>>(a);
   return check_launch(what);
 }

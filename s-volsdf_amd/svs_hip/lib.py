@@ -135,6 +135,9 @@ SIGNATURES = {
     "svs_scene_resize_cubic": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P]),
     "svs_scene_smooth": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P]),
     "svs_scene_mask": (c_int, [_P, c_float, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P]),
+    "svs_mvs_resize_cubic": (c_int, [_P, c_int, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P]),
+    "svs_mvs_resize_pack": (c_int, [_P, c_int, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "svs_mvs_codes": (c_int, [_P, c_int, c_int, _P, _P]),
     "svs_mask_dilate_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "svs_mask_dilate_disk": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P]),
     "svs_mask_resize_any": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P]),
