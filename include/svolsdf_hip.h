@@ -574,7 +574,7 @@ int svs_scene_mask(const uint8_t* mask, float divisor, int V, int Hs, int Ws, in
  * pointer, V < 1, C not 3 or 4, src_is_float not 0 or 1; SVS_ESHAPE: a size below 1, H or V above 65535, more than 2^26
  * pixels) writes nothing.  Neither synchronises nor allocates; one launch each.
  * svs_mvs_resize_cubic: general_eval.py:174 -- cv2.resize(img, (W,H), interpolation=cv2.INTER_CUBIC) of the float32
- *   image -> out (V,H,W,C) float32; coordinates, clamping, weights and order of operations as svs_scene_resize_cubic.
+ *   image -> out (V,H,W,C) float32; svs_scene_resize_cubic's kernel (csrc/svs_resize.h) with another code-to-float rule.
  *   Hs == H and Ws == W: a copy of the values (the tables may be null).
  * svs_mvs_resize_pack: the same resize fused with general_eval.py:254, 267-268 -> imgs (V,3,H,W), masks (V,1,H,W)
  *   float32 planes; C = 4: rgb * alpha (the product after the resize) and alpha; C = 3: rgb and ones.

@@ -1,5 +1,6 @@
 // Image-index helpers and argument checks shared by the evaluation-side kernels (svs_scene.hip, svs_mvsout.hip,
-// svs_ibr.hip, svs_mvsdata.hip): only index computation and validation live here, every kernel keeps its own arithmetic.
+// svs_ibr.hip, svs_mvsdata.hip): only index computation and validation live here, every kernel keeps its own arithmetic
+// -- but for the cubic resize, which both scan loaders run and svs_resize.h holds once.
 #pragma once
 #include "svs_common.h"
 

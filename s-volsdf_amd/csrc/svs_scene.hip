@@ -2,14 +2,10 @@
 // OpenCV -- the bicubic resize of the image, its Gaussian-smoothed copy and the resize of the mask -- for a batch of V
 // views of one size per call.  Restated in float64 in tests/scene_oracle.py.
 //
-// svs_scene_resize_cubic = cv2.resize(code * (1/255), (W,H), interpolation=cv2.INTER_CUBIC) of 8-bit RGB codes: a
-//   separable 4-tap filter (Keys' cubic, A = -0.75), source coordinate (d + 0.5) * scale - 0.5, every tap index clamped
-//   to the image on its own, no prefilter when shrinking.  As OpenCV does, the HOST builds one table per axis (the
-//   first tap's index and four float32 coefficients per destination column / row: svs_hip/images.py::cubic_table) and
-//   the kernel only gathers: rows first, h_r = ((p0 c0 + p1 c1) + p2 c2) + p3 c3 for the four source rows, then the
-//   same sum down the rows, float32, no fma contraction.  load_rgb's img_as_float32 MULTIPLIES the code by float32
-//   (1/255) (it does not divide; the two differ by one ulp at some codes): so does this.  Equal sizes: code * (1/255)
-//   alone (the reference skips the resize).
+// svs_scene_resize_cubic = cv2.resize(code * (1/255), (W,H), interpolation=cv2.INTER_CUBIC) of 8-bit RGB codes: the
+//   shared 4x4 gather of svs_resize.h (coordinates, clamping, order of operations: there) with ScaledCode as its
+//   code-to-float rule.  load_rgb's img_as_float32 MULTIPLIES the code by float32 (1/255) (it does not divide; the two
+//   differ by one ulp at some codes): so does this.  Equal sizes: code * (1/255) alone (the reference skips the resize).
 // svs_scene_smooth = cv2.GaussianBlur(img, (31,31), 90): separable, 31 float32 weights (exp(-(i-15)^2 / (2 90^2))
 //   normalised in float64, rounded to float32: 0.03197 .. 0.03242), BORDER_REFLECT_101 on both axes, rows first, then
 //   columns, float32 intermediate (the workspace).  Each pass sums as OpenCV's symmetric filters do: w15 x0 +
@@ -23,7 +19,7 @@
 //   channel, which the reference interpolates before it thresholds); the 0/1 result goes to all three channels.
 //
 // All three are bandwidth-trivial (about 20 MB of traffic per 576x768 view); plain vector loads and stores.
-#include "svs_image.h"
+#include "svs_resize.h"
 
 namespace svs {
 namespace scene {
@@ -40,48 +36,6 @@ constexpr int kRowW = 256, kRowH = 8, kRowHalo = 3 * kR;
 constexpr int kColW = 64, kColH = 64, kColPer = kColH / (kThreads / kColW);
 
 struct Weights { float w[kR + 1]; };                    // w[k]: the weight at distance k from the centre
-
-struct CubicArgs {
-  const uint8_t* src;                                   // (V,Hs,Ws,3)
-  Axis4 x, y;                                           // (W), (H): first tap = ofs[d] (may lie outside: clamped)
-  float* dst;                                           // (V,H,W,3)
-  int Hs, Ws, H, W;
-};
-
-// one thread per destination pixel, all three channels
-__global__ __launch_bounds__(kThreads) void resize_cubic_kernel(CubicArgs a) {
-  const int x = blockIdx.x * kThreads + threadIdx.x, y = blockIdx.y, v = blockIdx.z;
-  if (x >= a.W) return;
-  const float k255 = 1.0f / 255.0f;
-  const Taps4 tx = taps4(a.x, x, a.Ws), ty = taps4(a.y, y, a.Hs);
-  const float* cx = tx.w;
-  const float* cy = ty.w;
-  int ox[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) ox[k] = tx.i[k] * 3;
-  const uint8_t* img = a.src + (size_t)v * a.Hs * a.Ws * 3;
-  float h[4][3];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const uint8_t* row = img + (size_t)ty.i[r] * a.Ws * 3;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const float p0 = (float)row[ox[0] + c] * k255, p1 = (float)row[ox[1] + c] * k255;
-      const float p2 = (float)row[ox[2] + c] * k255, p3 = (float)row[ox[3] + c] * k255;
-      h[r][c] = ((p0 * cx[0] + p1 * cx[1]) + p2 * cx[2]) + p3 * cx[3];
-    }
-  }
-  float* out = a.dst + (((size_t)v * a.H + y) * a.W + x) * 3;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) out[c] = ((h[0][c] * cy[0] + h[1][c] * cy[1]) + h[2][c] * cy[2]) + h[3][c] * cy[3];
-}
-
-// equal sizes: code * (1/255), one thread per float
-__global__ __launch_bounds__(kThreads) void codes_to_float_kernel(const uint8_t* __restrict__ src, float* __restrict__ dst,
-                                                                 size_t n) {
-  const size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x;
-  if (i < n) dst[i] = (float)src[i] * (1.0f / 255.0f);
-}
 
 struct MaskArgs {
   const uint8_t* src;                                   // (V,Hs,Ws)
@@ -203,16 +157,8 @@ int svs_scene_resize_cubic(const uint8_t* codes, int V, int Hs, int Ws, int H, i
   if (!codes || !out) { set_error("%s: null argument", what); return SVS_EINVAL; }
   int rc = check_dst(what, V, H, W);
   if (rc || (rc = check_image(what, "Hs and Ws", Hs, Ws))) return rc;
-  hipStream_t s = (hipStream_t)hip_stream;
-  if (Hs == H && Ws == W) {
-    const size_t n = (size_t)V * H * W * 3;
-    codes_to_float_kernel<<<(unsigned)((n + kThreads - 1) / kThreads), kThreads, 0, s>>>(codes, out, n);
-    return check_launch(what);
-  }
-  if (!xofs || !xcoef || !yofs || !ycoef) { set_error("%s: null table", what); return SVS_EINVAL; }
-  CubicArgs a{codes, {xofs, xcoef}, {yofs, ycoef}, out, Hs, Ws, H, W};
-  resize_cubic_kernel<<<dim3((W + kThreads - 1) / kThreads, H, V), kThreads, 0, s>>>(a);
-  return check_launch(what);
+  return launch_resize<ScaledCode, 3, false>(what, codes, nullptr, V, Hs, Ws, H, W, xofs, xcoef, yofs, ycoef, out, nullptr,
+                                             hip_stream);
 }
 
 int svs_scene_smooth(const float* img, int V, int H, int W, void* workspace, float* out, void* hip_stream) {

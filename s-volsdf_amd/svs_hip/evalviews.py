@@ -26,9 +26,10 @@ import torch
 
 from . import lib as _lib
 from . import scene as _scene
-from .images import DATASETS, IMG_RES, device
+from .images import device
 from .ops import _f32, _ptr, _stream
 from .renderer import render_image
+from .scans import DATASETS, IMG_RES, get_eval_ids, get_trains_ids
 
 RENDER_KEYS = ("rgb_values", "normal_map", "depth_values", "weights")      # what eval_vsdf.py:220-225 keeps per chunk
 EPS_F32 = float(np.finfo(np.float32).eps)
@@ -235,8 +236,8 @@ def find_checkpoint(ckpt, checkpoint="latest"):
 def default_views(dataset, scan):
     """The views the reference renders (eval_vsdf.py:162-172): the evaluation ids, then the first three training ids (the
     sources of image-based rendering).  -> (views, train ids)"""
-    test = list(_scene.get_eval_ids(dataset, scan_id=scan))
-    train = list(_scene.get_trains_ids(dataset, f"scan{scan}", num_views=3))[:3]
+    test = list(get_eval_ids(dataset, scan_id=scan))
+    train = list(get_trains_ids(dataset, f"scan{scan}", num_views=3))[:3]
     if dataset == "BlendedMVS":
         assert test == [i for i in test if i not in train]
     return test + train, train
@@ -280,7 +281,7 @@ def evaluate(ckpt, data_dir_root, dataset, scan, img_res=IMG_RES, evals_folder="
     else:
         views = [int(v) for v in views]
         try:
-            train = list(_scene.get_trains_ids(dataset, f"scan{scan}", num_views=3))[:3]
+            train = list(get_trains_ids(dataset, f"scan{scan}", num_views=3))[:3]
         except LookupError:
             train = []
     src = [int(v) for v in src_views] if src_views is not None else [v for v in views if v in train]

@@ -1,58 +1,16 @@
-"""What the evaluation-side modules (fusion, ibr, nvs, scene, evalviews, mvsout) share: the GPU and the upload of an
-array to it, PNG decoding with the reference's mask rules, the dataset's constants and file layout, and the per-axis
-tables of the resize kernels.  Host code only; nothing here launches a kernel.
+"""What the evaluation-side modules (fusion, ibr, nvs, scene, mvsdata, evalviews, mvsout) share: the GPU and the upload
+of an array to it, the phase clock of a loader, PNG decoding with the reference's mask rules, and the per-axis tables of
+the resize kernels.  Host code only; nothing here launches a kernel.  (What is known about a scan -- constants, file
+layout, view ids -- is svs_hip/scans.py.)
 """
-import glob
-import os
+import time
+from collections import OrderedDict
 
 import numpy as np
 import torch
 
 from . import lib as _lib
-
-# ---- dataset facts ---------------------------------------------------------------------------------------------------
-IMG_RES = (576, 768)                                   # dataset.img_res of config/confs/dtu.conf and bmvs.conf
-DATASETS = ("DTU", "BlendedMVS")
-DTU_UNMASKED_SCANS = (1, 4, 11, 13, 48)                # scene_dataset.py:172: scored without eval masks
-BMVS_ALPHA_DIVISOR = 255.0                             # a BlendedMVS mask is the alpha channel / 255
-
-
-def glob_images(image_dir):
-    """sorted(glob_imgs(image_dir)) (volsdf/utils/general.py:18-22)"""
-    paths = []
-    for ext in ("*.png", "*.jpg", "*.JPEG", "*.JPG"):
-        paths.extend(glob.glob(os.path.join(image_dir, ext)))
-    return sorted(paths)
-
-
-# Two rules name a view's evaluation-mask file, and they differ for a DTU scan that holds both layouts in part.
-def scan_mask_files(data_dir_root, dataset, scan):
-    """The dataset's rule (scene_dataset.py:130-138,178,190-191), decided ONCE PER SCAN: DTU reads
-    eval_mask/scan{S}/mask/{v:03d}.png when mask/000.png exists and eval_mask/scan{S}/{v:03d}.png otherwise; BlendedMVS
-    reads eval_mask/scan{S}/mask/{v:08d}.png.  -> the function view -> file"""
-    mask_dir = os.path.join(data_dir_root, dataset, "eval_mask", f"scan{scan}")
-    if dataset == "DTU":
-        sub = "mask" if os.path.exists(os.path.join(mask_dir, "mask", "000.png")) else ""
-        return lambda v: os.path.join(mask_dir, sub, f"{v:03d}.png")
-    return lambda v: os.path.join(mask_dir, "mask", f"{v:08d}.png")
-
-
-def view_mask_file(data_dir_root, dataset, scan_name, view):
-    """The runner's rule (runner.py:351-360), decided PER FILE: BlendedMVS eval_mask/<scan>/mask/{view:08}.png; DTU
-    eval_mask/<scan>/mask/{view:03}.png, else eval_mask/<scan>/{view:03}.png.  -> the file, which exists"""
-    mask_dir = os.path.join(data_dir_root, dataset, "eval_mask", scan_name)
-    if dataset == "BlendedMVS":
-        path = os.path.join(mask_dir, "mask", "{:0>8}.png".format(view))
-    elif dataset == "DTU":
-        path = os.path.join(mask_dir, "mask", "{:0>3}.png".format(view))
-        if not os.path.exists(path):
-            path = os.path.join(mask_dir, "{:0>3}.png".format(view))
-    else:
-        raise NotImplementedError(f"dataset {dataset!r}: only DTU and BlendedMVS have evaluation masks")
-    if not os.path.exists(path):
-        raise FileNotFoundError(f"evaluation mask of view {view} not found: {path}")
-    return path
-
+from .scans import BMVS_ALPHA_DIVISOR
 
 # ---- the GPU ---------------------------------------------------------------------------------------------------------
 def device(module):
@@ -76,6 +34,31 @@ def to_device(a, dtype, module, what="array", ndim=None, expect=None, cast=True,
     if not torch.is_tensor(a):
         a = torch.from_numpy(np.ascontiguousarray(a, dtype=name))
     return a.detach().to(device=device(module), dtype=dtype, non_blocking=non_blocking).contiguous()
+
+
+class Phases:
+    """seconds per phase of a load; with sync=True the device is drained at every boundary so that they add up"""
+
+    def __init__(self, sync=False):
+        self.sync, self.s = sync, OrderedDict((k, 0.0) for k in ("decode", "upload", "kernels", "download"))
+        self.bytes_up = self.bytes_down = 0
+
+    def add(self, name, t0):
+        if self.sync and torch.cuda.is_available():
+            torch.cuda.synchronize()
+        self.s[name] += time.perf_counter() - t0
+        return time.perf_counter()
+
+    def summary(self, total):
+        return ("seconds: " + ", ".join(f"{k} {v:.3f}" for k, v in self.s.items()) + f", total {total:.3f}; "
+                f"{self.bytes_up / 1e6:.1f} MB up, {self.bytes_down / 1e6:.1f} MB down")
+
+
+def upload_codes(stack, phases):
+    """a stack of uint8 codes from the host -> the current GPU (the host tensor itself without one), counted in `phases`"""
+    t = torch.from_numpy(stack)
+    phases.bytes_up += t.numel()
+    return t.to("cuda", non_blocking=True) if torch.cuda.is_available() else t
 
 
 # ---- PNG files -------------------------------------------------------------------------------------------------------

@@ -21,17 +21,14 @@ coordinate rule of the cubic resize and `load_K_Rt_from_P` for anything but a pr
 svs_hip.scene.  A code's value here is read_img's `np.float32(code) / 255.`, a float32 division; svs_hip.scene follows
 load_rgb and multiplies by float32(1/255).  The two differ by one ulp at some codes.
 
-BlendedMVS keeps its MVS files under a folder named by a hash.  The table scan -> hash is the reference's own: it is read
-from its dataset module when a checkout is on the path, from a "hash" entry per scan in the JSON file SVS_SCENE_IDS
-names, or registered with `register_blendedmvs_hash`; a BlendedMVS scan without any of the three is a LookupError.
+BlendedMVS keeps its MVS files under a folder named by a hash: `scan2hash` and `register_blendedmvs_hash` are
+svs_hip/scans.py's and stay importable from here; a BlendedMVS scan whose folder name nobody supplied is a LookupError.
 
     python -m svs_hip.mvsdata --data-dir-root data_s_volsdf --dataset DTU --scan 106 \\
         [--max-h 576 --max-w 768 --no-x2] [--create-scene data_ibr]
 """
 import argparse
-import ast
 import copy
-import json
 import os
 import time
 from concurrent.futures import ThreadPoolExecutor
@@ -40,67 +37,17 @@ import numpy as np
 import torch
 
 from . import lib as _lib
-from . import refpath as _refpath
 from . import scene as _scene
-from .images import DATASETS, cubic_table, glob_images, read_png, tables_device, to_device
+from .images import Phases, cubic_table, read_png, tables_device, to_device, upload_codes
 from .ops import _ptr, _stream
+from .scans import _BMVS as _HASH                       # the one registry, under the name its folder names had here
+from .scans import DATASETS, get_eval_ids, get_trains_ids, open_scan, read_cameras, register_blendedmvs_hash, scan2hash
 
 NVIEWS_MAX = 5                 # general_eval.py:19
 X2_SIZE = (1152, 1536)         # general_eval.py:226-229
 MAX_DECODERS = 16
 LAUNCHES = {"resize": 0, "pack": 0, "codes": 0}        # entry-point calls made by this process (tests, bench_mvsdata.py)
 CODE_VALUES = np.arange(256, dtype=np.float32) / 255.  # np.array(img, dtype=np.float32) / 255. of every code (utils.py:27)
-
-# ---- the BlendedMVS folder names --------------------------------------------------------------------------------------
-_HASH = {}                     # scan id -> folder name
-_REF_SCAN2HASH = None
-
-
-def register_blendedmvs_hash(scan_id, folder):
-    """The folder of one BlendedMVS scan below mvs_data/ (its hash in the BlendedMVS release)."""
-    _HASH[int(scan_id)] = str(folder)
-
-
-def _reference_scan2hash():
-    """scan2hash of the reference's dataset module, compiled from its file at run time (the module itself imports cv2);
-    False without a checkout."""
-    global _REF_SCAN2HASH
-    if _REF_SCAN2HASH is None:
-        _REF_SCAN2HASH = False
-        try:
-            root = _refpath.reference_root()
-        except ImportError:
-            root = None
-        path = os.path.join(root, "volsdf", "datasets", "scene_dataset.py") if root else None
-        if path and os.path.isfile(path):
-            tree = ast.parse(open(path).read(), path)
-            body = [n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name == "scan2hash"]
-            ns = {}
-            exec(compile(ast.Module(body=body, type_ignores=[]), path, "exec"), ns)
-            _REF_SCAN2HASH = ns.get("scan2hash", False)
-    return _REF_SCAN2HASH
-
-
-def scan2hash(scan):
-    """'scanN' -> the folder of that BlendedMVS scan below mvs_data/ (scene_dataset.py:12-27), or LookupError."""
-    scan_id = int(str(scan)[4:])
-    if scan_id not in _HASH and os.environ.get("SVS_SCENE_IDS"):
-        with open(os.environ["SVS_SCENE_IDS"]) as f:
-            for k, t in json.load(f).get("BlendedMVS", {}).items():
-                if "hash" in t and int(k) not in _HASH:
-                    register_blendedmvs_hash(int(k), t["hash"])
-    if scan_id in _HASH:
-        return _HASH[scan_id]
-    ref = _reference_scan2hash()
-    if ref:
-        try:
-            return ref(f"scan{scan_id}")
-        except KeyError:
-            pass
-    raise LookupError(f"no BlendedMVS folder name for scan {scan_id}: put a checkout of the reference on the path "
-                      f"(SVOLSDF_REFERENCE_ROOT), give the scan a \"hash\" entry in the JSON file SVS_SCENE_IDS names, or "
-                      f"call svs_hip.mvsdata.register_blendedmvs_hash")
-
 
 # ---- the kernels -----------------------------------------------------------------------------------------------------
 _CODE_TABLES = {}
@@ -152,11 +99,19 @@ def prepare_views(codes, sizes, png=False):
     LAUNCHES["pack"] += 1
     if not png:
         return imgs, masks
-    out = torch.empty(V, H, W, 3, dtype=torch.uint8, device=d.device)
+    return imgs, masks, to_codes(imgs)
+
+
+def to_codes(imgs):
+    """imgs: (V,3,H,W) float32 planes on the device, contiguous.  -> (V,H,W,3) uint8 on the device:
+    np.clip(imgs * 255, 0, 255).astype(np.uint8), channel-last (runner.py:106); one launch per view."""
+    V, _, H, W = imgs.shape
+    L = _lib.load()
+    out = torch.empty(V, H, W, 3, dtype=torch.uint8, device=imgs.device)
     for v in range(V):
         _lib.check(L.svs_mvs_codes(_ptr(imgs[v]), H, W, _ptr(out[v]), _stream()), "svs_mvs_codes")
         LAUNCHES["codes"] += 1
-    return imgs, masks, out
+    return out
 
 
 # ---- host arithmetic -------------------------------------------------------------------------------------------------
@@ -204,7 +159,7 @@ class MVSDataset(torch.utils.data.Dataset):
         self.hparams = args if args is not None else dict()
         self.trains_i = trains_i
         self.fix_wh = False
-        self.phases = phases or _scene.Phases()
+        self.phases = phases or Phases()
         self.decoded_views = 0
         self._views, self._png, self._src_size = {}, {}, {}
 
@@ -222,20 +177,10 @@ class MVSDataset(torch.utils.data.Dataset):
     # ---- general_eval.py:40-81 ----
     def meta_from_idr(self, scan, data_dir):
         """camera matrices, the scale matrix and the image paths of the IDR-format folder"""
-        scan_id = scan[4:]
-        root = _arg(self.hparams, "data_dir_root")
-        instance_dir = os.path.join(root, data_dir, f"scan{scan_id}")
-        image_dir = f"{instance_dir}/image"
-        cam_file = f"{instance_dir}/cameras.npz"
-        if not os.path.exists(cam_file) and int(scan_id) < 200:               # DTU scans share scan114's cameras
-            cam_file = os.path.join(root, data_dir, "scan114", "cameras.npz")
+        _, image_dir, cam_file, self.image_paths_idr = open_scan(_arg(self.hparams, "data_dir_root"), data_dir, scan[4:])
         assert os.path.exists(image_dir), f"{image_dir} is empty"
         assert os.path.exists(cam_file), f"{cam_file} is empty"
-        self.image_paths_idr = glob_images(image_dir)
-        n_images = len(self.image_paths_idr)
-        cams = np.load(cam_file)
-        scale_mats = [cams[f"scale_mat_{i}"].astype(np.float32) for i in range(n_images)]
-        world_mats = [cams[f"world_mat_{i}"].astype(np.float32) for i in range(n_images)]
+        scale_mats, world_mats = read_cameras(cam_file, len(self.image_paths_idr))
         self.intrinsics_idr, self.pose_idr = [], []
         scan5 = scan == 'scan5'                              # that scan's scale_mat is wrong: 1 instead
         for scale_mat, world_mat in zip(scale_mats, world_mats):
@@ -393,7 +338,7 @@ class MVSDataset(torch.utils.data.Dataset):
             groups.setdefault(a.shape, []).append((v, a))
         t0 = ph.add("decode", t0)
         for shape, members in groups.items():
-            stack = _scene._upload(np.stack([a for _, a in members]), ph)
+            stack = upload_codes(np.stack([a for _, a in members]), ph)
             t0 = ph.add("upload", t0)
             out = prepare_views(stack, self.passes(shape[0], shape[1])[0], png=png)
             t0 = ph.add("kernels", t0)
@@ -464,7 +409,7 @@ def create_scene(out_folder, dataset, evals_i=None):
     from helpers.utils import write_cam
     scan = dataset.listfile[0]
     if evals_i is None:
-        evals_i = _scene.get_eval_ids(dataset.data_dir, int(scan[4:]))
+        evals_i = get_eval_ids(dataset.data_dir, int(scan[4:]))
     os.makedirs(os.path.join(out_folder, scan), exist_ok=True)
     metas = [dataset.sample_meta(i) for i in range(len(dataset))]
     ids = [int(m["filename"].split('/')[-1][:8]) for m in metas]
@@ -502,15 +447,12 @@ def main(argv=None):
     interval = a.interval_scale if a.interval_scale is not None else (1.06 if a.dataset == "DTU" else 1.0)
     args = dict(data_dir_root=a.data_dir_root, x2_mvsres=not a.no_x2)
     datapath = os.path.join(a.data_dir_root, a.dataset, "mvs_data")
-    trains_i = _scene.get_trains_ids(a.dataset, scan, a.num_view)
+    trains_i = get_trains_ids(a.dataset, scan, a.num_view)
 
     def dataset(ids):
         return MVSDataset(datapath, [scan], "test", a.num_view, a.dataset, a.ndepths, interval, max_h=a.max_h,
-                          max_w=a.max_w, trains_i=list(ids), args=args, phases=_scene.Phases(sync=True))
+                          max_w=a.max_w, trains_i=list(ids), args=args, phases=Phases(sync=True))
 
-    def seconds(ph, total):
-        return ("seconds: " + ", ".join(f"{k} {v:.3f}" for k, v in ph.s.items()) + f", total {total:.3f}; "
-                f"{ph.bytes_up / 1e6:.1f} MB up, {ph.bytes_down / 1e6:.1f} MB down")
     t0 = time.perf_counter()
     ds = dataset(trains_i)
     samples = ds.device_samples()
@@ -523,15 +465,15 @@ def main(argv=None):
     for i in range(len(ds)):
         print(f"  sample {i}: views {ds.view_ids(i)}, imgs {tuple(samples[i]['imgs'].shape)}, "
               f"mask covers {100.0 * float(samples[i]['masks'][0, 0].mean()):6.2f} %")
-    print(seconds(ds.phases, total))
+    print(ds.phases.summary(total))
     if a.create_scene:
-        evals_i = _scene.get_eval_ids(a.dataset, a.scan)
+        evals_i = get_eval_ids(a.dataset, a.scan)
         t0 = time.perf_counter()
         both = dataset(list(trains_i) + [i for i in evals_i if i not in trains_i])
         written = create_scene(a.create_scene, both, evals_i)
         total = time.perf_counter() - t0
         print(f"{os.path.join(a.create_scene, scan)}: {len(both)} cams, images {written} ({both.decoded_views} decoded)")
-        print(seconds(both.phases, total))
+        print(both.phases.summary(total))
     print(f"launches {dict(LAUNCHES)}")
 
 

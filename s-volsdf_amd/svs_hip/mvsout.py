@@ -26,8 +26,8 @@ import torch
 
 from . import lib as _lib
 from .images import linear_table, tables_device, to_device
-from .images import view_mask_file as eval_mask_path       # the file rule of runner.py:351-360, decided per file
 from .ops import _ptr, _stream
+from .scans import view_mask_file as eval_mask_path        # the file rule of runner.py:351-360, decided per file
 
 MAX_RADIUS = 32
 LAUNCHES = {"dilate": 0, "resize": 0, "confidence": 0}      # entry-point calls made by this process (tests, bench_mvsout.py)

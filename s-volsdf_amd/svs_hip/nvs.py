@@ -17,8 +17,8 @@ import numpy as np
 import torch
 
 from . import lib as _lib
-from .images import (DATASETS, DTU_UNMASKED_SCANS, IMG_RES, alpha_inside, glob_images, read_bmvs_alpha, read_dtu_mask,
-                     read_rgb8, scan_mask_files, to_device)
+from .images import alpha_inside, read_bmvs_alpha, read_dtu_mask, read_rgb8, to_device
+from .scans import DATASETS, DTU_UNMASKED_SCANS, IMG_RES, glob_images, scan_mask_files
 from .ops import _ptr, _stream
 
 def score_views(pred, gt, mask):

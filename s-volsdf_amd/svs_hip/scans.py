@@ -1,0 +1,216 @@
+"""What is known about a scan before any pixel is touched: the datasets' constants and file layout, the view-id tables,
+the BlendedMVS folder names, and how a scan folder is opened.  Host code only: numpy, no torch, no GPU.
+
+The DTU split is the public pixelNeRF / RegNeRF split.  What BlendedMVS needs per scan -- training, evaluation and
+nearest-training-view ids, and the hash that names its folder below mvs_data/ -- is the reference's own.  Each field is
+looked up where it was registered by hand (`register_blendedmvs_ids`, `register_blendedmvs_hash`) or given by the JSON
+file SVS_SCENE_IDS names, `{"BlendedMVS": {"3": {"train": [..], "train_interp": [..], "eval": [..], "near": {"0": 5, ..},
+"hash": "5a.."}}}` with any subset of the five per scan, then in the reference's dataset module when a checkout is on
+the path; a field found in neither is a LookupError that says how to supply it.
+"""
+import ast
+import glob
+import json
+import os
+
+import numpy as np
+
+from . import refpath as _refpath
+
+# ---- dataset facts ---------------------------------------------------------------------------------------------------
+IMG_RES = (576, 768)                                   # dataset.img_res of config/confs/dtu.conf and bmvs.conf
+DATASETS = ("DTU", "BlendedMVS")
+DTU_UNMASKED_SCANS = (1, 4, 11, 13, 48)                # scene_dataset.py:172: scored without eval masks
+BMVS_ALPHA_DIVISOR = 255.0                             # a BlendedMVS mask is the alpha channel / 255
+
+
+def glob_images(image_dir):
+    """sorted(glob_imgs(image_dir)) (volsdf/utils/general.py:18-22)"""
+    paths = []
+    for ext in ("*.png", "*.jpg", "*.JPEG", "*.JPG"):
+        paths.extend(glob.glob(os.path.join(image_dir, ext)))
+    return sorted(paths)
+
+
+# Two rules name a view's evaluation-mask file, and they differ for a DTU scan that holds both layouts in part.
+def scan_mask_files(data_dir_root, dataset, scan):
+    """The dataset's rule (scene_dataset.py:130-138,178,190-191), decided ONCE PER SCAN: DTU reads
+    eval_mask/scan{S}/mask/{v:03d}.png when mask/000.png exists and eval_mask/scan{S}/{v:03d}.png otherwise; BlendedMVS
+    reads eval_mask/scan{S}/mask/{v:08d}.png.  -> the function view -> file"""
+    mask_dir = os.path.join(data_dir_root, dataset, "eval_mask", f"scan{scan}")
+    if dataset == "DTU":
+        sub = "mask" if os.path.exists(os.path.join(mask_dir, "mask", "000.png")) else ""
+        return lambda v: os.path.join(mask_dir, sub, f"{v:03d}.png")
+    return lambda v: os.path.join(mask_dir, "mask", f"{v:08d}.png")
+
+
+def view_mask_file(data_dir_root, dataset, scan_name, view):
+    """The runner's rule (runner.py:351-360), decided PER FILE: BlendedMVS eval_mask/<scan>/mask/{view:08}.png; DTU
+    eval_mask/<scan>/mask/{view:03}.png, else eval_mask/<scan>/{view:03}.png.  -> the file, which exists"""
+    mask_dir = os.path.join(data_dir_root, dataset, "eval_mask", scan_name)
+    if dataset == "BlendedMVS":
+        path = os.path.join(mask_dir, "mask", "{:0>8}.png".format(view))
+    elif dataset == "DTU":
+        path = os.path.join(mask_dir, "mask", "{:0>3}.png".format(view))
+        if not os.path.exists(path):
+            path = os.path.join(mask_dir, "{:0>3}.png".format(view))
+    else:
+        raise NotImplementedError(f"dataset {dataset!r}: only DTU and BlendedMVS have evaluation masks")
+    if not os.path.exists(path):
+        raise FileNotFoundError(f"evaluation mask of view {view} not found: {path}")
+    return path
+
+
+# ---- the scan folder -------------------------------------------------------------------------------------------------
+def open_scan(data_dir_root, data_dir, scan_id):
+    """The IDR-format folder of a scan (scene_dataset.py:113-124, general_eval.py:42-52).
+    -> instance_dir, image_dir, cam_file (scan114's for a scan below 200 without cameras of its own: the DTU scans share
+    them), the sorted image paths.  Existence is the caller's to assert."""
+    instance_dir = os.path.join(data_dir_root, data_dir, f"scan{scan_id}")
+    image_dir = f"{instance_dir}/image"
+    cam_file = f"{instance_dir}/cameras.npz"
+    if not os.path.exists(cam_file) and int(scan_id) < 200:
+        cam_file = os.path.join(data_dir_root, data_dir, "scan114", "cameras.npz")
+    return instance_dir, image_dir, cam_file, glob_images(image_dir)
+
+
+def read_cameras(cam_file, n):
+    """-> scale_mats, world_mats: the first `n` of each in cameras.npz, float32 (4,4) arrays"""
+    cams = np.load(cam_file)
+    return ([cams[f"scale_mat_{i}"].astype(np.float32) for i in range(n)],
+            [cams[f"world_mat_{i}"].astype(np.float32) for i in range(n)])
+
+
+# ---- view ids and BlendedMVS folder names ----------------------------------------------------------------------------
+DTU_TRAIN_IDS = (25, 22, 28, 40, 44, 48, 0, 8, 13)                              # pixelNeRF / RegNeRF
+DTU_EXCLUDE_IDS = (3, 4, 5, 6, 7, 16, 17, 18, 19, 20, 21, 36, 37, 38, 39)      # (bad exposure: never evaluated)
+_BMVS = {}         # scan id -> dict with any of train, train_interp, eval, near, hash
+_IDS_READ = None   # the SVS_SCENE_IDS file that was merged into _BMVS
+_REF_FUNCS = None  # name -> function of the reference's dataset module; {} without a checkout
+
+
+def _entry(t):
+    """the fields of one scan as the registry keeps them"""
+    e = {k: [int(i) for i in t[k]] for k in ("train", "train_interp", "eval") if t.get(k) is not None}
+    if "train" in e and not e.get("train_interp"):
+        e["train_interp"] = e["train"]
+    if t.get("near") is not None:
+        e["near"] = {int(k): int(v) for k, v in dict(t["near"]).items()}
+    if t.get("hash") is not None:
+        e["hash"] = str(t["hash"])
+    return e
+
+
+def register_blendedmvs_ids(scan_id, train, eval, near, train_interp=None):
+    """The id tables of one BlendedMVS scan: `train` (3 ids), `eval` (ids scored), `near` {view: nearest training view}."""
+    _BMVS[int(scan_id)] = {**_BMVS.get(int(scan_id), {}),
+                           **_entry(dict(train=train, eval=eval, near=near, train_interp=train_interp))}
+
+
+def register_blendedmvs_hash(scan_id, folder):
+    """The folder of one BlendedMVS scan below mvs_data/ (its hash in the BlendedMVS release)."""
+    _BMVS[int(scan_id)] = {**_BMVS.get(int(scan_id), {}), **_entry(dict(hash=folder))}
+
+
+def _registered(scan_id, field):
+    """`field` of a scan as registered or as the JSON file gives it, else None.  The file is read once, when a lookup
+    first misses, and never overwrites what was registered by hand."""
+    global _IDS_READ
+    scan_id, path = int(scan_id), os.environ.get("SVS_SCENE_IDS")
+    if field not in _BMVS.get(scan_id, {}) and path and _IDS_READ != path:
+        with open(path) as f:
+            for k, t in json.load(f).get("BlendedMVS", {}).items():
+                _BMVS[int(k)] = {**_entry(t), **_BMVS.get(int(k), {})}
+        _IDS_READ = path
+    return _BMVS.get(scan_id, {}).get(field)
+
+
+def _reference_functions():
+    """get_trains_ids / get_eval_ids / get_near_id / scan2hash of the reference's dataset module, compiled from its file
+    at run time (the module itself imports cv2); {} without a checkout."""
+    global _REF_FUNCS
+    if _REF_FUNCS is None:
+        _REF_FUNCS = {}
+        try:
+            root = _refpath.reference_root()
+        except ImportError:
+            root = None
+        path = os.path.join(root, "volsdf", "datasets", "scene_dataset.py") if root else None
+        if path and os.path.isfile(path):
+            want = ("get_trains_ids", "get_eval_ids", "get_near_id", "scan2hash")
+            with open(path) as f:
+                tree = ast.parse(f.read(), path)
+            body = [n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name in want]
+            ns = {}
+            exec(compile(ast.Module(body=body, type_ignores=[]), path, "exec"), ns)
+            _REF_FUNCS = {k: ns[k] for k in want if k in ns}
+    return _REF_FUNCS
+
+
+def _reference(name, scan_id):
+    """the reference's function `name`, or the LookupError of a scan nobody knows"""
+    ref = _reference_functions().get(name)
+    if ref is None:
+        raise _unknown(scan_id, name)
+    return ref
+
+
+def _unknown(scan_id, name):
+    if name == "scan2hash":
+        what, register = "folder name", "mvsdata.register_blendedmvs_hash"
+        by_file = "give the scan a \"hash\" entry in the JSON file SVS_SCENE_IDS names"
+    else:
+        what, register, by_file = "id tables", "scene.register_blendedmvs_ids", "name a JSON file with SVS_SCENE_IDS"
+    return LookupError(f"no BlendedMVS {what} for scan {scan_id}: put a checkout of the reference on the path "
+                       f"(SVOLSDF_REFERENCE_ROOT), {by_file}, or call svs_hip.{register}")
+
+
+def get_trains_ids(data_dir, scan, num_views=0, for_interp=False):
+    """Training view ids of `scan` ('scanN'), the first `num_views` of them (scene_dataset.py:29-70)."""
+    if num_views <= 0:
+        raise NotImplementedError
+    if num_views == 49:
+        return list(range(49))
+    if data_dir == "DTU":
+        return list(DTU_TRAIN_IDS[:num_views])
+    if data_dir == "BlendedMVS":
+        t = _registered(str(scan)[4:], "train_interp" if for_interp else "train")
+        if t is not None:
+            assert num_views == 3
+            return list(t[:num_views])
+        return _reference("get_trains_ids", str(scan)[4:])(data_dir, scan, num_views=num_views, for_interp=for_interp)
+    raise NotImplementedError
+
+
+def get_eval_ids(data_dir, scan_id=None):
+    """Evaluation view ids (scene_dataset.py:72-83)."""
+    if data_dir == "DTU":
+        return [i for i in range(49) if i not in DTU_TRAIN_IDS + DTU_EXCLUDE_IDS]
+    if data_dir == "BlendedMVS":
+        t = _registered(scan_id, "eval")
+        if t is not None:
+            return list(t[:12])
+        return _reference("get_eval_ids", scan_id)(data_dir, scan_id=int(scan_id))
+    raise NotImplementedError
+
+
+def get_near_id(data_dir, scan_id, idx):
+    """The training view nearest to view `idx` of a BlendedMVS scan (scene_dataset.py:85-90)."""
+    if data_dir != "BlendedMVS":
+        raise NotImplementedError
+    t = _registered(scan_id, "near")
+    if t is not None:
+        return t[int(idx)]
+    return _reference("get_near_id", scan_id)(data_dir, int(scan_id), idx)
+
+
+def scan2hash(scan):
+    """'scanN' -> the folder of that BlendedMVS scan below mvs_data/ (scene_dataset.py:12-27), or LookupError."""
+    scan_id = int(str(scan)[4:])
+    t = _registered(scan_id, "hash")
+    if t is not None:
+        return t
+    try:
+        return _reference("scan2hash", scan_id)(f"scan{scan_id}")
+    except KeyError:                                    # a scan the reference's table does not hold
+        raise _unknown(scan_id, "scan2hash") from None

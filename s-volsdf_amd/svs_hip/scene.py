@@ -19,16 +19,13 @@ each against): the coordinate rule of the cubic / linear resize, the reference's
 `cv2.resize(mask, (W,H), cv2.INTER_NEAREST)` -- whose third positional parameter is `dst`, so INTER_LINEAR runs -- and
 `load_K_Rt_from_P` for anything but a proper camera.
 
-View ids.  The DTU split (training ids, excluded ids) is the public pixelNeRF / RegNeRF split.  The BlendedMVS tables
-(training, evaluation and nearest-training-view ids per scan) are the reference's own: they are read from its dataset
-module when a checkout is on the path, from the JSON file SVS_SCENE_IDS names, or registered with
-`register_blendedmvs_ids`; a BlendedMVS scan without any of the three is an error that says so.
+View ids (`get_trains_ids`, `get_eval_ids`, `get_near_id`, `register_blendedmvs_ids`) and the opening of the folder are
+svs_hip/scans.py's; the names stay importable from here.  A BlendedMVS scan whose id tables nobody supplied is a
+LookupError that says how to.
 
     python -m svs_hip.scene --data-dir-root data_s_volsdf --dataset DTU --scan 106 [--img-res 576 768]
 """
 import argparse
-import ast
-import json
 import os
 import random
 import time
@@ -39,114 +36,17 @@ import numpy as np
 import torch
 
 from . import lib as _lib
-from . import refpath as _refpath
-from .images import (BMVS_ALPHA_DIVISOR, DATASETS, DTU_UNMASKED_SCANS, IMG_RES, cubic_table, device, glob_images, linear_table,
-                     read_bmvs_alpha, read_dtu_mask, read_rgb8, scan_mask_files, tables_device, to_device)
+from .images import (Phases, cubic_table, linear_table, read_bmvs_alpha, read_dtu_mask, read_rgb8, tables_device, to_device,
+                     upload_codes)
 from .ops import _ptr, _stream
+from .scans import (_BMVS, BMVS_ALPHA_DIVISOR, DATASETS, DTU_EXCLUDE_IDS, DTU_TRAIN_IDS, DTU_UNMASKED_SCANS, IMG_RES,
+                    get_eval_ids, get_near_id, get_trains_ids, open_scan, read_cameras, register_blendedmvs_ids,
+                    scan_mask_files)                      # _BMVS: the one registry, under the name it had here
 
 CHUNK = 8                      # views per kernel call: bounds device memory (8 x 1200x1600 codes + 3 float images of 576x768)
 MAX_DECODERS = 16
 CACHE_ENTRIES = 4              # (scan, img_res) results kept: the full-size and the plot-size build of two scans
 LAUNCHES = {"resize": 0, "smooth": 0, "mask": 0}       # entry-point calls made by this process (tests, bench_scene.py)
-
-# ---- view ids -------------------------------------------------------------------------------------------------------
-DTU_TRAIN_IDS = (25, 22, 28, 40, 44, 48, 0, 8, 13)                              # pixelNeRF / RegNeRF
-DTU_EXCLUDE_IDS = (3, 4, 5, 6, 7, 16, 17, 18, 19, 20, 21, 36, 37, 38, 39)      # (bad exposure: never evaluated)
-_BMVS = {}                     # scan id -> dict(train, train_interp, eval, near)
-_REF_FUNCS = None
-
-
-def register_blendedmvs_ids(scan_id, train, eval, near, train_interp=None):
-    """The id tables of one BlendedMVS scan: `train` (3 ids), `eval` (ids scored), `near` {view: nearest training view}."""
-    _BMVS[int(scan_id)] = dict(train=[int(i) for i in train], eval=[int(i) for i in eval],
-                               train_interp=[int(i) for i in (train_interp or train)],
-                               near={int(k): int(v) for k, v in dict(near).items()})
-
-
-def _reference_id_functions():
-    """get_trains_ids / get_eval_ids / get_near_id of the reference's dataset module, compiled from its file at run time
-    (the module itself imports cv2); {} without a checkout."""
-    global _REF_FUNCS
-    if _REF_FUNCS is None:
-        _REF_FUNCS = {}
-        try:
-            root = _refpath.reference_root()
-        except ImportError:
-            root = None
-        path = os.path.join(root, "volsdf", "datasets", "scene_dataset.py") if root else None
-        if path and os.path.isfile(path):
-            want = ("get_trains_ids", "get_eval_ids", "get_near_id")
-            tree = ast.parse(open(path).read(), path)
-            body = [n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name in want]
-            ns = {}
-            exec(compile(ast.Module(body=body, type_ignores=[]), path, "exec"), ns)
-            _REF_FUNCS = {k: ns[k] for k in want if k in ns}
-    return _REF_FUNCS
-
-
-def _bmvs(scan_id):
-    scan_id = int(scan_id)
-    if scan_id not in _BMVS and os.environ.get("SVS_SCENE_IDS"):
-        with open(os.environ["SVS_SCENE_IDS"]) as f:
-            for k, t in json.load(f).get("BlendedMVS", {}).items():
-                if int(k) not in _BMVS:
-                    register_blendedmvs_ids(int(k), t["train"], t["eval"], t["near"], t.get("train_interp"))
-    return _BMVS.get(scan_id)
-
-
-def _no_table(scan_id):
-    return LookupError(f"no BlendedMVS id tables for scan {scan_id}: put a checkout of the reference on the path "
-                       f"(SVOLSDF_REFERENCE_ROOT), name a JSON file with SVS_SCENE_IDS, or call "
-                       f"svs_hip.scene.register_blendedmvs_ids")
-
-
-def get_trains_ids(data_dir, scan, num_views=0, for_interp=False):
-    """Training view ids of `scan` ('scanN'), the first `num_views` of them (scene_dataset.py:29-70)."""
-    if num_views <= 0:
-        raise NotImplementedError
-    if num_views == 49:
-        return list(range(49))
-    if data_dir == "DTU":
-        return list(DTU_TRAIN_IDS[:num_views])
-    if data_dir == "BlendedMVS":
-        t = _bmvs(str(scan)[4:])
-        if t is not None:
-            assert num_views == 3
-            return list(t["train_interp" if for_interp else "train"][:num_views])
-        ref = _reference_id_functions().get("get_trains_ids")
-        if ref is None:
-            raise _no_table(str(scan)[4:])
-        return ref(data_dir, scan, num_views=num_views, for_interp=for_interp)
-    raise NotImplementedError
-
-
-def get_eval_ids(data_dir, scan_id=None):
-    """Evaluation view ids (scene_dataset.py:72-83)."""
-    if data_dir == "DTU":
-        return [i for i in range(49) if i not in DTU_TRAIN_IDS + DTU_EXCLUDE_IDS]
-    if data_dir == "BlendedMVS":
-        t = _bmvs(scan_id)
-        if t is not None:
-            return list(t["eval"][:12])
-        ref = _reference_id_functions().get("get_eval_ids")
-        if ref is None:
-            raise _no_table(scan_id)
-        return ref(data_dir, scan_id=int(scan_id))
-    raise NotImplementedError
-
-
-def get_near_id(data_dir, scan_id, idx):
-    """The training view nearest to view `idx` of a BlendedMVS scan (scene_dataset.py:85-90)."""
-    if data_dir != "BlendedMVS":
-        raise NotImplementedError
-    t = _bmvs(scan_id)
-    if t is not None:
-        return t["near"][int(idx)]
-    ref = _reference_id_functions().get("get_near_id")
-    if ref is None:
-        raise _no_table(scan_id)
-    return ref(data_dir, int(scan_id), idx)
-
 
 # ---- the kernels -----------------------------------------------------------------------------------------------------
 def prepare_images(codes, img_res):
@@ -239,20 +139,6 @@ def _mask_files(data_dir_root, data_dir, scan_id, n_images):
     return files, BMVS_ALPHA_DIVISOR
 
 
-class Phases:
-    """seconds per phase of a load; with sync=True the device is drained at every boundary so that they add up"""
-
-    def __init__(self, sync=False):
-        self.sync, self.s = sync, OrderedDict((k, 0.0) for k in ("decode", "upload", "kernels", "download"))
-        self.bytes_up = self.bytes_down = 0
-
-    def add(self, name, t0):
-        if self.sync and torch.cuda.is_available():
-            torch.cuda.synchronize()
-        self.s[name] += time.perf_counter() - t0
-        return time.perf_counter()
-
-
 def _chunks(n, size):
     return [range(a, min(a + size, n)) for a in range(0, n, size)]
 
@@ -260,12 +146,6 @@ def _chunks(n, size):
 def _to_host(dst, src, ph):
     dst.copy_(src, non_blocking=True)
     ph.bytes_down += dst.numel() * dst.element_size()
-
-
-def _upload(stack, ph):
-    t = torch.from_numpy(stack)
-    ph.bytes_up += t.numel()
-    return t.to(device("scene"), non_blocking=True) if torch.cuda.is_available() else t
 
 
 def _host_tensor(*shape):
@@ -293,7 +173,7 @@ def load_images(image_paths, mask_files, mask_divisor, img_res, phases=None):
                     raise ValueError(f"{image_paths[i]}: {a.shape[:2]} differs from the first image's {size}")
             stack = np.stack(imgs)
             t0 = ph.add("decode", t0)
-            d = _upload(stack, ph)
+            d = upload_codes(stack, ph)
             t0 = ph.add("upload", t0)
             rgb, smooth = prepare_images(d, (H, W))
             t0 = ph.add("kernels", t0)
@@ -322,7 +202,7 @@ def load_images(image_paths, mask_files, mask_divisor, img_res, phases=None):
                     raise ValueError(f"{mask_files[views[ids[0]]]}: {msize} mask for {(H, W)} images that are not resized")
                 stack = np.stack(ms)
                 t0 = ph.add("decode", t0)
-                d = _upload(stack, ph)
+                d = upload_codes(stack, ph)
                 t0 = ph.add("upload", t0)
                 out = prepare_masks(d, (H, W), divisor=mask_divisor)
                 t0 = ph.add("kernels", t0)
@@ -380,19 +260,12 @@ class SceneDataset(torch.utils.data.Dataset):
         self.sampling_idx = None
         self.use_pixel_centers = False
 
-        instance_dir = os.path.join(data_dir_root, data_dir, f"scan{scan_id}")
-        image_dir = f"{instance_dir}/image"
-        self.cam_file = f"{instance_dir}/cameras.npz"
-        if not os.path.exists(self.cam_file) and int(scan_id) < 200:          # DTU scans share scan114's cameras
-            self.cam_file = os.path.join(data_dir_root, data_dir, "scan114", "cameras.npz")
+        instance_dir, image_dir, self.cam_file, image_paths = open_scan(data_dir_root, data_dir, scan_id)
         assert os.path.exists(image_dir), "Data directory is empty"
         assert os.path.exists(self.cam_file), "Data directory is empty"
-        image_paths = glob_images(image_dir)
         self.n_images = len(image_paths)
         assert self.n_images > 0, "Data directory is empty"
-        cams = np.load(self.cam_file)
-        scale_mats = [cams[f"scale_mat_{i}"].astype(np.float32) for i in range(self.n_images)]
-        world_mats = [cams[f"world_mat_{i}"].astype(np.float32) for i in range(self.n_images)]
+        scale_mats, world_mats = read_cameras(self.cam_file, self.n_images)
 
         from PIL import Image
         with Image.open(image_paths[0]) as im:
@@ -487,8 +360,7 @@ def main(argv=None):
           f"{len(ds.mask_views)} views with a mask file")
     for v in ds.mask_views:
         print(f"  view {v:3d}: mask covers {100.0 * float(ds.masks[v].mean()):6.2f} %")
-    print("seconds: " + ", ".join(f"{k} {v:.3f}" for k, v in ph.s.items()) + f", total {total:.3f}; "
-          f"{ph.bytes_up / 1e6:.1f} MB up, {ph.bytes_down / 1e6:.1f} MB down, launches {dict(LAUNCHES)}")
+    print(f"{ph.summary(total)}, launches {dict(LAUNCHES)}")
 
 
 if __name__ == "__main__":

@@ -73,6 +73,13 @@ def decompose_projection_matrix(P):
     return K[:3, :3], pose[:3, :3].astype(np.float64).T, np.concatenate([c, [1.0]])[:, None]
 
 
+def all_codes(H, W, C, seed):
+    """uint8 (H,W,C) that holds every code in every channel"""
+    rng = np.random.default_rng(seed)
+    assert H * W >= 512
+    return np.stack([rng.permutation(np.resize(np.arange(256, dtype=np.uint8), H * W)).reshape(H, W) for _ in range(C)], -1)
+
+
 # ---- synthetic scan folders --------------------------------------------------------------------------------------------
 def rgba_image(H, W, seed):
     """uint8 (H,W,4): scene_oracle's image with a soft-edged, partly transparent alpha channel"""

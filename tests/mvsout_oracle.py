@@ -6,7 +6,7 @@
                             with that structure, border value 0
     dilate_brute / dilate_spans     second opinions: "some set pixel within the footprint", and the OR of the footprint's
                             2r+1 horizontal spans
-    resize_any(mask, H, W)  cv2.resize(mask * 1., (W,H)) > 0. as a boolean rule on the taps of svs_hip.scene.linear_table
+    resize_any(mask, H, W)  cv2.resize(mask * 1., (W,H)) > 0. as a boolean rule on the taps of svs_hip.images.linear_table
     resize_any_float64      the same through the interpolated float64 values (tests/scene_oracle.py::resize_linear)
     final_confidence        cv2.resize(c1) * cv2.resize(c2) * cv2.resize(c3) in float32, every product and sum rounded on
                             its own (numpy never contracts); final_confidence64: the same taps and weights, float64 arithmetic
@@ -76,7 +76,7 @@ def dilate_spans(mask, r):
 
 
 def linear_table(dst, src):
-    from svs_hip.scene import linear_table as table
+    from svs_hip.images import linear_table as table
     return table(dst, src)
 
 

@@ -126,7 +126,7 @@ def test_default_views(ev, monkeypatch):
     assert views[:-3] == [i for i in range(49) if i not in scene.DTU_TRAIN_IDS + scene.DTU_EXCLUDE_IDS] and len(views) == 28
     scene.register_blendedmvs_ids(91, train=[4, 1, 2], eval=[0, 3, 5], near={i: 4 for i in range(6)})
     assert ev.default_views("BlendedMVS", 91) == ([0, 3, 5, 4, 1, 2], [4, 1, 2])
-    monkeypatch.setattr(scene, "_REF_FUNCS", {})
+    monkeypatch.setattr("svs_hip.scans._REF_FUNCS", {})
     monkeypatch.delenv("SVS_SCENE_IDS", raising=False)
     with pytest.raises(LookupError, match="register_blendedmvs_ids"):
         ev.default_views("BlendedMVS", 92)

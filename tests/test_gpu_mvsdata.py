@@ -53,16 +53,9 @@ def _bounds(n_passes, want_resized):
     return e_n, e_n
 
 
-def _all_codes(H, W, C, seed):
-    """uint8 (H,W,C) that holds every code in every channel"""
-    rng = np.random.default_rng(seed)
-    assert H * W >= 512
-    return np.stack([rng.permutation(np.resize(np.arange(256, dtype=np.uint8), H * W)).reshape(H, W) for _ in range(C)], -1)
-
-
 @pytest.mark.parametrize("C", [3, 4])
 def test_equal_sizes_are_the_code_values_bit_for_bit(mvsdata, C):
-    codes = np.stack([_all_codes(32, 64, C, 10 * C + v) for v in range(2)])
+    codes = np.stack([mo.all_codes(32, 64, C, 10 * C + v) for v in range(2)])
     assert all(set(np.unique(codes[..., c])) == set(range(256)) for c in range(C))
     imgs, masks = mvsdata.prepare_views(codes, [(32, 64)])
     assert imgs.is_cuda and imgs.dtype == masks.dtype == torch.float32

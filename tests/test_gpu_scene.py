@@ -67,6 +67,30 @@ def test_prepare_images(scene, src, dst, V):
     assert np.array_equal(again[1].cpu().numpy().reshape(smooth.shape), smooth)
 
 
+@pytest.mark.parametrize("src,dst", [((33, 47), (67, 259)),    # neither ratio rational, upscale, W: two workgroups, ragged tail
+                                     ((40, 50), (16, 16)),     # the smallest destination, taps clamp on all four borders
+                                     ((32, 64), (32, 64))])    # equal sizes, every code in every channel
+def test_cubic_resize_is_one_arithmetic(scene, dev, src, dst):
+    """The two loaders' resizes differ in the code-to-float rule and in nothing else: the MVS entry point, given the
+    scene loader's rule as its code table, returns the scene loader's bits."""
+    from svs_hip import lib
+    from svs_hip.images import cubic_table, tables_device
+    from svs_hip.ops import _ptr, _stream
+    from mvsdata_oracle import all_codes
+    V, (H, W) = 2, dst
+    image = (lambda v: all_codes(src[0], src[1], 3, v)) if src == dst else (lambda v: so.synthetic_image(src[0], src[1], 7 + v))
+    codes = torch.from_numpy(np.stack([image(v) for v in range(V)])).to(dev)
+    if src == dst:
+        assert all(len(np.unique(codes[v, ..., c].cpu().numpy())) == 256 for v in range(V) for c in range(3))
+    rgb = scene.prepare_images(codes, dst)[0]
+    table = torch.from_numpy(np.arange(256, dtype=np.float32) * np.float32(1.0 / 255.0)).to(dev)
+    tabs = [None] * 4 if src == dst else tables_device(cubic_table, H, W, src[0], src[1], dev)
+    out = torch.full((V, H, W, 3), 7.0, device=dev)
+    assert lib.load().svs_mvs_resize_cubic(_ptr(codes), 0, _ptr(table), V, src[0], src[1], 3, H, W, *[_ptr(t) for t in tabs],
+                                           _ptr(out), _stream()) == 0
+    assert torch.equal(rgb.reshape(V, H, W, 3), out)
+
+
 @pytest.mark.parametrize("src,dst", [((150, 200), (72, 96)), ((300, 400), (144, 192)), ((72, 96), (144, 192)),
                                      ((100, 130), (72, 96)), ((72, 96), (72, 96))])
 def test_prepare_masks(scene, src, dst):

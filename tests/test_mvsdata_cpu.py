@@ -228,7 +228,7 @@ def test_the_references_asserts(mvsdata, tmp_path):
 
 def test_blendedmvs_without_a_folder_name_says_so(mvsdata, monkeypatch, tmp_path):
     md, root = mvsdata, str(tmp_path)
-    monkeypatch.setattr(md, "_REF_SCAN2HASH", False)
+    monkeypatch.setattr("svs_hip.scans._REF_FUNCS", {})
     monkeypatch.delenv("SVS_SCENE_IDS", raising=False)
     kw = dict(mo.CASES["bmvs"]["scan"], scan=8)
     mvs = mo.write_mvs_scan(root, folder=FOLDER, **kw)
@@ -248,7 +248,8 @@ def test_folder_names_come_from_a_reference_checkout(mvsdata, monkeypatch):
     md = mvsdata
     monkeypatch.setenv("SVOLSDF_REFERENCE_ROOT", REFERENCE)
     monkeypatch.delenv("SVS_SCENE_IDS", raising=False)
-    monkeypatch.setattr(md, "_REF_SCAN2HASH", None)
+    monkeypatch.setattr("svs_hip.scans._REF_FUNCS", None)
+    monkeypatch.setattr("svs_hip.scans._IDS_READ", None)
     md._HASH.clear()
     names = [md.scan2hash(f"scan{i}") for i in range(1, 10)]
     assert len(set(names)) == 9 and all(len(n) == 24 and int(n, 16) >= 0 for n in names)

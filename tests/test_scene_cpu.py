@@ -125,9 +125,10 @@ def test_dtu_id_tables(scene):
                     reason=f"needs a checkout of the reference at {REFERENCE} (SVOLSDF_REFERENCE_ROOT)")
 def test_id_tables_equal_the_reference_checkout(scene, monkeypatch):
     monkeypatch.setenv("SVOLSDF_REFERENCE_ROOT", REFERENCE)
-    monkeypatch.setattr(scene, "_REF_FUNCS", None)
-    ref = scene._reference_id_functions()
-    assert set(ref) == {"get_trains_ids", "get_eval_ids", "get_near_id"}
+    from svs_hip import scans
+    monkeypatch.setattr(scans, "_REF_FUNCS", None)
+    ref = scans._reference_functions()
+    assert set(ref) == {"get_trains_ids", "get_eval_ids", "get_near_id", "scan2hash"}
     for n in (3, 4, 5, 6, 9, 49):
         assert scene.get_trains_ids("DTU", "scan24", n) == ref["get_trains_ids"]("DTU", "scan24", n)
     assert scene.get_eval_ids("DTU") == ref["get_eval_ids"]("DTU")
@@ -267,7 +268,7 @@ def test_blendedmvs_folder_items_and_cached_items(scene, monkeypatch, tmp_path):
 
 
 def test_blendedmvs_without_tables_says_so(scene, monkeypatch, tmp_path):
-    monkeypatch.setattr(scene, "_REF_FUNCS", {})
+    monkeypatch.setattr("svs_hip.scans._REF_FUNCS", {})
     monkeypatch.delenv("SVS_SCENE_IDS", raising=False)
     so.write_scan(str(tmp_path), "BlendedMVS", 8, 2, (20, 28))
     with pytest.raises(LookupError, match="register_blendedmvs_ids"):

@@ -54,7 +54,8 @@ def main():
     import scene_oracle as so
     from PIL import Image
     from svs_hip import mvsdata, scene
-    from svs_hip.images import glob_images
+    from svs_hip.images import Phases
+    from svs_hip.scans import glob_images
     if not torch.cuda.is_available():
         raise SystemExit("bench_mvsdata.py needs the GPU (there is no CPU path)")
     root = a.dir or tempfile.mkdtemp(prefix="bench_mvsdata_")
@@ -78,7 +79,7 @@ def main():
 
         def dataset(ids, sync):
             return mvsdata.MVSDataset(mvs, ["scan106"], "test", 3, "DTU", 192, 1.06, max_h=a.max_hw[0], max_w=a.max_hw[1],
-                                      trains_i=list(ids), args=args, phases=scene.Phases(sync=sync))
+                                      trains_i=list(ids), args=args, phases=Phases(sync=sync))
 
         def run(fn, ids, sync):
             mvsdata.LAUNCHES.update(resize=0, pack=0, codes=0)

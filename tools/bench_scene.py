@@ -45,6 +45,7 @@ def main():
     import torch
     import scene_oracle as so
     from svs_hip import scene
+    from svs_hip.images import Phases
     if not torch.cuda.is_available():
         raise SystemExit("bench_scene.py needs the GPU (there is no CPU path)")
     root = a.dir or tempfile.mkdtemp(prefix="bench_scene_")
@@ -64,7 +65,7 @@ def main():
             return ds, (time.perf_counter() - t0) * 1e3
 
         os.environ["SVS_SCENE_CACHE"] = "0"
-        ph = scene.Phases(sync=True)
+        ph = Phases(sync=True)
         ds, phased_ms = build(ph)
         calls = dict(scene.LAUNCHES)
         _, plain_ms = build()
