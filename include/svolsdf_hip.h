@@ -540,6 +540,45 @@ size_t svs_nvs_workspace_bytes(int V, int H, int W);
 int svs_nvs_score(const uint8_t* pred, const uint8_t* gt, const uint8_t* mask, int V, int H, int W, void* workspace,
                   double* out, void* hip_stream);
 
+/* ---- f5b  LPIPS, the third novel-view score (eval_vsdf.py:178, 208-209 -> lpips_tf.py:29-90) ------------------------
+ * The reference runs a downloaded frozen graph; the network is restated from the published LPIPS v0.1 model (net-lin,
+ * vgg): svs_hip/lpips.py holds the definition and what is not pinned (csrc/svs_lpips.hip).  Added without a version
+ * change: nothing that existed changed, and svs_version() stays the 101 every binding checks for.
+ * Every argument is checked before the first launch: a rejected call (SVS_EINVAL: null pointer, misaligned buffer, V < 1;
+ * SVS_ESHAPE: an unsupported (Cin, Cout) or a size) writes nothing.
+ * SVS_EOVERFLOW: an operand of the fp16x2 convolution -- a scaled weight, an input value, a layer's output that feeds the
+ * next layer -- is above 65504 in magnitude or not a number.  It is replaced by 0 (no inf or NaN is produced) and the call
+ * returns this code.  svs_conv3x3_mfma_pack, svs_conv3x3_mfma and svs_lpips_score read a device flag for it and therefore
+ * SYNCHRONISE the stream; the first two keep that flag in one device word per process, made at their first use, so they
+ * are not for concurrent use from several threads.
+ * svs_conv3x3_mfma: out (Cout,H,W) = relu?(conv2d(in (Cin,H,W), 3x3, padding 1, stride 1) + bias), float32 in and out,
+ *   Cin in {3, 64, 128, 256, 512}, Cout in {64, 128, 256, 512} (svs_conv3x3_mfma_supported), two-piece fp16 operands with
+ *   float32 accumulation.  weight (Cout,Cin,3,3) float32 is packed once by svs_conv3x3_mfma_pack into
+ *   svs_conv3x3_mfma_wfrag_bytes (0: unsupported) bytes, scaled per output channel by a power of two the kernel undoes.
+ *   bias may be NULL.  H, W >= 1, H*W <= 2^26.
+ * svs_maxpool2: out (C,H/2,W/2) = 2x2 max-pool, stride 2, floor mode, of in (C,H,W) float32; H, W >= 2.
+ * svs_lpips_head: *out (device double) = mean over the pixels of sum_c w[c] (n(f0)_c - n(f1)_c)^2 with
+ *   n(f) = f / (sqrt(sum_c f_c^2) + 1e-10); f0, f1 (C,H,W) float32, w [C]; C a multiple of 64 in 64..512.  float64, fixed
+ *   order.  One workgroup: meant for one tap at test sizes; svs_lpips_score runs the same kernel over many.
+ * svs_lpips_score: pred, gt, mask as for svs_nvs_score, H, W >= 16 (relu5_3 needs one pixel), H*W <= 2^24.  -> out: device
+ *   double [V], the LPIPS distance of each view's white-composited images.  packed_net: svs_lpips_net_bytes() bytes, 16-byte
+ *   aligned; svs_lpips_net_offset(what, index) is the byte offset of (what 0) the packed weights of convolution index
+ *   0..12, (1) its float32 bias, (2) the float32 lin weights of tap index 0..4; (size_t)-1 otherwise.  workspace:
+ *   svs_lpips_workspace_bytes() (0: rejected sizes), 16-byte aligned.  Bit-identical run to run. */
+#define SVS_EOVERFLOW (-4)
+int svs_conv3x3_mfma_supported(int Cin, int Cout);
+size_t svs_conv3x3_mfma_wfrag_bytes(int Cin, int Cout);
+int svs_conv3x3_mfma_pack(const float* weight, int Cin, int Cout, void* wfrag, void* hip_stream);
+int svs_conv3x3_mfma(const float* in, const void* wfrag, const float* bias, float* out, int Cin, int Cout, int H, int W,
+                     int relu, void* hip_stream);
+int svs_maxpool2(const float* in, float* out, int C, int H, int W, void* hip_stream);
+int svs_lpips_head(const float* f0, const float* f1, const float* w, int C, int H, int W, double* out, void* hip_stream);
+size_t svs_lpips_net_bytes(void);
+size_t svs_lpips_net_offset(int what, int index);
+size_t svs_lpips_workspace_bytes(int V, int H, int W);
+int svs_lpips_score(const uint8_t* pred, const uint8_t* gt, const uint8_t* mask, int V, int H, int W, const void* packed_net,
+                    void* workspace, double* out, void* hip_stream);
+
 /* ---- f6  scene loading: the image work of SceneDataset (volsdf/datasets/scene_dataset.py:163-206) --------------------
  * V views of one source size (Hs,Ws) to one destination size (H,W) per call; H, W >= 16 (the 31-tap smoothing reflects
  * once), V >= 1.  Every argument is checked before the first launch: a rejected call (SVS_EINVAL: null pointer, V < 1,

@@ -41,6 +41,7 @@ UNITS = {
     "svs_cloud.hip": ["-ffp-contract=off"],
     "svs_ibr.hip": ["-ffp-contract=off"],
     "svs_nvs.hip": ["-ffp-contract=off"],
+    "svs_lpips.hip": ["-ffp-contract=off"],
     "svs_scene.hip": ["-ffp-contract=off"],
     "svs_evalviews.hip": ["-ffp-contract=off"],
     "svs_mvsout.hip": ["-ffp-contract=off"],

@@ -7,6 +7,7 @@
 #define SVS_EINVAL (-1)
 #define SVS_ESHAPE (-2)
 #define SVS_ENOCONV (-3)   // an iteration did not settle within its round limit (include/svolsdf_hip.h)
+#define SVS_EOVERFLOW (-4) // an operand of the fp16x2 3x3 convolution does not fit fp16 (include/svolsdf_hip.h)
 
 // Activation blocks are written once and read once by a later kernel: non-temporal stores keep them from evicting the
 // packed weight stream (2-4.6 MB per network, re-read by every workgroup) from the 4 MB L2 of an XCD.

@@ -10,6 +10,7 @@ leave the device; a writer thread encodes view k while view k+1 renders.  The fo
     python -m svs_hip.evalviews --ckpt exps_vsdf/ours_106/2026_01_01_00_00_00/checkpoints --checkpoint latest \\
         --data-dir-root data_s_volsdf --dataset DTU --scan 106 [--img-res 576 768] [--evals-folder exps_result] \\
         [--expname ours] [--split-n-pixels 512] [--views 1 2 9 ...] [--ibr MVS_SCAN_FOLDER] [--score]
+        [--lpips-vgg vgg16.pth --lpips-lin vgg_lin.pth]
 
 dep_XXX.png needs matplotlib's `turbo` colour table, which is read from matplotlib at run time; without matplotlib that
 one file is skipped with one warning.  LPIPS is not computed; the mesh is `svs_hip.mesh`.
@@ -268,11 +269,12 @@ def load_model(ckpt_file, dataset, device):
 
 def evaluate(ckpt, data_dir_root, dataset, scan, img_res=IMG_RES, evals_folder="exps_result", expname="ours",
              checkpoint="latest", split_n_pixels=512, views=None, src_views=None, ibr=None, score=False, fast=-1,
-             rank=0, world=1, log=print):
+             rank=0, world=1, log=print, lpips=None):
     """Checkpoint -> {evals_folder}/{expname}_{scan}/rendering_{epoch} (eval_vsdf.py:157) with the files of every view.
     views: explicit ids, or None for default_views().  ibr: the scan's MVS folder (cams/, images/): blends every view that
     is not a source from `src_views` (default: the training ids among the views) with svs_hip.ibr; score: svs_hip.nvs
-    on those views ('blend' after ibr, 'default' otherwise).  -> dict(folder, epoch, views, written, seconds, scores)."""
+    on those views ('blend' after ibr, 'default' otherwise), with the LPIPS line when `lpips` is a svs_hip.lpips.LpipsNet.
+    -> dict(folder, epoch, views, written, seconds, scores)."""
     dev = device("evalviews")
     sec = OrderedDict((k, 0.0) for k in ("load", "render", "finish", "write"))
     t0 = time.perf_counter()
@@ -310,9 +312,9 @@ def evaluate(ckpt, data_dir_root, dataset, scan, img_res=IMG_RES, evals_folder="
         from . import nvs as _nvs
         t0 = time.perf_counter()
         res["scores"] = _nvs.score_scan(folder, data_dir_root, dataset, scan, refs, result_from="blend" if ibr else "default",
-                                        img_res=tuple(int(x) for x in img_res), scene=ds)
+                                        img_res=tuple(int(x) for x in img_res), scene=ds, **({} if lpips is None else dict(lpips=lpips)))
         sec["score"] = time.perf_counter() - t0
-        for line in _nvs.scan_lines(scan, res["scores"]["psnr"], res["scores"]["ssim"]):
+        for line in _nvs.scan_lines(scan, res["scores"]["psnr"], res["scores"]["ssim"], res["scores"].get("lpips")):
             log(line)
     return res
 
@@ -337,14 +339,18 @@ def parse_args(argv=None):
     p.add_argument("--ibr", metavar="MVS_SCAN_FOLDER", default=None,
                    help="blend the views with svs_hip.ibr; the folder holds cams/{:08d}_cam.txt and images/{:08d}.png")
     p.add_argument("--score", action="store_true", help="print the SCAN block of svs_hip.nvs for the rendered views")
+    from .nvs import add_lpips_arguments
+    add_lpips_arguments(p)
     return p.parse_args(argv)
 
 
 def main(argv=None):
     a = parse_args(argv)
+    from .nvs import lpips_from_arguments
+    net = lpips_from_arguments(a) if a.score else None
     return evaluate(a.ckpt, a.data_dir_root, a.dataset, a.scan, img_res=tuple(a.img_res), evals_folder=a.evals_folder,
                     expname=a.expname, checkpoint=a.checkpoint, split_n_pixels=a.split_n_pixels, views=a.views,
-                    src_views=a.src_views, ibr=a.ibr, score=a.score)
+                    src_views=a.src_views, ibr=a.ibr, score=a.score, lpips=net)
 
 
 if __name__ == "__main__":

@@ -198,6 +198,20 @@ SIGNATURES.update({
     "svs_mesh_face_areas": (c_int, [_P, _P, c_int, _P, _P, _P, _P]),
 })
 
+# svs_hip.lpips (csrc/svs_lpips.hip)
+SIGNATURES.update({
+    "svs_conv3x3_mfma_supported": (c_int, [c_int, c_int]),
+    "svs_conv3x3_mfma_wfrag_bytes": (c_size_t, [c_int, c_int]),
+    "svs_conv3x3_mfma_pack": (c_int, [_P, c_int, c_int, _P, _P]),
+    "svs_conv3x3_mfma": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
+    "svs_maxpool2": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
+    "svs_lpips_head": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, _P]),
+    "svs_lpips_net_bytes": (c_size_t, []),
+    "svs_lpips_net_offset": (c_size_t, [c_int, c_int]),
+    "svs_lpips_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "svs_lpips_score": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, _P, _P, _P]),
+})
+
 ABI_VERSION = 101          # svs_version() of the library this binding was written against (include/svolsdf_hip.h)
 
 

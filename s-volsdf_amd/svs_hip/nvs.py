@@ -3,11 +3,12 @@
 `score_views` is the reference's masked PSNR and scikit-image 0.17.2 SSIM for a stack of evaluation views in one
 `svs_nvs_score` call.  `load_gt` reads the ground truth and masks the reference's SceneDataset reads for those views, and
 `score_scan` scores the eval_blend_XXX.png (or eval_XXX.png) files of one scan.  The view ids are explicit: the
-reference's id tables stay in its dataset module.  LPIPS, the reference's third metric, needs VGG weights and
-TensorFlow and is not computed (INTEGRATION.md).
+reference's id tables stay in its dataset module.  LPIPS, the reference's third metric, is svs_hip.lpips: it is computed
+and printed when the two public weight files are given (--lpips-vgg / --lpips-lin), not otherwise.
 
     python -m svs_hip.nvs --data-dir-root data_s_volsdf --dataset DTU --scan 106 \\
-        --rendering-dir exps_result/ours_106/rendering_1562 --views 1 2 9 --result-from blend [--json scores.json]
+        --rendering-dir exps_result/ours_106/rendering_1562 --views 1 2 9 --result-from blend [--json scores.json] \\
+        [--lpips-vgg vgg16.pth --lpips-lin vgg_lin.pth]
 """
 import argparse
 import json
@@ -131,9 +132,10 @@ def prediction_path(rendering_dir, view, result_from="blend"):
 
 
 def score_scan(rendering_dir, data_dir_root, dataset, scan, views, result_from="blend", img_res=IMG_RES, mask=None,
-               scene=None):
+               scene=None, lpips=None):
     """Scores the rendered views of one scan against its ground truth (eval_vsdf.py:186-212 for explicit view ids).
-    scene: see load_gt.  -> dict(views, psnr, ssim): float64 arrays in view order."""
+    scene: see load_gt.  lpips: a svs_hip.lpips.LpipsNet adds `lpips`.  -> dict(views, psnr, ssim[, lpips]): float64
+    arrays in view order."""
     views = [int(v) for v in views]
     if not views:
         raise ValueError("no views to score")
@@ -144,19 +146,43 @@ def score_scan(rendering_dir, data_dir_root, dataset, scan, views, result_from="
         _check_size(p, img_res, fn)
         preds.append(p)
     gt, m = load_gt(data_dir_root, dataset, scan, views, img_res=img_res, mask=mask, scene=scene)
-    psnr, ssim = score_views(np.stack(preds), gt, m)
-    return dict(views=np.asarray(views), psnr=psnr, ssim=ssim)
+    preds = np.stack(preds)
+    psnr, ssim = score_views(preds, gt, m)
+    res = dict(views=np.asarray(views), psnr=psnr, ssim=ssim)
+    if lpips is not None:
+        res["lpips"] = lpips.score_views(preds, gt, m)
+    return res
 
 
-def scan_lines(scan, psnr, ssim):
-    """The reference's per-scan block (eval_vsdf.py:273-276) without its LPIPS line."""
+def scan_lines(scan, psnr, ssim, lpips=None):
+    """The reference's per-scan block (eval_vsdf.py:273-277); its LPIPS line only when `lpips` is given."""
     psnr, ssim = np.asarray(psnr, np.float64), np.asarray(ssim, np.float64)
-    return [f"SCAN {scan}:",
-            "    psnr mean = {0}, std {1}".format("%.4f" % psnr.mean(), "%.4f" % psnr.std()),
-            "    ssim mean = {0}, std {1}".format("%.4f" % ssim.mean(), "%.4f" % ssim.std())]
+    lines = [f"SCAN {scan}:",
+             "    psnr mean = {0}, std {1}".format("%.4f" % psnr.mean(), "%.4f" % psnr.std()),
+             "    ssim mean = {0}, std {1}".format("%.4f" % ssim.mean(), "%.4f" % ssim.std())]
+    if lpips is not None:
+        lpips = np.asarray(lpips, np.float64)
+        lines.append("    lpips mean = {0}, std {1}".format("%.4f" % lpips.mean(), "%.4f" % lpips.std()))
+    return lines
 
 
-def main(argv=None):
+def add_lpips_arguments(p, required=False):
+    p.add_argument("--lpips-vgg", required=required, help="VGG-16 state dict (.pth or .npz: torchvision's vgg16, or one "
+                                                         "file with the lin layers too): adds the LPIPS line")
+    p.add_argument("--lpips-lin", help="the lin layers (.pth or .npz: the lpips package's vgg.pth)")
+
+
+def lpips_from_arguments(a):
+    """-> a svs_hip.lpips.LpipsNet, or None without --lpips-vgg"""
+    if a.lpips_vgg is None:
+        if a.lpips_lin is not None:
+            raise SystemExit("--lpips-lin needs --lpips-vgg")
+        return None
+    from . import lpips as _lpips
+    return _lpips.LpipsNet(_lpips.load_weights(a.lpips_vgg, a.lpips_lin))
+
+
+def main(argv=None, require_lpips=False):
     p = argparse.ArgumentParser(description="GPU novel-view scores (the reference's eval_vsdf.py --result_from): masked "
                                             "PSNR and SSIM of the rendered evaluation views of one scan.")
     p.add_argument("--data-dir-root", required=True, help="holds {DTU|BlendedMVS}/scanN/image and .../eval_mask")
@@ -169,16 +195,20 @@ def main(argv=None):
     p.add_argument("--mask", choices=("auto", "on", "off"), default="auto",
                    help="auto: the reference's rule (DTU scans 1, 4, 11, 13, 48 unmasked)")
     p.add_argument("--json", help="write the per-view values here")
+    add_lpips_arguments(p, required=require_lpips)
     a = p.parse_args(argv)
     mask = {"auto": None, "on": True, "off": False}[a.mask]
     r = score_scan(a.rendering_dir, a.data_dir_root, a.dataset, a.scan, a.views, result_from=a.result_from,
-                   img_res=tuple(a.img_res), mask=mask)
-    for line in scan_lines(a.scan, r["psnr"], r["ssim"]):
+                   img_res=tuple(a.img_res), mask=mask, lpips=lpips_from_arguments(a))
+    for line in scan_lines(a.scan, r["psnr"], r["ssim"], r.get("lpips")):
         print(line)
     if a.json:
+        rec = dict(scan=a.scan, dataset=a.dataset, result_from=a.result_from, views=r["views"].tolist(),
+                   psnr=[float(x) for x in r["psnr"]], ssim=[float(x) for x in r["ssim"]])
+        if "lpips" in r:
+            rec["lpips"] = [float(x) for x in r["lpips"]]
         with open(a.json, "w") as f:
-            json.dump(dict(scan=a.scan, dataset=a.dataset, result_from=a.result_from, views=r["views"].tolist(),
-                           psnr=[float(x) for x in r["psnr"]], ssim=[float(x) for x in r["ssim"]]), f, indent=1)
+            json.dump(rec, f, indent=1)
 
 
 if __name__ == "__main__":
