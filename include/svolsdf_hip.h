@@ -481,6 +481,49 @@ int svs_prob_depth_conf(const float* reg, const float* depth_values, int D, int 
 int svs_depth_hypotheses(const float* prev_depth, int Hp, int Wp, int H_img, int W_img, int D, int scale, float dmin,
                          float dmax, float pix_interval, int inverse, float* out, void* hip_stream);
 
+/* ---- UCSNet, the second MVS backbone (models/ucsnet.py; csrc/svs_ucsnet.hip) ------------------------------------------
+ * svs_version() stays 101: entries are only added.
+ *
+ * Deconv2dUnit of the "unet" feature extractor (models/ucsnet.py:114-149, 225-226):
+ *   out (Cout,2H,2W) = relu?(conv_transpose2d(in (Cin,H,W), weight (Cin,Cout,3,3), stride 2, padding 1, output_padding 1) + bias)
+ * BatchNorm(eval) folded into weight / bias by the caller.  Channel c of the result is written at out + c * out_channel_stride
+ * floats (even, >= 4 H W; out 8-byte aligned), so that it can land in the first half of a concatenation buffer.
+ * svs_deconv2d: float32 vector kernel, any Cin / Cout, weight in torch's layout.  svs_deconv2d_mfma: the four output parity
+ * classes as implicit GEMMs on v_mfma_f32_16x16x32_f16 with two-piece fp16 operands and float32 accumulation, Cin in {16,32},
+ * Cout <= 16 (svs_deconv2d_mfma_supported); the weights are packed once per tensor by svs_deconv2d_mfma_pack into
+ * svs_deconv2d_mfma_wfrag_bytes bytes.  The fp16 split is NOT scaled: good for |activation|, |weight| < 65504 (beyond: inf,
+ * and NaN through the zero-padded k-step); an operand below 0.125 has its mid piece in the fp16 subnormals and carries 3e-8
+ * absolute (a weight of 1e-2: 3e-6 relative) instead of 22 bits. */
+int svs_deconv2d(const float* in, const float* weight, const float* bias, float* out, long long out_channel_stride, int Cin,
+                 int Cout, int H, int W, int relu, void* hip_stream);
+int svs_deconv2d_mfma_supported(int Cin, int Cout);
+size_t svs_deconv2d_mfma_wfrag_bytes(int Cin, int Cout);
+int svs_deconv2d_mfma_pack(const float* weight, int Cin, int Cout, void* wfrag, void* hip_stream);
+int svs_deconv2d_mfma(const float* in, const void* wfrag, const float* bias, float* out, long long out_channel_stride, int Cin,
+                      int Cout, int H, int W, int relu, void* hip_stream);
+/* The whole FeatExtNet (models/ucsnet.py:237-302, num_stage 3) for one image (3,H,W), H and W multiples of 4, enqueued by one
+ * call.  15 layers, weights[i] / biases[i] (biases[i] may be null), BatchNorm folded: i = conv0.0, conv0.1, conv1.0, conv1.1,
+ * conv1.2, conv2.0, conv2.1, conv2.2, out1, deconv1.deconv, deconv1.conv, out2, deconv2.deconv, deconv2.conv, out3.  The
+ * convolutions' weights are packed as for svs_conv2d; the two transposed layers' (9, 12) are (Cin,Cout,3,3) as for svs_deconv2d.
+ * wfrags: null, or 15 entries: wfrags[i] != null -> layer i runs on the matrix cores (svs_conv2d_mfma_pack, or
+ * svs_deconv2d_mfma_pack for 9 and 12).  torch.cat((x, x_pre)) of :233 is never copied: the workspace
+ * (svs_featurenet_unet_workspace_bytes) holds both concatenations, the transposed layer writes channels [0,C) and the encoder's
+ * last layer of that level (conv1.2, conv0.1) channels [C,2C).  -> stage1 (4b,H/4,W/4), stage2 (2b,H/2,W/2), stage3 (b,H,W). */
+size_t svs_featurenet_unet_workspace_bytes(int base_channels, int H, int W);
+int svs_featurenet_unet(const float* image, int H, int W, int base_channels, const float* const* weights,
+                        const float* const* biases, const void* const* wfrags, float* workspace, float* stage1, float* stage2,
+                        float* stage3, void* hip_stream);
+/* compute_depth's tail (models/ucsnet.py:381-394): svs_prob_depth_conf (the same device code: prob, depth, conf and index are
+ * bit-identical on the same input) and variance (H,W) = lamb * sqrt(sum_d prob_d (depth_values_d - depth)^2). */
+int svs_prob_depth_conf_var(const float* reg, const float* depth_values, int D, int H, int W, float lamb, float* prob,
+                            float* depth, float* conf, int* index, float* variance, void* hip_stream);
+/* uncertainty_aware_samples at stages 2 and 3 (models/ucsnet.py:450-452, 59-70): both maps (Hd,Wd) = (Hv,Wv) resized
+ * bilinearly (align_corners=False) to (Hs,Ws), then out[i] = ((cur + low) + step * i) + 1e-12 with low = -min(cur, var),
+ * step = (var - low) / (D - 1), in float32 in that order.  D < 2 or maps of different sizes: an error code, nothing launched.
+ * Stage 1 (:47-57) is svs_depth_hypotheses(prev_depth = NULL). */
+int svs_uncertainty_hypotheses(const float* prev_depth, int Hd, int Wd, const float* prev_var, int Hv, int Wv, int Hs, int Ws,
+                               int D, float* out, void* hip_stream);
+
 /* ---- f3  depth-map fusion (helpers/utils.py:75-132, runner.py:301-386) -------------------------------------------
  * svs_fuse_view: reproject_with_depth + check_geometric_consistency of ONE reference view against n_src <= 16 source
  * views, then the aggregation of filter_depth: geo_mask_sum, depth_est_averaged = (sum of the masked reprojected

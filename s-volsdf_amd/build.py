@@ -33,6 +33,7 @@ UNITS = {
     "svs_conv_gemm.hip": [],
     "svs_conv2d.hip": [],
     "svs_conv2d_mfma.hip": [],
+    "svs_ucsnet.hip": ["-ffp-contract=off"],
     "svs_wgrad.hip": [],
     "svs_mlp_bwd.hip": [],
     "svs_mlp_bwd_h2.hip": [],

@@ -1077,10 +1077,13 @@ __global__ __launch_bounds__(256, 4) void conv3d_c1_kernel(C1Args a) {
 // 256 threads = 256/DS consecutive pixels x DS interleaved depth slices (slice sl owns d = sl, sl + DS, ...): at stage 1
 // there are only 128 x 160 pixels, one thread per pixel would leave most of the chip idle behind 3 x 192 serial loads.
 // Partial maxima / sums meet in LDS and are combined in slice order (deterministic).
-template <int DS>
+// VAR (UCSNet, models/ucsnet.py:393-394): one more reduction over D behind the others, variance = lamb * sqrt(sum_d p_d
+// (z_d - depth)^2) with the pixel's combined depth; the instructions that form prob, depth, conf and index are the same.
+template <int DS, bool VAR = false>
 __global__ __launch_bounds__(256) void prob_depth_conf_kernel(const float* __restrict__ reg, const float* __restrict__ depth_values,
                                                               int D, int HW, float* __restrict__ prob, float* __restrict__ depth,
-                                                              float* __restrict__ conf, int* __restrict__ index) {
+                                                              float* __restrict__ conf, int* __restrict__ index,
+                                                              float lamb = 0.0f, float* __restrict__ variance = nullptr) {
   constexpr int PX = 256 / DS;
   __shared__ float red[3][DS][PX];
   const int lp = threadIdx.x % PX, sl = threadIdx.x / PX;
@@ -1158,7 +1161,35 @@ __global__ __launch_bounds__(256) void prob_depth_conf_kernel(const float* __res
 #pragma unroll
     for (int k = 0; k < DS; ++k) { dep += red[0][k][lp]; idxf += red[2][k][lp]; }
   }
+  float ev = 0.0f;
+  if constexpr (VAR) {
+    if (live) {
+      if (cached) {
+#pragma unroll
+        for (int i = 0; i < kSoftN; ++i) {
+          const int d = sl + i * DS;
+          if (d < D) {
+            const float dz = depth_values[(size_t)d * HW + p] - dep;
+            ev += (dz * dz) * (v[i] * inv);
+          }
+        }
+      } else {
+        for (int d = sl; d < D; d += DS) {
+          const float dz = depth_values[(size_t)d * HW + p] - dep;
+          ev += (dz * dz) * (__expf(reg[(size_t)d * HW + p] - m) * inv);
+        }
+      }
+    }
+    if (DS > 1) {
+      red[1][sl][lp] = ev;                    // (red[1] was last read before the barriers of the depth reduction)
+      __syncthreads();
+      ev = 0.0f;
+#pragma unroll
+      for (int k = 0; k < DS; ++k) ev += red[1][k][lp];
+    }
+  }
   if (!live || sl != 0) return;
+  if constexpr (VAR) variance[p] = lamb * __builtin_sqrtf(ev);
   int idx = (int)idxf;                       // .long() truncation
   idx = idx < 0 ? 0 : (idx > D - 1 ? D - 1 : idx);
   float c = 0.0f;                            // p[idx-1] + p[idx] + p[idx+1] + p[idx+2], zero padded
@@ -1250,6 +1281,21 @@ __global__ void depth_hypotheses_kernel(HypoArgs a) {
 
 using namespace svs;
 using namespace svs::costvol;
+
+// the tail's dispatch over D, shared by both entries: 8 / 4 / 1 depth slices per pixel
+template <bool VAR>
+static int launch_tail(const char* what, const float* reg, const float* depth_values, int D, int H, int W, float lamb, float* prob,
+                       float* depth, float* conf, int* index, float* variance, void* hip_stream) {
+  if (!reg || !depth_values || !prob || !depth || !conf || (VAR && !variance) || D < 1 || H < 1 || W < 1) {
+    set_error("%s: bad argument", what); return SVS_EINVAL;
+  }
+  hipStream_t s = (hipStream_t)hip_stream;
+  const int HW = H * W;
+  if (D >= 64) prob_depth_conf_kernel<8, VAR><<<(HW + 31) / 32, 256, 0, s>>>(reg, depth_values, D, HW, prob, depth, conf, index, lamb, variance);
+  else if (D >= 16) prob_depth_conf_kernel<4, VAR><<<(HW + 63) / 64, 256, 0, s>>>(reg, depth_values, D, HW, prob, depth, conf, index, lamb, variance);
+  else prob_depth_conf_kernel<1, VAR><<<(HW + 255) / 256, 256, 0, s>>>(reg, depth_values, D, HW, prob, depth, conf, index, lamb, variance);
+  return check_launch(what);
+}
 
 extern "C" {
 
@@ -1365,15 +1411,13 @@ int svs_conv3d_c1(const float* in, const float* weight, const float* bias, const
 
 int svs_prob_depth_conf(const float* reg, const float* depth_values, int D, int H, int W, float* prob, float* depth,
                         float* conf, int* index, void* hip_stream) {
-  if (!reg || !depth_values || !prob || !depth || !conf || D < 1 || H < 1 || W < 1) {
-    set_error("svs_prob_depth_conf: bad argument"); return SVS_EINVAL;
-  }
-  hipStream_t s = (hipStream_t)hip_stream;
-  const int HW = H * W;
-  if (D >= 64) prob_depth_conf_kernel<8><<<(HW + 31) / 32, 256, 0, s>>>(reg, depth_values, D, HW, prob, depth, conf, index);
-  else if (D >= 16) prob_depth_conf_kernel<4><<<(HW + 63) / 64, 256, 0, s>>>(reg, depth_values, D, HW, prob, depth, conf, index);
-  else prob_depth_conf_kernel<1><<<(HW + 255) / 256, 256, 0, s>>>(reg, depth_values, D, HW, prob, depth, conf, index);
-  return check_launch("svs_prob_depth_conf");
+  return launch_tail<false>("svs_prob_depth_conf", reg, depth_values, D, H, W, 0.0f, prob, depth, conf, index, nullptr, hip_stream);
+}
+
+// svs_prob_depth_conf with UCSNet's per-pixel uncertainty (models/ucsnet.py:393-394)
+int svs_prob_depth_conf_var(const float* reg, const float* depth_values, int D, int H, int W, float lamb, float* prob, float* depth,
+                            float* conf, int* index, float* variance, void* hip_stream) {
+  return launch_tail<true>("svs_prob_depth_conf_var", reg, depth_values, D, H, W, lamb, prob, depth, conf, index, variance, hip_stream);
 }
 
 int svs_depth_hypotheses(const float* prev_depth, int Hp, int Wp, int H_img, int W_img, int D, int scale, float dmin,

@@ -174,6 +174,8 @@ def x_is_device(t):
 
 class CostRegNet(nn.Module):
     """models/CasMVSNet.py:441-472."""
+    # attribute names of the three transposed layers (models/ucsnet.py:318-322 calls the same layers deconv7 / 8 / 9)
+    DECONV_NAMES = ("conv7", "conv9", "conv11")
 
     def __init__(self, in_channels, base_channels):
         super().__init__()
@@ -182,7 +184,8 @@ class CostRegNet(nn.Module):
         self.conv1, self.conv2 = Conv3d(b, 2 * b, stride=2), Conv3d(2 * b, 2 * b)
         self.conv3, self.conv4 = Conv3d(2 * b, 4 * b, stride=2), Conv3d(4 * b, 4 * b)
         self.conv5, self.conv6 = Conv3d(4 * b, 8 * b, stride=2), Conv3d(8 * b, 8 * b)
-        self.conv7, self.conv9, self.conv11 = Deconv3d(8 * b, 4 * b), Deconv3d(4 * b, 2 * b), Deconv3d(2 * b, b)
+        for name, cin in zip(self.DECONV_NAMES, (8 * b, 4 * b, 2 * b)):
+            setattr(self, name, Deconv3d(cin, cin // 2))
         self.prob = nn.Conv3d(b, 1, 3, stride=1, padding=1, bias=False)
         self._prob_w, self._prob_key = None, None
 
@@ -202,9 +205,10 @@ class CostRegNet(nn.Module):
         c2 = self.conv2(self.conv1(c0, split_out=fused12))
         c4 = self.conv4(self.conv3(c2))
         y = self.conv6(self.conv5(c4))
-        y = self.conv7(y, skip=c4)
-        y = self.conv9(y, skip=c2)
-        y = self.conv11(y, skip=c0)
+        up7, up9, up11 = (getattr(self, name) for name in self.DECONV_NAMES)
+        y = up7(y, skip=c4)
+        y = up9(y, skip=c2)
+        y = up11(y, skip=c0)
         key = (self.prob.weight.data_ptr(), self.prob.weight._version)
         if self._prob_key != key:
             w = self.prob.weight.detach()

@@ -1,6 +1,7 @@
 """torch-tensor wrappers for the CasMVSNet cost-volume kernels (csrc/svs_costvol.hip)."""
 import ctypes
 import os
+import weakref
 
 import numpy as np
 import torch
@@ -101,6 +102,9 @@ def clear_caches():
     _HWC_CACHE.clear()
     _RT_CACHE.clear()
     _HWC_BYTES = 0
+    _DECONV_FRAG_CACHE.clear()
+    for net in list(_UNETS):
+        net.forget()
     from . import ops
     ops.clear_lookup_caches()
 
@@ -416,6 +420,169 @@ class FeatureNetFpn:
         _lib.check(L.svs_featurenet_fpn2(_ptr(image), H, W, b, wt, bt, ft, _ptr(self._ws), _ptr(s1), _ptr(s2), _ptr(s3), _stream()),
                    "svs_featurenet_fpn2")
         return s1, s2, s3
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# UCSNet (models/ucsnet.py; csrc/svs_ucsnet.hip)
+# ---------------------------------------------------------------------------------------------------------------------
+_DECONV_FRAG_CACHE = {}
+
+
+def deconv2d_mfma_supported(Cin, Cout):
+    return bool(_lib.load().svs_deconv2d_mfma_supported(int(Cin), int(Cout)))
+
+
+def deconv2d_mfma_frag(weight):
+    """(Cin,Cout,3,3) float32 -> the fp16 hi / mid MFMA A fragments of svs_deconv2d_mfma (packed on the device, cached per
+    weight tensor: address + version)."""
+    key = (weight.data_ptr(), weight._version, tuple(weight.shape), weight.device)
+    hit = _DECONV_FRAG_CACHE.get(key)
+    if hit is not None:
+        return hit[0]
+    if len(_DECONV_FRAG_CACHE) > 64:
+        _DECONV_FRAG_CACHE.clear()
+    L = _lib.load()
+    Cin, Cout = weight.shape[:2]
+    w = _f32(weight.detach())
+    frag = torch.empty(L.svs_deconv2d_mfma_wfrag_bytes(Cin, Cout) // 2, dtype=torch.float16, device=weight.device)
+    _lib.check(L.svs_deconv2d_mfma_pack(_ptr(w), Cin, Cout, _ptr(frag), _stream()), "svs_deconv2d_mfma_pack")
+    _DECONV_FRAG_CACHE[key] = (frag, weight, w)            # keep `weight` alive: the key holds its address
+    return frag
+
+
+def deconv2d(x, weight, bias=None, relu=False, out=None, mfma=None):
+    """Deconv2dUnit's transposed convolution (models/ucsnet.py:135, 225: k3, s2, p1, output_padding 1): x (Cin,H,W), weight
+    (Cin,Cout,3,3) with BatchNorm folded -> (Cout,2H,2W) = relu?(conv_transpose2d + bias).  out: a contiguous float32
+    (C >= Cout, 2H, 2W) tensor whose first Cout channels are written (a concatenation buffer).  mfma: True = svs_deconv2d_mfma
+    (raises for unsupported shapes), False = the float32 vector kernel, None = the matrix cores where they support the shape."""
+    L = _lib.load()
+    x = _f32(x)
+    Cin, H, W = x.shape
+    if weight.dim() != 4 or weight.shape[0] != Cin or tuple(weight.shape[2:]) != (3, 3):
+        raise ValueError("weight must be (Cin,Cout,3,3)")
+    Cout = weight.shape[1]
+    if out is None:
+        out = torch.empty(Cout, 2 * H, 2 * W, device=x.device)
+    elif (out.dim() != 3 or out.shape[0] < Cout or tuple(out.shape[1:]) != (2 * H, 2 * W) or not out.is_contiguous()
+          or out.dtype != torch.float32):
+        raise ValueError("out must be a contiguous float32 (C >= Cout, 2H, 2W) tensor")
+    if mfma is None:
+        mfma = deconv2d_mfma_supported(Cin, Cout)
+    elif mfma and not deconv2d_mfma_supported(Cin, Cout):
+        raise ValueError("shape not supported by svs_deconv2d_mfma")
+    bias = _f32(bias) if bias is not None else None
+    if mfma:
+        _lib.check(L.svs_deconv2d_mfma(_ptr(x), _ptr(deconv2d_mfma_frag(weight)), _ptr(bias), _ptr(out), 4 * H * W, Cin, Cout, H, W,
+                                       int(bool(relu)), _stream()), "svs_deconv2d_mfma")
+    else:
+        _lib.check(L.svs_deconv2d(_ptr(x), _ptr(_f32(weight.detach())), _ptr(bias), _ptr(out), 4 * H * W, Cin, Cout, H, W,
+                                  int(bool(relu)), _stream()), "svs_deconv2d")
+    return out
+
+
+# (layer index -> stride) of svs_featurenet_unet's 15 layers; 9 and 12 are the transposed ones
+_UNET_STRIDES = (1, 1, 2, 1, 1, 2, 1, 1, 1, 2, 1, 1, 2, 1, 1)
+_UNET_DECONV = (9, 12)
+_UNETS = weakref.WeakSet()               # live wrappers: clear_caches() drops their tables and workspaces
+
+
+class FeatureNetUnet:
+    """The 15 layers of UCSNet's FeatExtNet (models/ucsnet.py:237-302) enqueued by ONE library call (svs_featurenet_unet), as
+    FeatureNetFpn does for the FPN; the two concatenations are formed in place in the workspace."""
+    LAYERS = 15
+
+    def __init__(self, base_channels, mfma=None, deconv_mfma=None):
+        """mfma = False: every layer on the float32 kernels.  deconv_mfma: True / False = both transposed layers on the matrix
+        cores / on the float32 kernel (the A/B comparison of tools/bench_ucsnet.py); None = the default, see tables()."""
+        self.b = int(base_channels)
+        self.mfma = True if mfma is None else bool(mfma)
+        self.deconv_mfma = (None if self.mfma else False) if deconv_mfma is None else bool(deconv_mfma)
+        self.forget()
+        _UNETS.add(self)
+
+    def forget(self):
+        self._ws, self._ws_key = None, None
+        self._tables, self._tables_key = None, None
+
+    def tables(self, layers):
+        """layers: 15 (weight, bias or None) pairs in the library's order, convolutions (Cout,Cin,k,k), the transposed layers
+        (Cin,Cout,3,3) -> pointer tables (cached until a tensor changes)."""
+        key = tuple((w.data_ptr(), w._version, None if b is None else (b.data_ptr(), b._version)) for w, b in layers)
+        if key != self._tables_key:
+            packed = [_f32(w.detach()) if i in _UNET_DECONV else conv2d_pack(w) for i, (w, _) in enumerate(layers)]
+            biases = [None if b is None else _f32(b) for _, b in layers]
+            frags = []
+            for i, (w, _) in enumerate(layers):
+                if i in _UNET_DECONV:
+                    # deconv1.deconv (32 -> 16) on the matrix cores: 0.017 ms against 0.041 at 288 x 384 -> 576 x 768.  Not
+                    # deconv2.deconv (16 -> 8, a half-full M tile): alone it is not faster there, 0.039 ms against 0.038 at
+                    # 576 x 768 -> 1152 x 1536 with overlapping ranges, cause not established; inside the extractor the choice
+                    # moves the 0.51 ms per image by about 1 % the other way (profiles/ucsnet_bench.txt)
+                    on = w.shape[1] > 8 if self.deconv_mfma is None else self.deconv_mfma
+                    frags.append(deconv2d_mfma_frag(w) if on and deconv2d_mfma_supported(w.shape[0], w.shape[1]) else None)
+                else:
+                    # the 3x3 / 5x5 layers with 8 / 16 / 32 input channels run on the matrix cores; not conv0.1 (8 -> 8 at
+                    # full resolution: a quarter-full M tile, slower than the vector kernel -- FeatureNetFpn.tables)
+                    frags.append(conv2d_mfma_frag(w) if (self.mfma and w.shape[2] > 1 and not (w.shape[1] <= 8 and w.shape[2] == 3)
+                                                         and conv2d_mfma_supported(w.shape[1], w.shape[0], w.shape[2], _UNET_STRIDES[i]))
+                                 else None)
+            self._tables = (_ptr_array(packed), _ptr_array(biases), packed, biases, layers, _ptr_array(frags), frags)
+            self._tables_key = key
+        return self._tables
+
+    def __call__(self, image, layers):
+        """image (3,H,W) -> stage1 (4b,H/4,W/4), stage2 (2b,H/2,W/2), stage3 (b,H,W)."""
+        L = _lib.load()
+        if len(layers) != self.LAYERS:
+            raise ValueError("15 layers expected")
+        image = _f32(image)
+        _, H, W = image.shape
+        if image.shape[0] != 3 or H % 4 or W % 4:
+            raise ValueError("image must be (3,H,W) with H, W multiples of 4")
+        dev, b = image.device, self.b
+        if self._ws_key != (H, W, dev):
+            self._ws = torch.empty(L.svs_featurenet_unet_workspace_bytes(b, H, W) // 4, device=dev)
+            self._ws_key = (H, W, dev)
+        tb = self.tables(layers)
+        wt, bt, ft = tb[0], tb[1], tb[5]
+        s1 = torch.empty(4 * b, H // 4, W // 4, device=dev)
+        s2 = torch.empty(2 * b, H // 2, W // 2, device=dev)
+        s3 = torch.empty(b, H, W, device=dev)
+        _lib.check(L.svs_featurenet_unet(_ptr(image), H, W, b, wt, bt, ft, _ptr(self._ws), _ptr(s1), _ptr(s2), _ptr(s3), _stream()),
+                   "svs_featurenet_unet")
+        return s1, s2, s3
+
+
+def prob_depth_conf_var(reg, depth_values, lamb):
+    """compute_depth's tail (models/ucsnet.py:381-394): reg (D,H,W), depth_values (D,H,W) -> prob (D,H,W), depth (H,W), conf
+    (H,W), index (H,W int32) as prob_depth_conf gives them, and variance (H,W) = lamb * sqrt(sum_d prob_d (z_d - depth)^2)."""
+    L = _lib.load()
+    reg, dv = _f32(reg), _f32(depth_values)
+    D, H, W = reg.shape
+    dev = reg.device
+    prob = torch.empty(D, H, W, device=dev)
+    depth = torch.empty(H, W, device=dev)
+    conf = torch.empty(H, W, device=dev)
+    var = torch.empty(H, W, device=dev)
+    idx = torch.empty(H, W, dtype=torch.int32, device=dev)
+    _lib.check(L.svs_prob_depth_conf_var(_ptr(reg), _ptr(dv), D, H, W, float(lamb), _ptr(prob), _ptr(depth), _ptr(conf), _ptr(idx),
+                                         _ptr(var), _stream()), "svs_prob_depth_conf_var")
+    return prob, depth, conf, idx, var
+
+
+def uncertainty_hypotheses(prev_depth, prev_var, hw, ndepth, dmin=None, dmax=None, inverse=False, device=None):
+    """uncertainty_aware_samples (models/ucsnet.py:44-72) -> (D,) + hw.  prev_depth None: stage 1, D planes dmin..dmax (linear,
+    or linear in 1/depth), the same for every pixel (svs_depth_hypotheses).  Else prev_depth, prev_var (Hp,Wp): both resized
+    bilinearly to hw, D samples from cur - min(cur, var) to cur + var."""
+    L = _lib.load()
+    Hs, Ws = hw
+    if prev_depth is None:
+        return depth_hypotheses(None, (Hs, Ws), ndepth, 1, dmin, dmax, 0.0, inverse, device)
+    pd, pv = _f32(prev_depth), _f32(prev_var)
+    out = torch.empty(max(int(ndepth), 0), Hs, Ws, device=pd.device)
+    _lib.check(L.svs_uncertainty_hypotheses(_ptr(pd), pd.shape[-2], pd.shape[-1], _ptr(pv), pv.shape[-2], pv.shape[-1], Hs, Ws,
+                                            int(ndepth), _ptr(out), _stream()), "svs_uncertainty_hypotheses")
+    return out
 
 
 _GEMM_ON = [True]

@@ -212,6 +212,19 @@ SIGNATURES.update({
     "svs_lpips_score": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, _P, _P, _P]),
 })
 
+# models.ucsnet (csrc/svs_ucsnet.hip, the tail in csrc/svs_costvol.hip)
+SIGNATURES.update({
+    "svs_deconv2d": (c_int, [_P, _P, _P, _P, c_longlong, c_int, c_int, c_int, c_int, c_int, _P]),
+    "svs_deconv2d_mfma_supported": (c_int, [c_int, c_int]),
+    "svs_deconv2d_mfma_wfrag_bytes": (c_size_t, [c_int, c_int]),
+    "svs_deconv2d_mfma_pack": (c_int, [_P, c_int, c_int, _P, _P]),
+    "svs_deconv2d_mfma": (c_int, [_P, _P, _P, _P, c_longlong, c_int, c_int, c_int, c_int, c_int, _P]),
+    "svs_featurenet_unet_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "svs_featurenet_unet": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "svs_prob_depth_conf_var": (c_int, [_P, _P, c_int, c_int, c_int, c_float, _P, _P, _P, _P, _P, _P]),
+    "svs_uncertainty_hypotheses": (c_int, [_P, c_int, c_int, _P, c_int, c_int, c_int, c_int, c_int, _P, _P]),
+})
+
 ABI_VERSION = 101          # svs_version() of the library this binding was written against (include/svolsdf_hip.h)
 
 

@@ -39,7 +39,9 @@ class StageLoop:
             img = imgs[:, v]
             key = self._fingerprint(img) if self.cache_features else None
             if key is None or key not in self._features:
-                f = self.model.feature(img)
+                # runner.py:192-195: UCSNet's extractor is `feature_extraction`, the other networks' is `feature`
+                extract = self.model.feature if hasattr(self.model, "feature") else self.model.feature_extraction
+                f = extract(img)
                 self.feature_calls += 1
                 if key is None:
                     out.append(f)
@@ -52,8 +54,9 @@ class StageLoop:
     def cost_volumes(self, stage_idx, samples, outs_samples, view_extra_samples=None, int_r=None, inverse_depth=False,
                      prevent_oom=False):
         """runner.py:182-207 for one stage: samples = the (device) samples of the scan's reference views;
-        outs_samples[i] = the previous stage's outputs of view i (None at stage 0).  Returns (outs, view_extras)."""
-        if int_r is None:
+        outs_samples[i] = the previous stage's outputs of view i (None at stage 0), view_extra_samples[i] = what the model
+        returned beside them (UCSNet: the previous stage's uncertainty; CasMVSNet: None).  Returns (outs, view_extras)."""
+        if int_r is None and hasattr(self.model, "depth_interals_ratio"):      # (UCSNet has none: int_r stays None, runner.py:179)
             int_r = self.model.depth_interals_ratio[stage_idx]
         n = len(samples)
         view_extra_samples = view_extra_samples or [None] * n
