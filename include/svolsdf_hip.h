@@ -524,6 +524,59 @@ int svs_prob_depth_conf_var(const float* reg, const float* depth_values, int D, 
 int svs_uncertainty_hypotheses(const float* prev_depth, int Hd, int Wd, const float* prev_var, int Hv, int Wv, int Hs, int Ws,
                                int D, float* out, void* hip_stream);
 
+/* ---- TransMVSNet, the third MVS backbone (models/TransMVSNet.py; csrc/svs_transmvs.hip) --------------------------------
+ * svs_version() stays 101: entries are only added.  float32 vector kernels throughout; a matrix-core form of the deformable
+ * convolution does not exist yet.  Every argument is checked before the first launch.
+ *
+ * svs_deform_conv2d: DCN.forward behind its conv_offset_mask (models/dcn.py:68-80: torchvision.ops.deform_conv2d, 3x3, stride 1,
+ * padding 1, dilation 1, one offset group, modulated) with the BatchNorm(eval) and ReLU that follow it in FeatureNet
+ * (models/module.py:364-397):  out (Cout,H,W) = relu?(scale * (deform_conv(in (32,H,W)) + bias) + shift).
+ * offset_mask (27,H,W) is conv_offset_mask's raw output: for tap k = 3 ky + kx, channels 2k and 2k+1 are dy and dx (the
+ * torch.cat((o1, o2)) of :68-69 is the first 18 channels in order) and sigmoid(channel 18+k) is the mask.  The tap samples
+ * (y + ky - 1 + dy, x + kx - 1 + dx) by torchvision's rule: 0 when y <= -1, y >= H, x <= -1 or x >= W, else four weighted
+ * corners of which one outside the image contributes 0; an offset that is not a number samples 0.  weight_packed: the layout of
+ * svs_conv2d, [ceil(Cout/8)][32][3][3][8].  bias, scale + shift (both or neither) may be null.  Cout in 1..32. */
+int svs_deform_conv2d(const float* in, const float* offset_mask, const float* weight_packed, const float* bias, const float* scale,
+                      const float* shift, float* out, int Cout, int H, int W, int relu, void* hip_stream);
+/* The Feature Matching Transformer (models/FMT.py), tokens channel-last (L,32), d_model 32, 8 heads of 4.
+ * svs_fmt_tokens_in: (32,H,W) + PositionEncodingSine(32, temp_bug_fix=True) (models/position_encoding.py:39-60; positions count
+ *   from 1) -> (H*W,32); div_term: HOST array of the 8 frequencies of :43.  svs_fmt_tokens_out: (H*W,32) -> (32,H,W).
+ *   (The einops.rearrange calls of :147-172.)
+ * svs_fmt_kv: LinearAttention's sums over the S source tokens (:23-32): K = elu(W_k s + b_k) + 1, V = W_v s + b_v,
+ *   kvsum[16 h + 4 m + d] = sum_s K[s,h,d] V[s,h,m], kvsum[128 + 4 h + d] = sum_s K[s,h,d] (160 floats).  Per-workgroup
+ *   partial sums go to `workspace` (svs_fmt_kv_workspace_bytes) and one last workgroup adds them in index order: no atomics,
+ *   the same bits on every launch.  Weights (32,32) row-major as nn.Linear holds them.
+ * svs_fmt_layer: EncoderLayer.forward (:96-111) per query token, given its source's kvsum: Q = elu(W_q x + b_q) + 1,
+ *   Z = 1 / (Q . Ksum + 1e-6) per head, attention, out-projection, LayerNorm1(x + .), 32 -> 64 -> 32 with ReLU, LayerNorm2
+ *   (eps 1e-5).  weights: HOST array of 12 device pointers: query_projection.{weight,bias}, out_projection.{weight,bias},
+ *   linear1.{weight,bias}, linear2.{weight,bias}, norm1.{weight,bias}, norm2.{weight,bias}. */
+int svs_fmt_tokens_in(const float* chw, int H, int W, const float* div_term, float* tokens, void* hip_stream);
+int svs_fmt_tokens_out(const float* tokens, int H, int W, float* chw, void* hip_stream);
+size_t svs_fmt_kv_workspace_bytes(int S);
+int svs_fmt_kv(const float* source, int S, const float* k_w, const float* k_b, const float* v_w, const float* v_b, float* workspace,
+               float* kvsum, void* hip_stream);
+int svs_fmt_layer(const float* x, int L, const float* kvsum, const float* const* weights, float* out, void* hip_stream);
+/* _upsample_add(dim_reduction(x), y) of the pathway (models/FMT.py:196-223): out (Cin/2,2h,2w) = bilinear_x2(conv1x1(x (Cin,h,w)))
+ * + y, align_corners=False, the reduction before the up-sampling as in the reference.  weight (Cin/2,Cin), Cin 32 or 16. */
+int svs_pathway_step(const float* x, const float* weight, const float* y, float* out, int Cin, int h, int w, void* hip_stream);
+/* DepthNet.forward steps 1-2 (models/TransMVSNet.py:52-91): per source view sim_v[d,y,x] = mean_c warped_v[c,d,y,x] ref[c,y,x],
+ * similarity (D,H,W) = sum_v sim_v w_v / (1e-5 + sum_v w_v).  The warp is the homo_warping of models/module.py:285-324, NOT
+ * CasMVSNet's: grid_sample with align_corners=True, and a hypothesis whose projected z is below 1e-6 samples 0 (:310-315).
+ * Arguments as svs_warp_variance: ref_feature (C,H,W), src_features_hwc: HOST array of n_src <= 4 DEVICE (H,W,C) maps,
+ * rot_trans: HOST, 12 floats per source; C in {8,16,32}.  prev_weights null (stage 1): w_v = max_d sigmoid(pixel_wise_net(
+ * sim_v)) with net = 177 floats, BatchNorm folded: scale0[16] shift0[16] W1[8][16] shift1[8] w2[8] b2 (:17-30); else
+ * prev_weights (n_src,H/2,W/2) is read at (y/2, x/2), the nearest x2 of :208 (H and W even).  weights_out (n_src,H,W) receives
+ * the weights at this stage's size either way.  workspace: svs_warp_similarity_workspace_bytes (the per-view similarities). */
+size_t svs_warp_similarity_workspace_bytes(int n_src, int D, int H, int W);
+int svs_warp_similarity(const float* ref_feature, const float* const* src_features_hwc, const float* rot_trans, int n_src, int C,
+                        int D, int H, int W, const float* depth_values, const float* prev_weights, const float* net,
+                        float* workspace, float* similarity, float* weights_out, void* hip_stream);
+/* TransMVSNet's tail (models/TransMVSNet.py:100-109, 225-227), the device code of svs_prob_depth_conf with a flag
+ * (csrc/svs_costvol.hip): prob is bit-identical to that entry's; index = the first plane that holds the maximum logit
+ * (torch.argmax's rule on exact ties), depth = depth_values[index], conf = prob[index]. */
+int svs_prob_wta(const float* reg, const float* depth_values, int D, int H, int W, float* prob, float* depth, float* conf,
+                 int* index, void* hip_stream);
+
 /* ---- f3  depth-map fusion (helpers/utils.py:75-132, runner.py:301-386) -------------------------------------------
  * svs_fuse_view: reproject_with_depth + check_geometric_consistency of ONE reference view against n_src <= 16 source
  * views, then the aggregation of filter_depth: geo_mask_sum, depth_est_averaged = (sum of the masked reprojected

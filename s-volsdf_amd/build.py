@@ -34,6 +34,7 @@ UNITS = {
     "svs_conv2d.hip": [],
     "svs_conv2d_mfma.hip": [],
     "svs_ucsnet.hip": ["-ffp-contract=off"],
+    "svs_transmvs.hip": [],
     "svs_wgrad.hip": [],
     "svs_mlp_bwd.hip": [],
     "svs_mlp_bwd_h2.hip": [],

@@ -1079,7 +1079,9 @@ __global__ __launch_bounds__(256, 4) void conv3d_c1_kernel(C1Args a) {
 // Partial maxima / sums meet in LDS and are combined in slice order (deterministic).
 // VAR (UCSNet, models/ucsnet.py:393-394): one more reduction over D behind the others, variance = lamb * sqrt(sum_d p_d
 // (z_d - depth)^2) with the pixel's combined depth; the instructions that form prob, depth, conf and index are the same.
-template <int DS, bool VAR = false>
+// WTA (TransMVSNet, models/TransMVSNet.py:100-109, 225-227): the same probabilities; index = the first plane that holds the
+// maximum (torch.argmax's rule on exact ties), depth = depth_values[index], conf = prob[index].
+template <int DS, bool VAR = false, bool WTA = false>
 __global__ __launch_bounds__(256) void prob_depth_conf_kernel(const float* __restrict__ reg, const float* __restrict__ depth_values,
                                                               int D, int HW, float* __restrict__ prob, float* __restrict__ depth,
                                                               float* __restrict__ conf, int* __restrict__ index,
@@ -1112,6 +1114,26 @@ __global__ __launch_bounds__(256) void prob_depth_conf_kernel(const float* __res
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < DS; ++k) m = __builtin_fmaxf(m, red[0][k][lp]);
+  }
+  int first = D;                             // WTA: the first plane of this slice, then of the pixel, that holds the maximum
+  if constexpr (WTA) {
+    if (live) {
+      if (cached) {
+#pragma unroll
+        for (int i = kSoftN - 1; i >= 0; --i)
+          if (sl + i * DS < D && v[i] == m) first = sl + i * DS;
+      } else {
+        for (int d = sl; d < D; d += DS)
+          if (reg[(size_t)d * HW + p] == m) { first = d; break; }
+      }
+    }
+    if (DS > 1) {
+      int* slot = reinterpret_cast<int*>(&red[2][0][0]);
+      slot[sl * PX + lp] = first;
+      __syncthreads();
+#pragma unroll
+      for (int k = 0; k < DS; ++k) first = first < slot[k * PX + lp] ? first : slot[k * PX + lp];
+    }
   }
   float s = 0.0f;
   if (live) {
@@ -1190,6 +1212,13 @@ __global__ __launch_bounds__(256) void prob_depth_conf_kernel(const float* __res
   }
   if (!live || sl != 0) return;
   if constexpr (VAR) variance[p] = lamb * __builtin_sqrtf(ev);
+  if constexpr (WTA) {
+    const int w = first > D - 1 ? D - 1 : first;          // (no plane equals a NaN maximum: the last plane then)
+    depth[p] = depth_values[(size_t)w * HW + p];
+    conf[p] = __expf(reg[(size_t)w * HW + p] - m) * inv;
+    if (index) index[p] = w;
+    return;
+  }
   int idx = (int)idxf;                       // .long() truncation
   idx = idx < 0 ? 0 : (idx > D - 1 ? D - 1 : idx);
   float c = 0.0f;                            // p[idx-1] + p[idx] + p[idx+1] + p[idx+2], zero padded
@@ -1283,7 +1312,7 @@ using namespace svs;
 using namespace svs::costvol;
 
 // the tail's dispatch over D, shared by both entries: 8 / 4 / 1 depth slices per pixel
-template <bool VAR>
+template <bool VAR, bool WTA = false>
 static int launch_tail(const char* what, const float* reg, const float* depth_values, int D, int H, int W, float lamb, float* prob,
                        float* depth, float* conf, int* index, float* variance, void* hip_stream) {
   if (!reg || !depth_values || !prob || !depth || !conf || (VAR && !variance) || D < 1 || H < 1 || W < 1) {
@@ -1291,9 +1320,9 @@ static int launch_tail(const char* what, const float* reg, const float* depth_va
   }
   hipStream_t s = (hipStream_t)hip_stream;
   const int HW = H * W;
-  if (D >= 64) prob_depth_conf_kernel<8, VAR><<<(HW + 31) / 32, 256, 0, s>>>(reg, depth_values, D, HW, prob, depth, conf, index, lamb, variance);
-  else if (D >= 16) prob_depth_conf_kernel<4, VAR><<<(HW + 63) / 64, 256, 0, s>>>(reg, depth_values, D, HW, prob, depth, conf, index, lamb, variance);
-  else prob_depth_conf_kernel<1, VAR><<<(HW + 255) / 256, 256, 0, s>>>(reg, depth_values, D, HW, prob, depth, conf, index, lamb, variance);
+  if (D >= 64) prob_depth_conf_kernel<8, VAR, WTA><<<(HW + 31) / 32, 256, 0, s>>>(reg, depth_values, D, HW, prob, depth, conf, index, lamb, variance);
+  else if (D >= 16) prob_depth_conf_kernel<4, VAR, WTA><<<(HW + 63) / 64, 256, 0, s>>>(reg, depth_values, D, HW, prob, depth, conf, index, lamb, variance);
+  else prob_depth_conf_kernel<1, VAR, WTA><<<(HW + 255) / 256, 256, 0, s>>>(reg, depth_values, D, HW, prob, depth, conf, index, lamb, variance);
   return check_launch(what);
 }
 
@@ -1418,6 +1447,12 @@ int svs_prob_depth_conf(const float* reg, const float* depth_values, int D, int 
 int svs_prob_depth_conf_var(const float* reg, const float* depth_values, int D, int H, int W, float lamb, float* prob, float* depth,
                             float* conf, int* index, float* variance, void* hip_stream) {
   return launch_tail<true>("svs_prob_depth_conf_var", reg, depth_values, D, H, W, lamb, prob, depth, conf, index, variance, hip_stream);
+}
+
+// svs_prob_depth_conf's softmax with TransMVSNet's winner-take-all depth, confidence and index
+int svs_prob_wta(const float* reg, const float* depth_values, int D, int H, int W, float* prob, float* depth, float* conf, int* index,
+                 void* hip_stream) {
+  return launch_tail<false, true>("svs_prob_wta", reg, depth_values, D, H, W, 0.0f, prob, depth, conf, index, nullptr, hip_stream);
 }
 
 int svs_depth_hypotheses(const float* prev_depth, int Hp, int Wp, int H_img, int W_img, int D, int scale, float dmin,

@@ -585,6 +585,157 @@ def uncertainty_hypotheses(prev_depth, prev_var, hw, ndepth, dmin=None, dmax=Non
     return out
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# TransMVSNet (models/transmvs.py; csrc/svs_transmvs.hip, the tail in csrc/svs_costvol.hip)
+# ---------------------------------------------------------------------------------------------------------------------
+def deform_conv2d(x, offset_mask, weight, bias=None, scale=None, shift=None, relu=False):
+    """DCN.forward behind its conv_offset_mask (models/dcn.py:68-80: torchvision's deform_conv2d, 3x3, stride 1, padding 1, one
+    offset group, modulated): x (32,H,W), offset_mask (27,H,W) the raw conv_offset_mask output (channels 2k, 2k+1 = dy, dx of
+    tap k = 3 ky + kx; channel 18+k -> sigmoid = its mask), weight (Cout <= 32,32,3,3) -> (Cout,H,W) =
+    relu?(scale * (deform_conv + bias) + shift); scale / shift (both or neither): the folded BatchNorm behind the layer."""
+    L = _lib.load()
+    x, om = _f32(x), _f32(offset_mask)
+    Cin, H, W = x.shape
+    Cout = weight.shape[0]
+    if Cin != 32 or tuple(om.shape) != (27, H, W) or tuple(weight.shape[1:]) != (32, 3, 3):
+        raise ValueError("deform_conv2d: x (32,H,W), offset_mask (27,H,W), weight (Cout,32,3,3)")
+    if (scale is None) != (shift is None):
+        raise ValueError("deform_conv2d: scale and shift come together")
+    opt = lambda t: _f32(t) if t is not None else None
+    bias, scale, shift = opt(bias), opt(scale), opt(shift)
+    out = torch.empty(Cout, H, W, device=x.device)
+    _lib.check(L.svs_deform_conv2d(_ptr(x), _ptr(om), _ptr(conv2d_pack(weight)), _ptr(bias), _ptr(scale), _ptr(shift), _ptr(out),
+                                   Cout, H, W, int(bool(relu)), _stream()), "svs_deform_conv2d")
+    return out
+
+
+_PE_DIV = []
+
+
+def _pe_div_term():
+    """PositionEncodingSine(32, temp_bug_fix=True)'s eight frequencies, in float32 as models/position_encoding.py:43 forms them."""
+    if not _PE_DIV:
+        import math
+        div = torch.exp(torch.arange(0, 16, 2).float() * (-math.log(10000.0) / 16))
+        _PE_DIV.append((ctypes.c_float * 8)(*[float(v) for v in div]))
+    return _PE_DIV[0]
+
+
+def fmt_tokens_in(feature):
+    """(32,H,W) -> (H*W,32) tokens with PositionEncodingSine added (models/FMT.py:147, 163)."""
+    L = _lib.load()
+    f = _f32(feature)
+    C, H, W = f.shape
+    if C != 32:
+        raise ValueError("the transformer's d_model is 32")
+    tok = torch.empty(H * W, 32, device=f.device)
+    _lib.check(L.svs_fmt_tokens_in(_ptr(f), H, W, _pe_div_term(), _ptr(tok), _stream()), "svs_fmt_tokens_in")
+    return tok
+
+
+def fmt_tokens_out(tokens, hw):
+    """(H*W,32) tokens -> (32,H,W)"""
+    L = _lib.load()
+    t = _f32(tokens)
+    H, W = hw
+    if tuple(t.shape) != (H * W, 32):
+        raise ValueError("tokens must be (H*W,32)")
+    out = torch.empty(32, H, W, device=t.device)
+    _lib.check(L.svs_fmt_tokens_out(_ptr(t), H, W, _ptr(out), _stream()), "svs_fmt_tokens_out")
+    return out
+
+
+def fmt_kv(source, k_w, k_b, v_w, v_b):
+    """LinearAttention's sums over the S source tokens (models/FMT.py:24-32): source (S,32) -> 160 floats, KV[h][m][d] =
+    sum_s K[s,h,d] V[s,h,m] (128) then Ksum[h][d] (32), K = elu(W_k s + b_k) + 1, V = W_v s + b_v.  Summed in a fixed order:
+    two calls on the same input give the same bits."""
+    L = _lib.load()
+    src = _f32(source)
+    S = src.shape[0]
+    if src.dim() != 2 or src.shape[1] != 32:
+        raise ValueError("source must be (S,32)")
+    ws = torch.empty(L.svs_fmt_kv_workspace_bytes(S) // 4, device=src.device)
+    out = torch.empty(160, device=src.device)
+    _lib.check(L.svs_fmt_kv(_ptr(src), S, _ptr(_f32(k_w)), _ptr(_f32(k_b)), _ptr(_f32(v_w)), _ptr(_f32(v_b)), _ptr(ws), _ptr(out),
+                            _stream()), "svs_fmt_kv")
+    return out
+
+
+def fmt_layer(x, kvsum, weights):
+    """EncoderLayer.forward (models/FMT.py:96-111) for the query tokens x (L,32), given fmt_kv's sums of its source.  weights: the
+    12 tensors query_projection.{weight,bias}, out_projection.{weight,bias}, linear1.{weight,bias}, linear2.{weight,bias},
+    norm1.{weight,bias}, norm2.{weight,bias}."""
+    L = _lib.load()
+    x = _f32(x)
+    if x.dim() != 2 or x.shape[1] != 32 or len(weights) != 12 or kvsum.numel() != 160:
+        raise ValueError("fmt_layer: x (L,32), 160 sums, 12 weight tensors")
+    ws = [_f32(w) for w in weights]
+    out = torch.empty_like(x)
+    _lib.check(L.svs_fmt_layer(_ptr(x), x.shape[0], _ptr(_f32(kvsum)), _ptr_array(ws), _ptr(out), _stream()), "svs_fmt_layer")
+    return out
+
+
+def pathway_step(x, weight, y):
+    """_upsample_add(dim_reduction(x), y) (models/FMT.py:196-223): x (Cin,h,w), weight (Cin/2,Cin,1,1), y (Cin/2,2h,2w) ->
+    bilinear_x2(conv1x1(x)) + y, align_corners=False, the reduction first."""
+    L = _lib.load()
+    x, y = _f32(x), _f32(y)
+    Cin, h, w = x.shape
+    if tuple(weight.shape[:2]) != (Cin // 2, Cin) or tuple(y.shape) != (Cin // 2, 2 * h, 2 * w):
+        raise ValueError("pathway_step: shapes do not match")
+    out = torch.empty_like(y)
+    _lib.check(L.svs_pathway_step(_ptr(x), _ptr(_f32(weight.detach().reshape(Cin // 2, Cin))), _ptr(y), _ptr(out), Cin, h, w,
+                                  _stream()), "svs_pathway_step")
+    return out
+
+
+def warp_similarity(features, proj_matrices, depth_values, view_weights=None, net=None):
+    """DepthNet.forward steps 1-2 (models/TransMVSNet.py:52-91) with the homo_warping of models/module.py:285-324.  features: list
+    of (1,C,H,W) (reference first), proj_matrices (1,V,2,4,4), depth_values (1,D,H,W).  view_weights None (stage 1): net = the
+    177 folded floats of pixel_wise_net, the weights are max_d sigmoid(net(sim_v)); else (1,V-1,H/2,W/2), the previous stage's,
+    read at (y/2, x/2).  -> similarity (1,1,D,H,W), the weights at this stage's size (1,V-1,H,W)."""
+    L = _lib.load()
+    ref = _f32(features[0][0])
+    C, H, W = ref.shape
+    D = depth_values.shape[1]
+    dev = ref.device
+    n_src = len(features) - 1
+    hwc = [_hwc(f[0]) for f in features[1:]]
+    rt = _rot_trans(proj_matrices)
+    dv = _f32(depth_values[0])
+    if view_weights is not None:
+        pw = _f32(view_weights[0])
+        if tuple(pw.shape) != (n_src, H // 2, W // 2) or H % 2 or W % 2:
+            raise ValueError("view_weights must be (1,V-1,H/2,W/2)")
+    else:
+        pw = None
+        if net is None or net.numel() != 177:
+            raise ValueError("stage 1 needs pixel_wise_net's 177 folded floats")
+        net = _f32(net)
+    ws = torch.empty(L.svs_warp_similarity_workspace_bytes(n_src, D, H, W) // 4, device=dev)
+    sim = torch.empty(1, 1, D, H, W, device=dev)
+    w_out = torch.empty(1, n_src, H, W, device=dev)
+    _lib.check(L.svs_warp_similarity(_ptr(ref), _ptr_array(hwc), rt, n_src, C, D, H, W, _ptr(dv), _ptr(pw),
+                                     _ptr(net) if pw is None else None, _ptr(ws), _ptr(sim), _ptr(w_out), _stream()),
+               "svs_warp_similarity")
+    return sim, w_out
+
+
+def prob_wta(reg, depth_values):
+    """TransMVSNet's tail (models/TransMVSNet.py:100-109, 225-227): reg (D,H,W), depth_values (D,H,W) -> prob (D,H,W) as
+    prob_depth_conf gives it, index (H,W int32) = the first argmax, depth = depth_values[index], conf = prob[index]."""
+    L = _lib.load()
+    reg, dv = _f32(reg), _f32(depth_values)
+    D, H, W = reg.shape
+    dev = reg.device
+    prob = torch.empty(D, H, W, device=dev)
+    depth = torch.empty(H, W, device=dev)
+    conf = torch.empty(H, W, device=dev)
+    idx = torch.empty(H, W, dtype=torch.int32, device=dev)
+    _lib.check(L.svs_prob_wta(_ptr(reg), _ptr(dv), D, H, W, _ptr(prob), _ptr(depth), _ptr(conf), _ptr(idx), _stream()), "svs_prob_wta")
+    return prob, depth, conf, idx
+
+
 _GEMM_ON = [True]
 
 

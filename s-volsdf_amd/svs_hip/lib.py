@@ -225,6 +225,20 @@ SIGNATURES.update({
     "svs_uncertainty_hypotheses": (c_int, [_P, c_int, c_int, _P, c_int, c_int, c_int, c_int, c_int, _P, _P]),
 })
 
+# models.transmvs (csrc/svs_transmvs.hip, the tail in csrc/svs_costvol.hip)
+SIGNATURES.update({
+    "svs_deform_conv2d": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
+    "svs_fmt_tokens_in": (c_int, [_P, c_int, c_int, POINTER(c_float), _P, _P]),
+    "svs_fmt_tokens_out": (c_int, [_P, c_int, c_int, _P, _P]),
+    "svs_fmt_kv_workspace_bytes": (c_size_t, [c_int]),
+    "svs_fmt_kv": (c_int, [_P, c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "svs_fmt_layer": (c_int, [_P, c_int, _P, _PP, _P, _P]),
+    "svs_pathway_step": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P]),
+    "svs_warp_similarity_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "svs_warp_similarity": (c_int, [_P, _PP, POINTER(c_float), c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "svs_prob_wta": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
+})
+
 ABI_VERSION = 101          # svs_version() of the library this binding was written against (include/svolsdf_hip.h)
 
 

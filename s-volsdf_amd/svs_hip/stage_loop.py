@@ -17,10 +17,13 @@ class StageLoop:
         self.cache_features = cache_features
         self._features = {}
         self.feature_calls = 0
+        self._matched = {}
+        self.fmt_calls = 0
 
     def clear(self):
         """forget the cached features (new scan) and what the cost-volume / prior look-up wrappers cached for the old one"""
         self._features.clear()
+        self._matched.clear()
         from . import costvol
         costvol.clear_caches()
 
@@ -51,18 +54,36 @@ class StageLoop:
         return out
 
     @torch.no_grad()
+    def matched_features(self, imgs):
+        """features(imgs), passed through the model's Feature Matching Transformer where it has one (TransMVSNet,
+        runner.py:196-197).  Its output depends on which view is the reference, so it belongs to the sample, not to an image:
+        it is kept per ordered tuple of image fingerprints, which makes the three stages of a sample share one run
+        (`fmt_calls` counts the real ones).  The per-image features stay as extracted: the model returns new dicts."""
+        feats = self.features(imgs)
+        if not hasattr(self.model, "FMT_with_pathway"):
+            return feats
+        key = tuple(self._fingerprint(imgs[:, v]) for v in range(imgs.size(1))) if self.cache_features else None
+        if key is not None and key in self._matched:
+            return self._matched[key]
+        out = self.model.FMT_with_pathway(feats)
+        self.fmt_calls += 1
+        if key is not None:
+            self._matched[key] = out
+        return out
+
+    @torch.no_grad()
     def cost_volumes(self, stage_idx, samples, outs_samples, view_extra_samples=None, int_r=None, inverse_depth=False,
                      prevent_oom=False):
         """runner.py:182-207 for one stage: samples = the (device) samples of the scan's reference views;
         outs_samples[i] = the previous stage's outputs of view i (None at stage 0), view_extra_samples[i] = what the model
-        returned beside them (UCSNet: the previous stage's uncertainty; CasMVSNet: None).  Returns (outs, view_extras)."""
+        returned beside them (UCSNet: the previous stage's uncertainty; TransMVSNet: its view weights; CasMVSNet: None).  Returns (outs, view_extras)."""
         if int_r is None and hasattr(self.model, "depth_interals_ratio"):      # (UCSNet has none: int_r stays None, runner.py:179)
             int_r = self.model.depth_interals_ratio[stage_idx]
         n = len(samples)
         view_extra_samples = view_extra_samples or [None] * n
         outs, view_extras = [None] * n, [None] * n
         for i, sample in enumerate(samples):
-            feats = self.features(sample["imgs"])
+            feats = self.matched_features(sample["imgs"])
             outs[i], view_extras[i] = self.model(stage_idx, sample, features=feats, extra=view_extra_samples[i],
                                                  outputs=outs_samples[i], int_r=int_r, prevent_oom=prevent_oom,
                                                  inverse_depth=inverse_depth)
