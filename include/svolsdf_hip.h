@@ -816,6 +816,26 @@ size_t svs_cloud_bounds_workspace_bytes(void);
 int svs_cloud_bounds(const double* pts, int n, double* workspace, double* lo_hi, void* hip_stream);
 int svs_cloud_mean_below(const double* dist, int n, double max_dist, double* workspace, double* mean_count, void* hip_stream);
 
+/* ---- f4b  BlendedMVS Chamfer evaluator and the error clouds of both evaluators (csrc/svs_chamfer.hip) -------------------
+ * svs_cloud_prepare: the PLY's coordinates -> the cloud the kd-tree sees (evals/eval_bmvs.py:127,129-134,196-197).
+ *   pts: DEVICE (n,3) float32 (is_f64 == 0) or float64; out: DEVICE (n,3) float64; matrix: HOST double[16] row-major, or NULL.
+ *   matrix == NULL (every scan but 5; :127,:196-197): out = (double)((float)x / (float)scale), one IEEE float32 division --
+ *   `astype('float32')` followed by the in-place `/= relative_scale[scan]` of a float32 array.
+ *   matrix != NULL (scan 5; :129-134,:197): p = (double)(float)x, t_a = ((m_a0 p_0 + m_a1 p_1) + m_a2 p_2) + m_a3,
+ *   out = t / scale, all float64, left to right, no contraction.  The reference forms t with a BLAS dot whose summation
+ *   order is the host library's, so this mode agrees with it up to the last bits only.
+ *   n == 0 is not an error; scale must be > 0.  Denormal float32 inputs are outside the contract.
+ * svs_cloud_error_colors: the colour step (evals/eval_bmvs.py:232-246, evals/eval_dtu.py:173-187) over a cloud of n_full
+ *   rows of which n_dist were evaluated.  select == NULL: row i has dist[i] (n_full == n_dist).  Otherwise select[i] == 0
+ *   is blue (0,0,1) and else the row has dist[rank[i]], rank[i] = number of selected rows before i (the offsets
+ *   svs_cloud_compact computes; a rank outside [0, n_dist) is never read: blue).  d >= max_dist (inf included): green
+ *   (0,1,0); else a = min(d, vis_dist) / vis_dist and the colour is (a + (1 - a), 1 - a, 1 - a) in float64 -- numpy's
+ *   R * a + W * (1 - a).  rgb_f64: (n_full,3) float64; rgb_u8: (n_full,3) = (uint8) rint(min(1, max(0, c)) * 255), what the
+ *   PLY stores; either may be NULL. */
+int svs_cloud_prepare(const void* pts, int is_f64, int n, const double* matrix, double scale, double* out, void* hip_stream);
+int svs_cloud_error_colors(const double* dist, int n_dist, const uint8_t* select, const int* rank, int n_full, double max_dist,
+                           double vis_dist, double* rgb_f64, uint8_t* rgb_u8, void* hip_stream);
+
 /* Evaluator --mode mesh (evals/eval_dtu.py:14-23 sample_single_tri, :62-90): the points the script samples on every
  * triangle of the predicted mesh before it proceeds as in point-cloud mode.  tri: DEVICE double[n_tri][11] =
  * [n1, n2, v1(3), v2(3), p0(3)] per triangle of non-zero area (:70-83; integer-valued n1 = floor(l1 / thr), n2).

@@ -41,6 +41,7 @@ UNITS = {
     "svs_optim.hip": ["-ffp-contract=off"],
     "svs_fusion.hip": ["-ffp-contract=off"],
     "svs_cloud.hip": ["-ffp-contract=off"],
+    "svs_chamfer.hip": ["-ffp-contract=off"],
     "svs_ibr.hip": ["-ffp-contract=off"],
     "svs_nvs.hip": ["-ffp-contract=off"],
     "svs_lpips.hip": ["-ffp-contract=off"],

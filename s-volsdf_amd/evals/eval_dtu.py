@@ -151,11 +151,13 @@ def mean_below(dist, max_dist):
 
 
 def evaluate_scan(data_pcd, stl, ObsMask, BB, Res, ground_plane, downsample_density=0.2, patch_size=60, max_dist=20,
-                  shuffle_rng=None, details=False):
+                  shuffle_rng=None, details=False, visualize=None):
     """evals/eval_dtu.py:99-192 for one scan -> (mean_d2s accuracy, mean_s2d completeness, overall) in mm.
     data_pcd (n,3): predicted cloud; stl (m,3): ground-truth scan; ObsMask (d0,d1,d2), BB (2,3), Res: ObsMask*.mat;
     ground_plane (4,): Plane*.mat 'P'.  shuffle_rng: numpy Generator for the reference's random index shuffle (:100-101;
-    None = a fresh default_rng() like the reference, False = keep the given order)."""
+    None = a fresh default_rng() like the reference, False = keep the given order).
+    visualize=vis_dist: the result is followed by the details dict, which then also holds the error clouds of :173-187, the
+    colours of data_down (`data_color`, `data_color_u8`) and of stl (`stl_color`, `stl_color_u8`)."""
     L = _lib.load()
     data_pcd = np.array(data_pcd, np.float64)
     if shuffle_rng is not False:
@@ -187,10 +189,15 @@ def evaluate_scan(data_pcd, stl, ObsMask, BB, Res, ground_plane, downsample_dens
     dist_s2d = nearest_neighbor(data_in, stl_above, max_dist)
     mean_s2d = mean_below(dist_s2d, max_dist)
     over_all = (mean_d2s + mean_s2d) / 2
-    if details:
-        return (mean_d2s, mean_s2d, over_all), dict(data_pcd=data_pcd, keep=keep, data_down=data_down, data_in=data_in,
-                                                     data_in_obs=data_in_obs, dist_d2s=dist_d2s, stl_above=stl_above,
-                                                     dist_s2d=dist_s2d)
+    if details or visualize is not None:
+        d = dict(data_pcd=data_pcd, keep=keep, data_down=data_down, data_in=data_in, data_in_obs=data_in_obs, dist_d2s=dist_d2s,
+                 stl_above=stl_above, dist_s2d=dist_s2d, in_obs=in_obs, above=above)
+        if visualize is not None:
+            from .eval_bmvs import error_colors
+            d["stl"] = stl_d
+            d["data_color"], d["data_color_u8"] = error_colors(dist_d2s, max_dist, visualize, select=in_obs)
+            d["stl_color"], d["stl_color_u8"] = error_colors(dist_s2d, max_dist, visualize, select=above)
+        return (mean_d2s, mean_s2d, over_all), d
     return mean_d2s, mean_s2d, over_all
 
 
@@ -221,6 +228,8 @@ def main(argv=None):
     parser.add_argument('--downsample_density', type=float, default=0.2)
     parser.add_argument('--patch_size', type=float, default=60)
     parser.add_argument('--max_dist', type=float, default=20)
+    parser.add_argument('--visualize_threshold', type=float, default=10)
+    parser.add_argument('-ve', '--visualize_error', action='store_true')
     args = parser.parse_args(argv)
     dataset_dir = os.path.join(args.data_dir_root, 'DTU', 'DTU_MVS_Data')
     scans = [21, 34, 38, 82, 24, 37, 40, 106, 110, 114, 118]
@@ -231,7 +240,15 @@ def main(argv=None):
     for scan in scans:
         try:
             r = evaluate_scan_files(scan, args.datadir, dataset_dir, mode=args.mode, downsample_density=args.downsample_density,
-                                    patch_size=args.patch_size, max_dist=args.max_dist)
+                                    patch_size=args.patch_size, max_dist=args.max_dist,
+                                    visualize=args.visualize_threshold if args.visualize_error else None)
+            if args.visualize_error:                          # the error clouds of :169-187
+                from .eval_bmvs import write_vis_pcd
+                r, d = r
+                vis_out_dir = os.path.join(args.datadir, 'result')
+                os.makedirs(vis_out_dir, exist_ok=True)
+                write_vis_pcd(f'{vis_out_dir}/vis_{scan:03}_d2s.ply', d["data_down"], d["data_color_u8"])
+                write_vis_pcd(f'{vis_out_dir}/vis_{scan:03}_s2d.ply', d["stl"], d["stl_color_u8"])
         except (OSError, ValueError):
             r = (10000., 10000., 10000.)                      # the reference's fallback row (:163-167)
         print('scan{:0>3} {:.2f} {:.2f} {:.2f}'.format(scan, trun_n_d(r[0], 2), trun_n_d(r[1], 2), trun_n_d(r[2], 2)))

@@ -239,6 +239,12 @@ SIGNATURES.update({
     "svs_prob_wta": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
 })
 
+# evals.eval_bmvs and the error clouds of both Chamfer evaluators (csrc/svs_chamfer.hip)
+SIGNATURES.update({
+    "svs_cloud_prepare": (c_int, [_P, c_int, c_int, POINTER(c_double), c_double, _P, _P]),
+    "svs_cloud_error_colors": (c_int, [_P, c_int, _P, _P, c_int, c_double, c_double, _P, _P, _P]),
+})
+
 ABI_VERSION = 101          # svs_version() of the library this binding was written against (include/svolsdf_hip.h)
 
 
