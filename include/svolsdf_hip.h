@@ -754,6 +754,33 @@ int svs_mvs_confidence(const float* conf1, int H1, int W1, const int* xofs1, con
                        const float* xcoef3, const int* yofs3, const float* ycoef3, int H, int W, float* out,
                        void* hip_stream);
 
+/* ---- f9  the save tail of a scan run (runner.py:283-290; csrc/svs_preview.hip) ---------------------------------------
+ * Added without a version change: nothing that existed changed, and svs_version() stays 101.  Every argument is checked
+ * before the first launch; a rejected call (SVS_EINVAL: null pointer, misaligned workspace, a count or a rank out of
+ * range; SVS_ESHAPE: a size) writes nothing.
+ * svs_select_sorted_pairs: exact order statistics of x (n float32 on the device, 1 <= n < 2^31).  ranks: HOST array of
+ *   n_ranks (1..4) zero-based ranks k_j in 0..n-1 -> values (2 n_ranks float32, device): values[2j] is the k_j-th
+ *   smallest element and values[2j+1] the min(k_j + 1, n - 1)-th, the pair numpy's `linear` quantile interpolates
+ *   between; counts (3 x uint32, device): how many elements are NaN, +inf, -inf.  The order is total: -inf < negatives <
+ *   -0.0 < +0.0 < positives < +inf < NaN (a NaN comes back as the quiet NaN 0x7fffffff); apart from the order of the two
+ *   zeros, which np.sort leaves open, values are bit for bit what np.sort(x) holds at those ranks.  Radix selection over
+ *   the order-preserving integer key, four passes of 8 bits shared by all ranks, histograms in LDS, integer atomics only,
+ *   every decision on the device: the same result from run to run, no host round trip.  8 launches and one memset;
+ *   x is read four times.  workspace: svs_select_workspace_bytes() bytes, 8-byte aligned.
+ * svs_depth_preview: helpers/utils.py::visualize_depth (:197-224) for n_maps (1..3) float32 maps of n_k pixels (1..2^26)
+ *   that share the bounds lo, hi: invalid = NaN or infinite; d clamped to [lo, hi], invalid -> hi; s = (d - lo) / (hi - lo)
+ *   and s * 255 each rounded to float32 on its own (IEEE division), c = the truncation.  direct != 0: out_k (n_k) uint8
+ *   = c; direct == 0: out_k (n_k,3) uint8 = row 255 - c of table (256,3) uint8 on the device (cv2.applyColorMap's
+ *   look-up: the table decides the channel order).  Invalid pixels are 0.  hi <= lo or a NaN bound: the reference
+ *   divides by zero and casts NaN to uint8, which is platform-defined; here every code is 0.  One launch.  Unused maps
+ *   may be null. */
+size_t svs_select_workspace_bytes(void);
+int svs_select_sorted_pairs(const float* x, long long n, const long long* ranks, int n_ranks, void* workspace, float* values,
+                            unsigned int* counts, void* hip_stream);
+int svs_depth_preview(const float* map0, int n0, uint8_t* out0, const float* map1, int n1, uint8_t* out1, const float* map2,
+                      int n2, uint8_t* out2, int n_maps, float lo, float hi, int direct, const uint8_t* table,
+                      void* hip_stream);
+
 /* ---- f7  the finish of an evaluation view (eval_vsdf.py:230-262, volsdf/utils/plots.py:392-468) ----------------------
  * What the reference does in numpy on the host after merge_output, on the render's device tensors.  Every argument is
  * checked before the launch: a rejected call (SVS_EINVAL: null pointer; SVS_ESHAPE: a size) writes nothing.

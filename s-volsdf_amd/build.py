@@ -48,6 +48,7 @@ UNITS = {
     "svs_scene.hip": ["-ffp-contract=off"],
     "svs_evalviews.hip": ["-ffp-contract=off"],
     "svs_mvsout.hip": ["-ffp-contract=off"],
+    "svs_preview.hip": ["-ffp-contract=off"],
     "svs_mvsdata.hip": ["-ffp-contract=off"],
     "svs_mesh.hip": ["-ffp-contract=off"],
     "svs_plan.hip": [],

@@ -245,6 +245,13 @@ SIGNATURES.update({
     "svs_cloud_error_colors": (c_int, [_P, c_int, _P, _P, c_int, c_double, c_double, _P, _P, _P]),
 })
 
+# svs_hip.run's save tail: order statistics and colour previews (csrc/svs_preview.hip)
+SIGNATURES.update({
+    "svs_select_workspace_bytes": (c_size_t, []),
+    "svs_select_sorted_pairs": (c_int, [_P, c_longlong, POINTER(c_longlong), c_int, _P, _P, _P, _P]),
+    "svs_depth_preview": (c_int, [_P, c_int, _P, _P, c_int, _P, _P, c_int, _P, c_int, c_float, c_float, c_int, _P, _P]),
+})
+
 ABI_VERSION = 101          # svs_version() of the library this binding was written against (include/svolsdf_hip.h)
 
 

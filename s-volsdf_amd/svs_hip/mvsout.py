@@ -4,7 +4,10 @@ reference's runner does on the host with OpenCV and scikit-image between `Cascad
     final_confidence(outputs)           conf_1 * conf_2 * photometric_confidence, each resized to the depth map's size
                                         with cv2.resize (INTER_LINEAR) -- the map filter_depth thresholds (runner.py:267-271)
     save_view(out_folder, view, ...)    the files later steps read: depth_est/ and confidence/ PFMs, cams/, images/
-                                        (runner.py:261-295 without the colour previews)
+                                        (runner.py:261-295); previews=True: the four colour previews as well
+    select_sorted_pairs(map, ranks)     exact order statistics of a float32 map (csrc/svs_preview.hip)
+    quantile(map, q), percentile(map, p)   np.quantile / np.percentile (method linear) of a float32 map, from them
+    depth_preview(maps, lo, hi, ...)    helpers.utils.visualize_depth per pixel, for the maps of a view that share bounds
     eval_mask(image, H, W, radius=12)   read_img's mask -> last channel -> binary_dilation(disk(12)) -> cv2.resize(.. * 1.,
                                         (W,H)) > 0. (runner.py:362-368), = resize_any(dilate_disk(image != 0), H, W)
     eval_mask_path(root, dataset, scan_name, view)      the file rule of runner.py:351-360
@@ -19,6 +22,7 @@ byte-identical with, what cv2.imwrite stores.
     python -m svs_hip.mvsout --scan-folder S --out-folder O --ply P --views 25 22 28 [--data-dir-root D --dataset DTU]
 """
 import argparse
+import ctypes
 import os
 
 import numpy as np
@@ -30,8 +34,11 @@ from .ops import _ptr, _stream
 from .scans import view_mask_file as eval_mask_path        # the file rule of runner.py:351-360, decided per file
 
 MAX_RADIUS = 32
-LAUNCHES = {"dilate": 0, "resize": 0, "confidence": 0}      # entry-point calls made by this process (tests, bench_mvsout.py)
-KERNELS_PER_CALL = {"dilate": 3, "resize": 1, "confidence": 1}
+# entry-point calls made by this process (tests, bench_mvsout.py, bench_run.py)
+LAUNCHES = {"dilate": 0, "resize": 0, "confidence": 0, "select": 0, "preview": 0}
+KERNELS_PER_CALL = {"dilate": 3, "resize": 1, "confidence": 1, "select": 8, "preview": 1}
+SELECT_MAX_RANKS = 4
+BYTES_DOWN = {"select": 0, "maps": 0, "previews": 0}       # what save_view and the order statistics brought to the host
 
 
 def _mask_dev(mask, what):
@@ -128,12 +135,162 @@ def _host(a):
     return a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
 
 
-def save_view(out_folder, view, outputs, cam, img, cam_near_far=None):
+# ---- order statistics and colour previews (csrc/svs_preview.hip) ---------------------------------------------------------
+def select_sorted_pairs(values, ranks):
+    """Exact order statistics of a float32 map on the device.  values: array or tensor of any shape (n elements); ranks: up
+    to 4 zero-based ranks k in 0..n-1.  -> pairs float32 (len(ranks),2): the k-th and the min(k+1, n-1)-th smallest
+    element, bit for bit what np.sort places there (but -0.0 orders before +0.0, which np.sort leaves open; NaNs last);
+    counts: dict(nan, posinf, neginf).  One call, whatever the number of ranks; its 8 + 3 words are the only download."""
+    L = _lib.load()
+    t = values if torch.is_tensor(values) else np.asarray(values)
+    d = to_device(t.reshape(-1), torch.float32, "mvsout", "values", cast=False)
+    n = d.numel()
+    ranks = [int(k) for k in ranks]
+    if not 1 <= len(ranks) <= SELECT_MAX_RANKS:
+        raise ValueError(f"ranks: 1..{SELECT_MAX_RANKS} ranks per call, got {len(ranks)}")
+    if n < 1 or any(not 0 <= k < n for k in ranks):
+        raise ValueError(f"ranks {ranks} outside 0..{n - 1}")
+    ws = torch.empty((int(L.svs_select_workspace_bytes()) + 7) // 8, dtype=torch.int64, device=d.device)
+    out = torch.empty(2 * SELECT_MAX_RANKS + 4, dtype=torch.int32, device=d.device)
+    arr = (ctypes.c_longlong * len(ranks))(*ranks)
+    _lib.check(L.svs_select_sorted_pairs(_ptr(d), n, arr, len(ranks), _ptr(ws), _ptr(out), _ptr(out[2 * SELECT_MAX_RANKS:]),
+                                         _stream()), "svs_select_sorted_pairs")
+    LAUNCHES["select"] += 1
+    host = out.cpu().numpy()
+    BYTES_DOWN["select"] += host.nbytes
+    pairs = host[:2 * len(ranks)].view(np.float32).reshape(len(ranks), 2).copy()
+    c = host[2 * SELECT_MAX_RANKS:].view(np.uint32)
+    return pairs, dict(nan=int(c[0]), posinf=int(c[1]), neginf=int(c[2]))
+
+
+def quantile_ranks(n, q):
+    """numpy's `linear` rule for n float32 values (numpy 2: lib/_function_base_impl.py::_quantile, _get_indexes,
+    _get_gamma), evaluated with numpy's own scalar arithmetic: a Python-number q is taken in the array's dtype, so the
+    virtual index (n - 1) * q, its floor and the weight gamma are float32.  q: float32 scalars in [0,1].
+    -> ranks (ints; n - 1 where the index reaches the end), gamma (float32 array)"""
+    q = np.asarray(q, dtype=np.float32).reshape(-1)
+    if not np.all((q >= 0) & (q <= 1)):
+        raise ValueError("Quantiles must be in the range [0, 1]")
+    virtual = np.asanyarray((n - 1) * q)
+    previous = np.floor(virtual)
+    above = virtual >= n - 1
+    previous[above] = -1
+    gamma = np.asanyarray(virtual - previous, dtype=virtual.dtype)
+    ranks = previous.astype(np.intp)
+    ranks[above] = n - 1
+    return [int(k) for k in ranks], gamma
+
+
+def lerp(a, b, t):
+    """numpy's _lerp in the operands' float32: a + (b - a) t for t < 0.5, b - (b - a)(1 - t) otherwise"""
+    a, b, t = (np.asarray(v, dtype=np.float32) for v in (a, b, t))
+    with np.errstate(invalid="ignore"):
+        diff = np.subtract(b, a)
+        out = np.asanyarray(np.add(a, diff * t))
+        np.subtract(b, diff * (1 - t), out=out, where=t >= 0.5)
+    return out
+
+
+def _quantiles(values, q, valid_only=False, select=None):
+    """np.quantile(values, q) for float32 scalars q (a list of up to 4) -> float32 array.  valid_only: of the finite
+    elements only, np.quantile(values[isfinite(values)], q): the ranks are asked for as if every element were finite and
+    asked for again when the counts say otherwise (finite elements sit between the -inf and the +inf / NaN in the order)."""
+    select = select or select_sorted_pairs
+    n = int(values.numel() if torch.is_tensor(values) else np.asarray(values).size)
+    ranks, gamma = quantile_ranks(n, q)
+    pairs, counts = select(values, ranks)
+    bad = counts["nan"] + counts["posinf"] + counts["neginf"]
+    if valid_only and bad:
+        m = n - bad
+        if m < 1:
+            raise ValueError("no finite value to take a percentile of")
+        ranks, gamma = quantile_ranks(m, q)
+        pairs, _ = select(values, [min(k + counts["neginf"], n - 1) for k in ranks])
+        last = [k == m - 1 for k in ranks]
+        pairs[last, 1] = pairs[last, 0]                  # (the element after the last finite one is not finite)
+    elif counts["nan"]:
+        return np.full(len(ranks), np.nan, np.float32)   # numpy: a slice with a NaN gives NaN
+    return lerp(pairs[:, 0], pairs[:, 1], gamma)
+
+
+def quantile(values, q, select=None):
+    """np.quantile(values, q) (method linear) of a float32 map on the device, bit for bit (the sign of a zero result
+    aside: see select_sorted_pairs).  q: a number, or up to 4 of them -> np.float32, or a float32 array.  A map with a
+    NaN gives NaN, as numpy does."""
+    out = _quantiles(values, np.asarray(q, dtype=np.float32), select=select)
+    return out[0] if np.ndim(q) == 0 else out
+
+
+def percentile(values, p, valid_only=False, select=None):
+    """np.percentile(values, p): `quantile` at p / float32(100), numpy's division."""
+    q = np.true_divide(p, np.float32(100))
+    out = _quantiles(values, np.asarray(q, dtype=np.float32), valid_only=valid_only, select=select)
+    return out[0] if np.ndim(p) == 0 else out
+
+
+_JET = {}
+
+
+def jet_table():
+    """matplotlib's `jet` sampled at 256 entries as uint8 (256,3) RGB codes -- the stand-in for cv2.COLORMAP_JET, UNPINNED
+    against it (INTEGRATION.md gives the cv2.applyColorMap call to check it with) -- or None, with one warning, when
+    matplotlib does not import."""
+    if "table" not in _JET:
+        try:
+            import matplotlib
+            _JET["table"] = np.ascontiguousarray(matplotlib.colormaps["jet"](np.arange(256), bytes=True)[:, :3], dtype=np.uint8)
+        except Exception as e:                          # noqa: BLE001  (no matplotlib, or one without the table)
+            import warnings
+            _JET["table"] = None
+            warnings.warn(f"matplotlib's jet colour table is not available ({e}): the colour previews are not written")
+    return _JET["table"]
+
+
+def depth_preview(maps, lo, hi, direct=False, table=None):
+    """helpers.utils.visualize_depth(map, depth_min=lo, depth_max=hi, direct=direct) (helpers/utils.py:197-224) of up to 3
+    float32 maps that share the bounds, in one launch.  maps: (H,W) arrays or device tensors, each of its own size.
+    direct=False: -> uint8 device tensors (H,W,3), row 255 - code of `table` (256,3) uint8 (default: `jet_table()`, RGB; the
+    channel order of the result is the table's); direct=True: -> (H,W) grey codes.  Invalid pixels (NaN, infinite) are 0.
+    hi <= lo, or a bound that is NaN: the reference divides by zero and casts NaN to uint8, which is platform-defined;
+    here the image is all zeros."""
+    L = _lib.load()
+    maps = [_map_dev(m, f"maps[{k}]") for k, m in enumerate(maps)]
+    if not 1 <= len(maps) <= 3:
+        raise ValueError(f"maps: 1..3 maps per call, got {len(maps)}")
+    dev = maps[0].device
+    tab = None
+    if not direct:
+        if table is None:
+            table = jet_table()
+            if table is None:
+                raise _lib.SvsError("no colour table: matplotlib is missing and none was passed")
+        tab = to_device(table, torch.uint8, "mvsout", "table", ndim=(2,), expect="(256,3) uint8", cast=False)
+        if tuple(tab.shape) != (256, 3):
+            raise ValueError(f"table: expected (256,3), got {tuple(tab.shape)}")
+    outs = [torch.empty(m.shape + (() if direct else (3,)), dtype=torch.uint8, device=dev) for m in maps]
+    args = []
+    for k in range(3):
+        args += [_ptr(maps[k]), maps[k].numel(), _ptr(outs[k])] if k < len(maps) else [None, 0, None]
+    if any(m.numel() < 1 for m in maps):
+        raise ValueError("maps: an empty map")
+    _lib.check(L.svs_depth_preview(*args, len(maps), float(lo), float(hi), int(bool(direct)), _ptr(tab), _stream()),
+               "svs_depth_preview")
+    LAUNCHES["preview"] += 1
+    return outs
+
+
+def save_view(out_folder, view, outputs, cam, img, cam_near_far=None, previews=False, dep_max=None, table=None):
     """The files of one view that later steps read (runner.py:261-295): depth_est/{view:08}.pfm (outputs['depth'], batch
     entry 0), confidence/{view:08}.pfm (`final_confidence`), cams/{view:08}_cam.txt (cam: (2,4,4) extrinsic, intrinsic),
-    images/{view:08}.jpg (img: (3,H,W) float in [0,1]; clip(img * 255, 0, 255) as uint8, JPEG quality 95).  The colour
-    previews of the reference (depth_est*.png, confidence_final.png) are not written: nothing reads them.
-    -> dict of the four file names."""
+    images/{view:08}.jpg (img: (3,H,W) float in [0,1]; clip(img * 255, 0, 255) as uint8, JPEG quality 95).
+    previews=True: the four colour previews of runner.py:283-290 as well -- depth_est/{view:08}.png, _1.png, _2.png
+    (outputs['depth'], ['stage1']['depth'], ['stage2']['depth'] between quantile(depth, 0.01) and dep_max, the sample's
+    depth_values.max(), through `table`, default jet) and confidence/{view:08}_final.png (the grey codes of the
+    confidence between the 5th and 95th percentile of its finite pixels).  PNGs are RGB through PIL; cv2.imwrite of the
+    BGR map shows the same colours.  Without a table (no matplotlib) the three colour previews are skipped.  Depth,
+    confidence and previews are formed on the device and only what a file holds is downloaded: two float32 maps and four
+    uint8 images; `prob_volume` never is.
+    -> dict of the file names."""
     from datasets.data_io import save_pfm
     from helpers.utils import write_cam
     from PIL import Image
@@ -141,9 +298,36 @@ def save_view(out_folder, view, outputs, cam, img, cam_near_far=None):
              for k, ext in (("depth_est", ".pfm"), ("confidence", ".pfm"), ("cams", "_cam.txt"), ("images", ".jpg"))}
     for f in names.values():
         os.makedirs(os.path.dirname(f), exist_ok=True)
-    depth = _host(outputs["depth"]).astype(np.float32, copy=False)
-    save_pfm(names["depth_est"], depth[0] if depth.ndim == 3 else depth)
-    save_pfm(names["confidence"], final_confidence(outputs).cpu().numpy())
+    if not previews:
+        depth = _host(outputs["depth"]).astype(np.float32, copy=False)
+        save_pfm(names["depth_est"], depth[0] if depth.ndim == 3 else depth)
+        save_pfm(names["confidence"], final_confidence(outputs).cpu().numpy())
+    else:
+        if dep_max is None:
+            raise ValueError("previews=True needs dep_max, the sample's depth_values.max()")
+        depth = _map_dev(outputs["depth"], "depth")
+        conf = final_confidence(outputs)
+        shots = {}
+        if table is None:
+            table = jet_table()
+        if table is not None:
+            lo = quantile(depth, 0.01)
+            col = depth_preview([depth, outputs["stage1"]["depth"], outputs["stage2"]["depth"]], lo, np.float32(dep_max),
+                                table=table)
+            shots.update(zip(("depth_png", "depth_1_png", "depth_2_png"), col))
+        c_lo, c_hi = percentile(conf, [5, 95], valid_only=True)
+        shots["confidence_png"] = depth_preview([conf], c_lo, c_hi, direct=True)[0]
+        for k, f in (("depth_est", depth), ("confidence", conf)):
+            a = f.cpu().numpy()
+            BYTES_DOWN["maps"] += a.nbytes
+            save_pfm(names[k], a)
+        for k, (sub, ext) in dict(depth_png=("depth_est", ".png"), depth_1_png=("depth_est", "_1.png"),
+                                  depth_2_png=("depth_est", "_2.png"), confidence_png=("confidence", "_final.png")).items():
+            if k in shots:
+                names[k] = os.path.join(out_folder, sub, "{:0>8}{}".format(view, ext))
+                a = shots[k].cpu().numpy()
+                BYTES_DOWN["previews"] += a.nbytes
+                Image.fromarray(a).save(names[k], compress_level=1)       # (cv2.imwrite's default PNG level)
     write_cam(names["cams"], _host(cam), cam_near_far)
     rgb = np.clip(np.transpose(_host(img), (1, 2, 0)) * 255, 0, 255).astype(np.uint8)
     Image.fromarray(rgb).save(names["images"], quality=95)
