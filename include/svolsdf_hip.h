@@ -421,6 +421,7 @@ int svs_conv3d_mfma(const float* in, const void* wfrag, const float* bias, const
  * Wp = 32 ceil(W/32) + 4.  svs_split_volume_dims returns its size in bytes (dims[0..1] = Hp, Wp); the caller zero-fills
  * the buffer once, the producers write the interior only.
  *   svs_warp_variance_split  = svs_warp_variance writing that form (DepthNet.forward steps 1-2, CasMVSNet.py:611-642);
+ *     SVS_ESHAPE where svs_split_volume_dims is 4 GiB or more or a feature map 2 GiB or more (32-bit byte offsets);
  *   svs_split_volume_pack    = the same form from a float32 (C,D,H,W) volume (tests, other callers);
  *   svs_conv3d_pair          = relu?(conv3d(volume, 3x3x3, stride 1, padding 1) + bias), Cin in {8,16,32}, Cout <= 8:
  *     the 16 rows of v_mfma_f32_16x16x32_f16 are 8 output channels x 2 neighbouring x positions, a column is that pair

@@ -13,6 +13,7 @@
 // That direct kernel now serves the 1x1 lateral convolutions only (memory-bound); 3x3 / 5x5 run on the LDS-tiled kernel
 // below.  svs_featurenet_fpn enqueues the whole pyramid (13 launches) from one call.
 #include "svs_common.h"
+#include "svs_conv2d_api.h"
 #include <cstdlib>
 
 namespace svs {
@@ -263,24 +264,6 @@ int launch_px(const Args& a, hipStream_t s) {
   return launch<K, S, 1>(a, s);
 }
 
-}  // namespace conv2d
-}  // namespace svs
-
-using namespace svs;
-using namespace svs::conv2d;
-
-namespace svs {
-namespace conv2dmfma {      // csrc/svs_conv2d_mfma.hip
-bool supported(int Cin, int Cout, int k, int stride);
-int run(const float* in, const void* wfrag, const float* bias, float* out, int Cin, int Cout, int H, int W, int k, int stride,
-        int relu, hipStream_t s);
-int run_lateral(const float* lat_in, const float* lat_w, const float* lat_b, const float* lat_add, const void* wfrag,
-                const float* bias, float* out, int Cout, int H, int W, int relu, hipStream_t s);
-}  // namespace conv2dmfma
-}  // namespace svs
-
-namespace {
-
 int run_conv(const float* in, const float* weight, const float* bias, const float* add, int add_upsample2, float* out,
              int Cin, int Cout, int H, int W, int k, int stride, int relu, hipStream_t s) {
   Args a;
@@ -293,6 +276,36 @@ int run_conv(const float* in, const float* weight, const float* bias, const floa
   if (stride == 1) return k == 3 ? launch_tiled<3, 1>(a, s) : launch_tiled<5, 1>(a, s);
   return k == 3 ? launch_tiled<3, 2>(a, s) : launch_tiled<5, 2>(a, s);
 }
+
+int run_encoder(const float* image, int H, int W, int b, const float* const* weights, const float* const* biases,
+                const void* const* wfrags, const EncoderBuffers& o, hipStream_t s) {
+  const int H2 = H / 2, W2 = W / 2, H4 = H / 4, W4 = W / 4;
+  int rc;
+  auto conv = [&](int i, const float* in, float* out, int Cin, int Cout, int h, int w, int k, int stride) -> int {
+    if (wfrags && wfrags[i] && conv2dmfma::supported(Cin, Cout, k, stride))
+      return conv2dmfma::run(in, wfrags[i], biases[i], out, Cin, Cout, h, w, k, stride, 1, s);
+    return run_conv(in, weights[i], biases[i], nullptr, 0, out, Cin, Cout, h, w, k, stride, 1, s);
+  };
+#define SVS_ENC(...) if ((rc = conv(__VA_ARGS__)) != SVS_OK) return rc
+  SVS_ENC(0, image, o.c0a, 3, b, H, W, 3, 1);
+  SVS_ENC(1, o.c0a, o.c0, b, b, H, W, 3, 1);
+  SVS_ENC(2, o.c0, o.c1a, b, 2 * b, H, W, 5, 2);
+  SVS_ENC(3, o.c1a, o.c1b, 2 * b, 2 * b, H2, W2, 3, 1);
+  SVS_ENC(4, o.c1b, o.c1, 2 * b, 2 * b, H2, W2, 3, 1);
+  SVS_ENC(5, o.c1, o.c2a, 2 * b, 4 * b, H2, W2, 5, 2);
+  SVS_ENC(6, o.c2a, o.c2b, 4 * b, 4 * b, H4, W4, 3, 1);
+  SVS_ENC(7, o.c2b, o.c2, 4 * b, 4 * b, H4, W4, 3, 1);
+#undef SVS_ENC
+  return SVS_OK;
+}
+
+}  // namespace conv2d
+}  // namespace svs
+
+using namespace svs;
+using namespace svs::conv2d;
+
+namespace {
 
 // workspace layout of svs_featurenet_fpn (floats), P = H * W, b = base channels
 struct FpnBuffers {
@@ -356,15 +369,10 @@ int svs_featurenet_fpn2(const float* image, int H, int W, int base_channels, con
     return run_conv(in, weights[i], biases[i], add, add_up2, out, Cin, Cout, h, w, k, stride, relu, s);
   };
 #define SVS_FPN(...) if ((rc = conv(__VA_ARGS__)) != SVS_OK) return rc
-  // bottom-up path (models/CasMVSNet.py:343-361): conv + folded BatchNorm + ReLU
-  SVS_FPN(0, image, nullptr, 0, ws + B.c0a, 3, b, H, W, 3, 1, 1);
-  SVS_FPN(1, ws + B.c0a, nullptr, 0, ws + B.c0, b, b, H, W, 3, 1, 1);
-  SVS_FPN(2, ws + B.c0, nullptr, 0, ws + B.c1a, b, 2 * b, H, W, 5, 2, 1);
-  SVS_FPN(3, ws + B.c1a, nullptr, 0, ws + B.c1b, 2 * b, 2 * b, H2, W2, 3, 1, 1);
-  SVS_FPN(4, ws + B.c1b, nullptr, 0, ws + B.c1, 2 * b, 2 * b, H2, W2, 3, 1, 1);
-  SVS_FPN(5, ws + B.c1, nullptr, 0, ws + B.c2a, 2 * b, 4 * b, H2, W2, 5, 2, 1);
-  SVS_FPN(6, ws + B.c2a, nullptr, 0, ws + B.c2b, 4 * b, 4 * b, H4, W4, 3, 1, 1);
-  SVS_FPN(7, ws + B.c2b, nullptr, 0, ws + B.c2, 4 * b, 4 * b, H4, W4, 3, 1, 1);
+  // bottom-up path (models/CasMVSNet.py:343-361)
+  if ((rc = run_encoder(image, H, W, b, weights, biases, wfrags, {ws + B.c0a, ws + B.c0, ws + B.c1a, ws + B.c1b, ws + B.c1,
+                                                                  ws + B.c2a, ws + B.c2b, ws + B.c2}, s)) != SVS_OK)
+    return rc;
   // top-down path (:413-431): the nearest x2 up-sampling is an index shift in the lateral convolution's epilogue
   SVS_FPN(8, ws + B.c2, nullptr, 0, stage1, 4 * b, 4 * b, H4, W4, 1, 1, 0);               // out1
   SVS_FPN(9, ws + B.c1, ws + B.c2, 1, ws + B.f1, 2 * b, 4 * b, H2, W2, 1, 1, 0);          // inner1 + up(c2)

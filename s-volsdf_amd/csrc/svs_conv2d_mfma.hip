@@ -12,6 +12,7 @@
 // x MT M tiles x KS k-steps x 3 MFMAs, the B fragments (16-byte channel vectors of one input pixel) read from LDS one k-step
 // ahead.  Pixel pitch in LDS: an odd multiple of 16 bytes (conflict-free 16-byte reads at pixel stride 1; stride 2: two-way).
 #include "svs_common.h"
+#include "svs_conv2d_api.h"
 
 namespace svs {
 namespace conv2dmfma {

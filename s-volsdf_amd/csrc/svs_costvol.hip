@@ -10,6 +10,7 @@
 #include "svs_common.h"
 #include <cstdlib>
 #include "svs_split_volume.h"
+#include "svs_warp_taps.h"
 
 namespace svs {
 namespace costvol {
@@ -26,12 +27,10 @@ __global__ void chw_to_hwc_kernel(const float* __restrict__ in, float* __restric
   out[idx] = in[(size_t)c * HW + p];
 }
 
-constexpr int kMaxSrc = 4;
+using warp::kMaxSrc;
 struct WarpArgs {
   const float* ref;              // (C,H,W) reference-view feature
-  const float* src_hwc[kMaxSrc]; // (H,W,C) source-view features
-  float rot[kMaxSrc][9];         // src_proj @ inv(ref_proj), rows
-  float trans[kMaxSrc][3];
+  warp::SourceViews src;         // per source view: (H,W,C) features, rotation, translation (svs_warp_taps.h)
   const float* depth_values;     // (D,H,W)
   float* variance;               // (C,D,H,W)
   int n_src, D, H, W;
@@ -89,32 +88,9 @@ __global__ __launch_bounds__(256, NS <= 2 ? 4 : 2) void warp_variance_kernel(War
       const int x = xt + vx;
       f32x4 w4 = {0.0f, 0.0f, 0.0f, 0.0f};
       i32x4 o4 = {0, 0, 0, 0};
-      if (x < W) {
-        const float depth = a.depth_values[((size_t)d * H + y) * W + x];
-        const float fx = (float)x, fy = (float)y;
-        const float* R = a.rot[v];
-        // rot @ [x,y,1] * depth + trans   (CasMVSNet.py:300-303)
-        const float qx = ((R[0] * fx + R[1] * fy) + R[2]) * depth + a.trans[v][0];
-        const float qy = ((R[3] * fx + R[4] * fy) + R[5]) * depth + a.trans[v][1];
-        const float qz = ((R[6] * fx + R[7] * fy) + R[8]) * depth + a.trans[v][2];
-        // correctly rounded divisions, the reference's operation order: at |coordinate| ~ 300 px one ulp of the
-        // quotient already moves a sample by 3e-5 px (once per voxel and source: not what bounds the kernel)
-        const float px = qx / qz, py = qy / qz;
-        // normalised with the (W-1)/2 formula, sampled with align_corners=False (:305-312)
-        const float gx = px / ((float)(W - 1) / 2.0f) - 1.0f, gy = py / ((float)(H - 1) / 2.0f) - 1.0f;
-        const float ix = ((gx + 1.0f) * (float)W - 1.0f) / 2.0f, iy = ((gy + 1.0f) * (float)H - 1.0f) / 2.0f;
-        const float x0 = __builtin_floorf(ix), y0 = __builtin_floorf(iy);
-        const float tx = ix - x0, ty = iy - y0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const float xx = x0 + (float)(k & 1), yy = y0 + (float)(k >> 1);
-          // zeros padding: a corner outside contributes nothing (NaN coordinates compare false)
-          if (xx >= 0.0f && xx <= (float)(W - 1) && yy >= 0.0f && yy <= (float)(H - 1)) {
-            w4[k] = ((k & 1) ? tx : 1.0f - tx) * ((k >> 1) ? ty : 1.0f - ty);
-            o4[k] = ((int)yy * W + (int)xx) * (C * 4);      // byte offset
-          }
-        }
-      }
+      // normalised with the (W-1)/2 formula, sampled with align_corners=False (CasMVSNet.py:305-312)
+      if (x < W)
+        warp::bilinear_taps<C, warp::kHalfPixel, false>(a.src, v, x, y, H, W, a.depth_values[((size_t)d * H + y) * W + x], w4, o4);
       tapw[i] = w4;
       tapo[i] = o4;
     }
@@ -128,7 +104,7 @@ __global__ __launch_bounds__(256, NS <= 2 ? 4 : 2) void warp_variance_kernel(War
       for (int v = 0; v < NS; ++v) {
         w4[v] = tapw[v * TW + vx];
         const i32x4 o4 = tapo[v * TW + vx];
-        const char* __restrict__ src = reinterpret_cast<const char*>(a.src_hwc[v]);   // uniform base + 32-bit offset
+        const char* __restrict__ src = reinterpret_cast<const char*>(a.src.src_hwc[v]);   // uniform base + 32-bit offset
 #pragma unroll
         for (int k = 0; k < 4; ++k) f[v][k] = *reinterpret_cast<const f32x4*>(src + ((unsigned)o4[k] + 16u * cg));
       }
@@ -205,152 +181,8 @@ __global__ __launch_bounds__(256, NS <= 2 ? 4 : 2) void warp_variance_kernel(War
 // kernel above).
 constexpr int kWarpDz = 4;
 
-// depth: the hypothesis of voxel (d, y, x), loaded by the caller (all of a thread's loads are requested before the first
-// projection: a load per loop iteration in front of its ~100 dependent instructions was a latency chain, round 5)
-template <int C>
-__device__ __forceinline__ void warp_taps(const WarpArgs& a, int v, int x, int y, int d, float depth, f32x4& w4, i32x4& o4) {
-  const int H = a.H, W = a.W;
-  w4 = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-  o4 = i32x4{0, 0, 0, 0};
-  if (x >= W || d >= a.D) return;
-  const float fx = (float)x, fy = (float)y;
-  const float* R = a.rot[v];
-  // rot @ [x,y,1] * depth + trans   (CasMVSNet.py:300-303); same operations, same order as warp_variance_kernel
-  const float qx = ((R[0] * fx + R[1] * fy) + R[2]) * depth + a.trans[v][0];
-  const float qy = ((R[3] * fx + R[4] * fy) + R[5]) * depth + a.trans[v][1];
-  const float qz = ((R[6] * fx + R[7] * fy) + R[8]) * depth + a.trans[v][2];
-  const float px = qx / qz, py = qy / qz;
-  const float gx = px / ((float)(W - 1) / 2.0f) - 1.0f, gy = py / ((float)(H - 1) / 2.0f) - 1.0f;
-  const float ix = ((gx + 1.0f) * (float)W - 1.0f) / 2.0f, iy = ((gy + 1.0f) * (float)H - 1.0f) / 2.0f;
-  const float x0 = __builtin_floorf(ix), y0 = __builtin_floorf(iy);
-  const float tx = ix - x0, ty = iy - y0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const float xx = x0 + (float)(k & 1), yy = y0 + (float)(k >> 1);
-    if (xx >= 0.0f && xx <= (float)(W - 1) && yy >= 0.0f && yy <= (float)(H - 1)) {
-      w4[k] = ((k & 1) ? tx : 1.0f - tx) * ((k >> 1) ? ty : 1.0f - ty);
-      o4[k] = ((int)yy * W + (int)xx) * (C * 4);      // byte offset
-    }
-  }
-}
-
-// passes over x per workgroup: the corner tables (kWarpDz x NS x TW x 32 B) stay at 40 KiB for two sources (four workgroups
-// per CU): TW = 160 voxels at C = 32, 128 at C = 16 and 8
-template <int C> constexpr int reuse_passes() { return C == 32 ? 5 : (C == 16 ? 2 : 1); }
-
-template <int C, int NS>
-__global__ __launch_bounds__(256, NS <= 2 ? 4 : 2) void warp_variance_reuse_kernel(WarpArgs a) {
-  constexpr int kPasses = reuse_passes<C>();
-  constexpr int LPV = C / 4, VPP = 256 / LPV, TW = kPasses * VPP;
-  __shared__ __attribute__((aligned(16))) f32x4 tapw[kWarpDz][NS][TW];
-  __shared__ __attribute__((aligned(16))) i32x4 tapo[kWarpDz][NS][TW];
-  const int tid = threadIdx.x;
-  const int cg = tid % LPV, vl = tid / LPV;
-  const int H = a.H, W = a.W, y = blockIdx.y;
-  const int xt = blockIdx.x * TW, d0 = blockIdx.z * kWarpDz;
-  const size_t HW = (size_t)H * W;
-  const float inv_nv = 1.0f / (float)(NS + 1);
-  const int Hp = splitvol::padded_h(H), Wp = splitvol::padded_w(W);
-  // ---- corner weights and offsets of all planes, one (plane, source, voxel) per thread and round; the depth hypotheses of
-  // all rounds first
-  constexpr int kRounds = (kWarpDz * NS * TW + 255) / 256;
-  float dep[kRounds];
-#pragma unroll
-  for (int k = 0; k < kRounds; ++k) {
-    const int i = tid + 256 * k;
-    const int dz = i / (NS * TW), r = i - dz * (NS * TW);
-    const int vx = r - (r / TW) * TW;
-    const int x = xt + vx, d = d0 + dz;
-    dep[k] = (i < kWarpDz * NS * TW && x < W && d < a.D) ? a.depth_values[((size_t)d * H + y) * W + x] : 0.0f;
-  }
-#pragma unroll
-  for (int k = 0; k < kRounds; ++k) {
-    const int i = tid + 256 * k;
-    if (i >= kWarpDz * NS * TW) break;
-    const int dz = i / (NS * TW), r = i - dz * (NS * TW);
-    const int v = r / TW, vx = r - v * TW;
-    f32x4 w4; i32x4 o4;
-    warp_taps<C>(a, v, xt + vx, y, d0 + dz, dep[k], w4, o4);
-    tapw[dz][v][vx] = w4;
-    tapo[dz][v][vx] = o4;
-  }
-  __syncthreads();
-  // Loads and stores retire from vmcnt in issue order: a wait for a plane's gathers also waited for the previous plane's
-  // stores to be acknowledged -- every plane paid a write latency (ablation, round 5: the stores cost 0.085 of the kernel's
-  // 0.205 ms although nothing reads them).  The plane loop is therefore skewed by one plane: a plane's two stores are issued
-  // BEHIND the table reads and (conditional) gathers of the next plane -- or of the next pass's first plane, which are
-  // unconditional: a new voxel -- so that the wait in front of the next blend leaves exactly those stores in flight.
-  f32x4 f[NS][4];
-  i32x4 held[NS];
-  f32x4 w4s[NS];
-  f32x4 ref;
-  auto first_gathers = [&](int pass) {
-    const int vxn = pass * VPP + vl;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) ref[j] = xt + vxn < W ? a.ref[(size_t)(4 * cg + j) * HW + (size_t)y * W + xt + vxn] : 0.0f;
-#pragma unroll
-    for (int v = 0; v < NS; ++v) {
-      w4s[v] = tapw[0][v][vxn];
-      const i32x4 o4 = tapo[0][v][vxn];
-      const char* __restrict__ src = reinterpret_cast<const char*>(a.src_hwc[v]);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) f[v][k] = *reinterpret_cast<const f32x4*>(src + ((unsigned)o4[k] + 16u * cg));
-      held[v] = o4;
-    }
-  };
-  first_gathers(0);
-#pragma unroll 1
-  for (int p = 0; p < kPasses; ++p) {
-    const int vx = p * VPP + vl, x = xt + vx;
-#pragma unroll
-    for (int dz = 0; dz < kWarpDz; ++dz) {
-      const int d = d0 + dz;
-      f32x4 sum = ref, sq = ref * ref;
-#pragma unroll
-      for (int v = 0; v < NS; ++v) {
-        f32x4 warped = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-          warped = __builtin_elementwise_fma(f32x4{w4s[v][k], w4s[v][k], w4s[v][k], w4s[v][k]}, f[v][k], warped);
-        sum += warped; sq = __builtin_elementwise_fma(warped, warped, sq);
-      }
-      const f32x4 m = sum * inv_nv;
-      const f32x4 res = sq * inv_nv - m * m;
-      f16x4 h, lo;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const _Float16 hh = (_Float16)res[j];
-        h[j] = hh;
-        lo[j] = (_Float16)(res[j] - (float)hh);
-      }
-      // the next plane's corner weights and (conditional) gathers: all sources requested before this plane's stores
-      if (dz + 1 < kWarpDz) {
-#pragma unroll
-        for (int v = 0; v < NS; ++v) {
-          w4s[v] = tapw[dz + 1][v][vx];
-          const i32x4 o4 = tapo[dz + 1][v][vx];
-          const char* __restrict__ src = reinterpret_cast<const char*>(a.src_hwc[v]);
-          // (a voxel's LPV lanes take the same branch; a corner outside the image has offset 0 and weight 0)
-          if (o4[0] != held[v][0] || o4[1] != held[v][1] || o4[2] != held[v][2] || o4[3] != held[v][3]) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) f[v][k] = *reinterpret_cast<const f32x4*>(src + ((unsigned)o4[k] + 16u * cg));
-            held[v] = o4;
-          }
-        }
-      } else if (p + 1 < kPasses) {
-        first_gathers(p + 1);
-      }
-      if (x < W && d < a.D) {
-        uint2* u = reinterpret_cast<uint2*>(a.split + splitvol::unit(d, y, 0, cg >> 1, x, C / 8, Hp, Wp)) + (cg & 1);
-        u[0] = __builtin_bit_cast(uint2, h);
-        u[(size_t)(C / 8) * Wp * 2] = __builtin_bit_cast(uint2, lo);
-      }
-    }
-  }
-}
-
 // ---- round 6: the producer re-written around its instruction count ---------------------------------------------------------
-// Per (voxel, plane) round 5's kernel executes ~1540 lane-instructions -- 2 x 250 for the two corner-table entries and 8 lanes x
+// Per (voxel, plane) round 5's kernel (the first form of this producer, since removed) executed ~1540 lane-instructions -- 2 x 250 for the two corner-table entries and 8 lanes x
 // 130 in the blend loop, of which ~50 are the blend, the variance and the fp16 split; the rest is per-lane overhead (table
 // reads, the moved-or-not test, 16 register copies around the conditional gathers, address arithmetic, waits).  This kernel:
 //   * the conditional re-gather is ONE inline-asm statement per source: exec is narrowed INSIDE it and the corner registers are
@@ -404,7 +236,7 @@ __device__ __forceinline__ float div_const_ieee(float n, float d, float r) {
   return n / d;
 }
 
-// warp_taps (above) for the eight-channel producer: the same operations in the same order, with the four divisions as
+// warp::bilinear_taps<C, kHalfPixel, false> (svs_warp_taps.h) for this producer: the same operations in the same order, with the four divisions as
 // above (hw = (W - 1) / 2, hh = (H - 1) / 2 and their refined reciprocals are formed once per thread) and the four corners
 // without branches (compare, select): an entry costs ~130 instructions instead of ~245.
 template <int C>
@@ -412,10 +244,10 @@ __device__ __forceinline__ void warp_taps8(const WarpArgs& a, int v, int x, int 
                                            float hh, float rhh, f32x4& w4, i32x4& o4) {
   const int H = a.H, W = a.W;
   const float fx = (float)x, fy = (float)y;
-  const float* R = a.rot[v];
-  const float qx = ((R[0] * fx + R[1] * fy) + R[2]) * depth + a.trans[v][0];
-  const float qy = ((R[3] * fx + R[4] * fy) + R[5]) * depth + a.trans[v][1];
-  const float qz = ((R[6] * fx + R[7] * fy) + R[8]) * depth + a.trans[v][2];
+  const float* R = a.src.rot[v];
+  const float qx = ((R[0] * fx + R[1] * fy) + R[2]) * depth + a.src.trans[v][0];
+  const float qy = ((R[3] * fx + R[4] * fy) + R[5]) * depth + a.src.trans[v][1];
+  const float qz = ((R[6] * fx + R[7] * fy) + R[8]) * depth + a.src.trans[v][2];
   float px, py;
   div2_ieee(qx, qy, qz, px, py);
   const float gx = div_const_ieee(px, hw, rhw) - 1.0f, gy = div_const_ieee(py, hh, rhh) - 1.0f;
@@ -567,7 +399,7 @@ __global__ __launch_bounds__((WarpCfg<C, CPL>::T), NS <= 2 ? 4 : 2) void warp_va
       const i32x4 o4 = tapo[0][v][vxn];
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        gload128(f[v][k][0], (unsigned)o4[k] + lane_off, a.src_hwc[v]);
+        gload128(f[v][k][0], (unsigned)o4[k] + lane_off, a.src.src_hwc[v]);
       }
       held[v] = o4;
     }
@@ -622,7 +454,7 @@ __global__ __launch_bounds__((WarpCfg<C, CPL>::T), NS <= 2 ? 4 : 2) void warp_va
           const i32x4 o4 = tapo[dz + 1][v][vx];
           // (a voxel's LPV lanes decide alike; a corner outside the image has offset 0 and weight 0)
           const bool moved = o4[0] != held[v][0] || o4[1] != held[v][1] || o4[2] != held[v][2] || o4[3] != held[v][3];
-          regather(f[v], o4, lane_off, a.src_hwc[v], __builtin_amdgcn_ballot_w64(moved));
+          regather(f[v], o4, lane_off, a.src.src_hwc[v], __builtin_amdgcn_ballot_w64(moved));
           held[v] = o4;
         }
       } else if (p + 1 < P) {
@@ -639,32 +471,17 @@ __global__ __launch_bounds__((WarpCfg<C, CPL>::T), NS <= 2 ? 4 : 2) void warp_va
   }
 }
 
+// THE BOUNDS OF THE SPLIT FORM: the producer addresses the split volume and the feature maps with 32-bit byte offsets, so the
+// volume (svs_split_volume_dims' byte count) stays below 4 GiB and a (H,W,C) feature map below 2 GiB.  The largest volume of
+// the project's workloads is well under 1 GiB; costvol.split_fits (svs_hip/costvol.py) asks before it chooses the split form.
 template <int C>
 static bool launch_warp_reuse2(const WarpArgs& a, hipStream_t s) {
-  // 32-bit byte offsets into the split volume and the feature maps
   const size_t vol = (size_t)(a.D + 2) * splitvol::padded_h(a.H) * 2 * (C / 8) * splitvol::padded_w(a.W) * 16;
   if (vol >= (1ull << 32) || (size_t)a.H * a.W * C * 4 >= (1ull << 31)) return false;
   constexpr int T = WarpCfg<C, 4>::T, tw = WarpCfg<C, 4>::P * (T / (C / 4));
   dim3 grid((a.W + tw - 1) / tw, a.H, (a.D + kWarpDz - 1) / kWarpDz), block(T);
-  switch (a.n_src) {
-    case 1: warp_variance_reuse2_kernel<C, 1, 4><<<grid, block, 0, s>>>(a); break;
-    case 2: warp_variance_reuse2_kernel<C, 2, 4><<<grid, block, 0, s>>>(a); break;
-    case 3: warp_variance_reuse2_kernel<C, 3, 4><<<grid, block, 0, s>>>(a); break;
-    default: warp_variance_reuse2_kernel<C, 4, 4><<<grid, block, 0, s>>>(a); break;
-  }
+  warp::dispatch_n_src(a.n_src, [&](auto ns) { warp_variance_reuse2_kernel<C, decltype(ns)::value, 4><<<grid, block, 0, s>>>(a); });
   return true;
-}
-
-template <int C>
-static void launch_warp_reuse(const WarpArgs& a, hipStream_t s) {
-  const int tw = reuse_passes<C>() * (256 / (C / 4));
-  dim3 grid((a.W + tw - 1) / tw, a.H, (a.D + kWarpDz - 1) / kWarpDz), block(256);
-  switch (a.n_src) {
-    case 1: warp_variance_reuse_kernel<C, 1><<<grid, block, 0, s>>>(a); break;
-    case 2: warp_variance_reuse_kernel<C, 2><<<grid, block, 0, s>>>(a); break;
-    case 3: warp_variance_reuse_kernel<C, 3><<<grid, block, 0, s>>>(a); break;
-    default: warp_variance_reuse_kernel<C, 4><<<grid, block, 0, s>>>(a); break;
-  }
 }
 
 template <int C>
@@ -672,12 +489,7 @@ static void launch_warp(const WarpArgs& a, hipStream_t s) {
   const int tw = kWarpPasses * (256 / (C / 4));
   const int dz = a.D >= 64 ? 4 : 1;                // few planes: one per workgroup, so that the launch fills the chip
   dim3 grid((a.W + tw - 1) / tw, a.H, (a.D + dz - 1) / dz), block(256);
-  switch (a.n_src) {
-    case 1: warp_variance_kernel<C, 1><<<grid, block, 0, s>>>(a, dz); break;
-    case 2: warp_variance_kernel<C, 2><<<grid, block, 0, s>>>(a, dz); break;
-    case 3: warp_variance_kernel<C, 3><<<grid, block, 0, s>>>(a, dz); break;
-    default: warp_variance_kernel<C, 4><<<grid, block, 0, s>>>(a, dz); break;
-  }
+  warp::dispatch_n_src(a.n_src, [&](auto ns) { warp_variance_kernel<C, decltype(ns)::value><<<grid, block, 0, s>>>(a, dz); });
 }
 
 // ---- 3x3x3 convolution, padding 1, stride 1/2, folded BN (scale in the weights, shift as bias), optional ReLU ----
@@ -1345,21 +1157,16 @@ static int warp_variance_any(const float* ref_feature, const float* const* src_f
   WarpArgs a;
   a.ref = ref_feature; a.depth_values = depth_values; a.variance = variance; a.n_src = n_src; a.D = D; a.H = H; a.W = W;
   a.raw_warp = raw_warp; a.split = reinterpret_cast<uint4*>(split);
-  for (int v = 0; v < n_src; ++v) {
-    if (!src_features_hwc[v]) { set_error("svs_warp_variance: null source %d", v); return SVS_EINVAL; }
-    a.src_hwc[v] = src_features_hwc[v];
-    for (int k = 0; k < 9; ++k) a.rot[v][k] = rot_trans[12 * v + k];      // HOST array: 9 rot + 3 trans per source
-    for (int k = 0; k < 3; ++k) a.trans[v][k] = rot_trans[12 * v + 9 + k];
-  }
+  if (const int rc = warp::fill_sources("svs_warp_variance", a.src, src_features_hwc, rot_trans, n_src)) return rc;
   if (C != 8 && C != 16 && C != 32) { set_error("svs_warp_variance: C must be 8, 16 or 32 (FeatureNet outputs)"); return SVS_ESHAPE; }
   hipStream_t s = (hipStream_t)hip_stream;
   if (a.split && !raw_warp) {
-    // the round-6 producer; round 5's kernel where its 32-bit offsets do not fit
     const bool ok = C == 8 ? launch_warp_reuse2<8>(a, s) : (C == 16 ? launch_warp_reuse2<16>(a, s) : launch_warp_reuse2<32>(a, s));
-    if (ok) return check_launch("svs_warp_variance_split");
-    if (C == 8) launch_warp_reuse<8>(a, s);
-    else if (C == 16) launch_warp_reuse<16>(a, s);
-    else launch_warp_reuse<32>(a, s);
+    if (!ok) {
+      set_error("svs_warp_variance_split: the split volume must stay below 4 GiB and a feature map below 2 GiB (32-bit offsets); "
+                "use svs_warp_variance");
+      return SVS_ESHAPE;
+    }
     return check_launch("svs_warp_variance_split");
   }
   if (C == 8) launch_warp<8>(a, s);

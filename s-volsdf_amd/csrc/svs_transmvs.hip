@@ -10,6 +10,7 @@
 // svs_conv2d reads its weights; per-lane data moves with vector loads and stores only.
 #include "svs_common.h"
 #include <cstdlib>
+#include "svs_warp_taps.h"
 
 namespace svs {
 namespace transmvs {
@@ -327,48 +328,16 @@ __global__ __launch_bounds__(256) void pathway_kernel(const float* __restrict__ 
 }
 
 // ---- d. similarity cost volume with per-pixel view weights ----------------------------------------------------------------
-constexpr int kMaxSrc = 4;
+using warp::kMaxSrc;
 constexpr int kSimDz = 8;                       // depth planes per workgroup (a multiple of every C / 4)
 
 struct SimArgs {
   const float* ref;               // (C,H,W)
-  const float* src_hwc[kMaxSrc];  // (H,W,C)
-  float rot[kMaxSrc][9];          // src_proj @ inv(ref_proj), rows
-  float trans[kMaxSrc][3];
+  warp::SourceViews src;          // per source view: (H,W,C) features, rotation, translation (svs_warp_taps.h)
   const float* depth_values;      // (D,H,W)
   float* sims;                    // (n_src,D,H,W): per-view similarities
   int D, H, W;
 };
-
-// The four bilinear corners of one voxel in one source view: models/module.py:296-321.  align_corners=True, so the pixel
-// coordinate is ((g + 1) / 2) * (size - 1); a hypothesis whose projected z is below 1e-6 (its grid coordinates are set to
-// -99 there) and a projection that is not a number sample nothing.
-template <int C>
-__device__ __forceinline__ void sim_taps(const SimArgs& a, int v, int x, int y, float depth, f32x4& w4, i32x4& o4) {
-  const int H = a.H, W = a.W;
-  w4 = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-  o4 = i32x4{0, 0, 0, 0};
-  const float fx = (float)x, fy = (float)y;
-  const float* R = a.rot[v];
-  const float qx = ((R[0] * fx + R[1] * fy) + R[2]) * depth + a.trans[v][0];
-  const float qy = ((R[3] * fx + R[4] * fy) + R[5]) * depth + a.trans[v][1];
-  const float qz = ((R[6] * fx + R[7] * fy) + R[8]) * depth + a.trans[v][2];
-  if (!(qz >= 1e-6f)) return;
-  const float px = qx / qz, py = qy / qz;
-  const float gx = px / ((float)(W - 1) / 2.0f) - 1.0f, gy = py / ((float)(H - 1) / 2.0f) - 1.0f;
-  const float ix = ((gx + 1.0f) / 2.0f) * (float)(W - 1), iy = ((gy + 1.0f) / 2.0f) * (float)(H - 1);
-  const float x0 = __builtin_floorf(ix), y0 = __builtin_floorf(iy);
-  const float tx = ix - x0, ty = iy - y0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const float xx = x0 + (float)(k & 1), yy = y0 + (float)(k >> 1);
-    // zeros padding: a corner outside contributes nothing (NaN coordinates compare false)
-    if (xx >= 0.0f && xx <= (float)(W - 1) && yy >= 0.0f && yy <= (float)(H - 1)) {
-      w4[k] = ((k & 1) ? tx : 1.0f - tx) * ((k >> 1) ? ty : 1.0f - ty);
-      o4[k] = ((int)yy * W + (int)xx) * (C * 4);      // byte offset
-    }
-  }
-}
 
 // C/4 adjacent lanes own one pixel, 4 channels each, as in svs_warp_variance: a bilinear corner of the (H,W,C) source is one
 // contiguous C-vector.  The group walks C/4 depth planes at a time: lane cg projects plane d0 + cg, the corners of each plane
@@ -396,14 +365,15 @@ __global__ __launch_bounds__(256) void warp_similarity_kernel(SimArgs a) {
     const int dm = d0 + cg;
     const float depth = a.depth_values[((size_t)(dm < d_end ? dm : d_end - 1) * H + y) * W + x];
 #pragma unroll
-    for (int v = 0; v < NS; ++v) sim_taps<C>(a, v, x, y, depth, w4[v], o4[v]);
+    // (models/module.py:296-321: align_corners=True, nothing sampled where the projected z is below 1e-6)
+    for (int v = 0; v < NS; ++v) warp::bilinear_taps<C, warp::kAlignCorners, true>(a.src, v, x, y, H, W, depth, w4[v], o4[v]);
 #pragma unroll
     for (int j = 0; j < LPV; ++j) {
       const int d = d0 + j;
       if (d >= d_end) break;                       // wave-uniform
 #pragma unroll
       for (int v = 0; v < NS; ++v) {
-        const char* __restrict__ src = reinterpret_cast<const char*>(a.src_hwc[v]);
+        const char* __restrict__ src = reinterpret_cast<const char*>(a.src.src_hwc[v]);
         f32x4 warped = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -491,21 +461,11 @@ __global__ __launch_bounds__(256) void sim_finish_kernel(SimFinishArgs a) {
   }
 }
 
-template <int C, int NS>
-static void launch_sim(const SimArgs& a, hipStream_t s) {
+template <int C>
+static void launch_sim(const SimArgs& a, int n_src, hipStream_t s) {
   constexpr int VPP = 256 / (C / 4);
   dim3 grid((a.W + VPP - 1) / VPP, a.H, (a.D + kSimDz - 1) / kSimDz);
-  warp_similarity_kernel<C, NS><<<grid, 256, 0, s>>>(a);
-}
-
-template <int C>
-static void launch_sim_ns(const SimArgs& a, int n_src, hipStream_t s) {
-  switch (n_src) {
-    case 1: launch_sim<C, 1>(a, s); break;
-    case 2: launch_sim<C, 2>(a, s); break;
-    case 3: launch_sim<C, 3>(a, s); break;
-    default: launch_sim<C, 4>(a, s); break;
-  }
+  warp::dispatch_n_src(n_src, [&](auto ns) { warp_similarity_kernel<C, decltype(ns)::value><<<grid, 256, 0, s>>>(a); });
 }
 
 }  // namespace transmvs
@@ -613,17 +573,11 @@ int svs_warp_similarity(const float* ref_feature, const float* const* src_featur
   if (C != 8 && C != 16 && C != 32) { set_error("svs_warp_similarity: C must be 8, 16 or 32"); return SVS_ESHAPE; }
   SimArgs a;
   a.ref = ref_feature; a.depth_values = depth_values; a.sims = workspace; a.D = D; a.H = H; a.W = W;
-  for (int v = 0; v < kMaxSrc; ++v) {
-    const int u = v < n_src ? v : 0;
-    if (!src_features_hwc[u]) { set_error("svs_warp_similarity: null source %d", u); return SVS_EINVAL; }
-    a.src_hwc[v] = src_features_hwc[u];
-    for (int k = 0; k < 9; ++k) a.rot[v][k] = rot_trans[12 * u + k];      // HOST array: 9 rot + 3 trans per source
-    for (int k = 0; k < 3; ++k) a.trans[v][k] = rot_trans[12 * u + 9 + k];
-  }
+  if (const int rc = warp::fill_sources("svs_warp_similarity", a.src, src_features_hwc, rot_trans, n_src)) return rc;
   hipStream_t s = (hipStream_t)hip_stream;
-  if (C == 8) launch_sim_ns<8>(a, n_src, s);
-  else if (C == 16) launch_sim_ns<16>(a, n_src, s);
-  else launch_sim_ns<32>(a, n_src, s);
+  if (C == 8) launch_sim<8>(a, n_src, s);
+  else if (C == 16) launch_sim<16>(a, n_src, s);
+  else launch_sim<32>(a, n_src, s);
   SimFinishArgs f{workspace, prev_weights, net, similarity, weights_out, n_src, D, H, W};
   if (!prev_weights) view_weights_kernel<<<dim3((H * W + 255) / 256, n_src), 256, 0, s>>>(f);
   sim_finish_kernel<<<(H * W + 255) / 256, 256, 0, s>>>(f);

@@ -20,15 +20,10 @@
 // times the zero weights of the padded k-step is NaN); a mid piece below 2^-14 (|value| < 0.125) is an fp16 subnormal, good to
 // 3e-8 absolute: weights of 1e-2 carry 3e-6 relative instead of 2e-7.  Within [0.125, 65504) both operands have 22 bits.
 #include "svs_common.h"
+#include "svs_conv2d_api.h"
 #include <cstdint>
 
 namespace svs {
-namespace conv2dmfma {      // csrc/svs_conv2d_mfma.hip
-bool supported(int Cin, int Cout, int k, int stride);
-int run(const float* in, const void* wfrag, const float* bias, float* out, int Cin, int Cout, int H, int W, int k, int stride,
-        int relu, hipStream_t s);
-}  // namespace conv2dmfma
-
 namespace ucsnet {
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
@@ -345,9 +340,6 @@ using namespace svs::ucsnet;
 
 extern "C" {
 
-int svs_conv2d(const float* in, const float* weight, const float* bias, const float* add, int add_upsample2, float* out,
-               int Cin, int Cout, int H, int W, int k, int stride, int relu, void* hip_stream);
-
 int svs_deconv2d_mfma_supported(int Cin, int Cout) { return deconv_supported(Cin, Cout) ? 1 : 0; }
 
 // bytes of the packed A fragments: [sum over the four classes of ceil(taps Cin / 32)][2][64][16 B]
@@ -397,7 +389,7 @@ int svs_featurenet_unet(const float* image, int H, int W, int base_channels, con
   auto conv = [&](int i, const float* in, float* out, int Cin, int Cout, int h, int w, int k, int stride, int relu) -> int {
     if (wfrags && wfrags[i] && svs::conv2dmfma::supported(Cin, Cout, k, stride))
       return svs::conv2dmfma::run(in, wfrags[i], biases[i], out, Cin, Cout, h, w, k, stride, relu, s);
-    return svs_conv2d(in, weights[i], biases[i], nullptr, 0, out, Cin, Cout, h, w, k, stride, relu, hip_stream);
+    return svs::conv2d::run_conv(in, weights[i], biases[i], nullptr, 0, out, Cin, Cout, h, w, k, stride, relu, s);
   };
   auto deconv = [&](int i, const float* in, float* out, int Cin, int Cout, int h, int w) -> int {
     if (wfrags && wfrags[i] && deconv_supported(Cin, Cout))
@@ -406,14 +398,9 @@ int svs_featurenet_unet(const float* image, int H, int W, int base_channels, con
   };
 #define SVS_UNET(call) if ((rc = (call)) != SVS_OK) return rc
   // encoder (models/ucsnet.py:244-259, 280-282): the last layer of levels 0 and 1 lands in the upper half of its concatenation
-  SVS_UNET(conv(0, image, ws + B.c0a, 3, b, H, W, 3, 1, 1));
-  SVS_UNET(conv(1, ws + B.c0a, ws + B.cat2 + b * P, b, b, H, W, 3, 1, 1));
-  SVS_UNET(conv(2, ws + B.cat2 + b * P, ws + B.c1a, b, 2 * b, H, W, 5, 2, 1));
-  SVS_UNET(conv(3, ws + B.c1a, ws + B.c1b, 2 * b, 2 * b, H2, W2, 3, 1, 1));
-  SVS_UNET(conv(4, ws + B.c1b, ws + B.cat1 + 2 * b * P2, 2 * b, 2 * b, H2, W2, 3, 1, 1));
-  SVS_UNET(conv(5, ws + B.cat1 + 2 * b * P2, ws + B.c2a, 2 * b, 4 * b, H2, W2, 5, 2, 1));
-  SVS_UNET(conv(6, ws + B.c2a, ws + B.c2b, 4 * b, 4 * b, H4, W4, 3, 1, 1));
-  SVS_UNET(conv(7, ws + B.c2b, ws + B.c2, 4 * b, 4 * b, H4, W4, 3, 1, 1));
+  SVS_UNET(svs::conv2d::run_encoder(image, H, W, b, weights, biases, wfrags,
+                                    {ws + B.c0a, ws + B.cat2 + b * P, ws + B.c1a, ws + B.c1b, ws + B.cat1 + 2 * b * P2,
+                                     ws + B.c2a, ws + B.c2b, ws + B.c2}, s));
   SVS_UNET(conv(8, ws + B.c2, stage1, 4 * b, 4 * b, H4, W4, 1, 1, 0));                    // out1
   // decoder (:289-295): transposed layer into channels [0, C), 3x3 over the concatenation, 1x1 head
   SVS_UNET(deconv(9, ws + B.c2, ws + B.cat1, 4 * b, 2 * b, H4, W4));                      // deconv1.deconv

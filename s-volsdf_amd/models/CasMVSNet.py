@@ -13,61 +13,15 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from svs_hip import costvol
+from models.blocks import (CachedFold, Conv2d, bn_tensors, encoder_trunk, fold_bn, range_hypotheses, stack_stages,  # noqa: F401
+                           stage_inputs)                                    # (Conv2d: the name the other backbones and tests import)
 
 Align_Corners_Range = False
 
 
 # ---------------------------------------------------------------------------------------------------------
-# FeatureNet (parameter names of models/CasMVSNet.py:24-55,338-439, arch_mode 'fpn')
+# FeatureNet (parameter names of models/CasMVSNet.py:24-55,338-439, arch_mode 'fpn'); Conv2d: models/blocks.py
 # ---------------------------------------------------------------------------------------------------------
-class Conv2d(nn.Module):
-    """conv + BatchNorm2d + ReLU with the reference's parameter names (`conv.weight`, `bn.*`).  On the device, in eval
-    mode, the block is ONE launch of svs_conv2d with the BatchNorm folded into the weights."""
-
-    def __init__(self, cin, cout, k, stride=1, relu=True, bn=True, **kw):
-        super().__init__()
-        self.conv = nn.Conv2d(cin, cout, k, stride=stride, bias=not bn, **kw)
-        self.bn = nn.BatchNorm2d(cout) if bn else None
-        self.relu, self.stride = relu, stride
-        self._folded, self._key = None, None
-
-    def folded(self):
-        ts = [self.conv.weight] + ([self.conv.bias] if self.conv.bias is not None else [])
-        if self.bn is not None:
-            ts += [self.bn.weight, self.bn.bias, self.bn.running_mean, self.bn.running_var]
-        key = tuple((t.data_ptr(), t._version) for t in ts)
-        if self._key != key:
-            w = self.conv.weight.detach().float()
-            b = self.conv.bias.detach().float() if self.conv.bias is not None else None
-            if self.bn is not None:
-                scale = (self.bn.weight / torch.sqrt(self.bn.running_var + self.bn.eps)).detach().float()
-                shift = (self.bn.bias - self.bn.running_mean * scale).detach().float()
-                w = w * scale.view(-1, 1, 1, 1)
-                b = shift if b is None else b * scale + shift
-            self._folded, self._key = (w.contiguous(), b.contiguous() if b is not None else None), key
-        return self._folded
-
-    def forward(self, x):
-        if x.is_cuda and not self.training:
-            w, b = self.folded()
-            return _conv_batch(x, w, b, stride=self.stride, relu=self.relu)
-        x = self.conv(x)
-        if self.bn is not None:
-            x = self.bn(x)
-        return F.relu(x) if self.relu else x
-
-
-def _conv_batch(x, w, b, add=None, add_upsample2=False, stride=1, relu=False):
-    """(B,Cin,H,W) -> (B,Cout,Ho,Wo): one launch per image, written straight into the batch tensor."""
-    k = w.shape[-1]
-    Ho, Wo = (x.shape[2] + 2 * (k // 2) - k) // stride + 1, (x.shape[3] + 2 * (k // 2) - k) // stride + 1
-    out = torch.empty(x.shape[0], w.shape[0], Ho, Wo, device=x.device)
-    for i in range(x.shape[0]):
-        costvol.conv2d(x[i], w, b, add=None if add is None else add[i], add_upsample2=add_upsample2, stride=stride, relu=relu,
-                       out=out[i])
-    return out
-
-
 class FeatureNet(nn.Module):
     def __init__(self, base_channels, num_stage=3, stride=4, arch_mode="fpn"):
         super().__init__()
@@ -75,11 +29,7 @@ class FeatureNet(nn.Module):
             raise NotImplementedError("only the default FPN / 3-stage feature net is declared")
         b = base_channels
         self.arch_mode, self.stride, self.base_channels, self.num_stage = arch_mode, stride, b, num_stage
-        self.conv0 = nn.Sequential(Conv2d(3, b, 3, 1, padding=1), Conv2d(b, b, 3, 1, padding=1))
-        self.conv1 = nn.Sequential(Conv2d(b, 2 * b, 5, stride=2, padding=2), Conv2d(2 * b, 2 * b, 3, 1, padding=1),
-                                   Conv2d(2 * b, 2 * b, 3, 1, padding=1))
-        self.conv2 = nn.Sequential(Conv2d(2 * b, 4 * b, 5, stride=2, padding=2), Conv2d(4 * b, 4 * b, 3, 1, padding=1),
-                                   Conv2d(4 * b, 4 * b, 3, 1, padding=1))
+        self.conv0, self.conv1, self.conv2 = encoder_trunk(b)
         self.out1 = nn.Conv2d(4 * b, 4 * b, 1, bias=False)
         self.inner1 = nn.Conv2d(2 * b, 4 * b, 1, bias=True)
         self.inner2 = nn.Conv2d(b, 4 * b, 1, bias=True)
@@ -101,9 +51,7 @@ class FeatureNet(nn.Module):
             if self._fpn is None:
                 self._fpn = costvol.FeatureNetFpn(self.base_channels)
             layers = self._layers()
-            per_image = [self._fpn(xi, layers) for xi in x]
-            return {f"stage{j + 1}": torch.stack([o[j] for o in per_image]) if len(per_image) > 1 else per_image[0][j][None]
-                    for j in range(3)}
+            return stack_stages([self._fpn(xi, layers) for xi in x])
         c0 = self.conv0(x)
         c1 = self.conv1(c0)
         c2 = self.conv2(c1)
@@ -130,22 +78,19 @@ class _Block3d(nn.Module):
         else:
             self.conv = nn.Conv3d(cin, cout, 3, stride=stride, padding=1, bias=False)
         self.bn = nn.BatchNorm3d(cout)
-        self._folded, self._key = None, None
+        self._fold = CachedFold()
 
     def folded(self):
-        ts = [self.conv.weight, self.bn.weight, self.bn.bias, self.bn.running_mean, self.bn.running_var]
-        key = tuple((t.data_ptr(), t._version) for t in ts)
-        if self._key != key:
-            scale = self.bn.weight / torch.sqrt(self.bn.running_var + self.bn.eps)
-            shift = self.bn.bias - self.bn.running_mean * scale
+        """(weight [Cin][27][Cout], bias), float32, the BatchNorm (eval) folded in"""
+        def make():
+            scale, shift = fold_bn(self.bn)
             w = self.conv.weight.detach()
             if self.transposed:          # (Cin,Cout,3,3,3) -> [Cin][27][Cout]
                 w = w.permute(0, 2, 3, 4, 1).reshape(w.shape[0], 27, w.shape[1])
             else:                        # (Cout,Cin,3,3,3) -> [Cin][27][Cout]
                 w = w.permute(1, 2, 3, 4, 0).reshape(w.shape[1], 27, w.shape[0])
-            self._folded = ((w * scale.view(1, 1, -1)).contiguous().float(), shift.detach().contiguous().float())
-            self._key = key
-        return self._folded
+            return (w * scale.view(1, 1, -1)).contiguous().float(), shift
+        return self._fold([self.conv.weight] + bn_tensors(self.bn), make)
 
     def forward(self, x, skip=None, split_out=False):
         if self.training:
@@ -187,7 +132,7 @@ class CostRegNet(nn.Module):
         for name, cin in zip(self.DECONV_NAMES, (8 * b, 4 * b, 2 * b)):
             setattr(self, name, Deconv3d(cin, cin // 2))
         self.prob = nn.Conv3d(b, 1, 3, stride=1, padding=1, bias=False)
-        self._prob_w, self._prob_key = None, None
+        self._prob_fold = CachedFold()
 
     def forward(self, x):
         """x (1,C,D,H,W), or the same volume as a costvol.SplitVolume (conv0 fused with its producer) -> (1,1,D,H,W)"""
@@ -209,12 +154,9 @@ class CostRegNet(nn.Module):
         y = up7(y, skip=c4)
         y = up9(y, skip=c2)
         y = up11(y, skip=c0)
-        key = (self.prob.weight.data_ptr(), self.prob.weight._version)
-        if self._prob_key != key:
-            w = self.prob.weight.detach()
-            self._prob_w = w.permute(1, 2, 3, 4, 0).reshape(w.shape[1], 27, 1).contiguous().float()
-            self._prob_key = key
-        return costvol.conv3d(y, self._prob_w, None, stride=1, relu=False)[None]
+        w = self.prob.weight
+        prob_w = self._prob_fold([w], lambda: w.detach().permute(1, 2, 3, 4, 0).reshape(w.shape[1], 27, 1).contiguous().float())
+        return costvol.conv3d(y, prob_w, None, stride=1, relu=False)[None]
 
 
 def homo_warping(src_fea, src_proj, ref_proj, depth_values):
@@ -268,27 +210,10 @@ class CascadeMVSNet(nn.Module):
     @torch.no_grad()
     def forward(self, stage_idx, sample_cuda, features, extra, outputs, int_r, depth=None, prevent_oom=False,
                 inverse_depth=False):
-        imgs, proj_matrices, depth_values = sample_cuda["imgs"], sample_cuda["proj_matrices"], sample_cuda["depth_values"]
-        if depth is None:
-            depth = outputs['depth'] if stage_idx > 0 else None
-        outputs = {} if outputs is None else outputs
-        dv = costvol.host_copy(depth_values)[0]
-        depth_min, depth_max = float(dv[0]), float(dv[-1])
-        depth_interval = (depth_max - depth_min) / depth_values.size(1)
-        H_img, W_img = imgs.shape[-2], imgs.shape[-1]
-        key = "stage{}".format(stage_idx + 1)
-        features_stage = [feat[key] for feat in features]
-        scale = int(self.stage_infos[key]["scale"])
-        nd = self.ndepths[stage_idx]
-        dev = features_stage[0].device
-        if depth is not None:
-            if inverse_depth:
-                pass    # stages 2,3 of the inverse variant use the same window (models/CasMVSNet.py:548-554)
-            hyp = costvol.depth_hypotheses(depth[0], (H_img, W_img), nd, scale, depth_min, depth_max,
-                                           int_r * depth_interval, False, dev)
-        else:
-            hyp = costvol.depth_hypotheses(None, (H_img, W_img), nd, scale, float(dv[0]), float(dv[-1]), 0.0,
-                                           inverse_depth, dev)
+        proj_matrices = sample_cuda["proj_matrices"]
+        key, features_stage, depth, outputs = stage_inputs(stage_idx, features, outputs, depth)
+        scale, nd = int(self.stage_infos[key]["scale"]), self.ndepths[stage_idx]
+        hyp = range_hypotheses(sample_cuda, depth, nd, scale, int_r, inverse_depth, features_stage[0].device)
         cr = self.cost_regularization if self.share_cr else self.cost_regularization[stage_idx]
         outputs_stage = self.DepthNet(features_stage, proj_matrices[key], depth_values=hyp[None], num_depth=nd,
                                       cost_regularization=cr, prevent_oom=prevent_oom)

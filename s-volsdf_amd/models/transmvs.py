@@ -13,15 +13,12 @@ import torch
 import torch.nn as nn
 
 from svs_hip import costvol
-from models.CasMVSNet import Conv2d, CostRegNet
+from models.blocks import (CachedFold, Conv2d, bn_tensors, encoder_trunk, fold_bn, range_hypotheses, stack_stages,
+                           stage_inputs)
+from models.CasMVSNet import CostRegNet
 
 Align_Corners_Range = False
-
-
-def _fold_bn(bn):
-    """eval-mode BatchNorm as (scale, shift)"""
-    scale = (bn.weight / torch.sqrt(bn.running_var + bn.eps)).detach().float()
-    return scale.contiguous(), (bn.bias - bn.running_mean * scale).detach().float().contiguous()
+_fold_bn = fold_bn
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -44,11 +41,12 @@ class DCN(nn.Module):
         nn.init.uniform_(self.weight, -bound, bound)
         nn.init.zeros_(self.conv_offset_mask.weight)
         nn.init.zeros_(self.conv_offset_mask.bias)
+        self._bn_fold = CachedFold()
 
     def forward(self, x, bn=None, relu=False):
         """x (32,H,W) on the device -> (Cout,H,W)"""
         om = costvol.conv2d(x, self.conv_offset_mask.weight.detach(), self.conv_offset_mask.bias.detach())
-        scale, shift = _fold_bn(bn) if bn is not None else (None, None)
+        scale, shift = self._bn_fold(bn_tensors(bn), lambda: fold_bn(bn)) if bn is not None else (None, None)
         return costvol.deform_conv2d(x, om, self.weight.detach(), self.bias.detach(), scale, shift, relu=relu)
 
 
@@ -65,11 +63,7 @@ class FeatureNet(nn.Module):
             raise NotImplementedError("base_channels 8 (the DCN kernel takes 32 input channels)")
         b = base_channels
         self.base_channels = b
-        self.conv0 = nn.Sequential(Conv2d(3, b, 3, 1, padding=1), Conv2d(b, b, 3, 1, padding=1))
-        self.conv1 = nn.Sequential(Conv2d(b, 2 * b, 5, stride=2, padding=2), Conv2d(2 * b, 2 * b, 3, 1, padding=1),
-                                   Conv2d(2 * b, 2 * b, 3, 1, padding=1))
-        self.conv2 = nn.Sequential(Conv2d(2 * b, 4 * b, 5, stride=2, padding=2), Conv2d(4 * b, 4 * b, 3, 1, padding=1),
-                                   Conv2d(4 * b, 4 * b, 3, 1, padding=1))
+        self.conv0, self.conv1, self.conv2 = encoder_trunk(b)
         self.out1 = _out_branch(1, 4 * b)
         self.inner1 = nn.Conv2d(2 * b, 4 * b, 1, bias=True)
         self.inner2 = nn.Conv2d(b, 4 * b, 1, bias=True)
@@ -103,7 +97,7 @@ class FeatureNet(nn.Module):
             f = costvol.conv2d(c0[0], self.inner2.weight.detach(), self.inner2.bias.detach(), add=f, add_upsample2=True)
             s3 = self._branch(self.out3, f)
             per_image.append((s1, s2, s3))
-        return {f"stage{j + 1}": torch.stack([o[j] for o in per_image]) for j in range(3)}
+        return stack_stages(per_image)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -223,23 +217,19 @@ class PixelwiseNet(nn.Module):
         self.conv0 = ConvBnReLU3D(1, 16)
         self.conv1 = ConvBnReLU3D(16, 8)
         self.conv2 = nn.Conv3d(8, 1, 1, stride=1, padding=0)
-        self._folded, self._key = None, None
+        self._fold = CachedFold()
 
     def folded(self):
         """the 177 floats svs_warp_similarity reads: scale0[16] shift0[16] W1[8][16] shift1[8] w2[8] b2, BatchNorm folded"""
-        ts = [self.conv0.conv.weight, self.conv1.conv.weight, self.conv2.weight, self.conv2.bias]
-        for bn in (self.conv0.bn, self.conv1.bn):
-            ts += [bn.weight, bn.bias, bn.running_mean, bn.running_var]
-        key = tuple((t.data_ptr(), t._version) for t in ts)
-        if self._key != key:
-            s0, t0 = _fold_bn(self.conv0.bn)
-            s1, t1 = _fold_bn(self.conv1.bn)
+        def make():
+            s0, t0 = fold_bn(self.conv0.bn)
+            s1, t1 = fold_bn(self.conv1.bn)
             w0 = self.conv0.conv.weight.detach().float().reshape(16) * s0
             w1 = self.conv1.conv.weight.detach().float().reshape(8, 16) * s1[:, None]
-            self._folded = torch.cat([w0, t0, w1.reshape(-1), t1, self.conv2.weight.detach().float().reshape(8),
-                                      self.conv2.bias.detach().float().reshape(1)]).contiguous()
-            self._key = key
-        return self._folded
+            return torch.cat([w0, t0, w1.reshape(-1), t1, self.conv2.weight.detach().float().reshape(8),
+                              self.conv2.bias.detach().float().reshape(1)]).contiguous()
+        ts = [self.conv0.conv.weight, self.conv1.conv.weight, self.conv2.weight, self.conv2.bias]
+        return self._fold(ts + bn_tensors(self.conv0.bn) + bn_tensors(self.conv1.bn), make)
 
 
 class DepthNet(nn.Module):
@@ -292,27 +282,12 @@ class TransMVSNet(nn.Module):
         if self.training:
             raise NotImplementedError("TransMVSNet is inference-only in S-VolSDF (runner.py:153); call .eval()")
         view_weights = extra
-        imgs, proj_matrices, depth_values = sample_cuda["imgs"], sample_cuda["proj_matrices"], sample_cuda["depth_values"]
+        imgs, proj_matrices = sample_cuda["imgs"], sample_cuda["proj_matrices"]
         if imgs.shape[0] != 1:
             raise NotImplementedError("batch size 1 (runner.py:122)")
-        if depth is None:
-            depth = outputs['depth'] if stage_idx > 0 else None
-        outputs = {} if outputs is None else outputs
-        dv = costvol.host_copy(depth_values)[0]
-        depth_min, depth_max = float(dv[0]), float(dv[-1])
-        depth_interval = (depth_max - depth_min) / depth_values.size(1)
-        H_img, W_img = imgs.shape[-2], imgs.shape[-1]
-        key = "stage{}".format(stage_idx + 1)
-        features_stage = [feat[key] for feat in features]
-        scale = int(self.stage_infos[key]["scale"])
-        nd = self.ndepths[stage_idx]
-        dev = features_stage[0].device
-        # :185-223 is CasMVSNet's text (get_depth_range_samples, then the trilinear resize to the stage): the same kernel
-        if depth is not None:
-            hyp = costvol.depth_hypotheses(depth[0], (H_img, W_img), nd, scale, depth_min, depth_max, int_r * depth_interval,
-                                           False, dev)
-        else:
-            hyp = costvol.depth_hypotheses(None, (H_img, W_img), nd, scale, depth_min, depth_max, 0.0, inverse_depth, dev)
+        key, features_stage, depth, outputs = stage_inputs(stage_idx, features, outputs, depth)
+        scale, nd = int(self.stage_infos[key]["scale"]), self.ndepths[stage_idx]
+        hyp = range_hypotheses(sample_cuda, depth, nd, scale, int_r, inverse_depth, features_stage[0].device)
         if (view_weights is None) != (stage_idx == 0):
             raise ValueError("view weights are produced at stage 1 and passed on to stages 2 and 3")
         outputs_stage, view_weights = self.DepthNet(features_stage, proj_matrices[key], depth_values=hyp[None], num_depth=nd,

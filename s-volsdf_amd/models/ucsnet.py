@@ -16,7 +16,8 @@ import torch.nn as nn
 
 from svs_hip import costvol
 from svs_hip.refpath import reference_module
-from models.CasMVSNet import Conv2d, Conv3d, CostRegNet as _CasCostRegNet
+from models.blocks import CachedFold, Conv2d, bn_tensors, encoder_trunk, fold_bn, stack_stages, stage_inputs
+from models.CasMVSNet import Conv3d, CostRegNet as _CasCostRegNet
 
 eps = 1e-12
 
@@ -29,18 +30,14 @@ class Deconv2dUnit(nn.Module):
         super().__init__()
         self.conv = nn.ConvTranspose2d(cin, cout, 3, stride=2, padding=1, output_padding=1, bias=False)
         self.bn = nn.BatchNorm2d(cout)
-        self._folded, self._key = None, None
+        self._fold = CachedFold()
 
     def folded(self):
         """(weight (Cin,Cout,3,3), bias) with the BatchNorm (eval) folded in"""
-        ts = [self.conv.weight, self.bn.weight, self.bn.bias, self.bn.running_mean, self.bn.running_var]
-        key = tuple((t.data_ptr(), t._version) for t in ts)
-        if self._key != key:
-            scale = (self.bn.weight / torch.sqrt(self.bn.running_var + self.bn.eps)).detach().float()
-            shift = (self.bn.bias - self.bn.running_mean * scale).detach().float()
-            w = self.conv.weight.detach().float() * scale.view(1, -1, 1, 1)
-            self._folded, self._key = (w.contiguous(), shift.contiguous()), key
-        return self._folded
+        def make():
+            scale, shift = fold_bn(self.bn)
+            return (self.conv.weight.detach().float() * scale.view(1, -1, 1, 1)).contiguous(), shift
+        return self._fold([self.conv.weight] + bn_tensors(self.bn), make)
 
 
 class Deconv2dBlock(nn.Module):
@@ -61,11 +58,7 @@ class FeatExtNet(nn.Module):
             raise NotImplementedError("only the 3-stage feature extractor is declared")
         b = base_channels
         self.base_channels, self.num_stage = b, num_stage
-        self.conv0 = nn.Sequential(Conv2d(3, b, 3, 1, padding=1), Conv2d(b, b, 3, 1, padding=1))
-        self.conv1 = nn.Sequential(Conv2d(b, 2 * b, 5, stride=2, padding=2), Conv2d(2 * b, 2 * b, 3, 1, padding=1),
-                                   Conv2d(2 * b, 2 * b, 3, 1, padding=1))
-        self.conv2 = nn.Sequential(Conv2d(2 * b, 4 * b, 5, stride=2, padding=2), Conv2d(4 * b, 4 * b, 3, 1, padding=1),
-                                   Conv2d(4 * b, 4 * b, 3, 1, padding=1))
+        self.conv0, self.conv1, self.conv2 = encoder_trunk(b)
         self.out1 = nn.Conv2d(4 * b, 4 * b, 1, bias=False)
         self.deconv1 = Deconv2dBlock(4 * b, 2 * b)
         self.deconv2 = Deconv2dBlock(2 * b, b)
@@ -89,9 +82,7 @@ class FeatExtNet(nn.Module):
         if self._unet is None:
             self._unet = costvol.FeatureNetUnet(self.base_channels)
         layers = self.layers()
-        per_image = [self._unet(xi, layers) for xi in x]
-        return {f"stage{j + 1}": torch.stack([o[j] for o in per_image]) if len(per_image) > 1 else per_image[0][j][None]
-                for j in range(3)}
+        return stack_stages([self._unet(xi, layers) for xi in x])
 
 
 class CostRegNet(_CasCostRegNet):
@@ -134,14 +125,9 @@ class UCSNet(nn.Module):
             raise NotImplementedError("UCSNet is inference-only in S-VolSDF (runner.py:153); call .eval()")
         exp_var = extra
         imgs, proj_matrices, depth_values = sample_cuda["imgs"], sample_cuda["proj_matrices"], sample_cuda["depth_values"]
-        if depth is None:
-            depth = outputs['depth'] if stage_idx > 0 else None
-        outputs = {} if outputs is None else outputs
-        key = "stage{}".format(stage_idx + 1)
-        features_stage = [feat[key] for feat in features]
-        scale = int(self.ds_ratio[key])
+        key, features_stage, depth, outputs = stage_inputs(stage_idx, features, outputs, depth)
+        scale, nd = int(self.ds_ratio[key]), self.stage_configs[stage_idx]
         cur_h, cur_w = imgs.shape[-2] // scale, imgs.shape[-1] // scale
-        nd = self.stage_configs[stage_idx]
         dev = features_stage[0].device
         if depth is not None:
             # the previous depth (possibly the rendered one, runner.py:240-243) and uncertainty, resized inside the kernel

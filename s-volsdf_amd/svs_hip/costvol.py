@@ -1,5 +1,6 @@
 """torch-tensor wrappers for the CasMVSNet cost-volume kernels (csrc/svs_costvol.hip)."""
 import ctypes
+import functools
 import os
 import weakref
 
@@ -22,88 +23,90 @@ def relative_projection(src_proj, ref_proj):
     return list(rel[:3, :3].reshape(-1)) + list(rel[:3, 3])
 
 
-_HOST_CACHE = {}
+def _tensor_key(t):
+    return (t.data_ptr(), t._version, t.shape, t.stride(), t.device, t.dtype)
+
+
+class _TensorCache:
+    """Values derived from a tensor, keyed on its storage address and torch version counter (plus shape, strides, device, dtype
+    and an optional tag).  An entry keeps its tensor alive: the storage cannot be handed to another tensor while the key
+    exists.  Bounded by entries and / or bytes, or unbounded; a full cache is emptied (the working set of a scan fits: the
+    bound is a guard against a leak, not an eviction policy)."""
+
+    def __init__(self, entries=None, nbytes=None):
+        self.entries, self.nbytes = entries, nbytes
+        self.clear()
+
+    def clear(self):
+        self._d, self._used = {}, 0
+
+    def get(self, t, make, tag=None, nbytes=0):
+        """the cached make() of tensor t"""
+        key = (tag, _tensor_key(t))
+        hit = self._d.get(key)
+        if hit is None:
+            value = make()
+            if (self.entries is not None and len(self._d) >= self.entries) or (self.nbytes is not None and self._used + nbytes > self.nbytes):
+                self.clear()
+            hit = self._d[key] = (t, value)
+            self._used += nbytes
+        return hit[1]
+
+
+_HOST_CACHE = _TensorCache(entries=64)
+_RT_CACHE = _TensorCache(entries=64)
+# bounded by bytes (a 32 x 1200 x 1600 float32 map and its copy are 490 MB), not by entries; `clear_caches()` drops everything
+# at the end of a scan / stage loop.  The key is (storage address, torch version counter, shape): a producer that rewrites a
+# cached feature map through this library's raw-pointer kernels does not bump the counter -- such buffers must not be recycled
+# while cached (the FeatureNet wrappers hand out fresh tensors).
+_HWC_CACHE = _TensorCache(nbytes=int(os.environ.get("SVS_HWC_CACHE_BYTES", str(1 << 30))))
+_WFRAG_CACHE = _TensorCache()               # the 3-D U-Net's weight fragments: a few MB per model, never dropped
+_W2D_CACHE = _TensorCache(entries=65)
+_W2D_MFMA_CACHE = _TensorCache(entries=65)
+_DECONV_FRAG_CACHE = _TensorCache(entries=65)
+_EXTRACTORS = weakref.WeakSet()             # live feature-extractor wrappers: clear_caches() drops their tables and workspaces
 
 
 def host_copy(t):
     """numpy copy of a small device tensor whose VALUES are launch arguments (projection matrices, the depth range):
     one device-to-host copy per distinct tensor, cached on storage + version -- the sample of a scan is the same
     tensor in every stage and every stage-loop iteration, so the stage loop runs without host synchronisation."""
-    key = (t.data_ptr(), t._version, tuple(t.shape), tuple(t.stride()), str(t.device), t.dtype)
-    hit = _HOST_CACHE.get(key)
-    if hit is None:
-        if len(_HOST_CACHE) >= 64:
-            _HOST_CACHE.clear()
-        # the entry keeps the tensor alive: its storage cannot be handed to another tensor while the key exists
-        hit = _HOST_CACHE[key] = (t, t.detach().cpu().numpy())
-    return hit[1]
-
-
-_RT_CACHE = {}
-_HWC_CACHE = {}
-
-
-def _tensor_key(t):
-    return (t.data_ptr(), t._version, tuple(t.shape), tuple(t.stride()), str(t.device), t.dtype)
+    return _HOST_CACHE.get(t, lambda: t.detach().cpu().numpy())
 
 
 def _rot_trans(proj_matrices):
     """(1,V,2,4,4) projection matrices -> ctypes float[12*(V-1)] for svs_warp_variance (host launch arguments).
     Cached per tensor like host_copy: a stage's matrices are the same tensor in every iteration of the stage loop."""
-    key = _tensor_key(proj_matrices)
-    hit = _RT_CACHE.get(key)
-    if hit is not None:
-        return hit[1]
-    P = host_copy(proj_matrices)[0]
-    n_src = P.shape[0] - 1
-    rt = (ctypes.c_float * (12 * n_src))()
-    for v in range(n_src):
-        for k, x in enumerate(relative_projection(P[v + 1], P[0])):
-            rt[12 * v + k] = float(x)
-    if len(_RT_CACHE) >= 64:
-        _RT_CACHE.clear()
-    _RT_CACHE[key] = (proj_matrices, rt)
-    return rt
+    def make():
+        P = host_copy(proj_matrices)[0]
+        n_src = P.shape[0] - 1
+        rt = (ctypes.c_float * (12 * n_src))()
+        for v in range(n_src):
+            for k, x in enumerate(relative_projection(P[v + 1], P[0])):
+                rt[12 * v + k] = float(x)
+        return rt
+    return _RT_CACHE.get(proj_matrices, make)
 
 
 def _hwc(f):
     """(C,H,W) source feature map -> its channel-last copy (H,W,C), cached per tensor (storage + version): a view's
     features are built once per scan and warped in every cost-volume build of the stage loop."""
-    key = _tensor_key(f)
-    hit = _HWC_CACHE.get(key)
-    if hit is not None:
-        return hit[1]
-    L = _lib.load()
-    C, H, W = f.shape
-    o = torch.empty(H, W, C, device=f.device)
-    _lib.check(L.svs_chw_to_hwc(_ptr(_f32(f)), _ptr(o), C, H, W, _stream()), "svs_chw_to_hwc")
-    # bounded by bytes (a 32 x 1200 x 1600 float32 map and its copy are 490 MB), not by entries; `clear_caches()` drops
-    # everything at the end of a scan / stage loop.  The key is (storage address, torch version counter, shape): a producer
-    # that rewrites a cached feature map through this library's raw-pointer kernels does not bump the counter -- such
-    # buffers must not be recycled while cached (the FeatureNet wrapper hands out fresh tensors).
-    global _HWC_BYTES
-    nbytes = 2 * f.numel() * 4
-    if _HWC_BYTES + nbytes > _HWC_BUDGET:
-        _HWC_CACHE.clear()
-        _HWC_BYTES = 0
-    _HWC_CACHE[key] = (f, o)          # keeps `f` alive: the key holds its address
-    _HWC_BYTES += nbytes
-    return o
-
-
-_HWC_BYTES = 0
-_HWC_BUDGET = int(os.environ.get("SVS_HWC_CACHE_BYTES", str(1 << 30)))
+    def make():
+        C, H, W = f.shape
+        o = torch.empty(H, W, C, device=f.device)
+        _lib.check(_lib.load().svs_chw_to_hwc(_ptr(_f32(f)), _ptr(o), C, H, W, _stream()), "svs_chw_to_hwc")
+        return o
+    return _HWC_CACHE.get(f, make, nbytes=2 * f.numel() * 4)
 
 
 def clear_caches():
-    """Drop the cached channel-last feature maps and projection constants, and the prior look-up's per-view constants (end of
-    a scan / stage loop; StageLoop calls it per scan, VolOpt.get_mvs_input per stage)."""
-    global _HWC_BYTES
+    """Drop the cached channel-last feature maps and projection constants, the feature extractors' tables and workspaces, and
+    the prior look-up's per-view constants (end of a scan / stage loop; StageLoop calls it per scan, VolOpt.get_mvs_input per
+    stage)."""
     _HWC_CACHE.clear()
     _RT_CACHE.clear()
-    _HWC_BYTES = 0
     _DECONV_FRAG_CACHE.clear()
-    for net in list(_UNETS):
+    for net in list(_EXTRACTORS):
         net.forget()
     from . import ops
     ops.clear_lookup_caches()
@@ -167,26 +170,33 @@ def pair_supported(C, Cout):
     return C in (8, 16, 32) and Cout <= 8
 
 
+def split_fits(C, D, H, W):
+    """Can svs_warp_variance_split produce this volume?  Its producer addresses the split volume and the feature maps with
+    32-bit byte offsets: the bounds are those of launch_warp_reuse2 (csrc/svs_costvol.hip, THE BOUNDS OF THE SPLIT FORM)."""
+    return _lib.load().svs_split_volume_dims(C, D, H, W, None) < (1 << 32) and H * W * C * 4 < (1 << 31)
+
+
+def _warp_inputs(features, proj_matrices, depth_values):
+    """What both cost-volume builders hand to the library: the reference feature (C,H,W), the channel-last source features,
+    the relative projections and the hypotheses (D,H,W)."""
+    ref = _f32(features[0][0])
+    return ref, [_hwc(f[0]) for f in features[1:]], _rot_trans(proj_matrices), _f32(depth_values[0])
+
+
 def warp_variance(features, proj_matrices, depth_values, split=False):
     """DepthNet.forward step 2 (models/CasMVSNet.py:611-642).  features: list of (1,C,H,W) (reference first),
     proj_matrices: (1,V,2,4,4), depth_values (1,D,H,W) -> variance (1,C,D,H,W), or with split=True the same values
-    as a SplitVolume (the producer side of the fused conv0, svs_conv3d_pair)."""
+    as a SplitVolume (the producer side of the fused conv0, svs_conv3d_pair) where `split_fits`."""
     L = _lib.load()
-    ref = _f32(features[0][0])
-    C, H, W = ref.shape
-    D = depth_values.shape[1]
-    dev = ref.device
-    n_src = len(features) - 1
-    hwc = [_hwc(f[0]) for f in features[1:]]
-    rt = _rot_trans(proj_matrices)
-    dv = _f32(depth_values[0])
-    if split:
-        sv = SplitVolume(C, D, H, W, dev)
-        _lib.check(L.svs_warp_variance_split(_ptr(ref), _ptr_array(hwc), rt, n_src, C, D, H, W, _ptr(dv), _ptr(sv.buf),
+    ref, hwc, rt, dv = _warp_inputs(features, proj_matrices, depth_values)
+    (C, H, W), D = ref.shape, dv.shape[0]
+    if split and split_fits(C, D, H, W):
+        sv = SplitVolume(C, D, H, W, ref.device)
+        _lib.check(L.svs_warp_variance_split(_ptr(ref), _ptr_array(hwc), rt, len(hwc), C, D, H, W, _ptr(dv), _ptr(sv.buf),
                                              _stream()), "svs_warp_variance_split")
         return sv
-    var = torch.empty(1, C, D, H, W, device=dev)
-    _lib.check(L.svs_warp_variance(_ptr(ref), _ptr_array(hwc), rt, n_src, C, D, H, W, _ptr(dv), _ptr(var), 0, _stream()),
+    var = torch.empty(1, C, D, H, W, device=ref.device)
+    _lib.check(L.svs_warp_variance(_ptr(ref), _ptr_array(hwc), rt, len(hwc), C, D, H, W, _ptr(dv), _ptr(var), 0, _stream()),
                "svs_warp_variance")
     return var
 
@@ -208,16 +218,27 @@ def homo_warp(src_fea, src_rel, depth_values):
     return out
 
 
-_WFRAG_CACHE = {}
+def _cached_fragments(tag):
+    """a fragment builder f(weight), cached per weight tensor in _WFRAG_CACHE"""
+    def wrap(build):
+        @functools.wraps(build)
+        def cached(weight):
+            return _WFRAG_CACHE.get(weight, lambda: build(weight), tag=tag)
+        return cached
+    return wrap
 
 
+def _hi_mid(w, ok):
+    """float32 fragment values (zero where not ok) -> (KS, 2, 64, 8) fp16: the hi piece and what it leaves, stacked per k-step"""
+    w = torch.where(ok, w, torch.zeros_like(w)).float()
+    hi = w.half()
+    return torch.stack([hi, (w - hi.float()).half()], 1).contiguous()
+
+
+@_cached_fragments("mfma")
 def mfma_weight_fragments(weight):
     """[Cin][27][Cout] folded float32 weights -> the fp16 hi / mid A fragments of svs_conv3d_mfma
     ([k-step][piece][lane][8] fp16, see include/svolsdf_hip.h).  One-time repacking per layer (cached)."""
-    key = (weight.data_ptr(), weight._version, tuple(weight.shape))
-    hit = _WFRAG_CACHE.get(key)
-    if hit is not None:
-        return hit[0]
     Cin, _, Cout = weight.shape
     dev = weight.device
     KS = (27 * Cin + 31) // 32
@@ -228,22 +249,14 @@ def mfma_weight_fragments(weight):
     tap, ci, co = kk // Cin, kk % Cin, (lane & 15).expand(KS, 64, 8)
     ok = (tap < 27) & (co < Cout)
     w = weight[ci.clamp(max=Cin - 1), tap.clamp(max=26), co.clamp(max=Cout - 1)]
-    w = torch.where(ok, w, torch.zeros_like(w)).float()
-    hi = w.half()
-    mid = (w - hi.float()).half()
-    frag = torch.stack([hi, mid], 1).contiguous()          # (KS, 2, 64, 8) fp16
-    _WFRAG_CACHE[key] = (frag, weight)                     # keep `weight` alive: the key holds its address
-    return frag
+    return _hi_mid(w, ok)
 
 
+@_cached_fragments("pair")
 def pair_weight_fragments(weight):
     """[Cin][27][Cout <= 8] folded float32 weights -> the fp16 hi / mid A fragments of svs_conv3d_pair
     ([k-step][piece][lane][8] fp16, include/svolsdf_hip.h): row m = (channel m & 7, x parity m >> 3),
     k = (((kd*3+kh)*4 + t)*G + g)*8 + c8 carries the weight of tap (kd, kh, kw = t - parity)."""
-    key = ("pair", weight.data_ptr(), weight._version, tuple(weight.shape))
-    hit = _WFRAG_CACHE.get(key)
-    if hit is not None:
-        return hit[0]
     Cin, _, Cout = weight.shape
     dev = weight.device
     G = Cin // 8
@@ -257,33 +270,19 @@ def pair_weight_fragments(weight):
     co, kw = m & 7, t - (m >> 3)
     ok = (kw >= 0) & (kw <= 2) & (co < Cout)
     w = weight[8 * g + c8, (row9 * 3 + kw.clamp(0, 2)), co.clamp(max=Cout - 1)]
-    w = torch.where(ok, w, torch.zeros_like(w)).float()
-    hi = w.half()
-    mid = (w - hi.float()).half()
-    frag = torch.stack([hi, mid], 1).contiguous()          # (KS, 2, 64, 8) fp16
-    _WFRAG_CACHE[key] = (frag, weight)
-    return frag
-
-
-_W2D_CACHE = {}
+    return _hi_mid(w, ok)
 
 
 def conv2d_pack(weight):
     """(Cout,Cin,k,k) -> [ceil(Cout/8)][Cin][k][k][8] float32, the layout svs_conv2d reads through the scalar cache
     (include/svolsdf_hip.h).  Cached per weight tensor (address + version)."""
-    key = (weight.data_ptr(), weight._version, tuple(weight.shape), weight.device)
-    hit = _W2D_CACHE.get(key)
-    if hit is not None:
-        return hit[0]
-    if len(_W2D_CACHE) > 64:
-        _W2D_CACHE.clear()
-    Cout, Cin, k, _ = weight.shape
-    G = (Cout + 7) // 8
-    w = torch.zeros(G * 8, Cin, k, k, device=weight.device, dtype=torch.float32)
-    w[:Cout] = weight.detach().float()
-    packed = w.view(G, 8, Cin, k, k).permute(0, 2, 3, 4, 1).contiguous()
-    _W2D_CACHE[key] = (packed, weight)                     # keep `weight` alive: the key holds its address
-    return packed
+    def make():
+        Cout, Cin, k, _ = weight.shape
+        G = (Cout + 7) // 8
+        w = torch.zeros(G * 8, Cin, k, k, device=weight.device, dtype=torch.float32)
+        w[:Cout] = weight.detach().float()
+        return w.view(G, 8, Cin, k, k).permute(0, 2, 3, 4, 1).contiguous()
+    return _W2D_CACHE.get(weight, make)
 
 
 def conv2d(x, weight, bias=None, add=None, add_upsample2=False, stride=1, relu=False, out=None):
@@ -310,9 +309,6 @@ def conv2d(x, weight, bias=None, add=None, add_upsample2=False, stride=1, relu=F
     return out
 
 
-_W2D_MFMA_CACHE = {}
-
-
 def conv2d_mfma_supported(Cin, Cout, k, stride):
     return bool(_lib.load().svs_conv2d_mfma_supported(int(Cin), int(Cout), int(k), int(stride)))
 
@@ -320,19 +316,14 @@ def conv2d_mfma_supported(Cin, Cout, k, stride):
 def conv2d_mfma_frag(weight):
     """(Cout,Cin,k,k) float32 -> the fp16 hi / mid MFMA A fragments svs_conv2d_mfma reads (packed on the device by
     svs_conv2d_mfma_pack; cached per weight tensor: address + version)."""
-    key = (weight.data_ptr(), weight._version, tuple(weight.shape), weight.device)
-    hit = _W2D_MFMA_CACHE.get(key)
-    if hit is not None:
-        return hit[0]
-    if len(_W2D_MFMA_CACHE) > 64:
-        _W2D_MFMA_CACHE.clear()
-    L = _lib.load()
-    Cout, Cin, k, _ = weight.shape
-    w = _f32(weight.detach())
-    frag = torch.empty(L.svs_conv2d_mfma_wfrag_bytes(Cin, Cout, k) // 2, dtype=torch.float16, device=weight.device)
-    _lib.check(L.svs_conv2d_mfma_pack(_ptr(w), Cin, Cout, k, _ptr(frag), _stream()), "svs_conv2d_mfma_pack")
-    _W2D_MFMA_CACHE[key] = (frag, weight, w)               # keep `weight` alive: the key holds its address
-    return frag
+    def make():
+        L = _lib.load()
+        Cout, Cin, k, _ = weight.shape
+        w = _f32(weight.detach())
+        frag = torch.empty(L.svs_conv2d_mfma_wfrag_bytes(Cin, Cout, k) // 2, dtype=torch.float16, device=weight.device)
+        _lib.check(L.svs_conv2d_mfma_pack(_ptr(w), Cin, Cout, k, _ptr(frag), _stream()), "svs_conv2d_mfma_pack")
+        return frag, w
+    return _W2D_MFMA_CACHE.get(weight, make)[0]
 
 
 def conv2d_mfma(x, weight, bias=None, stride=1, relu=False):
@@ -367,34 +358,45 @@ def conv2d_mfma_lateral(lat_in, lat_weight, lat_bias, lat_add, weight, bias=None
     return out
 
 
-_FPN_MFMA = os.environ.get("SVS_FPN_MFMA", "1") != "0"     # A/B: 0 = every layer of the pyramid on the float32 vector kernels
-# (layer index -> stride) of svs_featurenet_fpn's 13 convolutions
-_FPN_STRIDES = (1, 1, 2, 1, 1, 2, 1, 1, 1, 1, 1, 1, 1)
-_FPN_ADDEND = (9, 11)                                      # the lateral 1x1 convolutions take an addend: float32 kernels
-
-
-class FeatureNetFpn:
-    """The 13 convolutions of the 'fpn' FeatureNet enqueued by ONE library call (svs_featurenet_fpn): the per-launch host
-    cost of going through Python 13 times was as large as the kernels' run time."""
-    LAYERS = 13
+class _FeatureExtractor:
+    """A 2-D feature extractor enqueued by ONE library call: the per-launch host cost of going through Python once per layer
+    was as large as the kernels' run time.  Owns the workspace and the pointer tables (cached until a tensor changes;
+    clear_caches() drops both through forget()).  A subclass states its layers and which of them run on the matrix cores."""
+    LAYERS = 0              # number of layers
+    ENTRY = WORKSPACE = ""  # the library's entry point and its workspace-size function
+    STRIDES = ()            # layer index -> stride
+    TRANSPOSED = ()         # transposed layers: weight (Cin,Cout,3,3), handed over as it is
+    ADDEND = ()             # layers that take an addend: float32 kernels
 
     def __init__(self, base_channels):
         self.b = int(base_channels)
+        self.forget()
+        _EXTRACTORS.add(self)
+
+    def forget(self):
         self._ws, self._ws_key = None, None
         self._tables, self._tables_key = None, None
 
+    def fragment(self, i, w):
+        """the MFMA fragments of layer i, or None: the layer runs on the float32 kernels"""
+        raise NotImplementedError
+
+    def _conv_fragment(self, i, w):
+        # the 3x3 / 5x5 layers with 8 / 16 / 32 input channels run on the matrix cores (svs_conv2d_mfma)
+        # (not conv0.1, 8 -> 8 at full resolution: 15.5 us there against 13.4 on the vector kernel -- a quarter-full M tile)
+        if (i not in self.ADDEND and w.shape[2] > 1 and not (w.shape[1] <= 8 and w.shape[2] == 3)
+                and conv2d_mfma_supported(w.shape[1], w.shape[0], w.shape[2], self.STRIDES[i])):
+            return conv2d_mfma_frag(w)
+        return None
+
     def tables(self, layers):
-        """layers: 13 (weight (Cout,Cin,k,k), bias or None) pairs in the library's order -> pointer tables (cached until
-        a tensor changes)."""
+        """layers: LAYERS (weight, bias or None) pairs in the library's order, convolutions (Cout,Cin,k,k), transposed layers
+        (Cin,Cout,3,3) -> pointer tables (cached until a tensor changes)."""
         key = tuple((w.data_ptr(), w._version, None if b is None else (b.data_ptr(), b._version)) for w, b in layers)
         if key != self._tables_key:
-            packed = [conv2d_pack(w) for w, _ in layers]
+            packed = [_f32(w.detach()) if i in self.TRANSPOSED else conv2d_pack(w) for i, (w, _) in enumerate(layers)]
             biases = [None if b is None else _f32(b) for _, b in layers]
-            # the 3x3 / 5x5 layers with 8 / 16 / 32 input channels run on the matrix cores (svs_conv2d_mfma)
-            # (not conv0.1, 8 -> 8 at full resolution: 15.5 us there against 13.4 on the vector kernel -- a quarter-full M tile)
-            frags = [conv2d_mfma_frag(w) if (_FPN_MFMA and i not in _FPN_ADDEND and w.shape[2] > 1 and not (w.shape[1] <= 8 and w.shape[2] == 3)
-                                             and conv2d_mfma_supported(w.shape[1], w.shape[0], w.shape[2], _FPN_STRIDES[i])) else None
-                     for i, (w, _) in enumerate(layers)]
+            frags = [self.fragment(i, w) for i, (w, _) in enumerate(layers)]
             self._tables = (_ptr_array(packed), _ptr_array(biases), packed, biases, layers, _ptr_array(frags), frags)
             self._tables_key = key
         return self._tables
@@ -403,31 +405,41 @@ class FeatureNetFpn:
         """image (3,H,W) -> stage1 (4b,H/4,W/4), stage2 (2b,H/2,W/2), stage3 (b,H,W)."""
         L = _lib.load()
         if len(layers) != self.LAYERS:
-            raise ValueError("13 layers expected")
+            raise ValueError(f"{self.LAYERS} layers expected")
         image = _f32(image)
         _, H, W = image.shape
         if image.shape[0] != 3 or H % 4 or W % 4:
             raise ValueError("image must be (3,H,W) with H, W multiples of 4")
         dev, b = image.device, self.b
         if self._ws_key != (H, W, dev):
-            self._ws = torch.empty(L.svs_featurenet_fpn_workspace_bytes(b, H, W) // 4, device=dev)
+            self._ws = torch.empty(getattr(L, self.WORKSPACE)(b, H, W) // 4, device=dev)
             self._ws_key = (H, W, dev)
         tb = self.tables(layers)
         wt, bt, ft = tb[0], tb[1], tb[5]
         s1 = torch.empty(4 * b, H // 4, W // 4, device=dev)
         s2 = torch.empty(2 * b, H // 2, W // 2, device=dev)
         s3 = torch.empty(b, H, W, device=dev)
-        _lib.check(L.svs_featurenet_fpn2(_ptr(image), H, W, b, wt, bt, ft, _ptr(self._ws), _ptr(s1), _ptr(s2), _ptr(s3), _stream()),
-                   "svs_featurenet_fpn2")
+        _lib.check(getattr(L, self.ENTRY)(_ptr(image), H, W, b, wt, bt, ft, _ptr(self._ws), _ptr(s1), _ptr(s2), _ptr(s3), _stream()),
+                   self.ENTRY)
         return s1, s2, s3
+
+
+_FPN_MFMA = os.environ.get("SVS_FPN_MFMA", "1") != "0"     # A/B: 0 = every layer of the pyramid on the float32 vector kernels
+
+
+class FeatureNetFpn(_FeatureExtractor):
+    """The 13 convolutions of the 'fpn' FeatureNet (svs_featurenet_fpn2)."""
+    LAYERS, ENTRY, WORKSPACE = 13, "svs_featurenet_fpn2", "svs_featurenet_fpn_workspace_bytes"
+    STRIDES = (1, 1, 2, 1, 1, 2, 1, 1, 1, 1, 1, 1, 1)
+    ADDEND = (9, 11)                                       # the lateral 1x1 convolutions
+
+    def fragment(self, i, w):
+        return self._conv_fragment(i, w) if _FPN_MFMA else None
 
 
 # ---------------------------------------------------------------------------------------------------------------------
 # UCSNet (models/ucsnet.py; csrc/svs_ucsnet.hip)
 # ---------------------------------------------------------------------------------------------------------------------
-_DECONV_FRAG_CACHE = {}
-
-
 def deconv2d_mfma_supported(Cin, Cout):
     return bool(_lib.load().svs_deconv2d_mfma_supported(int(Cin), int(Cout)))
 
@@ -435,19 +447,14 @@ def deconv2d_mfma_supported(Cin, Cout):
 def deconv2d_mfma_frag(weight):
     """(Cin,Cout,3,3) float32 -> the fp16 hi / mid MFMA A fragments of svs_deconv2d_mfma (packed on the device, cached per
     weight tensor: address + version)."""
-    key = (weight.data_ptr(), weight._version, tuple(weight.shape), weight.device)
-    hit = _DECONV_FRAG_CACHE.get(key)
-    if hit is not None:
-        return hit[0]
-    if len(_DECONV_FRAG_CACHE) > 64:
-        _DECONV_FRAG_CACHE.clear()
-    L = _lib.load()
-    Cin, Cout = weight.shape[:2]
-    w = _f32(weight.detach())
-    frag = torch.empty(L.svs_deconv2d_mfma_wfrag_bytes(Cin, Cout) // 2, dtype=torch.float16, device=weight.device)
-    _lib.check(L.svs_deconv2d_mfma_pack(_ptr(w), Cin, Cout, _ptr(frag), _stream()), "svs_deconv2d_mfma_pack")
-    _DECONV_FRAG_CACHE[key] = (frag, weight, w)            # keep `weight` alive: the key holds its address
-    return frag
+    def make():
+        L = _lib.load()
+        Cin, Cout = weight.shape[:2]
+        w = _f32(weight.detach())
+        frag = torch.empty(L.svs_deconv2d_mfma_wfrag_bytes(Cin, Cout) // 2, dtype=torch.float16, device=weight.device)
+        _lib.check(L.svs_deconv2d_mfma_pack(_ptr(w), Cin, Cout, _ptr(frag), _stream()), "svs_deconv2d_mfma_pack")
+        return frag, w
+    return _DECONV_FRAG_CACHE.get(weight, make)[0]
 
 
 def deconv2d(x, weight, bias=None, relu=False, out=None, mfma=None):
@@ -480,94 +487,55 @@ def deconv2d(x, weight, bias=None, relu=False, out=None, mfma=None):
     return out
 
 
-# (layer index -> stride) of svs_featurenet_unet's 15 layers; 9 and 12 are the transposed ones
-_UNET_STRIDES = (1, 1, 2, 1, 1, 2, 1, 1, 1, 2, 1, 1, 2, 1, 1)
-_UNET_DECONV = (9, 12)
-_UNETS = weakref.WeakSet()               # live wrappers: clear_caches() drops their tables and workspaces
-
-
-class FeatureNetUnet:
-    """The 15 layers of UCSNet's FeatExtNet (models/ucsnet.py:237-302) enqueued by ONE library call (svs_featurenet_unet), as
-    FeatureNetFpn does for the FPN; the two concatenations are formed in place in the workspace."""
-    LAYERS = 15
+class FeatureNetUnet(_FeatureExtractor):
+    """The 15 layers of UCSNet's FeatExtNet (models/ucsnet.py:237-302; svs_featurenet_unet); the two concatenations are formed
+    in place in the workspace."""
+    LAYERS, ENTRY, WORKSPACE = 15, "svs_featurenet_unet", "svs_featurenet_unet_workspace_bytes"
+    STRIDES = (1, 1, 2, 1, 1, 2, 1, 1, 1, 2, 1, 1, 2, 1, 1)
+    TRANSPOSED = (9, 12)
 
     def __init__(self, base_channels, mfma=None, deconv_mfma=None):
         """mfma = False: every layer on the float32 kernels.  deconv_mfma: True / False = both transposed layers on the matrix
-        cores / on the float32 kernel (the A/B comparison of tools/bench_ucsnet.py); None = the default, see tables()."""
-        self.b = int(base_channels)
+        cores / on the float32 kernel (the A/B comparison of tools/bench_ucsnet.py); None = the default, see fragment()."""
         self.mfma = True if mfma is None else bool(mfma)
         self.deconv_mfma = (None if self.mfma else False) if deconv_mfma is None else bool(deconv_mfma)
-        self.forget()
-        _UNETS.add(self)
+        super().__init__(base_channels)
 
-    def forget(self):
-        self._ws, self._ws_key = None, None
-        self._tables, self._tables_key = None, None
-
-    def tables(self, layers):
-        """layers: 15 (weight, bias or None) pairs in the library's order, convolutions (Cout,Cin,k,k), the transposed layers
-        (Cin,Cout,3,3) -> pointer tables (cached until a tensor changes)."""
-        key = tuple((w.data_ptr(), w._version, None if b is None else (b.data_ptr(), b._version)) for w, b in layers)
-        if key != self._tables_key:
-            packed = [_f32(w.detach()) if i in _UNET_DECONV else conv2d_pack(w) for i, (w, _) in enumerate(layers)]
-            biases = [None if b is None else _f32(b) for _, b in layers]
-            frags = []
-            for i, (w, _) in enumerate(layers):
-                if i in _UNET_DECONV:
-                    # deconv1.deconv (32 -> 16) on the matrix cores: 0.017 ms against 0.041 at 288 x 384 -> 576 x 768.  Not
-                    # deconv2.deconv (16 -> 8, a half-full M tile): alone it is not faster there, 0.039 ms against 0.038 at
-                    # 576 x 768 -> 1152 x 1536 with overlapping ranges, cause not established; inside the extractor the choice
-                    # moves the 0.51 ms per image by about 1 % the other way (profiles/ucsnet_bench.txt)
-                    on = w.shape[1] > 8 if self.deconv_mfma is None else self.deconv_mfma
-                    frags.append(deconv2d_mfma_frag(w) if on and deconv2d_mfma_supported(w.shape[0], w.shape[1]) else None)
-                else:
-                    # the 3x3 / 5x5 layers with 8 / 16 / 32 input channels run on the matrix cores; not conv0.1 (8 -> 8 at
-                    # full resolution: a quarter-full M tile, slower than the vector kernel -- FeatureNetFpn.tables)
-                    frags.append(conv2d_mfma_frag(w) if (self.mfma and w.shape[2] > 1 and not (w.shape[1] <= 8 and w.shape[2] == 3)
-                                                         and conv2d_mfma_supported(w.shape[1], w.shape[0], w.shape[2], _UNET_STRIDES[i]))
-                                 else None)
-            self._tables = (_ptr_array(packed), _ptr_array(biases), packed, biases, layers, _ptr_array(frags), frags)
-            self._tables_key = key
-        return self._tables
-
-    def __call__(self, image, layers):
-        """image (3,H,W) -> stage1 (4b,H/4,W/4), stage2 (2b,H/2,W/2), stage3 (b,H,W)."""
-        L = _lib.load()
-        if len(layers) != self.LAYERS:
-            raise ValueError("15 layers expected")
-        image = _f32(image)
-        _, H, W = image.shape
-        if image.shape[0] != 3 or H % 4 or W % 4:
-            raise ValueError("image must be (3,H,W) with H, W multiples of 4")
-        dev, b = image.device, self.b
-        if self._ws_key != (H, W, dev):
-            self._ws = torch.empty(L.svs_featurenet_unet_workspace_bytes(b, H, W) // 4, device=dev)
-            self._ws_key = (H, W, dev)
-        tb = self.tables(layers)
-        wt, bt, ft = tb[0], tb[1], tb[5]
-        s1 = torch.empty(4 * b, H // 4, W // 4, device=dev)
-        s2 = torch.empty(2 * b, H // 2, W // 2, device=dev)
-        s3 = torch.empty(b, H, W, device=dev)
-        _lib.check(L.svs_featurenet_unet(_ptr(image), H, W, b, wt, bt, ft, _ptr(self._ws), _ptr(s1), _ptr(s2), _ptr(s3), _stream()),
-                   "svs_featurenet_unet")
-        return s1, s2, s3
+    def fragment(self, i, w):
+        if i not in self.TRANSPOSED:
+            return self._conv_fragment(i, w) if self.mfma else None
+        # deconv1.deconv (32 -> 16) on the matrix cores: 0.017 ms against 0.041 at 288 x 384 -> 576 x 768.  Not
+        # deconv2.deconv (16 -> 8, a half-full M tile): alone it is not faster there, 0.039 ms against 0.038 at
+        # 576 x 768 -> 1152 x 1536 with overlapping ranges, cause not established; inside the extractor the choice
+        # moves the 0.51 ms per image by about 1 % the other way (profiles/ucsnet_bench.txt)
+        on = w.shape[1] > 8 if self.deconv_mfma is None else self.deconv_mfma
+        return deconv2d_mfma_frag(w) if on and deconv2d_mfma_supported(w.shape[0], w.shape[1]) else None
 
 
-def prob_depth_conf_var(reg, depth_values, lamb):
-    """compute_depth's tail (models/ucsnet.py:381-394): reg (D,H,W), depth_values (D,H,W) -> prob (D,H,W), depth (H,W), conf
-    (H,W), index (H,W int32) as prob_depth_conf gives them, and variance (H,W) = lamb * sqrt(sum_d prob_d (z_d - depth)^2)."""
+def _tail(entry, reg, depth_values, lamb=None):
+    """One softmax tail (csrc/svs_costvol.hip: launch_tail): reg (D,H,W), depth_values (D,H,W) -> prob (D,H,W), depth (H,W), conf
+    (H,W), index (H,W int32); with lamb also the per-pixel uncertainty (H,W)."""
     L = _lib.load()
     reg, dv = _f32(reg), _f32(depth_values)
     D, H, W = reg.shape
     dev = reg.device
     prob = torch.empty(D, H, W, device=dev)
-    depth = torch.empty(H, W, device=dev)
-    conf = torch.empty(H, W, device=dev)
-    var = torch.empty(H, W, device=dev)
+    depth, conf = torch.empty(H, W, device=dev), torch.empty(H, W, device=dev)
     idx = torch.empty(H, W, dtype=torch.int32, device=dev)
-    _lib.check(L.svs_prob_depth_conf_var(_ptr(reg), _ptr(dv), D, H, W, float(lamb), _ptr(prob), _ptr(depth), _ptr(conf), _ptr(idx),
-                                         _ptr(var), _stream()), "svs_prob_depth_conf_var")
+    args = (_ptr(reg), _ptr(dv), D, H, W)
+    out = (_ptr(prob), _ptr(depth), _ptr(conf), _ptr(idx))
+    if lamb is None:
+        _lib.check(getattr(L, entry)(*args, *out, _stream()), entry)
+        return prob, depth, conf, idx
+    var = torch.empty(H, W, device=dev)
+    _lib.check(getattr(L, entry)(*args, float(lamb), *out, _ptr(var), _stream()), entry)
     return prob, depth, conf, idx, var
+
+
+def prob_depth_conf_var(reg, depth_values, lamb):
+    """compute_depth's tail (models/ucsnet.py:381-394): reg (D,H,W), depth_values (D,H,W) -> prob (D,H,W), depth (H,W), conf
+    (H,W), index (H,W int32) as prob_depth_conf gives them, and variance (H,W) = lamb * sqrt(sum_d prob_d (z_d - depth)^2)."""
+    return _tail("svs_prob_depth_conf_var", reg, depth_values, lamb)
 
 
 def uncertainty_hypotheses(prev_depth, prev_var, hw, ndepth, dmin=None, dmax=None, inverse=False, device=None):
@@ -695,14 +663,8 @@ def warp_similarity(features, proj_matrices, depth_values, view_weights=None, ne
     177 folded floats of pixel_wise_net, the weights are max_d sigmoid(net(sim_v)); else (1,V-1,H/2,W/2), the previous stage's,
     read at (y/2, x/2).  -> similarity (1,1,D,H,W), the weights at this stage's size (1,V-1,H,W)."""
     L = _lib.load()
-    ref = _f32(features[0][0])
-    C, H, W = ref.shape
-    D = depth_values.shape[1]
-    dev = ref.device
-    n_src = len(features) - 1
-    hwc = [_hwc(f[0]) for f in features[1:]]
-    rt = _rot_trans(proj_matrices)
-    dv = _f32(depth_values[0])
+    ref, hwc, rt, dv = _warp_inputs(features, proj_matrices, depth_values)
+    (C, H, W), D, dev, n_src = ref.shape, dv.shape[0], ref.device, len(hwc)
     if view_weights is not None:
         pw = _f32(view_weights[0])
         if tuple(pw.shape) != (n_src, H // 2, W // 2) or H % 2 or W % 2:
@@ -724,16 +686,7 @@ def warp_similarity(features, proj_matrices, depth_values, view_weights=None, ne
 def prob_wta(reg, depth_values):
     """TransMVSNet's tail (models/TransMVSNet.py:100-109, 225-227): reg (D,H,W), depth_values (D,H,W) -> prob (D,H,W) as
     prob_depth_conf gives it, index (H,W int32) = the first argmax, depth = depth_values[index], conf = prob[index]."""
-    L = _lib.load()
-    reg, dv = _f32(reg), _f32(depth_values)
-    D, H, W = reg.shape
-    dev = reg.device
-    prob = torch.empty(D, H, W, device=dev)
-    depth = torch.empty(H, W, device=dev)
-    conf = torch.empty(H, W, device=dev)
-    idx = torch.empty(H, W, dtype=torch.int32, device=dev)
-    _lib.check(L.svs_prob_wta(_ptr(reg), _ptr(dv), D, H, W, _ptr(prob), _ptr(depth), _ptr(conf), _ptr(idx), _stream()), "svs_prob_wta")
-    return prob, depth, conf, idx
+    return _tail("svs_prob_wta", reg, depth_values)
 
 
 _GEMM_ON = [True]
@@ -747,13 +700,10 @@ def gemm_enabled(on=None):
     return _GEMM_ON[0]
 
 
+@_cached_fragments("rows")
 def rows_weight_fragments(weight):
     """[16][27][Cout <= 16] folded float32 weights -> the fp16 hi / mid A fragments of svs_conv3d_rows
     ([k-step][piece][lane][8], include/svolsdf_hip.h): k-step s, lane group kg = combination 4 s + kg = tap * G + g."""
-    key = ("rows", weight.data_ptr(), weight._version, tuple(weight.shape))
-    hit = _WFRAG_CACHE.get(key)
-    if hit is not None:
-        return hit[0]
     Cin, _, Cout = weight.shape
     dev = weight.device
     G = Cin // 8
@@ -766,21 +716,13 @@ def rows_weight_fragments(weight):
     co = (lane & 15).expand(KS, 64, 8)
     ok = (tap < 27) & (co < Cout)
     w = weight[8 * g + j, tap.clamp(max=26), co.clamp(max=Cout - 1)]
-    w = torch.where(ok, w, torch.zeros_like(w)).float()
-    hi = w.half()
-    mid = (w - hi.float()).half()
-    frag = torch.stack([hi, mid], 1).contiguous()
-    _WFRAG_CACHE[key] = (frag, weight)
-    return frag
+    return _hi_mid(w, ok)
 
 
+@_cached_fragments("s2c8")
 def s2c8_weight_fragments(weight):
     """[8][27][Cout <= 16] folded float32 weights -> the fp16 hi / mid A fragments of svs_conv3d_s2c8
     ([9 k-steps][piece][lane][8], include/svolsdf_hip.h)."""
-    key = ("s2c8", weight.data_ptr(), weight._version, tuple(weight.shape))
-    hit = _WFRAG_CACHE.get(key)
-    if hit is not None:
-        return hit[0]
     Cin, _, Cout = weight.shape
     dev = weight.device
     s = torch.arange(9, device=dev).view(9, 1, 1)
@@ -792,27 +734,19 @@ def s2c8_weight_fragments(weight):
     ok = ((row < 9) & (co < Cout)).expand(9, 64, 8)
     tap = (row.clamp(max=8) * 3 + kx).expand(9, 64, 8)
     w = weight[j, tap, co.clamp(max=Cout - 1)]
-    w = torch.where(ok, w, torch.zeros_like(w)).float()
-    hi = w.half()
-    mid = (w - hi.float()).half()
-    frag = torch.stack([hi, mid], 1).contiguous()          # (9, 2, 64, 8) fp16
-    _WFRAG_CACHE[key] = (frag, weight)
-    return frag
+    return _hi_mid(w, ok)
 
 
 def gemm_weight_fragments(weight, transposed):
     """[Cin][27][Cout] folded float32 weights -> the A fragments of svs_conv3d_gemm (packed on the device, cached)."""
-    key = (weight.data_ptr(), weight._version, tuple(weight.shape), bool(transposed))
-    hit = _WFRAG_CACHE.get(key)
-    if hit is not None:
-        return hit[0]
-    L = _lib.load()
-    Cin, _, Cout = weight.shape
-    w = _f32(weight)
-    frag = torch.empty(L.svs_conv3d_gemm_wfrag_bytes(Cin, Cout, int(transposed)), dtype=torch.uint8, device=weight.device)
-    _lib.check(L.svs_conv3d_gemm_pack(_ptr(w), Cin, Cout, int(transposed), _ptr(frag), _stream()), "svs_conv3d_gemm_pack")
-    _WFRAG_CACHE[key] = (frag, weight)
-    return frag
+    def make():
+        L = _lib.load()
+        Cin, _, Cout = weight.shape
+        w = _f32(weight)
+        frag = torch.empty(L.svs_conv3d_gemm_wfrag_bytes(Cin, Cout, int(transposed)), dtype=torch.uint8, device=weight.device)
+        _lib.check(L.svs_conv3d_gemm_pack(_ptr(w), Cin, Cout, int(transposed), _ptr(frag), _stream()), "svs_conv3d_gemm_pack")
+        return frag
+    return _WFRAG_CACHE.get(weight, make, tag=("gemm", bool(transposed)))
 
 
 def rows_supported(Cin, Cout):
@@ -880,17 +814,7 @@ def conv3d(x, weight, bias=None, skip=None, stride=1, transposed=False, relu=Tru
 
 def prob_depth_conf(reg, depth_values):
     """reg (D,H,W), depth_values (D,H,W) -> prob (D,H,W), depth (H,W), conf (H,W), index (H,W int32)."""
-    L = _lib.load()
-    reg, dv = _f32(reg), _f32(depth_values)
-    D, H, W = reg.shape
-    dev = reg.device
-    prob = torch.empty(D, H, W, device=dev)
-    depth = torch.empty(H, W, device=dev)
-    conf = torch.empty(H, W, device=dev)
-    idx = torch.empty(H, W, dtype=torch.int32, device=dev)
-    _lib.check(L.svs_prob_depth_conf(_ptr(reg), _ptr(dv), D, H, W, _ptr(prob), _ptr(depth), _ptr(conf), _ptr(idx),
-                                     _stream()), "svs_prob_depth_conf")
-    return prob, depth, conf, idx
+    return _tail("svs_prob_depth_conf", reg, depth_values)
 
 
 def depth_hypotheses(prev_depth, img_hw, ndepth, scale, dmin, dmax, pix_interval, inverse, device):

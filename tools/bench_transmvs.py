@@ -23,7 +23,8 @@ import torch.nn.functional as Fn  # noqa: E402
 
 import synth  # noqa: E402
 import transmvs_oracle as to  # noqa: E402
-from models.transmvs import TransMVSNetHip, _fold_bn  # noqa: E402
+from models.blocks import fold_bn as _fold_bn  # noqa: E402
+from models.transmvs import TransMVSNetHip  # noqa: E402
 from svs_hip import costvol  # noqa: E402
 
 BATCH = 5
