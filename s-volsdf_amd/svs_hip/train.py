@@ -67,13 +67,15 @@ class TrainStreams:
 
 
 class WGradAccum:
-    def __init__(self, device):
-        # one allocation, one memset per step
-        n = [14 * 256 * LDW, 14 * 256, 260, 4]
+    """Kernel-order weight-gradient accumulators of `slots` layers: one allocation, one memset per step.  14 slots for the
+    foreground networks (0..8 SDF layers, 9..13 radiance layers), 11 for the background networks (0..8, 9..10)."""
+
+    def __init__(self, device, slots=14):
+        n = [slots * 256 * LDW, slots * 256, 260, 4]
         self.flat = torch.zeros(sum(n), device=device)
         parts = torch.split(self.flat, n)
-        self.dWk = parts[0].view(14, 256, LDW)
-        self.dbk = parts[1].view(14, 256)
+        self.dWk = parts[0].view(slots, 256, LDW)
+        self.dbk = parts[1].view(slots, 256)
         self.row0 = parts[2][:257]
         # fp16x2: maxima of the gradient-like GEMM operands, published by the sweeps: [0] SDF abar / u,
         # [1] radiance zbar, [2] feature-vector gradient
@@ -82,29 +84,115 @@ class WGradAccum:
     def zero(self):
         self.flat.zero_()
 
-
-def _unpack_all(jobs):
-    """[(dWk, dbk, ldw, map, rows, cols, row_off, v, g, row0, gv, gg, gb)] (c_void_p / None / int) -> one launch."""
-    L = _lib.load()
-    val = lambda x: x.value if isinstance(x, ctypes.c_void_p) else x
-    arr = (_lib.UnpackJob * len(jobs))(*[_lib.UnpackJob(*[val(x) for x in j]) for j in jobs])
-    _lib.check(L.svs_unpack_wgrad_multi(ctypes.cast(arr, ctypes.c_void_p), len(jobs), _stream()), "svs_unpack_wgrad_multi")
+    def bases(self):
+        """(dWk, dbk, absmax) device addresses: what a weight-gradient job table is built from"""
+        return self.dWk.data_ptr(), self.dbk.data_ptr(), self.absmax.data_ptr()
 
 
-def finalize(accum, sdf_params, rgb_params, out=None, nets=(0, 1)):
-    """kernel-order accumulators -> (sdf_grads, rgb_grads): lists of (grad_v, grad_g, grad_b) per layer; `out`
-    optionally names the destination tensors (views of a flat gradient buffer).  One launch for all 14 layers; `nets`
-    restricts it to the SDF network (0) or the radiance network (1): a data-parallel step unpacks the radiance gradients as
-    soon as their GEMM launch has retired, so that their bucket can be all-reduced beside the SDF backward (trainer.py)."""
+class _JobCache(dict):
+    """Memo of job tables and ctypes job arrays, built once per configuration: the KEY names every device address the jobs
+    hold (a step's scratch comes back at the same addresses from torch's caching allocator; a re-allocated buffer gives a
+    new key, never a stale address) besides the point counts and the precision.  ~40 ctypes structures a step otherwise."""
+
+    def memo(self, key, build):
+        hit = self.get(key)
+        if hit is None:
+            if len(self) >= 64:
+                self.clear()
+            hit = self[key] = build()
+        return hit
+
+
+def _job_array(jobs):
+    """job tuples -> (address, count, the ctypes array kept alive beside its address)"""
+    arr = (_lib.WGradJob * len(jobs))(*[_lib.WGradJob(*j) for j in jobs])
+    return ctypes.cast(arr, ctypes.c_void_p), len(jobs), arr
+
+
+# ---- job tables: plain functions of integers (device addresses in bytes, point counts, flags) -----------------------------------
+def _f(addr, n_floats):
+    """address `n_floats` floats behind `addr`"""
+    return addr + 4 * n_floats
+
+
+def wgrad_job(acc, slot, n_pts, amax, scaled, a0, sa0, b0, sb0, a1=None, sa1=0, b1=None, sb1=0, extra=None, sx=0,
+              rec0=None, rec1=None):
+    """One svs_wgrad_job (lib.WGradJob's field order): dW[slot] += A^T B over n_pts points, operands as [tile] blocks with the
+    given strides (floats), an optional second operand pair and extra B rows.  acc = WGradAccum.bases(); scaled: the operands
+    are scaled fp16x2 blocks -- their maximum (absmax[amax]) and records travel along; float32 blocks have neither."""
+    dWk, dbk, absmax = acc
+    return (a0, b0, sa0, sb0, a1, b1, sa1, sb1, extra, sx, n_pts, LDW, _f(dWk, slot * 256 * LDW), _f(dbk, slot * 256),
+            _f(absmax, amax) if scaled else None, rec0 if scaled else None, rec1 if scaled else None)
+
+
+def rgb_wgrad_table(n_main, h2, acc, zbuf, feat, rbuf):
+    """the five radiance layers (slots 9..13).  rbuf = [4 blocks][tile] + extras [tile][1024], zbuf = [5 blocks][tile]"""
+    LSm = block_stride(n_main)
+    zrec = lambda l: _f(zbuf, record_off(n_main, 5, l))
+    jobs = [wgrad_job(acc, 9, n_main, 1, h2, zbuf, KBLOCK, feat, KBLOCK, extra=_f(rbuf, 4 * LSm), sx=1024, rec0=zrec(0))]
+    for l in range(1, 5):
+        jobs.append(wgrad_job(acc, 9 + l, n_main, 1, h2, _f(zbuf, l * LSm), KBLOCK, _f(rbuf, (l - 1) * LSm), KBLOCK,
+                              rec0=zrec(l)))
+    return jobs
+
+
+def sdf_wgrad_table(n_total, n_main, h2, acc, abuf, ubuf, pebuf, hbuf, gbuf, feat_bar):
+    """the nine SDF layers (slots 0..8): lin0..lin7 with the second-order pair (ghat_l, u_l), lin8 over the ray samples"""
+    LS = block_stride(n_total)
+    arec = lambda l: _f(abuf, record_off(n_total, 8, l))
+    second = lambda l: dict(a1=_f(gbuf, l * LS), sa1=KBLOCK, b1=_f(ubuf, l * LS), sb1=KBLOCK,
+                            rec1=_f(ubuf, record_off(n_total, 9, l)))
+    jobs = [wgrad_job(acc, 0, n_total, 0, h2, abuf, KBLOCK, pebuf, KBLOCK, rec0=arec(0), **second(0))]
+    for l in range(1, 8):
+        jobs.append(wgrad_job(acc, l, n_total, 0, h2, _f(abuf, l * LS), KBLOCK, _f(hbuf, (l - 1) * LS), KBLOCK, rec0=arec(l),
+                              **second(l)))
+    jobs.append(wgrad_job(acc, 8, n_main, 2, h2, feat_bar, KBLOCK, _f(hbuf, 7 * LS), KBLOCK,
+                          rec0=_f(feat_bar, record_off(n_main, 1, 0))))
+    return jobs
+
+
+BGRBUF = KBLOCK + 1024
+
+
+def bg_wgrad_table(P, acc, abuf, zbuf, feat_bar, hbuf, pebuf, rbuf, feat):
+    """the background networks' eleven layers over P points: ordinary backprop (no second pair); their kernels publish
+    maxima and records at either precision"""
+    LS, Z2, T = block_stride(P), 2 * KBLOCK, n_tiles_padded(P)
+    job = lambda slot, amax, *a, **k: wgrad_job(acc, slot, P, amax, True, *a, **k)
+    arec = lambda l: _f(abuf, record_off(P, 8, l))
+    jobs = [job(0, 0, abuf, KBLOCK, pebuf, KBLOCK, rec0=arec(0))]
+    for l in range(1, 8):
+        jobs.append(job(l, 0, _f(abuf, l * LS), KBLOCK, _f(hbuf, (l - 1) * LS), KBLOCK, rec0=arec(l)))
+    jobs.append(job(8, 2, feat_bar, KBLOCK, _f(hbuf, 7 * LS), KBLOCK, rec0=_f(feat_bar, record_off(P, 1, 0))))
+    # bg zbuf slots are [tile][2 blocks]; its records, behind the slots, are [block][tile][64] like everywhere else
+    zrec = lambda b: _f(zbuf, 2 * T * KBLOCK + b * T * KREC)
+    jobs.append(job(9, 1, zbuf, Z2, feat, KBLOCK, rec0=zrec(0), extra=_f(rbuf, KBLOCK), sx=BGRBUF))
+    jobs.append(job(10, 1, _f(zbuf, KBLOCK), Z2, rbuf, BGRBUF, rec0=zrec(1)))
+    return jobs
+
+
+def unpack_table(dWk, dbk, row0, layers, maps):
+    """svs_unpack_job tuples (lib.UnpackJob's field order).  layers: [(net, l, slot, rows, cols, v, g, gv, gg, gb)] with
+    net 0 = the SDF-shaped network, 1 = its radiance network, and addresses (g / gg: None without weight-norm);
+    maps = (column map of the skip layer -- net 0, layer 4 --, column map of the radiance input layer -- net 1, layer 0).
+    Layer 8 of net 0 takes its first row from `row0` (svs_lin8_row0_grad)."""
+    jobs = []
+    for net, l, slot, rows, cols, v, g, gv, gg, gb in layers:
+        mp = maps[0] if (net == 0 and l == 4) else (maps[1] if (net == 1 and l == 0) else 0)
+        last = net == 0 and l == 8
+        jobs.append((_f(dWk, slot * 256 * LDW), _f(dbk, slot * 256), LDW, mp, rows, cols, 1 if last else 0, v, g,
+                     row0 if last else None, gv, gg, gb))
+    return jobs
+
+
+def _unpack(accum, nets, maps, out, which=(0, 1)):
+    """kernel-order accumulators -> parameter gradients of the networks `which` of nets = ((v, g, first slot), ...), g = None
+    without weight-norm: [(grad_v, grad_g, grad_b)] per network, in `out`'s tensors where given.  One launch."""
     dev = accum.dWk.device
-    res, jobs, keep = [], [], []
-    for gi, (params, base, n) in enumerate(((sdf_params, 0, 9), (rgb_params, 9, 5))):
-        v, g, _ = params
+    res, layers, keep = [], [], []
+    for gi, (v, g, base) in enumerate(nets):
         group = []
-        if gi not in nets:
-            res.append(group)
-            continue
-        for l in range(n):
+        for l in range(len(v)) if gi in which else ():
             rows, cols = v[l].shape
             if out is not None:
                 gv, gg, gb = out[gi][l]
@@ -112,18 +200,25 @@ def finalize(accum, sdf_params, rgb_params, out=None, nets=(0, 1)):
                 gv = torch.empty(rows, cols, device=dev)
                 gg = torch.empty(rows, 1, device=dev) if g is not None else None
                 gb = torch.empty(rows, device=dev)
-            is_sdf = gi == 0
-            mp = 1 if (is_sdf and l == 4) else (2 if (not is_sdf and l == 0) else 0)
-            row_off = 1 if (is_sdf and l == 8) else 0
-            row0 = _ptr(accum.row0) if (is_sdf and l == 8) else None
             vl, gl = _f32(v[l]), (_f32(g[l]) if g is not None else None)
             keep += [vl, gl]
-            jobs.append((_off(accum.dWk, (base + l) * 256 * LDW), _off(accum.dbk, (base + l) * 256), LDW, mp, rows, cols,
-                         row_off, _ptr(vl), _ptr(gl), row0, _ptr(gv), _ptr(gg), _ptr(gb)))
+            layers.append((gi, l, base + l, rows, cols, _ptr(vl), _ptr(gl), _ptr(gv), _ptr(gg), _ptr(gb)))
             group.append((gv, gg, gb))
         res.append(group)
-    _unpack_all(jobs)
-    return res[0], res[1]
+    jobs = unpack_table(_ptr(accum.dWk), _ptr(accum.dbk), _ptr(accum.row0), layers, maps)
+    arr = (_lib.UnpackJob * len(jobs))(*[_lib.UnpackJob(*j) for j in jobs])
+    _lib.check(_lib.load().svs_unpack_wgrad_multi(ctypes.cast(arr, ctypes.c_void_p), len(jobs), _stream()),
+               "svs_unpack_wgrad_multi")
+    return res
+
+
+def finalize(accum, sdf_params, rgb_params, out=None, nets=(0, 1)):
+    """kernel-order accumulators -> (sdf_grads, rgb_grads): lists of (grad_v, grad_g, grad_b) per layer; `out`
+    optionally names the destination tensors (views of a flat gradient buffer).  One launch for all 14 layers; `nets`
+    restricts it to the SDF network (0) or the radiance network (1): a data-parallel step unpacks the radiance gradients as
+    soon as their GEMM launch has retired, so that their bucket can be all-reduced beside the SDF backward (trainer.py)."""
+    (sv, sg, _), (rv, rg, _) = sdf_params, rgb_params
+    return tuple(_unpack(accum, ((sv, sg, 0), (rv, rg, 9)), (1, 2), out, nets))
 
 
 class MlpBackward:
@@ -135,7 +230,7 @@ class MlpBackward:
         self.accum = accum or WGradAccum(device)
         self._n = None
         self._side = None
-        self._job_cache = {}
+        self._job_cache = _JobCache()
         self.time_wgrad = False
         self.timer_events = None
 
@@ -160,13 +255,6 @@ class MlpBackward:
         # no concatenation launch between the radiance backward and pass A
         self.d_grad_full = torch.zeros(n_total, 3, device=self.dev)
         self._n = (n_total, n_main)
-
-    def _cache_jobs(self, key, jobs):
-        if len(self._job_cache) >= 64:
-            self._job_cache.clear()
-        arr = (_lib.WGradJob * len(jobs))(*jobs)
-        hit = self._job_cache[key] = (ctypes.cast(arr, ctypes.c_void_p), len(jobs), arr)    # (arr kept alive beside its address)
-        return hit[:2]
 
     def sdf_grad_out(self, n_total, n_main):
         """(n_main,1) view of the persistent d_sdf buffer: compositing's backward writes into it directly."""
@@ -198,42 +286,20 @@ class MlpBackward:
             raise NotImplementedError("rays*samples of a group must be a multiple of 32")
         self._alloc(n_total, n_main)
         dev, acc, S = self.dev, self.accum, self.streams
-        LS = block_stride(n_total)
         hbuf, gbuf, mask = keep["hbuf"], keep["gbuf"], keep["clamp_mask"]
         rbuf, feat = keep["rbuf"], keep["feat_tiles"]
 
         prec = S.precision
         h2 = is_h2(prec)
 
-        def addr(x):
-            return x.value if isinstance(x, ctypes.c_void_p) else x
+        cache, bases = self._job_cache, acc.bases()
 
-        def job(slot, n_pts, amax, a0, sa0, b0, sb0, a1=None, sa1=0, b1=None, sb1=0, extra=None, sx=0, rec0=None, rec1=None):
-            return _lib.WGradJob(addr(a0), addr(b0), sa0, sb0, addr(a1), addr(b1), sa1, sb1,
-                                 addr(extra), sx, n_pts, LDW, addr(_off(acc.dWk, slot * 256 * LDW)),
-                                 addr(_off(acc.dbk, slot * 256)), addr(_off(acc.absmax, amax)) if h2 else None,
-                                 addr(rec0) if h2 else None, addr(rec1) if h2 else None)
-
-        def wgrad_multi(cached):
-            arr, n = cached
+        def wgrad_multi(key, build, more):
+            """the group's own jobs (+ those of a folded-in group) in one launch"""
+            own = cache.memo(key, build)
+            arr, n, _ = cache.memo(("arr",) + key + ((more["key"],) if more else ()),
+                                   lambda: _job_array(own + (more["jobs"] if more else [])))
             _lib.check(L.svs_wgrad_multi(arr, n, prec, _stream()), "svs_wgrad_multi")
-
-        def job_list(key, build):
-            """the group's own jobs (ctypes structures), built once per configuration"""
-            hit = self._job_cache.get(key)
-            if hit is None:
-                if len(self._job_cache) >= 64:
-                    self._job_cache.clear()
-                hit = self._job_cache[key] = build()
-            return hit
-
-        def job_array(key, own, more):
-            """own jobs (+ those of a folded-in group) as the array one launch takes"""
-            key = ("arr",) + key + ((more["key"],) if more else ())
-            hit = self._job_cache.get(key)
-            if hit is None:
-                return self._cache_jobs(key, list(own) + (list(more["jobs"]) if more else []))
-            return hit[:2]
 
         # ---- radiance MLP: input gradients
         d_rgb = _f32(d_rgb)
@@ -263,24 +329,12 @@ class MlpBackward:
         if os.environ.get("SVS_RGB_WGRAD_SIDE", "1") == "0":   # A/B switch: the radiance weight gradients in line, in front of pass A
             side = False
         side_stream = self._side if side else main          # side=False: everything on the current stream
-        # the job lists are a function of the buffers' addresses and the point counts: built once per configuration (a
-        # step's scratch comes back at the same addresses from torch's caching allocator), ~40 ctypes structures a step
-        rkey = ("rgb", n_main, prec, self.zbuf.data_ptr(), feat.data_ptr(), rbuf.data_ptr(), acc.dWk.data_ptr())
-
-        def rgb_jobs():
-            LSm = block_stride(n_main)          # rbuf = [4 blocks][tile] + extras [tile][1024], zbuf = [5 blocks][tile]
-            zrec = lambda l: _off(self.zbuf, record_off(n_main, 5, l))
-            jobs = [job(9, n_main, 1, _off(self.zbuf, 0), KBLOCK, _ptr(feat), KBLOCK, extra=_off(rbuf, 4 * LSm), sx=1024,
-                        rec0=zrec(0))]
-            for l in range(1, 5):
-                jobs.append(job(9 + l, n_main, 1, _off(self.zbuf, l * LSm), KBLOCK, _off(rbuf, (l - 1) * LSm), KBLOCK,
-                                rec0=zrec(l)))
-            return jobs
-
+        rkey = ("rgb", n_main, prec, self.zbuf.data_ptr(), feat.data_ptr(), rbuf.data_ptr(), bases[0])
+        rgb_jobs = lambda: rgb_wgrad_table(n_main, h2, bases, _ptr(self.zbuf), _ptr(feat), _ptr(rbuf))
         deferred = None
         if defer_wgrad:
             ev_rgb = torch.cuda.Event(); ev_rgb.record(main)
-            deferred = dict(rgb=dict(jobs=job_list(rkey, rgb_jobs), key=rkey), ev_rgb=ev_rgb)
+            deferred = dict(rgb=dict(jobs=cache.memo(rkey, rgb_jobs), key=rkey), ev_rgb=ev_rgb)
             join = None
         else:
             fork = torch.cuda.Event(); fork.record(main)
@@ -289,7 +343,7 @@ class MlpBackward:
                     side_stream.wait_event(fork)
                 if extra is not None:
                     side_stream.wait_event(extra["ev_rgb"])
-                wgrad_multi(job_array(rkey, job_list(rkey, rgb_jobs), extra["rgb"] if extra else None))
+                wgrad_multi(rkey, rgb_jobs, extra["rgb"] if extra else None)
                 join = torch.cuda.Event(); join.record(side_stream)
         # ---- SDF MLP: pass A (needs nbar), pass B (needs sbar, fbar), then its weight gradients
         st = _stream()
@@ -309,28 +363,17 @@ class MlpBackward:
         if ev:
             ev[0].record()
         skey = ("sdf", n_total, n_main, prec, self.abuf.data_ptr(), self.ubuf.data_ptr(), self.pebuf.data_ptr(),
-                hbuf.data_ptr(), gbuf.data_ptr(), self.feat_bar.data_ptr(), acc.dWk.data_ptr())
-
-        def sdf_jobs():
-            arec = lambda l: _off(self.abuf, record_off(n_total, 8, l))
-            urec = lambda l: _off(self.ubuf, record_off(n_total, 9, l))
-            second = lambda l: dict(a1=_off(gbuf, l * LS), sa1=KBLOCK, b1=_off(self.ubuf, l * LS), sb1=KBLOCK, rec1=urec(l))
-            jobs = [job(0, n_total, 0, _off(self.abuf, 0), KBLOCK, _ptr(self.pebuf), KBLOCK, rec0=arec(0), **second(0))]
-            for l in range(1, 8):
-                jobs.append(job(l, n_total, 0, _off(self.abuf, l * LS), KBLOCK, _off(hbuf, (l - 1) * LS), KBLOCK, rec0=arec(l),
-                                **second(l)))
-            jobs.append(job(8, n_main, 2, _ptr(self.feat_bar), KBLOCK, _off(hbuf, 7 * LS), KBLOCK,
-                            rec0=_off(self.feat_bar, record_off(n_main, 1, 0))))
-            return jobs
-
+                hbuf.data_ptr(), gbuf.data_ptr(), self.feat_bar.data_ptr(), bases[0])
+        sdf_jobs = lambda: sdf_wgrad_table(n_total, n_main, h2, bases, _ptr(self.abuf), _ptr(self.ubuf), _ptr(self.pebuf),
+                                           _ptr(hbuf), _ptr(gbuf), _ptr(self.feat_bar))
         if defer_wgrad:
-            deferred["sdf"] = dict(jobs=job_list(skey, sdf_jobs), key=skey)
+            deferred["sdf"] = dict(jobs=cache.memo(skey, sdf_jobs), key=skey)
             deferred["ev_all"] = torch.cuda.Event(); deferred["ev_all"].record(main)
             deferred["hold"] = self._hold = (d_grad, d_sdf_full, d_normals, d_rgb)
             return deferred
         if extra is not None:
             main.wait_event(extra["ev_all"])
-        wgrad_multi(job_array(skey, job_list(skey, sdf_jobs), extra["sdf"] if extra else None))
+        wgrad_multi(skey, sdf_jobs, extra["sdf"] if extra else None)
         if ev:
             ev[1].record()
         if wait and side:
@@ -350,8 +393,6 @@ class BgBackward:
     """Training backward of the background networks of VolSDFNetworkBG (bg_implicit_network: ordinary backprop, no
     second-order sweep because its input gradient is never used; bg_rendering_network): the kernels of csrc/svs_bg_h2.hip
     (fp16x2) or csrc/svs_bg_f32.hip (float32 MFMA) + the shared pass-B sweep and weight-gradient kernels."""
-    BGRBUF = KBLOCK + 1024
-
     def __init__(self, device, precision=None):
         L = _lib.load()
         self.dev = device
@@ -359,14 +400,9 @@ class BgBackward:
         self.sdf_stream = torch.empty(L.svs_stream_bytes(6) // 4, device=device)
         self.rgb_stream = torch.empty(L.svs_stream_bytes(8) // 4, device=device)
         self.ws = torch.empty(L.svs_pack_workspace_bytes() // 4, device=device)
-        # one allocation, one memset per step (as WGradAccum)
-        n = [11 * 256 * LDW, 11 * 256, 260, 4]
-        self.flat = torch.zeros(sum(n), device=device)
-        parts = torch.split(self.flat, n)
-        self.dWk = parts[0].view(11, 256, LDW)                   # 0..8 implicit layers, 9..10 radiance layers
-        self.dbk = parts[1].view(11, 256)
-        self.row0 = parts[2][:257]
-        self.absmax = parts[3]
+        self.accum = WGradAccum(device, slots=11)                # 0..8 implicit layers, 9..10 radiance layers
+        self.dWk, self.dbk, self.row0, self.absmax = self.accum.dWk, self.accum.dbk, self.accum.row0, self.accum.absmax
+        self._job_cache = _JobCache()
         self._scratch = {}          # per concurrent ray group: (n, zbuf, feat_bar, abuf, sbar); the accumulators are shared
 
     def pack(self, sdf_wb, rgb_wb):
@@ -379,7 +415,7 @@ class BgBackward:
                                          _stream()), "svs_pack_stream(bg backward)")
 
     def zero(self):
-        self.flat.zero_()
+        self.accum.zero()
 
     def _alloc(self, n, slot):
         cur = self._scratch.get(slot)
@@ -407,51 +443,20 @@ class BgBackward:
         _lib.check(L.svs_bg_sdf_bwd(P, _ptr(d_bg_out0), _ptr(feat_bar), _ptr(hbuf), _ptr(ghat7), _ptr(self.sdf_stream), prec,
                                     _ptr(abuf), _ptr(sbar), _ptr(self.absmax), st), "svs_bg_sdf_bwd")
         _lib.check(L.svs_lin8_row0_grad(_ptr(hbuf), None, _ptr(sbar), P, prec, _ptr(self.row0), st), "svs_lin8_row0_grad")
-        LS, Z2 = block_stride(P), 2 * KBLOCK
-        T = n_tiles_padded(P)
-
-        def addr(x):
-            return x.value if isinstance(x, ctypes.c_void_p) else x
-
-        def job(slot, amax, a0, sa0, b0, sb0, rec0, extra=None, sx=0):
-            return _lib.WGradJob(addr(a0), addr(b0), sa0, sb0, None, None, 0, 0, addr(extra), sx, P, LDW,
-                                 addr(_off(self.dWk, slot * 256 * LDW)), addr(_off(self.dbk, slot * 256)),
-                                 addr(_off(self.absmax, amax)), addr(rec0), None)
-
-        arec = lambda l: _off(abuf, record_off(P, 8, l))
-        jobs = [job(0, 0, _off(abuf, 0), KBLOCK, _ptr(pebuf), KBLOCK, arec(0))]
-        for l in range(1, 8):
-            jobs.append(job(l, 0, _off(abuf, l * LS), KBLOCK, _off(hbuf, (l - 1) * LS), KBLOCK, arec(l)))
-        jobs.append(job(8, 2, _ptr(feat_bar), KBLOCK, _off(hbuf, 7 * LS), KBLOCK, _off(feat_bar, record_off(P, 1, 0))))
-        # bg zbuf slots are [tile][2 blocks]; its records, behind the slots, are [block][tile][64] like everywhere else
-        zrec = lambda b: _off(zbuf, 2 * T * KBLOCK + b * T * KREC)
-        jobs.append(job(9, 1, _off(zbuf, 0), Z2, _ptr(feat), KBLOCK, zrec(0), extra=_off(rbuf, KBLOCK), sx=self.BGRBUF))
-        jobs.append(job(10, 1, _off(zbuf, KBLOCK), Z2, _ptr(rbuf), self.BGRBUF, zrec(1)))
-        arr = (_lib.WGradJob * len(jobs))(*jobs)
-        _lib.check(L.svs_wgrad_multi(ctypes.cast(arr, ctypes.c_void_p), len(jobs), prec, st), "svs_wgrad_multi(bg)")
+        ptrs = tuple(_ptr(t) for t in (abuf, zbuf, feat_bar, hbuf, pebuf, rbuf, feat))
+        bases = self.accum.bases()
+        arr, n, _ = self._job_cache.memo(("bg", P, prec) + ptrs + bases[:1],
+                                         lambda: _job_array(bg_wgrad_table(P, bases, *ptrs)))
+        _lib.check(L.svs_wgrad_multi(arr, n, prec, st), "svs_wgrad_multi(bg)")
         self._hold = getattr(self, "_hold", {})
         self._hold[slot] = (d_bg_rgb, d_bg_out0)
 
     def finalize(self, sdf_wb, rgb_wb, out=None):
         """kernel-order accumulators -> ([(grad_w, grad_b)] * 9, [(grad_w, grad_b)] * 2); one launch"""
-        res, jobs, keep = [], [], []
-        for gi, ((w, b), base) in enumerate(((sdf_wb, 0), (rgb_wb, 9))):
-            group = []
-            for l in range(len(w)):
-                rows, cols = w[l].shape
-                gw, gb = out[gi][l] if out is not None else (torch.empty(rows, cols, device=self.dev), torch.empty(rows, device=self.dev))
-                is_sdf = gi == 0
-                mp = 3 if (is_sdf and l == 4) else (4 if (not is_sdf and l == 0) else 0)
-                row_off = 1 if (is_sdf and l == 8) else 0
-                row0 = _ptr(self.row0) if (is_sdf and l == 8) else None
-                wl = _f32(w[l])
-                keep.append(wl)
-                jobs.append((_off(self.dWk, (base + l) * 256 * LDW), _off(self.dbk, (base + l) * 256), LDW, mp, rows, cols, row_off,
-                             _ptr(wl), None, row0, _ptr(gw), None, _ptr(gb)))
-                group.append((gw, gb))
-            res.append(group)
-        _unpack_all(jobs)
-        return res[0], res[1]
+        if out is not None:
+            out = [[(gw, None, gb) for gw, gb in group] for group in out]
+        res = _unpack(self.accum, ((sdf_wb[0], None, 0), (rgb_wb[0], None, 9)), (3, 4), out)
+        return tuple([(gw, gb) for gw, _, gb in group] for group in res)
 
 
 def algorithmic_bytes_per_point(precision=None):

@@ -5,15 +5,17 @@ launch, and the single RCCL all-reduce of the flat gradient for ray-sharded data
 `on_after_backward` sequence of VolOpt.train_step (volsdf/vsdf.py:214-219); `TrainStep` is the whole
 train_step (vsdf.py:196-235) without the dataset / logging plumbing, used by bench.py and the tests.
 """
-import ctypes
-
 import os
 
 import torch
+import torch.distributed as dist
+from volsdf.model.network import cut_ray_tensor, pad_rays, repeat_last_ray
 
 from . import lib as _lib
 from . import ops
+from .captured import CapturedSteps, _LaunchPlan
 from .ops import _ptr, _stream
+from .train import BgBackward, MlpBackward, TrainStreams, WGradAccum, finalize
 
 
 class FlatParams:
@@ -87,16 +89,14 @@ def shard_rays(uv, rank, world):
 
 
 def allreduce_flat_grad(flat_grad, world):
-    """The one collective of a data-parallel step: sum the flat float32 gradient over ranks (RCCL over xGMI on the GPU
-    box, gloo in the CPU tests).  The loss of each rank is already divided by the GLOBAL ray count."""
-    import torch.distributed as dist
-    if world > 1 or (dist.is_available() and dist.is_initialized()):
+    """Sum the whole flat float32 gradient over ranks in one collective (RCCL over xGMI on the GPU box, gloo in the CPU
+    tests).  The loss of each rank is already divided by the GLOBAL ray count."""
+    if data_parallel(world):
         dist.all_reduce(flat_grad, op=dist.ReduceOp.SUM)
     return flat_grad
 
 
 def data_parallel(world):
-    import torch.distributed as dist
     return world > 1 or (dist.is_available() and dist.is_initialized())
 
 
@@ -115,94 +115,93 @@ def allreduce_range(flat_grad, lo, hi, async_op=False):
     rank the same values as reducing it whole -- bit for bit with two ranks (a + b commutes), and with a ring of more ranks up
     to the order in which the ranks' contributions meet, which depends on where an element falls in the collective's chunks:
     the replicas stay identical among themselves either way (tests/test_dist_gloo.py::test_bucketed_allreduce_equals_single_world2)."""
-    import torch.distributed as dist
     return dist.all_reduce(flat_grad[lo:hi], op=dist.ReduceOp.SUM, async_op=async_op)
 
 
-_DP_BUCKETS = os.environ.get("SVS_DP_BUCKETS", "1") == "1"        # A/B: 0 = one all-reduce of the whole flat gradient at the end
+def allreduce_buckets(flat_grad, buckets, early=None):
+    """THE collective sequence of a data-parallel step, whatever path launched it (eager, captured, planned, "linear",
+    deterministic): one all-reduce per bucket of grad_buckets(), in that order.  Which path a step takes is decided per rank
+    (a capture key holds device addresses), so ranks may differ in it; what they post must not.  early: the Work handle of
+    the FIRST bucket where the step already started it (eager steps do, on their comm stream, beside the SDF backward);
+    the current stream then waits for it behind the remaining buckets."""
+    for lo, hi in buckets[1:] if early is not None else buckets:
+        allreduce_range(flat_grad, lo, hi)
+    if early is not None:
+        early.wait()
 
 
-class _GroupedOutputs(dict):
-    """Model outputs of a step that ran as ray groups: per-ray tensors are concatenated in ray order on first access
-    (the step itself never needs the merged tensors; logging does, every 50 steps)."""
+class _LazyDict(dict):
+    """Read-only mapping over the keys of `source` whose values are made on first access (`_make(key)`) and kept: the step
+    never needs them, logging does, every 50 steps.  The whole read protocol sees every key, made or not."""
 
-    def __init__(self, results):
+    def __init__(self, source):
         super().__init__()
-        self._parts = [r[1] for r in results]
+        self._source = source
 
     def __missing__(self, key):
-        vals = [p[key] for p in self._parts]
-        self[key] = torch.cat(vals, 0) if torch.is_tensor(vals[0]) and vals[0].dim() > 0 else vals[0]
-        return self[key]
+        if key not in self._source:
+            raise KeyError(key)
+        self[key] = val = self._make(key)
+        return val
 
     def __contains__(self, key):
-        return key in self._parts[0]
+        return key in self._source
 
     def keys(self):
-        return self._parts[0].keys()
-
-
-class _ValidRays(dict):
-    """Model outputs of a step whose batch was padded to a multiple of the kernels' ray granularity: per-ray tensors are cut
-    back to the caller's rays on access (grad_theta: its two per-ray halves)."""
-
-    def __init__(self, outputs, n_valid, n_padded):
-        super().__init__()
-        self._o, self._v, self._p = outputs, n_valid, n_padded
-
-    def __missing__(self, key):
-        t = self._o[key]
-        if torch.is_tensor(t) and t.dim() > 0:
-            if key == "grad_theta" and t.shape[0] == 2 * self._p:
-                t = torch.cat([t[:self._v], t[self._p:self._p + self._v]], 0)
-            elif t.shape[0] == self._p:
-                t = t[:self._v]
-            elif t.shape[0] % self._p == 0 and t.shape[0] > self._p:       # flattened (rays x samples, ...) tensors
-                t = t.reshape(self._p, -1, *t.shape[1:])[:self._v].reshape(-1, *t.shape[1:])
-        self[key] = t
-        return t
-
-    def __contains__(self, key):
-        return key in self._o
-
-    def keys(self):
-        return self._o.keys()
-
-
-class _GroupedLosses(dict):
-    """Loss terms of a step that ran as ray groups: each group's terms are already normalised by the whole batch, so a
-    term is the sum over the groups -- formed on first access (logging reads them every 50 steps; summed eagerly they
-    were ten 5-us launches on the main stream between Adam and the next step's first kernel)."""
-
-    def __init__(self, results):
-        super().__init__()
-        self._parts = [r[0] for r in results]
-
-    def __missing__(self, key):
-        vals = [p[key] for p in self._parts]
-        self[key] = torch.stack(vals).sum(0) if torch.is_tensor(vals[0]) else sum(vals)
-        return self[key]
-
-    def __contains__(self, key):
-        return key in self._parts[0]
-
-    def keys(self):
-        return self._parts[0].keys()
-
-    def items(self):
-        return [(k, self[k]) for k in self.keys()]
-
-    def values(self):
-        return [self[k] for k in self.keys()]
+        return self._source.keys()
 
     def __iter__(self):
-        return iter(self.keys())
+        return iter(self._source)
 
     def __len__(self):
-        return len(self._parts[0])
+        return len(self._source)
+
+    def items(self):
+        return [(k, self[k]) for k in self._source]
+
+    def values(self):
+        return [self[k] for k in self._source]
 
     def get(self, key, default=None):
-        return self[key] if key in self else default
+        return self[key] if key in self._source else default
+
+
+class _GroupedOutputs(_LazyDict):
+    """Model outputs of a step that ran as ray groups: per-ray tensors are concatenated in ray order."""
+
+    def __init__(self, results):
+        self._parts = [r[1] for r in results]
+        super().__init__(self._parts[0])
+
+    def _make(self, key):
+        vals = [p[key] for p in self._parts]
+        return torch.cat(vals, 0) if torch.is_tensor(vals[0]) and vals[0].dim() > 0 else vals[0]
+
+
+class _ValidRays(_LazyDict):
+    """Model outputs of a step whose batch was padded to a multiple of the kernels' ray granularity: per-ray tensors are cut
+    back to the caller's rays (volsdf.model.network.cut_rays, one tensor at a time)."""
+
+    def __init__(self, outputs, n_valid, n_padded):
+        super().__init__(outputs)
+        self._v, self._p = n_valid, n_padded
+
+    def _make(self, key):
+        return cut_ray_tensor(key, self._source[key], self._v, self._p)
+
+
+class _GroupedLosses(_LazyDict):
+    """Loss terms of a step that ran as ray groups: each group's terms are already normalised by the whole batch, so a
+    term is the sum over the groups (summed eagerly they were ten 5-us launches on the main stream between Adam and the
+    next step's first kernel)."""
+
+    def __init__(self, results):
+        self._parts = [r[0] for r in results]
+        super().__init__(self._parts[0])
+
+    def _make(self, key):
+        vals = [p[key] for p in self._parts]
+        return torch.stack(vals).sum(0) if torch.is_tensor(vals[0]) else sum(vals)
 
 
 class _Scratch:
@@ -212,7 +211,6 @@ class _Scratch:
     re-allocated by a step of another shape)."""
 
     def __init__(self, dev, is_bg):
-        from .train import BgBackward, MlpBackward, TrainStreams, WGradAccum
         self.dev = dev
         self.tstreams = TrainStreams(dev)
         self.accum = WGradAccum(dev)
@@ -236,59 +234,6 @@ class _Scratch:
         while len(self.bwd) < n:
             self.bwd.append(self._new_bwd())
             self.sides.append(torch.cuda.Stream(device=self.dev))
-
-
-class _LaunchPlan:
-    """The launch sequence of a captured step as a plan of the library (csrc/svs_plan.hip): the capture's nodes and edges
-    read once, then enqueued per step by one call -- plain launches on the step's stream topology, no hipGraphLaunch, no
-    interpreter between the launches (the call releases the GIL)."""
-
-    def __init__(self, graph, side_streams=()):
-        import ctypes
-        from .lib import check, load
-        self._lib, self._check = load(), check
-        self.graph = graph                               # the kernel arguments live in the graph's nodes
-        self.side_streams = list(side_streams)           # torch streams the side chains run on (kept alive here)
-        arr = (ctypes.c_void_p * max(1, len(self.side_streams)))(*[s.cuda_stream for s in self.side_streams])
-        handle = ctypes.c_void_p()
-        check(self._lib.svs_plan_build(ctypes.c_void_p(int(graph.raw_cuda_graph())), arr, len(self.side_streams),
-                                       ctypes.byref(handle)), "svs_plan_build")
-        self.handle = handle
-        counts = (ctypes.c_int * 8)()
-        check(self._lib.svs_plan_info(handle, counts), "svs_plan_info")
-        self.info = dict(zip(("nodes", "kernels", "copies", "memsets", "empty", "streams", "events", "entry_streams"),
-                             list(counts)))
-
-    def describe(self):
-        """one line per node, in issue order (stream, kernel name and launch shape, events waited for / recorded)"""
-        import ctypes
-        buf = ctypes.create_string_buffer(1 << 18)
-        self._check(self._lib.svs_plan_describe(self.handle, buf, len(buf)), "svs_plan_describe")
-        return buf.value.decode()
-
-    def run(self):
-        self._check(self._lib.svs_plan_run(self.handle, torch.cuda.current_stream().cuda_stream), "svs_plan_run")
-
-    def __del__(self):
-        h, self.handle = getattr(self, "handle", None), None
-        if h:
-            try:
-                self._lib.svs_plan_destroy(h)
-            except Exception:
-                pass
-
-
-class _CapturedStep:
-    """One captured launch sequence (hipGraph) of the device part of a step, with the static tensors it reads."""
-
-    def __init__(self):
-        self.graph = None
-        self.plan = None            # graph == "plan": the capture replayed as eager launches by the library
-        self.static = {}            # name -> persistent device tensor (inputs, random draws, step-varying scalars)
-        self.scratch = None
-        self.result = None          # what the eager step would have returned: tensors inside the graph's pool
-        self.hold = None
-        self.calls = 0
 
 
 class TrainStep:
@@ -324,7 +269,6 @@ class TrainStep:
     valid until the next step."""
 
     def __init__(self, model, loss, lr=5e-4, grad_clip=True, world=1, rank=0, groups=None, graph=None, shard_draws=False):
-        import os
         self.model, self.loss = model, loss
         # world > 1 and shard_draws: every rank makes the train-mode draws of the WHOLE batch (world x local rays; the
         # ranks' host generators are in the same state) and keeps the rows of its own rays -- the sharded step then sees
@@ -348,7 +292,6 @@ class TrainStep:
         self.beta_grad = next(it)
         n_sdf = sum(t.numel() for grp in self.grad_out[0] for t in grp if t is not None)
         self._buckets = grad_buckets(n_sdf, self.fp.n)
-        self._early_work = None
         self._comm = None                                   # stream the early bucket is unpacked and reduced on
         dev = self.fp.flat.device
         self.is_bg = hasattr(model, "bg_implicit_network")      # VolSDFNetworkBG: fg + inverted-sphere background
@@ -364,7 +307,7 @@ class TrainStep:
         self.schedule = {}                              # groups == "auto": ray count -> dict(choice, ms_split, ms_whole)
         self._tune = {}
         self._force_groups = None
-        self.scratch = _Scratch(dev, self.is_bg)
+        self.scratch = self._new_scratch()
         if graph is None:
             graph = os.environ.get("SVS_TRAIN_GRAPH", "auto")
             graph = {"0": False, "off": False, "1": True}.get(graph, graph)
@@ -374,13 +317,18 @@ class TrainStep:
         # read into a launch plan and enqueued as plain launches by the library: csrc/svs_plan.hip) | "auto" (plans for
         # single-group batches, eager launches otherwise)
         self.graph = graph
-        self._captured = {}
-        self._graph_pool = None
+        self._captured = CapturedSteps()              # (svs_hip/captured.py)
 
-    # compatibility with code that reached into the former attributes
-    @property
-    def bwd(self):
-        return self.scratch.bwd
+    # what a captured step (svs_hip/captured.py) is made of
+    def _new_scratch(self):
+        return _Scratch(self.fp.flat.device, self.is_bg)
+
+    def _new_plan(self, graph, side_streams):
+        return _LaunchPlan(graph, side_streams)
+
+    def _draw_shard(self):
+        """(world, rank) for model.draw_rays: the whole batch's draws, sliced, only when the ranks share them"""
+        return (self.world, self.rank) if self.world > 1 and self.shard_draws else (1, 0)
 
     @property
     def accum(self):
@@ -411,15 +359,10 @@ class TrainStep:
         return R * (self.samples_per_ray() + 2) < 2 * 256 * 128
 
     def samples_per_ray(self):
-        rs = self.model.ray_sampler
-        return rs.N_samples + rs.N_samples_extra + 2 - (1 if self.is_bg else 0)
+        return self.model.samples_per_ray()
 
     def ray_multiple(self):
-        """The fused MLP kernels work on 32-point wave tiles and the ray samples of a launch (R x S points) must end on a
-        tile boundary, where the eikonal points start: R x S % 32 == 0, i.e. R % 16 == 0 for the DTU model (S = 98) and
-        R % 32 == 0 for the fg + background model (S = 97)."""
-        import math
-        return 32 // math.gcd(self.samples_per_ray(), 32)
+        return self.model.ray_multiple()
 
     def check_batch(self, R):
         """Any ray count > 0 is accepted (as by the reference).  A count that is not a multiple of ray_multiple() is padded
@@ -431,15 +374,11 @@ class TrainStep:
     def _pad_batch(self, model_input, ground_truth):
         """-> (model_input, ground_truth, n_valid): inputs padded to a multiple of ray_multiple() rays, n_valid = the true
         ray count (== the padded count when nothing was added)."""
-        R = model_input["uv"].shape[1]
-        m = self.ray_multiple()
-        pad = (-R) % m
-        if pad == 0:
+        mi, R, n_pad = pad_rays(model_input, self.ray_multiple())
+        if n_pad == R:
             return model_input, ground_truth, R
-        rep = lambda t: torch.cat([t, t[:, -1:].expand(t.shape[0], pad, *t.shape[2:])], 1)
-        mi = dict(model_input)
-        mi["uv"] = rep(model_input["uv"])
-        gt = {k: (rep(v) if torch.is_tensor(v) and v.dim() == 3 and v.shape[1] == R else v) for k, v in ground_truth.items()}
+        gt = {k: (repeat_last_ray(v, n_pad - R) if torch.is_tensor(v) and v.dim() == 3 and v.shape[1] == R else v)
+              for k, v in ground_truth.items()}
         return mi, gt, R
 
     @staticmethod
@@ -460,8 +399,7 @@ class TrainStep:
     def __call__(self, model_input, ground_truth, mvs=None, fast=1):
         """mvs: optional dict(views=[...], same_view=int, img_res=(H,W), inverse_depth=bool) for cost_mapping."""
         model_input, ground_truth, n_valid = self._pad_batch(model_input, ground_truth)
-        self._n_valid = n_valid
-        out = self._step(model_input, ground_truth, mvs, fast)
+        out = self._step(model_input, ground_truth, mvs, fast, n_valid)
         if n_valid == model_input["uv"].shape[1]:
             return out
         losses, outputs = out
@@ -469,11 +407,11 @@ class TrainStep:
 
     TUNE_START, TUNE_STEPS, TUNE_SKIP = 24, 12, 2
 
-    def _groups_for(self, R):
+    def _groups_for(self, R, n_valid=None):
         groups = self._groups_raw(R)
         # a padded batch (up to ray_multiple() - 1 repeated rays at the end): no ray group may consist of padding only
         # (its loss would be a mean over zero rays); such a batch runs as one group
-        if len(groups) > 1 and groups[-1][0] >= getattr(self, "_n_valid", R):
+        if len(groups) > 1 and n_valid is not None and groups[-1][0] >= n_valid:
             return [(0, R)]
         return groups
 
@@ -527,7 +465,7 @@ class TrainStep:
             self.schedule[R] = dict(choice=choice, ms_split=med["split"], ms_whole=med["whole"], spread=spread)
             del self._tune[R]
 
-    def _step(self, model_input, ground_truth, mvs=None, fast=1):
+    def _step(self, model_input, ground_truth, mvs, fast, n_valid):
         m = self.model
         m.train()
         uv = model_input["uv"]
@@ -537,7 +475,7 @@ class TrainStep:
         if self.graph == "auto":
             captured = self._auto_plans(R)
         if captured:
-            out = self._step_captured(model_input, ground_truth, mvs, fast)
+            out = self._captured.step(self, model_input, ground_truth, mvs, fast, n_valid)
             if out is not None:
                 return self._finish(out)
         # (an eager step works on device tensors; a caller of the captured path may hand over the DataLoader's host tensors)
@@ -549,18 +487,12 @@ class TrainStep:
             ground_truth = {k: (v.to(dev, non_blocking=True) if torch.is_tensor(v) else v) for k, v in ground_truth.items()}
         tune = None if captured else self._tune_begin(R)
         try:
-            n_valid = getattr(self, "_n_valid", R)
-            if self.world > 1 and self.shard_draws:
-                rng = m.slice_rng(m.draw_train_rng(n_valid * self.world, uv.device, stream=self.scratch.prep),
-                                  self.rank * n_valid, (self.rank + 1) * n_valid)
-            else:
-                rng = m.draw_train_rng(n_valid, uv.device, stream=self.scratch.prep)  # uploads on the (idle) pack stream
-            if n_valid < R:                      # padded batch: the random stream is consumed as for the caller's rays
-                from volsdf.model.network import pad_rng
-                rng = pad_rng(rng, R)
+            # (uploads on the -- idle -- pack stream)
+            rng = m.draw_rays(n_valid, R, uv.device, *self._draw_shard(), stream=self.scratch.prep)
             self._draws_done()
             gt = {"rgb": ground_truth["rgb"].reshape(-1, 3), "rgb_smooth": ground_truth["rgb_smooth"].reshape(-1, 3)}
-            results, holds = self._device_step(self.scratch, model_input, gt, mvs, fast, rng, dyn=None, serial=self.deterministic)
+            results, holds = self._device_step(self.scratch, model_input, gt, mvs, fast, rng, dyn=None,
+                                               serial=self.deterministic, n_valid=n_valid)
             self._hold = holds
             out = self._finish(results)
         except BaseException:
@@ -603,17 +535,13 @@ class TrainStep:
                 g[k] = torch.cat([t, t.new_zeros((Rg - v,) + tuple(t.shape[1:]))], 0)
         return lo_out, g
 
+    _early_work = None      # Work handle of the first bucket's all-reduce, where _device_step started it (eager steps)
+
     def _finish(self, results):
-        """What follows the gradient: the one collective of a data-parallel step, the fused optimiser, host counters."""
-        early, self._early_work = getattr(self, "_early_work", None), None
-        if early is not None:
-            # the early bucket (radiance / beta / background networks) is being reduced on the comm stream since its GEMM
-            # launch retired; the SDF bucket is complete now; the optimiser waits for both
-            lo, hi = self._buckets[1]
-            allreduce_range(self.fp.grad, lo, hi)
-            early.wait()
-        else:
-            allreduce_flat_grad(self.fp.grad, self.world)
+        """What follows the gradient: the collectives of a data-parallel step, the fused optimiser, host counters."""
+        early, self._early_work = self._early_work, None
+        if data_parallel(self.world):
+            allreduce_buckets(self.fp.grad, self._buckets, early)
         self.opt.step()
         self.model.invalidate_packed()          # the fused kernel bypasses torch's version counters
         self.loss.iter_step += 1
@@ -623,19 +551,20 @@ class TrainStep:
         return _GroupedLosses(results), _GroupedOutputs(results)
 
     # ---- the device part of a step: everything between the uploaded inputs and the flat gradient ---------------------------
-    def _device_step(self, sc, model_input, gt, mvs, fast, rng, dyn, serial=False):
+    def _device_step(self, sc, model_input, gt, mvs, fast, rng, dyn, serial=False, n_valid=None):
         """Launches forward, prior lookup, loss and backward of every ray group and leaves d loss / d parameters (this
         rank's share, before the all-reduce) in the flat gradient.  No host synchronisation, no host decision that
         depends on device data: the sequence can be captured.  dyn: None, or dict(same_view=int32[1], anneal=float32[2])
-        device tensors that carry the step-varying scalars of a captured sequence."""
-        from .train import finalize
+        device tensors that carry the step-varying scalars of a captured sequence.  n_valid: the caller's ray count when the
+        batch was padded (the rays behind it are left out of the loss)."""
         m = self.model
         uv = model_input["uv"]
         R = uv.shape[1]
-        dev = uv.device
-        groups = [(0, R)] if serial else self._groups_for(R)
+        n_valid = R if n_valid is None else n_valid
+        groups = [(0, R)] if serial else self._groups_for(R, n_valid)
         sc.for_groups(len(groups))
         sdf_p, rgb_p = m.mlp_params()
+        bg_wb = m.bg_params() if self.is_bg else None
         main = torch.cuda.current_stream()
         prep = main if serial else sc.prep
         # Only the SDF forward streams are packed on the main stream (the sampler needs them first).  The radiance forward
@@ -658,11 +587,9 @@ class TrainStep:
             m.rendering_network.pack_into(pk)
             rgb_packed = torch.cuda.Event(); rgb_packed.record(prep)
             sc.tstreams.pack(sdf_p, rgb_p)
-            if self.is_bg:
-                bg_sdf_wb, bg_rgb_wb = m.bg_params()
-                sc.bg_bwd.pack(bg_sdf_wb, bg_rgb_wb)
             # the accumulators are zeroed here too: nothing adds into them before a stream has waited for `packed`
             if self.is_bg:
+                sc.bg_bwd.pack(*bg_wb)
                 sc.bg_bwd.zero()
             sc.accum.zero()
             packed = torch.cuda.Event(); packed.record(prep)
@@ -688,310 +615,124 @@ class TrainStep:
                     stream.wait_event(fork)
                 inp = dict(model_input)
                 inp["uv"] = uv[:, lo:hi].contiguous()
-                inp["_skip_xyz"] = True              # the prior lookup below works from (cam, dirs, z): no (R,S,3) point list
+                inp["_skip_xyz"] = True              # the prior lookup works from (cam, dirs, z): no (R,S,3) point list
                 inp["_before_rgb"] = lambda stream=stream: stream.wait_event(rgb_packed)
                 if bg_packed is not None:
                     inp["_before_bg"] = lambda: torch.cuda.current_stream().wait_event(bg_packed)
-                keep = {}
-                # (a capture tolerates the background forward's side stream only below the ORIGIN stream: the note above)
-                m._side_ok_in_capture = gi == 0 and not serial
-                out = m._forward_impl(inp, fast, keep, rng=m.slice_rng(rng, lo, hi))
-                m._side_ok_in_capture = False
-                if mvs is not None:
-                    out['pj'], out['pi'], _ = ops.cost_lookup(mvs["views"], mvs["same_view"], mvs["img_res"],
-                                                              cam=keep["cam_loc"], dirs=keep["ray_dirs"], z=keep["z_vals"],
-                                                              inverse_depth=mvs.get("inverse_depth", False),
-                                                              same_view_dev=dyn["same_view"] if dyn else None)
                 g_gt = {"rgb": gt["rgb"][lo:hi], "rgb_smooth": gt["rgb_smooth"][lo:hi]}
-                n_valid = getattr(self, "_n_valid", R)
                 valid_g = max(0, min(hi, n_valid) - lo)          # rays of this group that are not padding
-                if valid_g == hi - lo:
-                    lo_out = self.loss(out, g_gt, norm=loss_norm(n_valid, self.world), advance=False,
-                                       anneal_dev=dyn["anneal"] if dyn else None,
-                                       grad_theta_out=sc.bwd[gi].grad_extra_out(keep["src"].n, keep["rgb_flat"].shape[0]))
-                    g = self.loss.last_grads
-                else:
-                    lo_out, g = self._loss_on_valid(out, g_gt, valid_g, hi - lo, loss_norm(n_valid, self.world),
-                                                    dyn["anneal"] if dyn else None)
+                keep, out, lo_out, g = self._group_forward_loss(sc.bwd[gi], inp, g_gt, mvs, fast, m.slice_rng(rng, lo, hi), dyn,
+                                                                valid_g, loss_norm(n_valid, self.world),
+                                                                side_ok=gi == 0 and not serial)
                 stream.wait_event(packed)
-                if self.is_bg:
-                    # the loss read depth_values_all (fg + bg, loss.py:72-73): its gradient enters as such
-                    d_sdf, d_rgb, d_bo, d_brgb, d_beta = ops.composite_bg_bwd(
-                        keep["z_vals"], keep["z_max"], keep["sdf"], keep["rgb_flat"], keep["depth_scale"], m.density.beta,
-                        m.density.beta_min_value, keep["z_bg"], keep["bg_out0"], keep["bg_rgb"], g["rgb_values"],
-                        g["weights"], None, d_depth_values_all=g["depth_values"], bg_depth=keep["bg_depth"],
-                        d_sdf_out=sc.bwd[gi].sdf_grad_out(keep["src"].n, keep["rgb_flat"].shape[0]),
-                        d_beta_out=beta_out(gi))
-                    # The background networks' backward (radiance backward, pass B, weight gradients: three launches that
-                    # depend on compositing's backward only) runs BESIDE the fg backward on a stream of its own -- at 256
-                    # rays per GPU (config 4 over 8 GPUs) its 64 workgroups and the fg sweeps' 200 fit the chip together.
-                    # Like the radiance weight-gradient stream it joins the ORIGIN stream, not its parent group stream.
-                    if serial or os.environ.get("SVS_BG_SIDE", "1") == "0":
-                        sc.bg_bwd.accumulate(keep, d_brgb, d_bo, slot=gi)
-                    else:
-                        # (a stream of its own: re-using the stream of the group's background FORWARD was measured slower at
-                        # 1024 rays, 4.87 against 4.58 ms)
-                        bs = sc.bg_stream(gi)
-                        ev = torch.cuda.Event(); ev.record(stream)
-                        with torch.cuda.stream(bs):
-                            bs.wait_event(ev)
-                            sc.bg_bwd.accumulate(keep, d_brgb, d_bo, slot=gi)
-                            evj = torch.cuda.Event(); evj.record(bs); joins.append(evj)
+                defer = fold and gi == 1
+                d_sdf, d_rgb, done = self._group_backward(sc, gi, keep, g, beta_out(gi), joins, serial, defer,
+                                                          extra=folded if (fold and gi == 0) else None)
+                if defer:
+                    folded = done
                 else:
-                    gw = m.white_bkgd_weight_grad(g["rgb_values"], g["weights"], keep["z_vals"].shape[1])
-                    d_sdf, d_rgb, d_beta = ops.composite_bwd(
-                        keep["z_vals"], keep["sdf"], keep["rgb_flat"], keep["depth_scale"], m.density.beta,
-                        m.density.beta_min_value, g["rgb_values"], gw, g["depth_values"],
-                        d_sdf_out=sc.bwd[gi].sdf_grad_out(keep["src"].n, keep["rgb_flat"].shape[0]),
-                        d_beta_out=beta_out(gi))
-                if d_beta.data_ptr() != beta_out(gi).data_ptr():
-                    beta_out(gi).copy_(d_beta)
-                if fold and gi == 1:
-                    folded = sc.bwd[gi].accumulate(keep, d_rgb, d_sdf, g["grad_theta"], wait=False, side=False, defer_wgrad=True)
-                else:
-                    joins.append(sc.bwd[gi].accumulate(keep, d_rgb, d_sdf, g["grad_theta"], wait=False,
-                                                       side=not serial,
-                                                       extra=folded if (fold and gi == 0) else None))
+                    joins.append(done)
                 results[gi] = (lo_out, out)
                 holds[gi] = (keep, g, d_sdf, d_rgb, inp, g_gt, folded)
                 if gi:
                     ev = torch.cuda.Event(); ev.record(stream); joins.append(ev)
-        # Data-parallel eager steps (SVS_DP_BUCKETS=0: one collective at the end): everything but the SDF network's gradients
-        # is final once the radiance GEMM launch (and the background backward) has retired -- `joins` holds exactly those
-        # events plus the small group's -- while pass A / pass B / the SDF GEMM still run on `main`.  A comm stream waits for
-        # them, unpacks the radiance (and background) gradients into the flat gradient and starts the all-reduce of that
-        # bucket; `_finish` reduces the SDF bucket and waits for both.  Captured sequences keep the single collective (the
-        # capture ends at the flat gradient; a collective inside a launch plan is not something the plan builder replays).
-        early = (dyn is None and not serial and _DP_BUCKETS and data_parallel(self.world)
+        early = (dyn is None and not serial and data_parallel(self.world)
                  and not torch.cuda.is_current_stream_capturing())
         if early:
-            if self._comm is None:
-                self._comm = torch.cuda.Stream(device=dev)
-            comm = self._comm
-            with torch.cuda.stream(comm):
-                for ev in joins:
-                    comm.wait_event(ev)
-                finalize(sc.accum, sdf_p, rgb_p, out=self.grad_out, nets=(1,))
-                if self.is_bg:
-                    sc.bg_bwd.finalize(bg_sdf_wb, bg_rgb_wb, out=self.bg_grad_out)
-                if len(groups) > 1:
-                    torch.sum(sc.d_beta[:len(groups)], dim=0, keepdim=True, out=self.beta_grad.view(1))
-                lo, hi = self._buckets[0]
-                self._early_work = allreduce_range(self.fp.grad, lo, hi, async_op=True)
+            self._early_work = self._start_early_bucket(sc, joins, sdf_p, rgb_p, bg_wb, len(groups))
         for ev in joins:
             main.wait_event(ev)
         finalize(sc.accum, sdf_p, rgb_p, out=self.grad_out, nets=(0,) if early else (0, 1))
-        if self.is_bg and not early:
-            sc.bg_bwd.finalize(bg_sdf_wb, bg_rgb_wb, out=self.bg_grad_out)
-        if len(groups) == 1 or early:
-            pass                                         # (written in place: d_beta_out above / summed on the comm stream)
-        else:
-            torch.sum(sc.d_beta[:len(groups)], dim=0, keepdim=True, out=self.beta_grad.view(1))
+        if not early:
+            self._unpack_rest(sc, bg_wb, len(groups))
         return results, holds
 
-    # ---- captured steps -----------------------------------------------------------------------------------------------------
-    def _capture_key(self, model_input, mvs, fast):
-        R = model_input["uv"].shape[1]
-        mk = None
+    def _group_forward_loss(self, bwd, inp, g_gt, mvs, fast, rng, dyn, valid_g, norm, side_ok):
+        """One ray group on the current stream: forward, MVS prior lookup, fused loss with its output gradients.
+        -> (keep: what the backward needs, model outputs, loss terms, d loss / d outputs).  valid_g: the group's rays that are
+        not padding; side_ok: the capture tolerates the background forward's side stream (only below the ORIGIN stream)."""
+        m = self.model
+        keep = {}
+        m._side_ok_in_capture = side_ok
+        out = m._forward_impl(inp, fast, keep, rng=rng)
+        m._side_ok_in_capture = False
         if mvs is not None:
-            # everything ops.cost_lookup hands to the kernel BY VALUE is baked into the capture: the cost / z range
-            # addresses and shapes, and the camera parameters of every view (an MVS re-run can return a re-used address
-            # with different cameras)
-            def view_key(v):
-                ptrs = tuple((int(v[k].data_ptr()), tuple(v[k].shape)) for k in ("cost", "z_mvs") if torch.is_tensor(v.get(k)))
-                cams = []
-                for k in sorted(v):
-                    if k in ("cost", "z_mvs"):
-                        continue
-                    x = v[k]
-                    if torch.is_tensor(x):
-                        cams.append((k, int(x.data_ptr()), x._version, tuple(x.shape)))
-                    else:
-                        cams.append((k, repr(x)))
-                return ptrs, tuple(cams)
-            mk = (len(mvs["views"]), tuple(mvs["img_res"]), bool(mvs.get("inverse_depth", False)),
-                  tuple(view_key(v) for v in mvs["views"]))
-        return (R, getattr(self, "_n_valid", R), tuple(self._groups_for(R)), fast, mk, str(self.fp.flat.device), self.graph)
+            out['pj'], out['pi'], _ = ops.cost_lookup(mvs["views"], mvs["same_view"], mvs["img_res"],
+                                                      cam=keep["cam_loc"], dirs=keep["ray_dirs"], z=keep["z_vals"],
+                                                      inverse_depth=mvs.get("inverse_depth", False),
+                                                      same_view_dev=dyn["same_view"] if dyn else None)
+        anneal = dyn["anneal"] if dyn else None
+        Rg = inp["uv"].shape[1]
+        if valid_g == Rg:
+            lo_out = self.loss(out, g_gt, norm=norm, advance=False, anneal_dev=anneal,
+                               grad_theta_out=bwd.grad_extra_out(keep["src"].n, keep["rgb_flat"].shape[0]))
+            return keep, out, lo_out, self.loss.last_grads
+        lo_out, g = self._loss_on_valid(out, g_gt, valid_g, Rg, norm, anneal)
+        return keep, out, lo_out, g
 
-    def _upload(self, cs, model_input, ground_truth, mvs):
-        """Host -> static tensors of a captured step, on the current stream (ordered before the replay).  Everything
-        except the random draws -- pixels, camera, target colours, the two annealing scalars, the rendered-view index --
-        has a fixed place in ONE static device buffer and travels in one transfer from a 4-deep ring of pinned staging
-        buffers (the host waits for the transfer made FOUR steps ago, i.e. never in practice: with one staging buffer it
-        waited for the previous step's, which sits behind that step's kernels -- host and GPU took turns).  An input that
-        already lives on the device is copied into its place by a device copy behind the transfer."""
-        st = cs.static
-        dev = self.fp.flat.device
-        annealed, anneal_sparse = self.loss.anneal_state()
-        target = ground_truth["rgb_smooth"] if annealed else ground_truth["rgb"]
-        origin = {k: model_input[k] for k in ("uv", "intrinsics", "pose")}
-        origin["target"] = target
-        pieces = [(k, model_input[k]) for k in ("uv", "intrinsics", "pose")] + [("target", target.reshape(-1, 3))]
-        if "_all" not in st:
-            off = 4                                          # words 0..1: annealing state, word 2: rendered-view index (int32)
-            st["_layout"] = {}
-            for k, src in pieces:
-                st["_layout"][k] = (off, tuple(src.shape))
-                off += (src.numel() + 3) // 4 * 4            # 16-byte aligned pieces
-            st["_all"] = torch.zeros(off, dtype=torch.float32, device=dev)
-            st["_ring"] = [dict(pin=torch.zeros(off, dtype=torch.float32).pin_memory(), ev=None) for _ in range(4)]
-            st["_i"] = 0
-            for k, (o, shape) in st["_layout"].items():
-                n = 1
-                for d in shape:
-                    n *= d
-                st[k] = st["_all"][o:o + n].view(shape)
-            st["anneal"] = st["_all"][0:2]
-            st["same_view"] = st["_all"][2:3].view(torch.int32)
-            st["rng"] = {}
-        slot = st["_ring"][st["_i"] % 4]
-        st["_i"] += 1
-        if slot["ev"] is not None:
-            slot["ev"].synchronize()
-        pin = slot["pin"]
-        pin[0] = 1.0 if annealed else 0.0
-        pin[1] = float(anneal_sparse)
-        pin[2:3].view(torch.int32)[0] = int(mvs["same_view"]) if mvs is not None else -1
-        on_device, host = [], False
-        seen = st.setdefault("_seen", {})
-        for k, src in pieces:
-            o, shape = st["_layout"][k]
-            if tuple(src.shape) != shape:
-                raise ValueError(f"captured step: input {k} changed shape {shape} -> {tuple(src.shape)}")
-            if src.is_cuda:
-                # a device tensor the caller hands over unchanged step after step is in place: the SAME tensor object (kept
-                # referenced here, so its storage cannot have been handed to another tensor) at the same version
-                tag = (origin[k], origin[k]._version)
-                old = seen.get(k)
-                if old is None or old[0] is not tag[0] or old[1] != tag[1]:
-                    on_device.append((k, src, tag))
+    def _group_backward(self, sc, gi, keep, g, beta_out, joins, serial, defer, extra):
+        """Ray group gi's backward on the current stream, from d loss / d outputs `g` into the accumulators: compositing,
+        the background networks (beside the rest, on a stream of their own whose end goes into `joins`), the fused MLPs.
+        -> (d_sdf, d_rgb, what MlpBackward.accumulate returned: the radiance weight-gradient stream's end, or with `defer`
+        the group's weight-gradient jobs for group 0 to take along as its `extra`)."""
+        m, bwd = self.model, sc.bwd[gi]
+        d_sdf_out = bwd.sdf_grad_out(keep["src"].n, keep["rgb_flat"].shape[0])
+        if self.is_bg:
+            # the loss read depth_values_all (fg + bg, loss.py:72-73): its gradient enters as such
+            d_sdf, d_rgb, d_bo, d_brgb, d_beta = ops.composite_bg_bwd(
+                keep["z_vals"], keep["z_max"], keep["sdf"], keep["rgb_flat"], keep["depth_scale"], m.density.beta,
+                m.density.beta_min_value, keep["z_bg"], keep["bg_out0"], keep["bg_rgb"], g["rgb_values"],
+                g["weights"], None, d_depth_values_all=g["depth_values"], bg_depth=keep["bg_depth"],
+                d_sdf_out=d_sdf_out, d_beta_out=beta_out)
+            # The background networks' backward (radiance backward, pass B, weight gradients: three launches that
+            # depend on compositing's backward only) runs BESIDE the fg backward on a stream of its own -- at 256
+            # rays per GPU (config 4 over 8 GPUs) its 64 workgroups and the fg sweeps' 200 fit the chip together.
+            # Like the radiance weight-gradient stream it joins the ORIGIN stream, not its parent group stream.
+            if serial:
+                sc.bg_bwd.accumulate(keep, d_brgb, d_bo, slot=gi)
             else:
-                pin[o:o + src.numel()].copy_(src.reshape(-1))
-                host = True
-                seen.pop(k, None)
-        head = (float(pin[0]), float(pin[1]), int(pin[2:3].view(torch.int32)[0]))
-        if host:
-            # (pieces that live on the device keep their place in the static buffer: the transfer writes their region of the
-            # staging buffer -- stale -- over them, so they are copied again behind it)
-            if any(src.is_cuda for _, src in pieces):
-                on_device = [(k, src, (origin[k], origin[k]._version)) for k, src in pieces if src.is_cuda]
-            ops.stage_in(st["_all"], pin)
-        elif st.get("_head") != head:
-            ops.stage_in(st["_all"][:4], pin[:4])                  # the three scalars only
-        if host or st.get("_head") != head:
-            slot["ev"] = torch.cuda.Event()
-            slot["ev"].record()
-            st["_head"] = head
-        for k, src, tag in on_device:
-            st[k].copy_(src, non_blocking=True)
-            seen[k] = tag
-        n_valid, n_pad = getattr(self, "_n_valid", model_input["uv"].shape[1]), model_input["uv"].shape[1]
-        m = self.model
-        sharded = self.world > 1 and self.shard_draws
-        if sharded or n_valid < n_pad:
-            # (as the eager step: a data-parallel rank draws for the whole batch and keeps its rays' rows; a padded batch
-            # consumes the random stream of the caller's rays)
-            if sharded:
-                drawn = m.slice_rng(m.draw_train_rng(n_valid * self.world, dev), self.rank * n_valid, (self.rank + 1) * n_valid)
-            else:
-                drawn = m.draw_train_rng(n_valid, dev)
-            if n_valid < n_pad:
-                from volsdf.model.network import pad_rng
-                drawn = pad_rng(drawn, n_pad)
-            for k, v in drawn.items():
-                if k.startswith("_"):
-                    continue
-                if k not in st["rng"]:
-                    st["rng"][k] = torch.empty_like(v)
-                st["rng"][k].copy_(v, non_blocking=True)
+                # (a stream of its own: re-using the stream of the group's background FORWARD was measured slower at
+                # 1024 rays, 4.87 against 4.58 ms)
+                bs = sc.bg_stream(gi)
+                ev = torch.cuda.Event(); ev.record()
+                with torch.cuda.stream(bs):
+                    bs.wait_event(ev)
+                    sc.bg_bwd.accumulate(keep, d_brgb, d_bo, slot=gi)
+                    evj = torch.cuda.Event(); evj.record(bs); joins.append(evj)
         else:
-            m.draw_train_rng(n_pad, dev, out=st["rng"])
+            gw = m.white_bkgd_weight_grad(g["rgb_values"], g["weights"], keep["z_vals"].shape[1])
+            d_sdf, d_rgb, d_beta = ops.composite_bwd(
+                keep["z_vals"], keep["sdf"], keep["rgb_flat"], keep["depth_scale"], m.density.beta,
+                m.density.beta_min_value, g["rgb_values"], gw, g["depth_values"], d_sdf_out=d_sdf_out, d_beta_out=beta_out)
+        if d_beta.data_ptr() != beta_out.data_ptr():
+            beta_out.copy_(d_beta)
+        if defer:
+            return d_sdf, d_rgb, bwd.accumulate(keep, d_rgb, d_sdf, g["grad_theta"], wait=False, side=False, defer_wgrad=True)
+        return d_sdf, d_rgb, bwd.accumulate(keep, d_rgb, d_sdf, g["grad_theta"], wait=False, side=not serial, extra=extra)
 
-    def _step_captured(self, model_input, ground_truth, mvs, fast):
-        """-> results of the step (replayed from its graph), or None when this call has to run eagerly: the first step of
-        a configuration runs eagerly (it also performs the one-time kernel attribute set-up), the second is captured."""
-        key = self._capture_key(model_input, mvs, fast)
-        cs = self._captured.get(key)
-        if cs is None:
-            if len(self._captured) >= 4:                 # a few configurations at most (stages, render previews)
-                # the evicted graph's result tensors may still be the caller's: it is destroyed one step later
-                self._evicted = self._captured.pop(next(iter(self._captured)))
-            cs = self._captured[key] = _CapturedStep()
-        cs.calls += 1
-        if cs.calls == 1:
-            return None
-        m = self.model
-        self._upload(cs, model_input, ground_truth, mvs)
-        self._draws_done()
-        if cs.graph is None:
-            st = cs.static
-            cs.scratch = _Scratch(self.fp.flat.device, self.is_bg)
-            inp = dict(model_input)
-            inp.update(uv=st["uv"], intrinsics=st["intrinsics"], pose=st["pose"])
-            gt = {"rgb": st["target"], "rgb_smooth": st["target"]}
-            dyn = dict(same_view=st["same_view"], anneal=st["anneal"])
-            # one eager pass over the capture's own scratch first: what a step allocates once and keeps (the backward's blocks,
-            # zero-initialised: ~1 GB per 256 rays) must exist BEFORE the recording -- allocated inside it, the zero fills would
-            # be recorded as launches and repeated by every replay (that, not the replay mechanism, was what made the captured
-            # step of round 3 slower than the eager one)
-            # -- on the stream the recording will run on: the model keeps per-stream workspaces (the sampler's, the side
-            # streams of the background networks), which would otherwise be created, and zero-filled, inside the recording
-            if getattr(self, "_capture_stream", None) is None:
-                self._capture_stream = torch.cuda.Stream(device=self.fp.flat.device)
-            cap = self._capture_stream
-            cap.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(cap):
-                self._device_step(cs.scratch, inp, gt, mvs, fast, st["rng"], dyn, serial=self.graph == "linear")
-            torch.cuda.current_stream().wait_stream(cap)
-            m.invalidate_packed()                        # the capture must contain the weight packing
-            plan_mode = self.graph in ("plan", "auto")
-            # (keep_graph: the capture stays a hipGraph_t that svs_plan_build can read; it is never instantiated)
-            graph = torch.cuda.CUDAGraph(keep_graph=True) if plan_mode else torch.cuda.CUDAGraph()
-            if self._graph_pool is None:
-                self._graph_pool = torch.cuda.graph_pool_handle()
-            # (thread_local: a helper thread that prepares the next batch meanwhile -- VolOpt.run -- does not disturb the capture)
-            # No cyclic garbage collection while the recording runs: a collection that finds an earlier TrainStep's
-            # capture (a graph + its memory pool) would free device memory in the middle of this one, which the runtime
-            # refuses -- from a destructor, i.e. the process aborts.  (torch.cuda.graph collects once on entry.)
-            import gc
-            gc_was_on = gc.isenabled()
-            gc.disable()
-            try:
-                with torch.cuda.graph(graph, pool=self._graph_pool, stream=cap, capture_error_mode="thread_local"):
-                    cs.result, cs.hold = self._device_step(cs.scratch, inp, gt, mvs, fast, st["rng"], dyn,
-                                                           serial=self.graph == "linear")
-            finally:
-                if gc_was_on:
-                    gc.enable()
-            cs.graph = graph
-            if plan_mode:
-                # the side chains run on streams of the capture's own scratch (torch pool streams, as in the eager schedule)
-                sc = cs.scratch
-                side = ([sc.prep] + list(sc.sides) + [b._side for b in sc.bwd] + list(getattr(m, "_bg_streams", {}).values())
-                        + list(sc._bg_streams.values()))
-                try:
-                    cs.plan = _LaunchPlan(graph, [x for x in side if x is not None])
-                except _lib.SvsError as e:
-                    # "auto" never costs a run: a sequence the plan builder refuses (a node type it cannot replay) is
-                    # launched as the graph it is (hipGraphLaunch: same results, slower above ~500 rays)
-                    if self.graph != "auto":
-                        raise
-                    import warnings
-                    warnings.warn(f"launch plan refused, this configuration replays its hipGraph instead: {e}")
-                    cs.plan = None
-                    graph.instantiate()
-                    if os.environ.get("SVS_PLAN_DEBUG") == "1":
-                        import sys
-                        print(f"launch plan refused: {e}", file=sys.stderr)
-                if cs.plan is not None and os.environ.get("SVS_PLAN_DEBUG") == "1":
-                    import sys
-                    print(cs.plan.info, file=sys.stderr)
-                    print(cs.plan.describe(), file=sys.stderr)
-        if cs.plan is not None:
-            cs.plan.run()
-        else:
-            cs.graph.replay()
-        return cs.result
+    def _unpack_rest(self, sc, bg_wb, n_groups):
+        """what the first gradient bucket holds besides the radiance network: the background networks, d loss / d beta"""
+        if self.is_bg:
+            sc.bg_bwd.finalize(*bg_wb, out=self.bg_grad_out)
+        if n_groups > 1:                                 # (one group wrote it in place: d_beta_out)
+            torch.sum(sc.d_beta[:n_groups], dim=0, keepdim=True, out=self.beta_grad.view(1))
+
+    def _start_early_bucket(self, sc, joins, sdf_p, rgb_p, bg_wb, n_groups):
+        """Data-parallel eager steps: everything but the SDF network's gradients is final once the radiance GEMM launch
+        (and the background backward) has retired -- `joins` holds exactly those events plus the small group's -- while pass A /
+        pass B / the SDF GEMM still run on the main stream.  A comm stream waits for them, unpacks the first bucket into the flat
+        gradient and starts its all-reduce -> the Work handle; `_finish` posts the SDF bucket and waits for both.  Captured
+        sequences end at the flat gradient (a collective is not something the plan builder replays): their buckets are
+        posted by `_finish`, the same two in the same order (allreduce_buckets)."""
+        if self._comm is None:
+            self._comm = torch.cuda.Stream(device=self.fp.flat.device)
+        with torch.cuda.stream(self._comm):
+            for ev in joins:
+                self._comm.wait_event(ev)
+            finalize(sc.accum, sdf_p, rgb_p, out=self.grad_out, nets=(1,))
+            self._unpack_rest(sc, bg_wb, n_groups)
+            lo, hi = self._buckets[0]
+            return allreduce_range(self.fp.grad, lo, hi, async_op=True)
 
 
 def loss_norm(n_rays_local, world):

@@ -5,6 +5,8 @@ forward() contract (volsdf/model/network.py), evaluated by the fused HIP kernels
 when s-volsdf_amd/ precedes the reference on sys.path; checkpoints interchange with the reference
 (`implicit_network.lin{0..8}.{weight_g,weight_v,bias}`, `rendering_network.lin{0..4}.*`, `density.beta`).
 """
+import math
+
 import numpy as np
 import torch
 import torch.nn as nn
@@ -138,23 +140,10 @@ class RenderingNetwork(nn.Module):
         return pk
 
 
-class VolSDFNetwork(nn.Module):
-    """network.py:192-295.  forward(input, fast) -> dict with the reference's keys."""
-
-    def __init__(self, conf):
-        super().__init__()
-        self.feature_vector_size = conf.get_int('feature_vector_size')
-        self.scene_bounding_sphere = conf.get_float('scene_bounding_sphere', default=1.0)
-        self.white_bkgd = conf.get_bool('white_bkgd', default=False)
-        self.register_buffer("bg_color", torch.tensor(conf.get_list("bg_color", default=[1.0, 1.0, 1.0])).float(),
-                             persistent=False)
-        self.implicit_network = ImplicitNetwork(self.feature_vector_size,
-                                                0.0 if self.white_bkgd else self.scene_bounding_sphere,
-                                                **conf.get_config('implicit_network'))
-        self.rendering_network = RenderingNetwork(self.feature_vector_size, **conf.get_config('rendering_network'))
-        self.density = LaplaceDensity(**conf.get_config('density'))
-        self.ray_sampler = ErrorBoundSampler(self.scene_bounding_sphere, **conf.get_config('ray_sampler'))
-        self._pk = None
+class VolSDFBase(nn.Module):
+    """What VolSDFNetwork and VolSDFNetworkBG share: the foreground networks' packed weights and parameter order, and the
+    train-mode random draws.  A subclass creates implicit_network, rendering_network, density and ray_sampler."""
+    _pk = None
 
     def packed_mlp(self, rgb=True):
         """Packed weight streams (re-packed only when a parameter changed).  rgb=False: the SDF streams only (the fused
@@ -168,7 +157,7 @@ class VolSDFNetwork(nn.Module):
 
     # ---- parameters in a fixed order (shared by the autograd bridge and the fused trainer) -----------------
     def mlp_params(self):
-        """((sdf weight_v, weight_g, bias), (rgb weight_v, weight_g, bias)) as lists per layer."""
+        """((sdf weight_v, weight_g, bias), (rgb weight_v, weight_g, bias)) of the foreground networks, as lists per layer."""
         def grab(net, n):
             lins = [getattr(net, f"lin{l}") for l in range(n)]
             if net.weight_norm:
@@ -177,9 +166,8 @@ class VolSDFNetwork(nn.Module):
         return grab(self.implicit_network, 9), grab(self.rendering_network, 5)
 
     def _flat_param_list(self):
-        (sv, sg, sb), (rv, rg, rb) = self.mlp_params()
         out = []
-        for v, g, b in ((sv, sg, sb), (rv, rg, rb)):
+        for v, g, b in self.mlp_params():
             for l in range(len(v)):
                 out += [v[l]] + ([g[l]] if g is not None else []) + [b[l]]
         return out + [self.density.beta]
@@ -190,17 +178,20 @@ class VolSDFNetwork(nn.Module):
         if self._pk is not None:
             self._pk._sdf_key = self._pk._rgb_key = None
 
-    def forward(self, input, fast=-1):
-        if self.training and torch.is_grad_enabled():
-            params = self._flat_param_list()
-            input, n_valid, n_pad = pad_rays(input, self.ray_sampler.N_samples + self.ray_sampler.N_samples_extra + 2)
-            res = _RenderFunction.apply(self, input, fast, *params)
-            rgb_values, depth_values, weights, grad_theta, depth_vals, xyz = res
-            out = {'rgb_values': rgb_values, 'depth_values': depth_values, 'depth_vals': depth_vals, 'weights': weights,
-                   'xyz': xyz, 'grad_theta': grad_theta}
-            return cut_rays(out, n_valid, n_pad)
-        return self._forward_impl(input, fast, None)
+    # ---- batch geometry -------------------------------------------------------------------------------------
+    def samples_per_ray(self):
+        """Composited samples per ray: the sampler's N + extra + 2; the inverse-sphere sampler's last one is the foreground's
+        far bound (z_max), not a sample."""
+        rs = self.ray_sampler
+        return rs.N_samples + rs.N_samples_extra + 2 - (1 if rs.inverse_sphere_bg else 0)
 
+    def ray_multiple(self):
+        """The fused MLP kernels work on 32-point wave tiles and the ray samples of a launch (R x S points) must end on a
+        tile boundary, where the eikonal points start: R x S % 32 == 0, i.e. R % 16 == 0 for the DTU model (S = 98) and
+        R % 32 == 0 for the fg + background model (S = 97)."""
+        return 32 // math.gcd(self.samples_per_ray(), 32)
+
+    # ---- train-mode random draws ----------------------------------------------------------------------------
     def draw_train_rng(self, R, dev, out=None, stream=None):
         """All train-mode random draws of one forward for R rays, in the reference's order (sampler draws, then the
         uniform eikonal points of network.py:261).  Slices of it can be handed to _forward_impl per ray group."""
@@ -221,6 +212,58 @@ class VolSDFNetwork(nn.Module):
     def slice_rng(rng, lo, hi):
         return {k: (v if k == "perm" else v[lo:hi].contiguous()) for k, v in rng.items() if not k.startswith("_")}
 
+    def draw_rays(self, n_valid, n_pad, dev, world=1, rank=0, out=None, stream=None):
+        """The train-mode draws of a batch of n_valid rays padded to n_pad.  The CPU generator is consumed as for the caller's
+        rays: the padding repeats the last ray's rows (pad_rng).  world > 1: this is rank `rank`'s shard of a batch of
+        world x n_valid rays -- the draws of the WHOLE batch are made (the ranks' generators are in the same state) and
+        this rank's rows kept, so the sharded step sees the draws the single-GPU step of that batch sees.
+        out: persistent device tensors to fill (a captured step's static inputs); stream: as draw_train_rng."""
+        if world == 1 and n_valid == n_pad:
+            return self.draw_train_rng(n_pad, dev, out=out, stream=stream)
+        rng = self.draw_train_rng(n_valid * world, dev, stream=stream)
+        if world > 1:
+            rng = self.slice_rng(rng, rank * n_valid, (rank + 1) * n_valid)
+        if n_valid < n_pad:
+            rng = pad_rng(rng, n_pad)
+        if out is None:
+            return rng
+        for k, v in rng.items():
+            if k.startswith("_"):
+                continue
+            if k not in out:
+                out[k] = torch.empty_like(v)
+            out[k].copy_(v, non_blocking=True)
+        return out
+
+
+class VolSDFNetwork(VolSDFBase):
+    """network.py:192-295.  forward(input, fast) -> dict with the reference's keys."""
+
+    def __init__(self, conf):
+        super().__init__()
+        self.feature_vector_size = conf.get_int('feature_vector_size')
+        self.scene_bounding_sphere = conf.get_float('scene_bounding_sphere', default=1.0)
+        self.white_bkgd = conf.get_bool('white_bkgd', default=False)
+        self.register_buffer("bg_color", torch.tensor(conf.get_list("bg_color", default=[1.0, 1.0, 1.0])).float(),
+                             persistent=False)
+        self.implicit_network = ImplicitNetwork(self.feature_vector_size,
+                                                0.0 if self.white_bkgd else self.scene_bounding_sphere,
+                                                **conf.get_config('implicit_network'))
+        self.rendering_network = RenderingNetwork(self.feature_vector_size, **conf.get_config('rendering_network'))
+        self.density = LaplaceDensity(**conf.get_config('density'))
+        self.ray_sampler = ErrorBoundSampler(self.scene_bounding_sphere, **conf.get_config('ray_sampler'))
+
+    def forward(self, input, fast=-1):
+        if self.training and torch.is_grad_enabled():
+            params = self._flat_param_list()
+            input, n_valid, n_pad = pad_rays(input, self.ray_multiple())
+            res = _RenderFunction.apply(self, input, fast, *params)
+            rgb_values, depth_values, weights, grad_theta, depth_vals, xyz = res
+            out = {'rgb_values': rgb_values, 'depth_values': depth_values, 'depth_vals': depth_vals, 'weights': weights,
+                   'xyz': xyz, 'grad_theta': grad_theta}
+            return cut_rays(out, n_valid, n_pad)
+        return self._forward_impl(input, fast, None)
+
     def _forward_impl(self, input, fast, keep, rng=None):
         """network.py:206-279 on the HIP kernels.  keep: dict that receives what the backward kernels need.
         rng: optional pre-drawn random draws for exactly these rays (train mode)."""
@@ -233,10 +276,7 @@ class VolSDFNetwork(nn.Module):
         num_pixels = ray_dirs.shape[0]
 
         if self.training and rng is None:
-            n_valid = input.get("_valid_rays", num_pixels)
-            rng = self.draw_train_rng(n_valid, ray_dirs.device)
-            if n_valid < num_pixels:
-                rng = pad_rng(rng, num_pixels)
+            rng = self.draw_rays(input.get("_valid_rays", num_pixels), num_pixels, ray_dirs.device)
         z_vals, z_samples_eik = self.ray_sampler.get_z_vals(ray_dirs, cam_loc, self, fast=fast,
                                                             iter_step=input.get("iter_step", 1), rng=rng)
         N_samples = z_vals.shape[1]
@@ -333,38 +373,44 @@ def pad_rng(rng, n_pad):
     return out
 
 
-def pad_rays(input, samples_per_ray):
-    """The backward kernels want rays x samples to be a multiple of 32 (svs_hip/train.py): a batch that is not gets its last
-    ray repeated.  -> (input, rays of the caller, rays after padding)."""
-    import math
+def repeat_last_ray(t, pad):
+    """(B, R, ...) -> (B, R + pad, ...): the last ray repeated"""
+    return torch.cat([t, t[:, -1:].expand(t.shape[0], pad, *t.shape[2:])], 1)
+
+
+def pad_rays(input, ray_multiple):
+    """The backward kernels want rays x samples to be a multiple of 32 (VolSDFBase.ray_multiple): a batch that is not a
+    multiple of `ray_multiple` rays gets its last ray repeated; the padding rays run through the kernels and are cut from
+    what the caller sees (cut_rays).  -> (input, rays of the caller, rays after padding)."""
     R = input["uv"].shape[1]
-    pad = (-R) % (32 // math.gcd(samples_per_ray, 32))
+    pad = (-R) % ray_multiple
     if pad == 0:
         return input, R, R
-    uv = input["uv"]
     inp = dict(input)
-    inp["uv"] = torch.cat([uv, uv[:, -1:].expand(uv.shape[0], pad, uv.shape[2])], 1)
-    inp["_valid_rays"] = R                  # _forward_impl draws for R rays and repeats the last ray's draws (pad_rng)
+    inp["uv"] = repeat_last_ray(input["uv"], pad)
+    inp["_valid_rays"] = R                  # _forward_impl draws for R rays and repeats the last ray's draws (draw_rays)
     return inp, R, R + pad
+
+
+def cut_ray_tensor(key, t, n_valid, n_pad):
+    """One model output of a padded batch without the padding rays: per-ray tensors, grad_theta (its two per-ray halves) and
+    flattened (rays x samples, ...) tensors are sliced, anything else is returned as it is."""
+    if n_valid == n_pad or not torch.is_tensor(t) or t.dim() == 0:
+        return t
+    if key == "grad_theta" and t.shape[0] == 2 * n_pad:
+        return torch.cat([t[:n_valid], t[n_pad:n_pad + n_valid]], 0)
+    if t.shape[0] == n_pad:
+        return t[:n_valid]
+    if t.shape[0] % n_pad == 0 and t.shape[0] > n_pad:                      # flattened (rays x samples, ...) tensors
+        return t.reshape(n_pad, -1, *t.shape[1:])[:n_valid].reshape(-1, *t.shape[1:])
+    return t
 
 
 def cut_rays(out, n_valid, n_pad):
     """Model outputs of a padded batch without the padding rays.  Plain slicing: autograd hands the padding zero gradients."""
     if n_valid == n_pad:
         return out
-    res = {}
-    for k, t in out.items():
-        if not torch.is_tensor(t) or t.dim() == 0:
-            res[k] = t
-        elif k == "grad_theta" and t.shape[0] == 2 * n_pad:
-            res[k] = torch.cat([t[:n_valid], t[n_pad:n_pad + n_valid]], 0)
-        elif t.shape[0] == n_pad:
-            res[k] = t[:n_valid]
-        elif t.shape[0] % n_pad == 0:                      # flattened (rays x samples, ...) tensors
-            res[k] = t.reshape(n_pad, -1, *t.shape[1:])[:n_valid].reshape(-1, *t.shape[1:])
-        else:
-            res[k] = t
-    return res
+    return {k: cut_ray_tensor(k, t, n_valid, n_pad) for k, t in out.items()}
 
 
 class _RenderFunction(torch.autograd.Function):

@@ -7,18 +7,15 @@ svs_render.hip for the inverse-sphere points and the fg/bg compositing).
 `implicit_network.*`, `rendering_network.*`, `density.beta`, `bg_implicit_network.lin{0..8}.{weight,bias}`,
 `bg_rendering_network.lin{0,1}.{weight,bias}`.
 """
-import os
-
 import torch
-import torch.nn as nn
 
 from svs_hip import ops
 from volsdf.model.density import AbsDensity, LaplaceDensity
-from volsdf.model.network import ImplicitNetwork, RenderingNetwork, _dev
+from volsdf.model.network import ImplicitNetwork, RenderingNetwork, VolSDFBase, _dev, cut_rays, pad_rays
 from volsdf.model.ray_sampler import ErrorBoundSampler
 
 
-class VolSDFNetworkBG(nn.Module):
+class VolSDFNetworkBG(VolSDFBase):
     def __init__(self, conf):
         super().__init__()
         self.feature_vector_size = conf.get_int('feature_vector_size')
@@ -40,19 +37,11 @@ class VolSDFNetworkBG(nn.Module):
                 not br.weight_norm and br.num_layers == 3 and br.lin0.weight.shape == (128, 283)):
             raise NotImplementedError("the background kernels are built for bmvs.yaml's bg_network (4-D PE-10 8x256 "
                                       "skip-4 implicit network, 283->128->3 'nerf' radiance network, no weight-norm)")
-        self._pk = self._pk_bg = None
+        self._pk_bg = None
         self._bg_key = None
         self._bg_streams = {}              # per calling stream: the stream the background networks' forward runs on
 
     # ---- packed weights -------------------------------------------------------------------------------------
-    def packed_mlp(self, rgb=True):
-        if self._pk is None or self._pk.device != _dev(self):
-            self._pk = ops.PackedMlp(_dev(self))
-        self.implicit_network.packed(owner=self._pk)
-        if rgb:
-            self.rendering_network.pack_into(self._pk)
-        return self._pk
-
     def bg_params(self):
         bi, br = self.bg_implicit_network, self.bg_rendering_network
         sw = [getattr(bi, f"lin{l}").weight for l in range(9)], [getattr(bi, f"lin{l}").bias for l in range(9)]
@@ -69,57 +58,23 @@ class VolSDFNetworkBG(nn.Module):
             self._bg_key = key
         return self._pk_bg
 
-    def mlp_params(self):
-        """((sdf weight_v, weight_g, bias), (rgb weight_v, weight_g, bias)) of the foreground networks"""
-        def grab(net, n):
-            lins = [getattr(net, f"lin{l}") for l in range(n)]
-            return [m.weight_v for m in lins], [m.weight_g for m in lins], [m.bias for m in lins]
-        return grab(self.implicit_network, 9), grab(self.rendering_network, 5)
-
     def _flat_param_list(self):
-        (sv, sg, sb), (rv, rg, rb) = self.mlp_params()
-        out = []
-        for v, g, b in ((sv, sg, sb), (rv, rg, rb)):
-            for l in range(len(v)):
-                out += [v[l], g[l], b[l]]
-        out.append(self.density.beta)
+        out = super()._flat_param_list()
         for w, b in self.bg_params():
             for l in range(len(w)):
                 out += [w[l], b[l]]
         return out
 
     def invalidate_packed(self):
-        self.implicit_network._packed_key = None
-        if self._pk is not None:
-            self._pk._sdf_key = self._pk._rgb_key = None
+        super().invalidate_packed()
         self._bg_key = None
 
     # ---- forward --------------------------------------------------------------------------------------------
-    def draw_train_rng(self, R, dev, out=None, stream=None):
-        rb = self.scene_bounding_sphere
-
-        def eik(slot, n):
-            if n is None:
-                slot["eik_points"] = torch.empty(R, 3).uniform_(-rb, rb)
-                return ["eik_points"]
-            if "eik_points" not in slot:
-                slot["eik_points"] = torch.empty(R, 3).pin_memory()
-            slot["eik_points"].uniform_(-rb, rb)
-            return ["eik_points"]
-
-        return self.ray_sampler.draw_train_rng(R, dev, extra=eik, out=out, stream=stream)
-
-    @staticmethod
-    def slice_rng(rng, lo, hi):
-        return {k: (v if k == "perm" else v[lo:hi].contiguous()) for k, v in rng.items() if not k.startswith("_")}
-
     def forward(self, input, fast=-1):
         if self.training and torch.is_grad_enabled():
             # autograd bridge: the reference's own train_step (loss.backward(), clip_grad_norm_, torch Adam,
             # volsdf/vsdf.py:214-219) drives the hand-written backward kernels, as with the DTU model
-            from .network import cut_rays, pad_rays
-            rs = self.ray_sampler
-            input, n_valid, n_pad = pad_rays(input, rs.N_samples + rs.N_samples_extra + 1)
+            input, n_valid, n_pad = pad_rays(input, self.ray_multiple())
             res = _RenderFunctionBG.apply(self, input, fast, *self._flat_param_list())
             rgb_values, depth_values_all, depth_values, weights, grad_theta, depth_vals, xyz = res
             return cut_rays({'rgb_values': rgb_values, 'depth_values_all': depth_values_all, 'depth_values': depth_values,
@@ -174,11 +129,7 @@ class VolSDFNetworkBG(nn.Module):
         ray_dirs, cam_loc, depth_scale = ops.rays_from_uv(uv[0], pose[0], intrinsics[0])
         R = ray_dirs.shape[0]
         if self.training and rng is None:
-            n_valid = input.get("_valid_rays", R)
-            rng = self.draw_train_rng(n_valid, ray_dirs.device)
-            if n_valid < R:
-                from .network import pad_rng
-                rng = pad_rng(rng, R)
+            rng = self.draw_rays(input.get("_valid_rays", R), R, ray_dirs.device)
         self.ray_sampler.return_bg_ascending = False          # (this model takes the background samples from _bg_last)
         try:
             (z_all, _), z_samples_eik = self.ray_sampler.get_z_vals(ray_dirs, cam_loc, self, fast=fast,
@@ -211,7 +162,7 @@ class VolSDFNetworkBG(nn.Module):
         # being captured (a fork of a forked stream that joins its parent: the runtime defect of trainer._device_step's note).
         bg_join = None
         cur = torch.cuda.current_stream()
-        if (self.training and keep is not None and os.environ.get("SVS_BG_SIDE", "1") != "0"
+        if (self.training and keep is not None
                 and (not torch.cuda.is_current_stream_capturing() or getattr(self, "_side_ok_in_capture", False))):
             key = cur.cuda_stream
             bs = self._bg_streams.get(key)

@@ -336,13 +336,11 @@ def test_no_ray_group_of_pure_padding():
     sys.path.insert(0, os.path.join(ROOT, "s-volsdf_amd"))
     from types import SimpleNamespace
     from svs_hip.trainer import TrainStep
-    me = SimpleNamespace(_force_groups=None, groups=[(0, 992), (992, 1008)], schedule={}, _n_valid=990)
+    me = SimpleNamespace(_force_groups=None, groups=[(0, 992), (992, 1008)], schedule={})
     me._groups_raw = lambda R: TrainStep._groups_raw(me, R)
-    assert TrainStep._groups_for(me, 1008) == [(0, 1008)]                  # rays 990..1007 are padding: the tail group is all padding
-    me._n_valid = 1000
-    assert TrainStep._groups_for(me, 1008) == [(0, 992), (992, 1008)]      # 8 real rays in the tail group: the split stays
-    me._n_valid = 1008
-    assert TrainStep._groups_for(me, 1008) == [(0, 992), (992, 1008)]
+    assert TrainStep._groups_for(me, 1008, 990) == [(0, 1008)]             # rays 990..1007 are padding: the tail group is all padding
+    assert TrainStep._groups_for(me, 1008, 1000) == [(0, 992), (992, 1008)]    # 8 real rays in the tail group: the split stays
+    assert TrainStep._groups_for(me, 1008, 1008) == [(0, 992), (992, 1008)]
 
 
 # --------------------------------------------------------------------------------------------------------------
@@ -388,5 +386,53 @@ def test_bucketed_allreduce_equals_single_world2():
     for p in procs:
         p.join(timeout=60)
         assert p.exitcode == 0
+    assert all(same for _, same, _ in res)
+    np.testing.assert_array_equal(res[0][2], res[1][2])
+
+
+# --------------------------------------------------------------------------------------------------------------
+# one collective policy (trainer.allreduce_buckets): which path launches a step is decided per rank, so one rank may run the
+# eager form (first bucket started early, the second at the end) while the other runs the captured form (both at the end)
+def _mixed_path_worker(rank, world, port, q):
+    sys.path.insert(0, os.path.join(ROOT, "s-volsdf_amd"))
+    import torch.distributed as dist
+    from svs_hip.trainer import allreduce_buckets, allreduce_flat_grad, allreduce_range, grad_buckets
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    n, n_sdf = 797883, 556545
+    g = torch.Generator().manual_seed(100 + rank)
+    grad = torch.randn(n, generator=g) * torch.exp(torch.randn(n, generator=g) * 4.0)
+    whole = grad.clone()
+    allreduce_flat_grad(whole, world)
+    buckets = grad_buckets(n_sdf, n)
+    early = None
+    if rank == 0:
+        early = allreduce_range(grad, *buckets[0], async_op=True)
+    allreduce_buckets(grad, buckets, early)
+    q.put((rank, torch.equal(whole, grad), grad.numpy().copy()))
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def test_collectives_do_not_depend_on_the_launch_path_world2():
+    """an eager rank and a captured-path rank post the same two all-reduces in the same order: both finish (a mismatch would
+    leave them waiting for each other: the queue's timeout fails the test) and hold one all-reduce of the whole buffer, bit
+    for bit"""
+    world = 2
+    port = _free_port()
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    procs = [ctx.Process(target=_mixed_path_worker, args=(r, world, port, q)) for r in range(world)]
+    for p in procs:
+        p.start()
+    try:
+        res = sorted([q.get(timeout=180) for _ in range(world)], key=lambda t: t[0])
+        for p in procs:
+            p.join(timeout=60)
+            assert p.exitcode == 0
+    finally:
+        for p in procs:
+            if p.is_alive():
+                p.kill()
     assert all(same for _, same, _ in res)
     np.testing.assert_array_equal(res[0][2], res[1][2])

@@ -503,6 +503,54 @@ def test_deterministic_mode_repeats_bit_for_bit(dev, model_kind, R):
     assert float((ga[0] - gd[0]).abs().max()) <= 1e-4 * float(ga[0].abs().max())
 
 
+def test_cached_job_tables_follow_reallocated_scratch(dev):
+    """The weight-gradient job arrays are built once per configuration and kept (train._JobCache); their key names every
+    address a job holds.  Steps of 32, 64 and 32 rays (ray_multiple() == 32: the smallest counts on each side of a scratch
+    re-allocation) must give the same bits whether the arrays come from the caches or are rebuilt for every step -- an entry
+    that outlived its buffers would hand the kernels a freed address."""
+    from svs_hip import lib as _lib
+    from svs_hip.trainer import TrainStep
+    from volsdf.model.loss import VolSDFLoss
+    K, pose = synth.make_camera()
+    rs = np.random.default_rng(6)
+    batches = []
+    for R in (32, 64, 32):
+        inp = {"intrinsics": G(K, dev)[None], "uv": G(synth.make_uv(R, seed=4), dev)[None], "pose": G(pose, dev)[None]}
+        batches.append((inp, {"rgb": G(rs.uniform(0, 1, (1, R, 3)).astype(np.float32), dev),
+                              "rgb_smooth": G(rs.uniform(0, 1, (1, R, 3)).astype(np.float32), dev)}))
+
+    def run(clear):
+        m = _model(dev, 0.1).train()
+        loss = VolSDFLoss(rgb_loss="torch.nn.L1Loss", eikonal_weight=0.1, rgb_weight=1.0, mvs_weight=1.0, sparse_weight=1.0,
+                          anneal_rgb=200, gce=0.5, confi=1e-3)
+        loss.iter_step = 250
+        ts = TrainStep(m, loss)
+        assert ts.deterministic and ts.ray_multiple() == 32
+        torch.manual_seed(13)
+        grads = []
+        for inp, gt in batches:
+            if clear:
+                for b in ts.scratch.bwd:
+                    b._job_cache.clear()
+                ts.scratch.bg_bwd._job_cache.clear()
+            ts(inp, gt)
+            grads.append(ts.fp.grad.clone())
+        torch.cuda.synchronize()
+        assert clear or (ts.scratch.bg_bwd._job_cache and ts.scratch.bwd[0]._job_cache)
+        return grads, ts.fp.flat.clone()
+
+    L = _lib.load()
+    was = L.svs_set_deterministic(1)
+    try:
+        (ga, pa), (gb, pb) = run(False), run(True)
+    finally:
+        L.svs_set_deterministic(was)
+    for i, (x, y) in enumerate(zip(ga, gb)):
+        assert torch.equal(x, y), f"step {i}: {int((x != y).sum())} gradient entries differ"
+    assert torch.equal(pa, pb)
+    assert float(ga[0].abs().max()) > 0 and torch.isfinite(pa).all()
+
+
 @pytest.mark.parametrize("S", [2, 65, 255])
 @pytest.mark.parametrize("beta_param", [0.0, 1e-12, 1e-3, -1e-3, 0.02, 0.1])
 def test_composite_bg_backward_edges(dev, beta_param, S):

@@ -493,32 +493,39 @@ def test_rccl_path_on_one_gpu(dev):
     rs = np.random.default_rng(5)
     gt = {"rgb": G(rs.uniform(0, 1, (1, R, 3)).astype(F32), dev), "rgb_smooth": G(rs.uniform(0, 1, (1, R, 3)).astype(F32), dev)}
 
-    def one_step():
+    def one_step(graph=None, steps=1):
         m, loss = _setup(dev)
-        ts = TrainStep(m, loss, world=1, rank=0)
+        ts = TrainStep(m, loss, world=1, rank=0, graph=graph)
         torch.manual_seed(11)
-        lo, out = ts(inp, gt)
+        for _ in range(steps):
+            lo, out = ts(inp, gt)
         torch.cuda.synchronize()
-        return out["rgb_values"].clone(), out["weights"].clone(), ts.fp.grad.clone(), ts.fp.flat.clone()
+        planned = any(c.plan is not None for c in ts._captured.values())
+        return out["rgb_values"].clone(), out["weights"].clone(), ts.fp.grad.clone(), ts.fp.flat.clone(), planned
 
     plain = one_step()
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     assert not dist.is_initialized()
     dist.init_process_group("nccl", init_method=f"tcp://127.0.0.1:{port}", rank=0, world_size=1, device_id=dev)
     try:
-        calls = []
+        calls, calls_plan = [], []
         orig = dist.all_reduce
-        dist.all_reduce = lambda t, *a, **k: (calls.append(t.numel()), orig(t, *a, **k))[1]
         try:
+            dist.all_reduce = lambda t, *a, **k: (calls.append(t.numel()), orig(t, *a, **k))[1]
             with_pg = one_step()
+            # graph="plan": an eager step, the capture, a replay from the launch plan
+            dist.all_reduce = lambda t, *a, **k: (calls_plan.append(t.numel()), orig(t, *a, **k))[1]
+            planned = one_step(graph="plan", steps=3)
         finally:
             dist.all_reduce = orig
     finally:
         dist.destroy_process_group()
-    # two collectives that tile the flat gradient: the radiance / beta bucket (reduced beside the SDF backward), then the SDF
-    # network's bucket (trainer.grad_buckets); SVS_DP_BUCKETS=0: one collective over the whole buffer
+    # two collectives that tile the flat gradient, on every launch path: the radiance / beta bucket (an eager step reduces it
+    # beside the SDF backward), then the SDF network's bucket (trainer.grad_buckets, allreduce_buckets)
     n_sdf = sum(p.numel() for n, p in _setup(dev)[0].named_parameters() if n.startswith("implicit_network."))
     assert calls == [plain[2].numel() - n_sdf, n_sdf], calls
+    assert planned[4] and calls_plan == 3 * [plain[2].numel() - n_sdf, n_sdf], calls_plan
+    assert bool(torch.isfinite(planned[3]).all())
     assert torch.equal(plain[0], with_pg[0]) and torch.equal(plain[1], with_pg[1])
     assert float((plain[2] - with_pg[2]).abs().max()) <= 1e-5 * float(plain[2].abs().max())
     d = (plain[3] - with_pg[3]).abs()
