@@ -14,7 +14,9 @@
 #include "svs_common.h"
 #include "svs_mlp_layout.h"
 #include "svs_ticket.h"
+#include "svs_wgrad_maps.h"
 #include <cstdlib>
+#include <type_traits>
 
 namespace svs {
 namespace wgrad {
@@ -142,30 +144,38 @@ __global__ __launch_bounds__(256, 1) void wgrad_kernel(Args a) {
 
 
 // --------------------------------------------------------------------------------------------------------------
-// fp16x2 variant: the same contraction on v_mfma_f32_32x32x16_f16, reading the operand blocks in the forms the sweeps
+// fp16x2 variant: the same contraction on v_mfma_f32_16x16x32_f16, reading the operand blocks in the forms the sweeps
 // store them in (svs_blocks_h2.h): no conversion, no split, no staging registers.
 //   pair 0:  A = abar_l / zbar_l / fbar  scaled block, per-point scale
 //            B = h_l / r_l / feature     pair block
 //   pair 1:  A = ghat_l                  stored unscaled
 //            B = u_l                     scaled block, per-point scale
 //   narrow:  B = the 16 / 32 extra input rows of a radiance network's first layer, ONE float32 tile (split here)
-// GP = true (precision SVS_MMA_F16X2): every operand with both fp16 pieces, three MFMAs per k-step and B tile (hi hi + mid
-// hi + hi mid: the float32 accuracy class), 64 KiB per item, a ring of 2 item slots.
+// GP = true (precision SVS_MMA_F16X2): every operand with both fp16 pieces, three MFMAs per 16 x 16 output tile and item (hi
+// mid + mid hi + hi hi: the float32 accuracy class), 64 KiB per item, a ring of 2 item slots.
 // GP = false (SVS_MMA_F16X2_HALF): hi planes only (the scaled blocks hold nothing else), one MFMA, 32 KiB per item, a ring
 // of 4 slots with 3 items in flight.
 //
 // The contraction index is the POINT, which lives on the lanes of the fragments.  A 16-KiB plane is copied into LDS as it
 // stands by LDS-DMA (global_load_lds_dwordx4, 1 KiB per wave-instruction) into a ring of four item slots (A plane, B
-// plane), three items ahead of the one being multiplied; the MFMA fragments (8 consecutive points of one feature per
-// lane) are read TRANSPOSED out of the plane with ds_read_b64_tr_b16 -- the slot permutation of the planes
-// (piece_slot(), svs_blocks_h2.h) is what makes these reads conflict-free: for the 32 lanes of a half
+// plane), three items ahead of the one being multiplied.  One MFMA contracts a whole 32-point tile: a wave's 32 rows x 256
+// columns are 2 row tiles x 16 column tiles of 16 x 16 (32 accumulators of 4 registers), 2 x 16 x 3 MFMAs per item, every B
+// fragment feeding both row tiles.  The MFMA fragments (one feature, 8 points per lane; lane group g = lane >> 4 selects WHICH
+// 8 points) are read TRANSPOSED out of the plane with ds_read_b64_tr_b16 (16 lanes: 16 features x 4 points), two reads per
+// fragment.  The order of the points inside the contraction is free as long as A, B and the factor table agree, and is chosen
+// for the banks: with the slot permutation of the planes (piece_slot(), svs_blocks_h2.h)
 //     byte = 1024 s + 256 (a >> 1) + 128 ((a & 1) ^ (s & 1)) + 64 (p & 1) + 16 q + 8 (p >> 1)
-// with s = feature / 16 (two values per half: the two 16-lane groups), a = point / 4, q = point % 4, p = the lane's
-// column quad: 32 distinct 8-byte slots of one 256-byte line.
+// (s = feature / 16 = the tile, shared by all four lane groups; a = point / 4, q = point % 4, p = the lane's column quad) lane
+// groups 0, 1, 2, 3 take the point quads {0, 2}, {1, 3}, {4, 6}, {5, 7}: the two groups of a 32-lane half differ in the parity
+// of a and hit 32 distinct 8-byte slots of one 256-byte line.  The maps are the constexpr functions of svs_wgrad_maps.h, where
+// this is proved for every read of the loop by static_assert.  (Why this shape and not 32x32x16, on which the kernel was bound
+// by its multiply phase at the clock the chip holds under that load; the flush measured; 64 x 128 wave tiles built and
+// dropped: DESIGN.md section 4, profiles/wgrad_shape.txt.)
 //
 // Scaled operands carry value * s_p with one power of two s_p per point (the point's largest element at ~2^4); a
-// contraction over points needs ONE scale, so every A fragment is multiplied by the factors s / s_p of its 8 points in
-// fp16 (exact: powers of two) -- for pair 1 the factors of B's points are applied to A, which is the same product -- with
+// contraction over points needs ONE scale, so every A fragment is multiplied by the factors s / s_p of its 8 points (a table
+// in the fragments' point order, maps::factor_pos) in fp16 (exact: powers of two) -- for pair 1 the factors of B's points
+// are applied to A, which is the same product -- with
 // s chosen from the published maximum of the scaled operand (absmax) so that the largest element of the launch is
 // ~2^10; the accumulators are multiplied by 1 / s before the flush.  Factors are clamped to 2^15; points beyond the
 // batch get factor 0.
@@ -179,7 +189,7 @@ typedef short s16x4 __attribute__((__vector_size__(4 * sizeof(short))));
 #define SVS_LDS(T, ptr) ((__attribute__((address_space(3))) T*)(ptr))
 
 constexpr int kPlane = 16384;          // bytes of one fp16 plane of a block (svs_blocks_h2.h)
-constexpr int kExtraPiece = 32 * 64;   // narrow B tile: [32 points][32 features] fp16, 64-byte rows (hi, then mid)
+constexpr int kExtraPiece = 32 * 64;   // narrow B tile: [2 column tiles][32 points][16 features] fp16, 32-byte rows (hi, then mid)
 constexpr int kNarrowImg = 8192;       // a narrow job has no B plane: its float32 B tile lands (LDS-DMA) at the B plane's
                                        // place, its fp16 image (hi, mid) kNarrowImg bytes further
 constexpr int kRecBytes = 8 * 256;     // per ring slot: every wave's copy of the scaled operand's record (64 floats)
@@ -198,10 +208,22 @@ struct Ring {
 // LDS reads of the main loop go through inline asm: hipcc's waitcnt pass makes every LDS access it can see wait for ALL
 // LDS-DMA in flight (vmcnt(0): it cannot tell the ring slots apart), which would un-pipeline the ring.  The reads are
 // ordered against the copies by the counted vmcnt waits + barriers of the loop; lds_wait() is the lgkmcnt side.
+// A fragment is two transposed reads 256 bytes apart (the lane group's two point quads, svs_wgrad_maps.h); everything that is
+// the same for all lanes goes into the instruction's offset field, so an item's reads share a handful of base registers.
 struct Frag { s16x4 lo, hi; };
-__device__ __forceinline__ void tr_issue(Frag& v, unsigned a0, unsigned a1) {
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v.lo) : "v"(a0));
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v.hi) : "v"(a1));
+template <int OFF>
+__device__ __forceinline__ void tr_issue(Frag& v, unsigned base) {
+  static_assert(OFF >= 0 && OFF + 256 < 65536, "ds offset field");
+  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v.lo) : "v"(base), "n"(OFF));
+  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v.hi) : "v"(base), "n"(OFF + 256));
+}
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): loops whose index ends up in an offset field
+template <int N, typename F>
+__device__ __forceinline__ void static_for(F&& f) {
+  if constexpr (N > 0) {
+    static_for<N - 1>(f);
+    f(std::integral_constant<int, N - 1>{});
+  }
 }
 __device__ __forceinline__ f16x8 frag_of(const Frag& v) { return __builtin_bit_cast(f16x8, v); }
 __device__ __forceinline__ void lds_read128(f32x4& v, unsigned a) { asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(a)); }
@@ -248,7 +270,15 @@ constexpr int kMaxJobs = 20;
 struct MultiArgs { Job job[kMaxJobs]; int n_jobs; int touch; int reverse; };
 static_assert(sizeof(MultiArgs) <= 4096, "kernel arguments");
 
-constexpr int kThreadsW = 512;          // 8 waves: wave w owns output tile w (32 rows) x all B tiles
+// 8 waves: wave w owns output rows 32 w .. 32 w + 31 x all 256 columns, as kRT x kCT tiles of 16 x 16 -- 32 accumulators
+// of 4 registers
+constexpr int kThreadsW = 512;
+constexpr int kRT = 2, kCT = 16;
+// the bank-conflict proof of every transposed read of the loop (svs_wgrad_maps.h), with the regions the reads are offset by
+static_assert(maps::plane_reads_ok(kPlane), "transposed reads of the operand planes: bank conflict");
+static_assert(maps::narrow_reads_ok(kExtraPiece), "transposed reads of the narrow B image: bank conflict");
+static_assert(kPlane % 256 == 0 && kNarrowImg % 256 == 0 && kExtraPiece % 256 == 0 && Ring<true>::kSlotAll % 256 == 0 &&
+              Ring<false>::kSlotAll % 256 == 0, "every region the reads are offset by starts on a 256-byte bank row");
 
 typedef const __attribute__((address_space(1))) void* gvoid;
 
@@ -267,24 +297,29 @@ __global__ __launch_bounds__(kThreadsW, 1) void wgrad_h2_multi_kernel(MultiArgs 
   float s_grad, inv_s;
   scale_from_absmax(a.absmax, s_grad, inv_s);
 
-  f32x16 acc[8];
+  f32x4 acc[kRT][kCT];
 #pragma unroll
-  for (int i = 0; i < 8; ++i) acc[i] = (f32x16)(0.0f);
-  float bsum = 0.0f;     // bias gradient: this lane's row (lane & 31 of the wave's output tile) over its half's points
+  for (int o = 0; o < kRT; ++o)
+#pragma unroll
+    for (int i = 0; i < kCT; ++i) acc[o][i] = (f32x4)(0.0f);
+  float bsum[kRT];       // bias gradient: this lane's row (lane & 15 of row tile o) over its lane group's 8 points
+#pragma unroll
+  for (int o = 0; o < kRT; ++o) bsum[o] = 0.0f;
 
   unsigned char* ring = smem_h2;
 
-  // ---- transposed-read addresses inside a plane (see the header): this lane is row q', column quad p' of its 16-lane
-  // group; group g of its half reads k-step (feature block) 2 tile + g; k-step ks of the contraction adds 512 bytes;
-  // the second read of a fragment (points + 4) flips bit 7
-  const int rq = (lane & 15) >> 2, rp = lane & 3, rg = (lane >> 4) & 1, rh = lane >> 5;
-  const int rd0 = 1024 * rg + 256 * rh + 128 * rg + 64 * (rp & 1) + 16 * rq + 8 * (rp >> 1);
-  const int a_rd = 2048 * wave + rd0;
-  // narrow B image reads ([32 points][32 features], 64-byte rows)
-  const int rx0 = 64 * (8 * rh + rq) + 32 * rg + 8 * rp, rx1 = rx0 + 64 * 4;
-  // narrow B image writer (threads 0..255): float4 tid of the float32 tile = registers 4 (tid >> 6) .. +3 of lane tid & 63
+  // ---- transposed-read addresses (svs_wgrad_maps.h): the lane's part for even and for odd tiles of a plane and the wave's
+  // first row tile of A; tile number, plane and the fragment's second read are offset fields
+  const int rg = lane >> 4;
+  const int rd_even = maps::plane_base(0, lane), rd_odd = maps::plane_base(1, lane);
+  const int a_off = 1024 * kRT * wave;
+  const int rx = maps::narrow_base(lane);
+  // narrow B image writer (threads 0..255): float4 tid of the float32 tile = registers 4 (tid >> 6) .. +3 of lane tid & 63,
+  // features 8 (tid >> 6) + 4 (lane >> 5) .. + 3 of point lane & 31
   const int wp = lane & 31, whf = lane >> 5;
-  const int wxoff = 64 * wp + 16 * (wave & 3) + 8 * whf;
+  const int wxoff = maps::narrow_at(8 * (wave & 3) + 4 * whf, wp);
+  // column tiles of the job: a narrow job's 32 columns are two
+  const int n_ct = narrow ? 2 : kCT;
 
   const bool two_pairs = a.n_pairs == 2;               // (1 or 2)
   const int my_tiles = a.n_tiles > wg ? (a.n_tiles - 1 - wg) / nwg + 1 : 0;
@@ -370,7 +405,8 @@ __global__ __launch_bounds__(kThreadsW, 1) void wgrad_h2_multi_kernel(MultiArgs 
     }
     if (wp >= live) f = 0.0f;
     // (inline assembly: a store hipcc can see is made to wait for every LDS-DMA in flight)
-    if (lane < 32) asm volatile("ds_write_b16 %0, %1" :: "v"(lds_addr(slot + kSlot + kRecBytes + wave * 64 + 2 * lane)), "v"((_Float16)f) : "memory");
+    // (the table is in the fragments' point order: maps::factor_pos)
+    if (lane < 32) asm volatile("ds_write_b16 %0, %1" :: "v"(lds_addr(slot + kSlot + kRecBytes + wave * 64 + 2 * maps::factor_pos(wp))), "v"((_Float16)f) : "memory");
   };
   auto stage_narrow = [&](int item) {
     unsigned char* slot = ring + (item % kRing) * kSlotAll;
@@ -436,77 +472,95 @@ __global__ __launch_bounds__(kThreadsW, 1) void wgrad_h2_multi_kernel(MultiArgs 
     const unsigned la = lds_addr(ring + (item % kRing) * kSlotAll);
     const unsigned lb = la + kB;
     const unsigned ftab = la + kSlot + kRecBytes + wave * 64;
-    const unsigned nimg = lb + kNarrowImg;
+    const unsigned a_even = la + a_off + rd_even, a_odd = la + a_off + rd_odd;
+    const unsigned b_even = lb + rd_even, b_odd = lb + rd_odd;
+    const unsigned n_rd = lb + kNarrowImg + rx;
     const bool want_bias = has_db && p0;
     const bool two = narrow;             // only the narrow float32 tile is split into two pieces
-    // The A fragments of BOTH contraction k-steps (hi and mid pieces, their factors) are requested together, the next item's
+    // The wave's A fragments (hi and mid pieces of its kRT row tiles) and their factors are requested together, the next item's
     // copies are issued behind the requests, and the fragments are waited for once: the item period is the multiply phase plus
-    // what precedes it serially in every wave (section 3f of NOTES/r06.md), and the form before (copies first, then per k-step
-    // hi then mid, a full LDS round trip each) put four round trips there.
-    Frag fa2[2], fam2[2];
-    f32x4 fraw2[2];
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      tr_issue(fa2[ks], la + 512 * ks + a_rd, la + 512 * ks + (a_rd ^ 128));
-      if (GP) tr_issue(fam2[ks], la + kPlane + 512 * ks + a_rd, la + kPlane + 512 * ks + (a_rd ^ 128));
-      lds_read128(fraw2[ks], ftab + 32 * ks + 16 * rh);   // the factors of the fragment's 8 points (16 ks + 8 half + 0..7)
-    }
+    // what precedes it serially in every wave (section 3f of NOTES/r06.md).
+    Frag fa[kRT], fam[kRT];
+    f32x4 fraw;
+    static_for<kRT>([&](auto oc) {
+      constexpr int o = decltype(oc)::value;
+      tr_issue<1024 * o>(fa[o], o & 1 ? a_odd : a_even);
+      if (GP) tr_issue<kPlane + 1024 * o>(fam[o], o & 1 ? a_odd : a_even);
+    });
+    lds_read128(fraw, ftab + 16 * rg);   // the factors of the lane group's 8 points
     issue_next();        // (the next item's copies are issued while these reads are on their way)
     lds_wait();
+    f16x8 ah[kRT], am[kRT];
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      const f16x8 ah = frag_of(fa2[ks]) * __builtin_bit_cast(f16x8, fraw2[ks]);
-      const f16x8 am = GP ? frag_of(fam2[ks]) * __builtin_bit_cast(f16x8, fraw2[ks]) : ah;
+    for (int o = 0; o < kRT; ++o) {
+      ah[o] = frag_of(fa[o]) * __builtin_bit_cast(f16x8, fraw);
+      am[o] = GP ? frag_of(fam[o]) * __builtin_bit_cast(f16x8, fraw) : ah[o];
       if (want_bias) {
-        // row sums of A: the fragment holds 8 points of row lane & 31 (the other lane half holds the other 8)
+        // row sums of A: the fragment holds 8 points of row lane & 15 (the other three lane groups hold the other 24)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          const f16x2 h2v = {ah[2 * j], ah[2 * j + 1]};
-          bsum = __builtin_amdgcn_fdot2(h2v, one2, bsum, false);
+          const f16x2 h2v = {ah[o][2 * j], ah[o][2 * j + 1]};
+          bsum[o] = __builtin_amdgcn_fdot2(h2v, one2, bsum[o], false);
           if (GP) {
-            const f16x2 m2v = {am[2 * j], am[2 * j + 1]};
-            bsum = __builtin_amdgcn_fdot2(m2v, one2, bsum, false);
+            const f16x2 m2v = {am[o][2 * j], am[o][2 * j + 1]};
+            bsum[o] = __builtin_amdgcn_fdot2(m2v, one2, bsum[o], false);
           }
         }
       }
-      // the two waves of a SIMD cover each other's LDS latency: no software pipelining of the B fragments (requesting tile
-      // i + 1's fragments before tile i's MFMAs, two register sets and a counted lgkmcnt: bit-identical, <= 1 % -- NOTES/r06.md 3f)
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        if (i > 0 && narrow) break;
+    }
+    // the two waves of a SIMD cover each other's LDS latency: no software pipelining of the B fragments (requesting tile
+    // i + 1's fragments before tile i's MFMAs, two register sets and a counted lgkmcnt: bit-identical, <= 1 % -- NOTES/r06.md 3f)
+    static_for<kCT>([&](auto ic) {
+      constexpr int i = decltype(ic)::value;
+      if (i < n_ct) {
         Frag fh, fm;
         if (!narrow) {
-          const unsigned rd = lb + 2048 * i + 512 * ks + rd0;
-          tr_issue(fh, rd, rd ^ 128);
-          if (GP) tr_issue(fm, rd + kPlane, (rd ^ 128) + kPlane);
-        } else {
-          tr_issue(fh, nimg + ks * 1024 + rx0, nimg + ks * 1024 + rx1);
-          tr_issue(fm, nimg + kExtraPiece + ks * 1024 + rx0, nimg + kExtraPiece + ks * 1024 + rx1);
+          tr_issue<1024 * i>(fh, i & 1 ? b_odd : b_even);
+          if (GP) tr_issue<kPlane + 1024 * i>(fm, i & 1 ? b_odd : b_even);
+        } else if constexpr (i < 2) {
+          tr_issue<1024 * i>(fh, n_rd);
+          tr_issue<kExtraPiece + 1024 * i>(fm, n_rd);
         }
         lds_wait();
-        if (two || GP) acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, frag_of(fm), acc[i], 0, 0, 0);
-        if (GP) acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(am, frag_of(fh), acc[i], 0, 0, 0);
-        acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, frag_of(fh), acc[i], 0, 0, 0);
+        // every B fragment feeds all the wave's row tiles; per accumulator the products stay in the order hi mid, mid hi, hi hi
+        const f16x8 bh = frag_of(fh), bm = frag_of(fm);
+        if (two || GP) {
+#pragma unroll
+          for (int o = 0; o < kRT; ++o) acc[o][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[o], bm, acc[o][i], 0, 0, 0);
+        }
+        if (GP) {
+#pragma unroll
+          for (int o = 0; o < kRT; ++o) acc[o][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(am[o], bh, acc[o][i], 0, 0, 0);
+        }
+#pragma unroll
+        for (int o = 0; o < kRT; ++o) acc[o][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[o], bh, acc[o][i], 0, 0, 0);
       }
-    }
+    });
   }
   asm volatile("s_waitcnt vmcnt(0)" :: "v"(sink) : "memory");          // the last touch has returned; `sink` lived until here
-  // flush: C[row = rho(r) + 4*half][col]; two 128-byte row segments per wave-instruction
-  const int half = lane >> 5, col = lane & 31;
+  // flush: C[row = 4 (lane >> 4) + r][col = lane & 15] per tile, four 64-byte row segments per wave-instruction.  (Measured at
+  // the rate of the two-segment shape a v_permlane16_swap of neighbouring column tiles gives: profiles/wgrad_shape.txt.)
+  const int fcol = lane & 15;
   det::wait_turn(a.ticket, wg);
+  static_for<kCT>([&](auto ic) {
+    constexpr int i = decltype(ic)::value;
+    const int c = a.col0 + 16 * i + fcol;
+    if (i < n_ct && c < a.ldw) {
 #pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    if (i > 0 && narrow) break;
+      for (int o = 0; o < kRT; ++o)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int row = 32 * wave + rho(r) + 4 * half;
-      const int c = a.col0 + 32 * i + col;
-      if (c < a.ldw) atomicAdd(&a.dW[(size_t)row * a.ldw + c], acc[i][r] * inv_s);
+        for (int r = 0; r < 4; ++r)
+          atomicAdd(&a.dW[(size_t)(16 * (kRT * wave + o) + 4 * rg + r) * a.ldw + c], acc[o][i][r] * inv_s);
     }
-  }
+  });
   if (a.db) {
-    bsum += __shfl_xor(bsum, 32);
-    if (half == 0) atomicAdd(&a.db[32 * wave + col], bsum * inv_s);
+#pragma unroll
+    for (int o = 0; o < kRT; ++o) {
+      float sum = bsum[o];
+      sum += __shfl_xor(sum, 16);
+      sum += __shfl_xor(sum, 32);
+      if (lane < 16) atomicAdd(&a.db[16 * (kRT * wave + o) + lane], sum * inv_s);
+    }
   }
   det::pass_turn(a.ticket, wg);
 }
