@@ -928,6 +928,37 @@ int svs_mesh_components(const int* faces, int n_faces, int n_verts, int max_roun
 int svs_mesh_face_areas(const float* verts, const int* faces, int n_faces, const int* labels, double* area, int* face_label,
                         void* hip_stream);
 
+/* ---- TSDF fusion of a scan's depth maps (svs_hip.tsdf; csrc/svs_tsdf.hip) ---------------------------------------------
+ * The volume between fusion.fuse_view's per-view depth and svs_mc_classify / svs_mc_emit.  The reference has no such step;
+ * the arithmetic below is this project's (tests/tsdf_oracle.py restates it in numpy float64).
+ *
+ * svs_tsdf_integrate: integrates n_views <= 16 views into the volume in one launch.  tsdf (n0,n1,n2) float32 (initially 1),
+ *   weight (n0,n1,n2) float32 (initially 0), rgb planar (3,n0,n1,n2) float32 or NULL; last axis contiguous, 64-bit indexing.
+ *   origin: HOST double[3]; voxel, trunc > 0.  depths: HOST array of n_views DEVICE float (H,W) maps (as svs_fuse_view's
+ *   src_depths); masks: the same of DEVICE uint8 (H,W), NULL or NULL entries = no mask; images: DEVICE float (H,W,3) in
+ *   [0,1], required for every view when rgb is given and ignored otherwise.  mats: DEVICE double[n_views][21] = K row-major
+ *   (9), then the top three rows of E (12).  Per voxel p = origin + (i,j,k) * voxel and per view, all in float64:
+ *   cam = E (p,1), z = cam.z, skipped if z <= 0; pix = K cam, u = pix.x / pix.z + 0.5, v = pix.y / pix.z + 0.5, iu = floor(u),
+ *   iv = floor(v), skipped outside [0,W) x [0,H); d = depth[iv,iu], skipped if the mask is 0 there or d is not finite or
+ *   d <= 0; sdf = d - z, skipped if sdf < -trunc; t = min(1, sdf / trunc).  With n = the views that counted:
+ *   w_new = w_old + n, tsdf = (w_old * tsdf_old + sum t) / w_new, colours likewise from image[iv,iu], rounded to float32 once
+ *   per launch; a voxel with n = 0 is not written.  SVS_ESHAPE for more than 16 views or H * W == 0, SVS_EINVAL for
+ *   voxel or trunc <= 0.  16 B accesses need 16 B aligned arrays (and, for the colour planes, a voxel count that is a
+ *   multiple of 4); other volumes take scalar accesses.
+ * svs_tsdf_face_keep: cells[f] = the node index (i*n1 + j)*n2 + k of the cell face f came from (svs_mc_emit's active node,
+ *   repeated per triangle); keep[f] = 1 iff all eight nodes of that cell have weight >= min_weight: the rule that drops the
+ *   faces a TSDF grows between observed and never-observed space.
+ * svs_tsdf_vertex_colors: verts DEVICE float[n_verts][3] in volume index units -> out DEVICE float[n_verts][3]: trilinear
+ *   over the eight nodes around the vertex in float64 (base index clamped to [0, n-2]), over the nodes with weight > 0 only,
+ *   normalised by the sum of their trilinear weights; 0 where that sum is 0. */
+int svs_tsdf_integrate(float* tsdf, float* weight, float* rgb, int n0, int n1, int n2, const double* origin, double voxel,
+                       double trunc, const float* const* depths, const uint8_t* const* masks, const float* const* images,
+                       const double* mats, int n_views, int H, int W, void* hip_stream);
+int svs_tsdf_face_keep(const float* weight, int n0, int n1, int n2, const int* cells, int n_faces, float min_weight,
+                       uint8_t* keep, void* hip_stream);
+int svs_tsdf_vertex_colors(const float* rgb, const float* weight, int n0, int n1, int n2, const float* verts, int n_verts,
+                           float* out, void* hip_stream);
+
 /* ---- numeric-contract self tests (used by tests/test_gpu_parity.py) --------------------------------------- */
 int svs_selftest_exp(const float* x, float* y_exp, float* y_expm1, int n, void* hip_stream);
 int svs_selftest_arith(const float* a, const float* b, float* quotient, float* sqrt_abs_a, int n, void* hip_stream);

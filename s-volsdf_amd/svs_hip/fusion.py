@@ -230,13 +230,9 @@ def filter_depth(views, pairs, conf=0.0, filter_dist=1, filter_diff=0.01, thres_
     return xyz, rgb, stats
 
 
-def filter_depth_folder(scan_folder, out_folder, plyfilename, view_ids, conf=0.0, filter_dist=1, filter_diff=0.01,
-                        thres_view=1, *, eval_mask_root=None, dataset=None, eval_mask_radius=12):
-    """The file-level form (runner.py:301-332): cams/{id:08}_cam.txt and images/{id:08}.jpg under scan_folder,
-    depth_est/ and confidence/ PFMs under out_folder; all-vs-all pairs of view_ids.  With eval_mask_root (the reference's
-    data_dir_root; `dataset` 'DTU' or 'BlendedMVS') every view's final mask is cut by its evaluation mask, as with the
-    reference's default eval_mask: true (runner.py:350-368): the file of `svs_hip.mvsout.eval_mask_path` for the scan
-    named by out_folder's last component, dilated by disk(eval_mask_radius) and resized to the depth map on the GPU."""
+def folder_views(scan_folder, out_folder, view_ids):
+    """{view: dict(K, E, img, depth, confidence)} of a scan folder: cams/{id:08}_cam.txt and images/{id:08}.jpg under
+    scan_folder, depth_est/ and confidence/ PFMs under out_folder (runner.py:312-332)"""
     from datasets.data_io import read_pfm
     from helpers.utils import read_camera_parameters, read_img
     views = {}
@@ -245,12 +241,29 @@ def filter_depth_folder(scan_folder, out_folder, plyfilename, view_ids, conf=0.0
         views[v] = dict(K=K, E=E, img=read_img(os.path.join(scan_folder, "images/{:0>8}.jpg".format(v))),
                         depth=np.ascontiguousarray(read_pfm(os.path.join(out_folder, "depth_est/{:0>8}.pfm".format(v)))[0]),
                         confidence=np.ascontiguousarray(read_pfm(os.path.join(out_folder, "confidence/{:0>8}.pfm".format(v)))[0]))
+    return views
+
+
+def folder_eval_masks(views, out_folder, eval_mask_root, dataset, eval_mask_radius=12):
+    """The evaluation masks of `folder_views`' views for the scan named by out_folder's last component (None without
+    eval_mask_root): `svs_hip.mvsout.folder_eval_masks`, dilated and resized to the depth maps on the GPU."""
+    if eval_mask_root is None:
+        return None
+    from . import mvsout
+    scan_name = os.path.normpath(out_folder).split(os.sep)[-1]
+    return mvsout.folder_eval_masks(eval_mask_root, dataset, scan_name, list(views),
+                                    {v: views[v]["depth"].shape for v in views}, radius=eval_mask_radius)
+
+
+def filter_depth_folder(scan_folder, out_folder, plyfilename, view_ids, conf=0.0, filter_dist=1, filter_diff=0.01,
+                        thres_view=1, *, eval_mask_root=None, dataset=None, eval_mask_radius=12):
+    """The file-level form (runner.py:301-332): cams/{id:08}_cam.txt and images/{id:08}.jpg under scan_folder,
+    depth_est/ and confidence/ PFMs under out_folder; all-vs-all pairs of view_ids.  With eval_mask_root (the reference's
+    data_dir_root; `dataset` 'DTU' or 'BlendedMVS') every view's final mask is cut by its evaluation mask, as with the
+    reference's default eval_mask: true (runner.py:350-368): the file of `svs_hip.mvsout.eval_mask_path` for the scan
+    named by out_folder's last component, dilated by disk(eval_mask_radius) and resized to the depth map on the GPU."""
+    views = folder_views(scan_folder, out_folder, view_ids)
     pairs = [(v, [x for x in view_ids if x != v]) for v in view_ids]
-    eval_masks = None
-    if eval_mask_root is not None:
-        from . import mvsout
-        scan_name = os.path.normpath(out_folder).split(os.sep)[-1]
-        eval_masks = mvsout.folder_eval_masks(eval_mask_root, dataset, scan_name, view_ids,
-                                              {v: views[v]["depth"].shape for v in view_ids}, radius=eval_mask_radius)
+    eval_masks = folder_eval_masks(views, out_folder, eval_mask_root, dataset, eval_mask_radius)
     return filter_depth(views, pairs, conf, filter_dist, filter_diff, thres_view, plyfilename, eval_masks=eval_masks,
                         mask_dir=os.path.join(out_folder, "mask"))

@@ -198,6 +198,14 @@ SIGNATURES.update({
     "svs_mesh_face_areas": (c_int, [_P, _P, c_int, _P, _P, _P, _P]),
 })
 
+# svs_hip.tsdf (csrc/svs_tsdf.hip)
+SIGNATURES.update({
+    "svs_tsdf_integrate": (c_int, [_P, _P, _P, c_int, c_int, c_int, POINTER(c_double), c_double, c_double, _PP, _PP, _PP, _P,
+                                   c_int, c_int, c_int, _P]),
+    "svs_tsdf_face_keep": (c_int, [_P, c_int, c_int, c_int, _P, c_int, c_float, _P, _P]),
+    "svs_tsdf_vertex_colors": (c_int, [_P, _P, c_int, c_int, c_int, _P, c_int, _P, _P]),
+})
+
 # svs_hip.lpips (csrc/svs_lpips.hip)
 SIGNATURES.update({
     "svs_conv3x3_mfma_supported": (c_int, [c_int, c_int]),

@@ -13,6 +13,8 @@ filter_depth_folder`) -> {outdir}/mvsnet{scan:03}_l3.ply.
     apply_overrides(a, argv) hydra's command-line form: key=value, dotted keys, +key=value, vol=dtu|bmvs
     run_help(args)           derived values, the six assertions (ValueError naming the key), all_scans.yaml, the device
     save_depth / save_scene_depth / pcd_filter / create_scenes / main
+    +tsdf_voxel=V [+tsdf_trunc=T]   after the point clouds, every scan's depth maps meshed by `svs_hip.tsdf` into
+                             {outdir}/tsdf/mvsnet{scan:03}_l3.ply (`python -m evals.eval_dtu --datadir {outdir}/tsdf --mode mesh`)
 
 Differences from the reference, all deliberate: `gpu: auto` keeps the current device (there is no GPUtil probe) and an
 integer selects it with torch.cuda.set_device; `prevent_oom` is taken as given; the five-second sleep before the first
@@ -375,6 +377,32 @@ def pcd_filter(args, testlist, clocks=None):
     return out
 
 
+def tsdf_ply_name(outdir, scan):
+    """the mesh of a scan: the point cloud's name one folder down, where `evals.eval_dtu --mode mesh` finds it"""
+    return ply_name(os.path.join(outdir, "tsdf"), scan)
+
+
+def tsdf_meshes(args, testlist):
+    """+tsdf_voxel=V [+tsdf_trunc=T]: every scan's filtered depth maps meshed by `tsdf.fuse_folder` into
+    {outdir}/tsdf/mvsnet{scan:03}_l3.ply, with the filter settings and evaluation masks of `pcd_filter`; one time line per
+    scan.  -> {scene: fuse_folder's stats}"""
+    from . import tsdf
+    from .scans import get_trains_ids
+    data_dir = args["vol"]["dataset"]["data_dir"]
+    out = OrderedDict()
+    for scan in testlist:
+        folder = os.path.join(args["outdir"], scan)
+        masks = dict(eval_mask_root=args["data_dir_root"], dataset=data_dir) if args["eval_mask"] else {}
+        stats = tsdf.fuse_folder(folder, folder, get_trains_ids(data_dir, scan, args["num_view"]), args["tsdf_voxel"],
+                                 trunc=args.get("tsdf_trunc"), ply=tsdf_ply_name(args["outdir"], scan), conf=args["conf"],
+                                 filter_dist=args["filter_dist"], filter_diff=args["filter_diff"],
+                                 thres_view=args["thres_view"], **masks)[3]
+        info(f"saving the TSDF mesh to {stats['file']} ({stats['n_verts']} vertices, {stats['n_faces']} faces)")
+        info(f"{scan} tsdf seconds: " + ", ".join(f"{k} {v:.3f}" for k, v in stats["seconds"].items()))
+        out[scan] = stats
+    return out
+
+
 def create_scenes(args, testlist):
     """runner.py:74-108, 447-452: the folder of cameras and images that image-based rendering reads, per scan"""
     from . import mvsdata
@@ -416,6 +444,8 @@ def main(argv=None, scan_fn=None):
     result["clouds"] = pcd_filter(args, testlist, clocks)
     for scene, clock in clocks.items():
         info(clock.line(scene))
+    if args.get("tsdf_voxel"):
+        result["meshes"] = tsdf_meshes(args, testlist)
     return result
 
 
