@@ -1,26 +1,23 @@
-"""BlendedMVS Chamfer evaluation on the HIP path (reference: evals/eval_bmvs.py:56-79,102-252), and the
-error clouds (`-ve/--visualize_error`) of both Chamfer evaluators.
+"""BlendedMVS Chamfer evaluation on the HIP path (reference: evals/eval_bmvs.py:56-79,102-252), with its
+error clouds (`-ve/--visualize_error`).
 
 The reference brings a BlendedMVS cloud to the DTU scale (`relative_scale = cam_scale_mat[scan] / cam_scale_DTU`) and
 then follows the DTU settings (max_dist = 20) without down-sampling or masks.  As in evals/eval_dtu.py the protocol is
-exposed as functions on arrays (`evaluate_scan`, `error_colors`), on the file layout (`evaluate_scan_files`) and as
-`main(argv)` with the script's flags.  Every per-point step runs on the GPU: the float32 bookkeeping of the clouds and the
-colour step in csrc/svs_chamfer.hip, the searches and means in csrc/svs_cloud.hip.  Host code: the PLY reader and writer
-and the random order of the prediction.
+exposed as functions on arrays (`evaluate_scan`), on the file layout (`evaluate_scan_files`) and as `main(argv)` with the
+script's flags.  Every per-point step runs on the GPU through the operators of svs_hip/clouds.py: the float32 bookkeeping
+of the clouds (`prepare_cloud`), the searches and means, the colour step (`error_colors`).  Host code: the PLY reader and
+writer (svs_hip/ply.py) and the random order of the prediction.
 """
 import argparse
-import ctypes
 import os
 import sys
 
 import numpy as np
 import torch
 
-from svs_hip import lib as _lib
-from svs_hip.ops import _ptr, _stream
+from svs_hip import ply
+from svs_hip.clouds import error_colors, mean_below, nearest_neighbor, prepare_cloud
 from svs_hip.scans import scan2hash  # noqa: F401  -- re-exported, as the reference's module defines it
-
-from .eval_dtu import _dev, mean_below, nearest_neighbor
 
 # relative_scale of evals/eval_bmvs.py:115: BlendedMVS scale_mat_0[0,0] of scans 1..9 over DTU scan114's (`get_scales`)
 RELATIVE_SCALE = {1: 0.0010051393651899145, 2: 0.0015733906993148704, 3: 0.0012326845045689896, 4: 0.0015294108512811993,
@@ -39,32 +36,6 @@ def get_scales(data_dir_root):
     dtu_scale = scale("DTU", 114)
     bmvs_scale = {scan_id: scale("BlendedMVS", scan_id) for scan_id in SCANS}
     return dtu_scale, bmvs_scale, {scan_id: s / dtu_scale for scan_id, s in bmvs_scale.items()}
-
-
-def _raw_cloud(a):
-    """(n,3) on the device in the dtype the file gave: float32 stays float32 (half the upload), the rest is float64"""
-    if not torch.is_tensor(a):
-        a = np.asarray(a)
-        a = torch.from_numpy(np.ascontiguousarray(a, np.float32 if a.dtype == np.float32 else np.float64))
-    a = a.detach().to(_dev())
-    return (a if a.dtype in (torch.float32, torch.float64) else a.to(torch.float64)).reshape(-1, 3).contiguous()
-
-
-def prepare_cloud(pts, relative_scale, scale_mat=None):
-    """The cloud the kd-tree sees, (n,3) float64 on the device: `.astype('float32')`, [scan 5: the (4,4) scale_mat,]
-    `/= relative_scale` (evals/eval_bmvs.py:127-134,187,196-197)."""
-    L = _lib.load()
-    pts = _raw_cloud(pts)
-    out = torch.empty(pts.shape[0], 3, dtype=torch.float64, device=pts.device)
-    mat = None
-    if scale_mat is not None:
-        m = np.ascontiguousarray(np.asarray(scale_mat, np.float64))
-        if m.shape != (4, 4):
-            raise ValueError("Transformation matrix must be (4, 4)!")
-        mat = (ctypes.c_double * 16)(*m.reshape(-1))
-    _lib.check(L.svs_cloud_prepare(_ptr(pts), int(pts.dtype == torch.float64), pts.shape[0], mat, float(relative_scale), _ptr(out),
-                                   _stream()), "svs_cloud_prepare")
-    return out
 
 
 def shuffle_rows(pts, shuffle_rng=None):
@@ -95,62 +66,26 @@ def evaluate_scan(data_pcd, gt_pcd, relative_scale, scale_mat=None, max_dist=20,
     return mean_d2s, mean_s2d, over_all
 
 
-def error_colors(dist, max_dist=20, vis_dist=10, select=None):
-    """The colour step of both scripts (evals/eval_bmvs.py:232-246, evals/eval_dtu.py:173-187) -> (rgb_f64 (n,3) float64,
-    rgb_u8 (n,3) uint8) on the device.  White to red up to vis_dist, red up to max_dist, green from max_dist on.
-    select (n,): the rows of the full cloud that `dist` belongs to, in order; the others are blue."""
-    L = _lib.load()
-    dist = dist.detach().to(device=_dev(), dtype=torch.float64).contiguous()
-    rank = None
-    if select is not None:
-        select = select.detach().to(device=dist.device)
-        select = (select if select.dtype == torch.uint8 else (select != 0).to(torch.uint8)).contiguous()
-        chosen = (select != 0).to(torch.int32)
-        rank = torch.cumsum(chosen, 0, dtype=torch.int32) - chosen          # selected rows before each row
-    n_full = dist.shape[0] if select is None else select.shape[0]
-    rgb = torch.empty(n_full, 3, dtype=torch.float64, device=dist.device)
-    rgb_u8 = torch.empty(n_full, 3, dtype=torch.uint8, device=dist.device)
-    _lib.check(L.svs_cloud_error_colors(_ptr(dist), dist.shape[0], _ptr(select), _ptr(rank), n_full, float(max_dist), float(vis_dist),
-                                        _ptr(rgb), _ptr(rgb_u8), _stream()), "svs_cloud_error_colors")
-    return rgb, rgb_u8
-
-
-def write_vis_pcd(file, points, colors_u8):
-    """An error cloud as a binary little-endian PLY: double x,y,z + uchar red,green,blue per vertex."""
-    points = np.asarray(points.cpu() if torch.is_tensor(points) else points, np.float64)
-    colors_u8 = np.asarray(colors_u8.cpu() if torch.is_tensor(colors_u8) else colors_u8, np.uint8)
-    rec = np.empty(len(points), dtype=[("x", "<f8"), ("y", "<f8"), ("z", "<f8"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
-    for i, k in enumerate("xyz"):
-        rec[k] = points[:, i]
-    for i, k in enumerate(("red", "green", "blue")):
-        rec[k] = colors_u8[:, i]
-    with open(file, "wb") as f:
-        f.write(("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty double x\nproperty double y\n"
-                 "property double z\nproperty uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n" % len(rec)).encode("ascii"))
-        rec.tofile(f)
-
-
 def evaluate_scan_files(scan, datadir, data_dir_root, no_crop=False, visualize_error=False, **kw):
     """The reference's file layout (:114,125,131-133,139,183-184,230,241,246): {datadir}/mvsnet{scan:03}_l3.ply against
     {data_dir_root}/BlendedMVS/stl/scan{scan}_crop.ply (scan{scan}.ply with no_crop); scan 5 reads scale_mat_0 of
     {data_dir_root}/BlendedMVS/scan5/cameras.npz.  visualize_error writes {datadir}/result/{scan}_d2s.ply (the prediction
     in its shuffled order) and {scan}_s2d.ply (the ground truth)."""
-    from svs_hip.fusion import read_ply_points
-    data_pcd, _ = read_ply_points(os.path.join(datadir, "mvsnet{:0>3}_l3.ply".format(scan)))
+    data_pcd, _ = ply.read_points(os.path.join(datadir, "mvsnet{:0>3}_l3.ply".format(scan)))
     scale_mat = None
     if scan == MATRIX_SCAN:
         scale_mat = np.load(os.path.join(data_dir_root, "BlendedMVS", f"scan{scan}", "cameras.npz"))["scale_mat_0"]
     gt_file = os.path.join(data_dir_root, "BlendedMVS", "stl", f"scan{scan}.ply" if no_crop else f"scan{scan}_crop.ply")
     assert os.path.exists(gt_file), gt_file
-    gt_pcd, _ = read_ply_points(gt_file)
+    gt_pcd, _ = ply.read_points(gt_file)
     want_details = kw.pop("details", False)
     res, d = evaluate_scan(data_pcd, gt_pcd, RELATIVE_SCALE[scan], scale_mat=scale_mat, details=True, **kw)
     if visualize_error:
         vis_out_dir = os.path.join(datadir, "result")
         os.makedirs(vis_out_dir, exist_ok=True)
         max_dist = kw.get("max_dist", 20)
-        write_vis_pcd(f"{vis_out_dir}/{scan}_d2s.ply", d["data_pcd"], error_colors(d["dist_d2s"], max_dist, 10)[1])
-        write_vis_pcd(f"{vis_out_dir}/{scan}_s2d.ply", d["gt_pcd"], error_colors(d["dist_s2d"], max_dist, 10)[1])
+        ply.write(f"{vis_out_dir}/{scan}_d2s.ply", d["data_pcd"], error_colors(d["dist_d2s"], max_dist, 10)[1], coords="double")
+        ply.write(f"{vis_out_dir}/{scan}_s2d.ply", d["gt_pcd"], error_colors(d["dist_s2d"], max_dist, 10)[1], coords="double")
     return (res, d) if want_details else res
 
 

@@ -3,16 +3,16 @@
 `fuse_view` is one iteration of the reference's filter_depth loop (runner.py:312-386): geometric consistency of a
 reference view against its source views, photometric mask, depth averaging and the coloured world-space points of the
 surviving pixels.  `filter_depth` is the whole function on in-memory views or on a scan folder, ending in the same
-binary PLY (`write_ply`).  The small camera matrices are formed on the host exactly as the reference forms them
+binary PLY (`ply.write`).  The small camera matrices are formed on the host exactly as the reference forms them
 (float32 inverses / products), everything per pixel runs on the GPU.
 """
-import ctypes
 import os
 
 import numpy as np
 import torch
 
 from . import lib as _lib
+from . import ply
 from .images import device, to_device
 from .ops import _ptr, _ptr_array, _stream
 
@@ -81,124 +81,12 @@ def fuse_view(ref, srcs, conf=0.0, filter_dist=1, filter_diff=0.01, thres_view=1
     return out
 
 
-def write_ply(filename, xyz, rgb):
-    """The vertex-only binary PLY that runner.py:389-400 writes through plyfile: little-endian records of
-    float x,y,z + uchar red,green,blue."""
-    xyz = np.asarray(xyz.cpu() if torch.is_tensor(xyz) else xyz, np.float32)
-    rgb = np.asarray(rgb.cpu() if torch.is_tensor(rgb) else rgb, np.uint8)
-    rec = np.empty(len(xyz), dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
-    for i, k in enumerate("xyz"):
-        rec[k] = xyz[:, i]
-    for i, k in enumerate(("red", "green", "blue")):
-        rec[k] = rgb[:, i]
-    with open(filename, "wb") as f:
-        f.write(("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\n"
-                 "property float z\nproperty uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n" % len(rec)).encode("ascii"))
-        rec.tofile(f)
-
-
-_PLY_TYPES = {"float": "f4", "float32": "f4", "double": "f8", "float64": "f8", "uchar": "u1", "uint8": "u1", "char": "i1",
-              "int8": "i1", "short": "i2", "int16": "i2", "ushort": "u2", "uint16": "u2", "int": "i4", "int32": "i4",
-              "uint": "u4", "uint32": "u4"}
-
-
-def read_ply_points(filename):
-    """Vertex positions (n,3) float64 [and colours (n,3) uint8 or None] of an ascii / binary PLY -- what the Chamfer
-    evaluator takes from open3d.io.read_point_cloud (evals/eval_dtu.py:96-97,139-140)."""
-    with open(filename, "rb") as f:
-        if f.readline().strip() != b"ply":
-            raise ValueError("not a PLY file")
-        fmt, n, props, in_vertex = None, 0, [], False
-        while True:
-            line = f.readline()
-            if not line:
-                raise ValueError("PLY header without end_header")
-            tok = line.decode("ascii").split()
-            if not tok or tok[0] == "comment":
-                continue
-            if tok[0] == "format":
-                fmt = tok[1]
-            elif tok[0] == "element":
-                in_vertex = tok[1] == "vertex"
-                if in_vertex:
-                    n = int(tok[2])
-            elif tok[0] == "property" and in_vertex:
-                if tok[1] == "list":
-                    raise ValueError("list property in the vertex element")
-                props.append((tok[2], _PLY_TYPES[tok[1]]))
-            elif tok[0] == "end_header":
-                break
-        if fmt == "ascii":
-            rows = np.loadtxt(f, max_rows=n, ndmin=2)
-            cols = {name: rows[:, i] for i, (name, _) in enumerate(props)}
-        else:
-            order = "<" if fmt == "binary_little_endian" else ">"
-            rec = np.fromfile(f, dtype=[(name, order + t) for name, t in props], count=n)
-            cols = {name: rec[name] for name, _ in props}
-    pts = np.stack([np.asarray(cols[k], np.float64) for k in "xyz"], 1)
-    rgb = np.stack([np.asarray(cols[k], np.uint8) for k in ("red", "green", "blue")], 1) if "red" in cols else None
-    return pts, rgb
-
-
-def read_ply_mesh(filename):
-    """(vertices (n,3) float64, triangles (m,3) int64) of an ascii / binary PLY with a face element -- what the Chamfer
-    evaluator's mesh mode takes from open3d.io.read_triangle_mesh (evals/eval_dtu.py:65-68).  Faces with more than three
-    corners are fanned around their first corner, as open3d's reader does."""
-    with open(filename, "rb") as f:
-        if f.readline().strip() != b"ply":
-            raise ValueError("not a PLY file")
-        fmt, elements = None, []                       # [name, count, [(property name, type) or (name, count type, item type)]]
-        while True:
-            line = f.readline()
-            if not line:
-                raise ValueError("PLY header without end_header")
-            tok = line.decode("ascii").split()
-            if not tok or tok[0] == "comment":
-                continue
-            if tok[0] == "format":
-                fmt = tok[1]
-            elif tok[0] == "element":
-                elements.append([tok[1], int(tok[2]), []])
-            elif tok[0] == "property":
-                elements[-1][2].append((tok[4], _PLY_TYPES[tok[2]], _PLY_TYPES[tok[3]]) if tok[1] == "list"
-                                       else (tok[2], _PLY_TYPES[tok[1]]))
-            elif tok[0] == "end_header":
-                break
-        order = "<" if fmt == "binary_little_endian" else ">"
-        vertices, faces = None, []
-        for name, n, props in elements:
-            has_list = any(len(q) == 3 for q in props)
-            if not has_list:
-                if fmt == "ascii":
-                    rows = np.loadtxt(f, max_rows=n, ndmin=2) if n else np.zeros((0, len(props)))
-                    cols = {q[0]: rows[:, i] for i, q in enumerate(props)}
-                else:
-                    rec = np.fromfile(f, dtype=[(q[0], order + q[1]) for q in props], count=n)
-                    cols = {q[0]: rec[q[0]] for q in props}
-                if name == "vertex":
-                    vertices = np.stack([np.asarray(cols[k], np.float64) for k in "xyz"], 1)
-                continue
-            for _ in range(n):                           # elements with list properties: record by record
-                if fmt == "ascii":
-                    tok = f.readline().split()
-                    at = 0
-                for q in props:
-                    if len(q) == 2:
-                        if fmt == "ascii":
-                            at += 1
-                        else:
-                            f.read(np.dtype(q[1]).itemsize)
-                        continue
-                    if fmt == "ascii":
-                        k = int(tok[at]); items = [int(float(v)) for v in tok[at + 1:at + 1 + k]]; at += 1 + k
-                    else:
-                        k = int(np.frombuffer(f.read(np.dtype(q[1]).itemsize), order + q[1])[0])
-                        items = np.frombuffer(f.read(k * np.dtype(q[2]).itemsize), order + q[2]).astype(np.int64).tolist()
-                    if name == "face" and q[0] in ("vertex_indices", "vertex_index"):
-                        faces.extend((items[0], items[i], items[i + 1]) for i in range(1, k - 1))
-    if vertices is None:
-        raise ValueError("PLY file without a vertex element")
-    return vertices, np.asarray(faces, np.int64).reshape(-1, 3)
+def fuse_views(views, pairs, eval_masks=None, **kw):
+    """(ref_view, fuse_view's dict) per pair of `pairs` = [(ref_view, [src_view, ...]), ...], every reference view cut by
+    its entry of eval_masks when there are any; kw: fuse_view's settings"""
+    for ref_view, src_views in pairs:
+        yield ref_view, fuse_view(views[ref_view], [views[s] for s in src_views],
+                                  extra_mask=None if eval_masks is None else eval_masks[ref_view], **kw)
 
 
 def filter_depth(views, pairs, conf=0.0, filter_dist=1, filter_diff=0.01, thres_view=1, plyfilename=None, eval_masks=None,
@@ -211,10 +99,8 @@ def filter_depth(views, pairs, conf=0.0, filter_dist=1, filter_diff=0.01, thres_
     the three masks per view under mask_dir."""
     from helpers.utils import save_mask
     vertexs, colors, stats = [], [], []
-    for ref_view, src_views in pairs:
-        ref = views[ref_view]
-        out = fuse_view(ref, [views[s] for s in src_views], conf=conf, filter_dist=filter_dist, filter_diff=filter_diff,
-                        thres_view=thres_view, extra_mask=None if eval_masks is None else eval_masks[ref_view])
+    for ref_view, out in fuse_views(views, pairs, eval_masks, conf=conf, filter_dist=filter_dist, filter_diff=filter_diff,
+                                    thres_view=thres_view):
         vertexs.append(out["xyz"])
         colors.append(out["rgb"])
         m = torch.stack([out[k].float().mean() for k in ("photo_mask", "geo_mask", "final_mask")]).cpu().numpy()
@@ -226,7 +112,7 @@ def filter_depth(views, pairs, conf=0.0, filter_dist=1, filter_diff=0.01, thres_
     xyz = torch.cat(vertexs, 0).cpu().numpy() if vertexs else np.zeros((0, 3), np.float32)
     rgb = torch.cat(colors, 0).cpu().numpy() if colors else np.zeros((0, 3), np.uint8)
     if plyfilename is not None:
-        write_ply(plyfilename, xyz, rgb)
+        ply.write(plyfilename, xyz, rgb)
     return xyz, rgb, stats
 
 
@@ -244,26 +130,28 @@ def folder_views(scan_folder, out_folder, view_ids):
     return views
 
 
-def folder_eval_masks(views, out_folder, eval_mask_root, dataset, eval_mask_radius=12):
-    """The evaluation masks of `folder_views`' views for the scan named by out_folder's last component (None without
-    eval_mask_root): `svs_hip.mvsout.folder_eval_masks`, dilated and resized to the depth maps on the GPU."""
-    if eval_mask_root is None:
-        return None
-    from . import mvsout
-    scan_name = os.path.normpath(out_folder).split(os.sep)[-1]
-    return mvsout.folder_eval_masks(eval_mask_root, dataset, scan_name, list(views),
-                                    {v: views[v]["depth"].shape for v in views}, radius=eval_mask_radius)
+def scan_inputs(scan_folder, out_folder, view_ids, eval_mask_root=None, dataset=None, eval_mask_radius=12):
+    """What a fused scan folder gives -> (views: `folder_views`, pairs: every view against all the others, eval_masks).
+    eval_masks: None without eval_mask_root (the reference's data_dir_root; `dataset` 'DTU' or 'BlendedMVS'), else per view
+    the file of `svs_hip.mvsout.eval_mask_path` for the scan named by out_folder's last component, dilated by
+    disk(eval_mask_radius) and resized to the depth map on the GPU (runner.py:350-368)."""
+    view_ids = list(view_ids)
+    views = folder_views(scan_folder, out_folder, view_ids)
+    pairs = [(v, [x for x in view_ids if x != v]) for v in view_ids]
+    eval_masks = None
+    if eval_mask_root is not None:
+        from . import mvsout
+        scan_name = os.path.normpath(out_folder).split(os.sep)[-1]
+        eval_masks = mvsout.folder_eval_masks(eval_mask_root, dataset, scan_name, view_ids,
+                                              {v: views[v]["depth"].shape for v in view_ids}, radius=eval_mask_radius)
+    return views, pairs, eval_masks
 
 
 def filter_depth_folder(scan_folder, out_folder, plyfilename, view_ids, conf=0.0, filter_dist=1, filter_diff=0.01,
                         thres_view=1, *, eval_mask_root=None, dataset=None, eval_mask_radius=12):
     """The file-level form (runner.py:301-332): cams/{id:08}_cam.txt and images/{id:08}.jpg under scan_folder,
-    depth_est/ and confidence/ PFMs under out_folder; all-vs-all pairs of view_ids.  With eval_mask_root (the reference's
-    data_dir_root; `dataset` 'DTU' or 'BlendedMVS') every view's final mask is cut by its evaluation mask, as with the
-    reference's default eval_mask: true (runner.py:350-368): the file of `svs_hip.mvsout.eval_mask_path` for the scan
-    named by out_folder's last component, dilated by disk(eval_mask_radius) and resized to the depth map on the GPU."""
-    views = folder_views(scan_folder, out_folder, view_ids)
-    pairs = [(v, [x for x in view_ids if x != v]) for v in view_ids]
-    eval_masks = folder_eval_masks(views, out_folder, eval_mask_root, dataset, eval_mask_radius)
+    depth_est/ and confidence/ PFMs under out_folder; all-vs-all pairs of view_ids.  With eval_mask_root every view's
+    final mask is cut by its evaluation mask, as with the reference's default eval_mask: true (`scan_inputs`)."""
+    views, pairs, eval_masks = scan_inputs(scan_folder, out_folder, view_ids, eval_mask_root, dataset, eval_mask_radius)
     return filter_depth(views, pairs, conf, filter_dist, filter_diff, thres_view, plyfilename, eval_masks=eval_masks,
                         mask_dir=os.path.join(out_folder, "mask"))

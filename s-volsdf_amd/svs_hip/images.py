@@ -37,10 +37,11 @@ def to_device(a, dtype, module, what="array", ndim=None, expect=None, cast=True,
 
 
 class Phases:
-    """seconds per phase of a load; with sync=True the device is drained at every boundary so that they add up"""
+    """seconds per named phase (default: a loader's four); with sync=True the device is drained at every boundary so that
+    they add up"""
 
-    def __init__(self, sync=False):
-        self.sync, self.s = sync, OrderedDict((k, 0.0) for k in ("decode", "upload", "kernels", "download"))
+    def __init__(self, names=("decode", "upload", "kernels", "download"), sync=False):
+        self.sync, self.s = sync, OrderedDict((k, 0.0) for k in names)
         self.bytes_up = self.bytes_down = 0
 
     def add(self, name, t0):
@@ -52,6 +53,16 @@ class Phases:
     def summary(self, total):
         return ("seconds: " + ", ".join(f"{k} {v:.3f}" for k, v in self.s.items()) + f", total {total:.3f}; "
                 f"{self.bytes_up / 1e6:.1f} MB up, {self.bytes_down / 1e6:.1f} MB down")
+
+
+def tick(timers, name, t0):
+    """adds the seconds since t0 to timers[name] after a device synchronise -> the new t0; without timers nothing waits"""
+    if timers is None:
+        return t0
+    torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    timers[name] = timers.get(name, 0.0) + (t1 - t0)
+    return t1
 
 
 def upload_codes(stack, phases):

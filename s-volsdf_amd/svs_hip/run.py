@@ -265,33 +265,18 @@ def _device_samples(ds):
     return [put(s) for s in torch.utils.data.DataLoader(ds, 1, shuffle=False, num_workers=0, drop_last=False)]
 
 
-class Clock:
-    """seconds per phase of one scan (svs_hip.images.Phases with the runner's phases; the device is drained at every
-    boundary so that they add up)"""
-
-    def __init__(self):
-        from .images import Phases
-        self.phases = Phases(sync=True)
-        self.phases.s = OrderedDict((k, 0.0) for k in PHASES)
-        self.t0 = time.perf_counter()
-
-    def add(self, name):
-        self.t0 = self.phases.add(name, self.t0)
-
-    def line(self, scene):
-        return f"{scene} seconds: " + ", ".join(f"{k} {v:.3f}" for k, v in self.phases.s.items())
-
-
 def save_scene_depth(args, scene):
-    """runner.py:111-299 for one scan.  -> dict(loop, vol_opt, clock, files: [save_view's names per view])"""
+    """runner.py:111-299 for one scan.  -> dict(loop, vol_opt, clock: the seconds per phase of PHASES (the device is drained
+    at every boundary so that they add up), files: [save_view's names per view])"""
     import torch
     from . import mvsout
+    from .images import Phases
     from .scans import get_trains_ids
     from .stage_loop import StageLoop
     from volsdf.vsdf import VolOpt
     os.makedirs(os.path.join(args["outdir"], scene), exist_ok=True)
     save_yaml(os.path.join(args["outdir"], scene, "args.yaml"), args)
-    clock = Clock()
+    clock, t0 = Phases(PHASES, sync=True), time.perf_counter()
 
     trains_i = get_trains_ids(args["vol"]["dataset"]["data_dir"], scene, args["num_view"])
     ds = mvs_dataset(args, scene, trains_i)
@@ -310,7 +295,7 @@ def save_scene_depth(args, scene):
                          checkpoint="latest", scan=scene)
         vol_opt.trains_i = trains_i
         assert vol_opt.trains_i == vol_opt.train_dataset.trains_ids()
-    clock.add("load")
+    t0 = clock.add("load", t0)
 
     loop = StageLoop(model)
     loop.clear()
@@ -322,8 +307,8 @@ def save_scene_depth(args, scene):
         # (a) cost volume
         outs, view_extras = loop.cost_volumes(stage_idx, samples, outs_samples, view_extra_samples, int_r=int_r,
                                               inverse_depth=args["inverse_depth"], prevent_oom=args["prevent_oom"])
-        clock.add(f"mvs{stage_idx}")
-        info(f"time(gen cost volume)={clock.phases.s[f'mvs{stage_idx}']:.2f}")
+        t0 = clock.add(f"mvs{stage_idx}", t0)
+        info(f"time(gen cost volume)={clock.s[f'mvs{stage_idx}']:.2f}")
         # (b) volume optimisation
         if not args["ablate"] and opt_stepNs[stage_idx] > 0 and use_nerf_d[stage_idx] > 0:
             vol_opt.gen_dataset(stage_idx)
@@ -331,13 +316,13 @@ def save_scene_depth(args, scene):
             vol_opt.loss.set_stg(stage_idx)
             vol_opt.get_mvs_input(outs)
             epoch = vol_opt.run(opt_stepNs[stage_idx]) if opt_stepNs[stage_idx] > 1 else 0
-            clock.add("optimise")
+            t0 = clock.add("optimise", t0)
             info(f"render volsdf at {vol_opt.plots_dir} ..")
             for i, id_k in enumerate(trains_i):
                 depths[i], _ = vol_opt.render_mvs(id_k, epoch)
             info(f"mvs_depth replaced by vol_depth at stg={stage_idx} in 0,1,2")
             outs = StageLoop.hand_off_depth(outs, stage_idx, depths)
-            clock.add("render")
+            t0 = clock.add("render", t0)
         outs_samples, view_extra_samples = outs, view_extras
 
     files = []
@@ -346,7 +331,7 @@ def save_scene_depth(args, scene):
         files.append(mvsout.save_view(os.path.join(args["outdir"], scene), view, outputs,
                                       sample["proj_matrices"]["stage3"][0, 0], sample["imgs"][0, 0], previews=True,
                                       dep_max=float(sample["depth_values"].max())))
-    clock.add("save")
+    clock.add("save", t0)
     del outs_samples, view_extra_samples
     loop.clear()
     torch.cuda.empty_cache()
@@ -371,8 +356,7 @@ def pcd_filter(args, testlist, clocks=None):
             info("processing {}, ref-view{:0>2}, photo/geo/final-mask:{:.3f}/{:.3f}/{:.3f}".format(folder, v, photo, geo, final))
         info(f"saving the final MVS result to {ply}")
         if clocks is not None and scan in clocks:
-            clocks[scan].t0 = t0
-            clocks[scan].add("fusion")
+            clocks[scan].add("fusion", t0)
         out[scan] = (xyz, rgb, stats)
     return out
 
@@ -443,7 +427,7 @@ def main(argv=None, scan_fn=None):
     clocks = {s: r["clock"] for s, r in result["scans"].items() if isinstance(r, dict) and "clock" in r}
     result["clouds"] = pcd_filter(args, testlist, clocks)
     for scene, clock in clocks.items():
-        info(clock.line(scene))
+        info(f"{scene} seconds: " + ", ".join(f"{k} {v:.3f}" for k, v in clock.s.items()))
     if args.get("tsdf_voxel"):
         result["meshes"] = tsdf_meshes(args, testlist)
     return result

@@ -25,9 +25,11 @@ import numpy as np
 import torch
 
 from . import lib as _lib
+from . import fusion
 from . import mesh as _mesh
+from . import ply as _ply
 from .images import device as _device
-from .images import to_device
+from .images import tick, to_device
 from .ops import _f32, _ptr, _ptr_array, _stream
 
 MAX_VIEWS = 16                       # views per launch (csrc/svs_tsdf.hip kMaxViews)
@@ -154,13 +156,13 @@ class Volume:
         verts, faces = _mesh.compact(verts, faces)
         if largest:
             verts, faces = _mesh.largest_component(verts, faces)
-        t0 = _mesh._tick(timers, "keep", t0)
+        t0 = tick(timers, "keep", t0)
         rgb = None
         if self.rgb is not None:
             rgb = colors_u8(vertex_colors(self.rgb, self.weight, (verts.double() / self.voxel).float()))
         origin = torch.as_tensor(self.origin, dtype=torch.float64, device=verts.device)
         verts = (verts.double() + origin).float()
-        _mesh._tick(timers, "colors", t0)
+        tick(timers, "colors", t0)
         return verts, faces, rgb
 
 
@@ -194,7 +196,6 @@ def fuse_folder(scan_folder, out_folder, view_ids, voxel, trunc=None, ply=None, 
     bounds: (x0,y0,z0,x1,y1,z1); default: the fused points of all views padded by trunc + voxel.  The evaluation masks as
     filter_depth_folder takes them.  -> verts (V,3) float32, faces (F,3) int32, rgb (V,3) uint8 (numpy), stats: dict(file,
     shape, origin, n_verts, n_faces, launches, seconds per phase)."""
-    from . import fusion
     if depth not in ("averaged", "raw"):
         raise ValueError(f"depth: 'averaged' or 'raw', got {depth!r}")
     voxel = float(voxel)
@@ -202,20 +203,16 @@ def fuse_folder(scan_folder, out_folder, view_ids, voxel, trunc=None, ply=None, 
     sec = OrderedDict((k, 0.0) for k in ("read", "filter", "bounds", "integrate", "scan", "classify", "emit", "keep", "colors",
                                          "download", "write"))
     t0 = time.perf_counter()
-    view_ids = list(view_ids)
-    views = fusion.folder_views(scan_folder, out_folder, view_ids)
-    eval_masks = fusion.folder_eval_masks(views, out_folder, eval_mask_root, dataset, eval_mask_radius)
-    t0 = _mesh._tick(sec, "read", t0)
+    views, pairs, eval_masks = fusion.scan_inputs(scan_folder, out_folder, view_ids, eval_mask_root, dataset, eval_mask_radius)
+    t0 = tick(sec, "read", t0)
     tviews, clouds = [], []
-    for v in view_ids:
-        out = fusion.fuse_view(views[v], [views[s] for s in view_ids if s != v], conf=conf, filter_dist=filter_dist,
-                               filter_diff=filter_diff, thres_view=thres_view,
-                               extra_mask=None if eval_masks is None else eval_masks[v], points=bounds is None)
+    for v, out in fusion.fuse_views(views, pairs, eval_masks, conf=conf, filter_dist=filter_dist, filter_diff=filter_diff,
+                                    thres_view=thres_view, points=bounds is None):
         if bounds is None:
             clouds.append(out["xyz"])
         d, m = (out["depth_avg"].float(), out["final_mask"]) if depth == "averaged" else (views[v]["depth"], out["photo_mask"])
         tviews.append(dict(K=views[v]["K"], E=views[v]["E"], depth=d, mask=m, img=views[v]["img"]))
-    t0 = _mesh._tick(sec, "filter", t0)
+    t0 = tick(sec, "filter", t0)
     if bounds is None:
         pts = torch.cat(clouds, 0)
         if pts.shape[0] == 0:
@@ -225,19 +222,19 @@ def fuse_folder(scan_folder, out_folder, view_ids, voxel, trunc=None, ply=None, 
     else:
         b = np.asarray(bounds, np.float64).reshape(2, 3)
         origin, shape = bounds_from_points(b, voxel, 0.0, max_voxels)
-    t0 = _mesh._tick(sec, "bounds", t0)
+    t0 = tick(sec, "bounds", t0)
     vol = Volume(origin, shape, voxel, trunc)
     vol.integrate(tviews)
-    t0 = _mesh._tick(sec, "integrate", t0)
+    t0 = tick(sec, "integrate", t0)
     verts, faces, rgb = vol.mesh(min_weight=min_weight, largest=largest, timers=sec)
     sec.pop("workspace_bytes", None)
     t0 = time.perf_counter()
     v, f, c = verts.cpu().numpy(), faces.cpu().numpy(), rgb.cpu().numpy()
-    t0 = _mesh._tick(sec, "download", t0)
+    t0 = tick(sec, "download", t0)
     ply = os.path.join(out_folder, "tsdf.ply") if ply is None else ply
     os.makedirs(os.path.dirname(ply) or ".", exist_ok=True)
-    _mesh.write_ply_mesh(ply, v, f, colors=c)
-    _mesh._tick(sec, "write", t0)
+    _ply.write(ply, v, c, f)
+    tick(sec, "write", t0)
     stats = dict(file=ply, shape=shape, origin=origin, n_verts=len(v), n_faces=len(f), launches=vol.launches, seconds=sec)
     if log is not None:
         log(f"tsdf: {ply} ({len(v)} vertices, {len(f)} faces, volume {shape[0]} x {shape[1]} x {shape[2]})")

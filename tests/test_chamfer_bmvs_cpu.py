@@ -203,22 +203,23 @@ def test_dtu_command_line_keeps_its_flags_and_gains_two():
 
 
 def test_vis_pcd_round_trip(tmp_path):
-    from svs_hip.fusion import read_ply_points
+    from svs_hip import ply
+    from svs_hip.ply import read_points
     rng = np.random.default_rng(2)
     pts = rng.normal(0, 100, (257, 3))
     pts[0] = [1e30, -0.0, np.nextafter(1.0, 2.0)]                                    # float64 survives the file
     rgb = rng.integers(0, 256, (257, 3)).astype(np.uint8)
     fn = str(tmp_path / "cloud.ply")
-    eval_bmvs.write_vis_pcd(fn, pts, rgb)
-    got_pts, got_rgb = read_ply_points(fn)
+    ply.write(fn, pts, rgb, coords="double")
+    got_pts, got_rgb = read_points(fn)
     np.testing.assert_array_equal(got_pts, pts); np.testing.assert_array_equal(got_rgb, rgb)
     header = open(fn, "rb").read(400).split(b"end_header\n")[0].decode().split("\n")
     assert header[:3] == ["ply", "format binary_little_endian 1.0", "element vertex 257"]
     assert header[3:9] == ["property double x", "property double y", "property double z", "property uchar red",
                            "property uchar green", "property uchar blue"]
     assert os.path.getsize(fn) == len("\n".join(header)) + len("end_header\n") + 257 * 27
-    eval_bmvs.write_vis_pcd(fn, np.zeros((0, 3)), np.zeros((0, 3), np.uint8))
-    assert read_ply_points(fn)[0].shape == (0, 3)
+    ply.write(fn, np.zeros((0, 3)), np.zeros((0, 3), np.uint8), coords="double")
+    assert read_points(fn)[0].shape == (0, 3)
 
 
 def test_argument_errors_come_back_as_codes():

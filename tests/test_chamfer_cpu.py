@@ -71,7 +71,7 @@ def _write_mesh_ply(fn, vertices, faces, binary, extra_vertex_prop=False):
 
 def test_read_ply_mesh(tmp_path):
     """The mesh reader behind --mode mesh: ascii and binary, an extra vertex property, a quad (fanned into two triangles)."""
-    from svs_hip.fusion import read_ply_mesh, read_ply_points
+    from svs_hip.ply import read_mesh, read_points
     rng = np.random.default_rng(5)
     vertices = rng.normal(0, 10, (9, 3)).astype(np.float32)
     faces = [(0, 1, 2), (2, 3, 4, 5), (6, 7, 8), (8, 0, 4)]
@@ -80,12 +80,12 @@ def test_read_ply_mesh(tmp_path):
         for extra in (False, True):
             fn = str(tmp_path / ("m%d%d.ply" % (binary, extra)))
             _write_mesh_ply(fn, vertices, faces, binary, extra)
-            v, t = read_ply_mesh(fn)
+            v, t = read_mesh(fn)
             assert v.dtype == np.float64 and t.dtype == np.int64
             np.testing.assert_array_equal(v, vertices.astype(np.float64))
             np.testing.assert_array_equal(t, want)
-            np.testing.assert_array_equal(read_ply_points(fn)[0], v)       # the point reader skips the faces
+            np.testing.assert_array_equal(read_points(fn)[0], v)       # the point reader skips the faces
     fn = str(tmp_path / "nofaces.ply")
     _write_mesh_ply(fn, vertices, [], True)
-    v, t = read_ply_mesh(fn)
+    v, t = read_mesh(fn)
     assert t.shape == (0, 3) and len(v) == 9

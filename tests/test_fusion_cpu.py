@@ -95,24 +95,25 @@ def test_camera_text_round_trip(tmp_path):
 
 
 def test_ply_writer_and_reader(tmp_path):
-    from svs_hip.fusion import read_ply_points, write_ply
+    from svs_hip import ply
+    from svs_hip.ply import read_points
     rng = np.random.default_rng(8)
     xyz = rng.normal(0, 100, (37, 3)).astype(F32)
     rgb = rng.integers(0, 256, (37, 3)).astype(np.uint8)
     fn = str(tmp_path / "c.ply")
-    write_ply(fn, xyz, rgb)
+    ply.write(fn, xyz, rgb)
     assert open(fn, "rb").read() == forc.ply_bytes(xyz, rgb)
-    pts, col = read_ply_points(fn)
+    pts, col = read_points(fn)
     np.testing.assert_array_equal(pts, xyz.astype(np.float64))
     np.testing.assert_array_equal(col, rgb)
     asc = tmp_path / "a.ply"
     asc.write_text("ply\nformat ascii 1.0\ncomment made by hand\nelement vertex 2\nproperty double x\nproperty double y\n"
                    "property double z\nelement face 0\nproperty list uchar int vertex_indices\nend_header\n1 2 3\n4.5 5 6\n")
-    pts, col = read_ply_points(str(asc))
+    pts, col = read_points(str(asc))
     np.testing.assert_array_equal(pts, [[1, 2, 3], [4.5, 5, 6]])
     assert col is None
-    write_ply(fn, np.zeros((0, 3), F32), np.zeros((0, 3), np.uint8))               # empty cloud
-    assert read_ply_points(fn)[0].shape == (0, 3)
+    ply.write(fn, np.zeros((0, 3), F32), np.zeros((0, 3), np.uint8))               # empty cloud
+    assert read_points(fn)[0].shape == (0, 3)
 
 
 def load_filter_depth(golden_dir):

@@ -42,11 +42,12 @@ def test_mesh_mode_matches_reference_script(dev, golden_dir, tmp_path):
     """--mode mesh end to end: the sampled cloud is the script's point for point (fixture chamfer_mesh_ref.npz), and so are
     the protocol's results on it; once on arrays, once through the file layout and the command line."""
     from evals import eval_dtu
+    from svs_hip import clouds
     from scipy.io import savemat
     g = dict(np.load(os.path.join(golden_dir, "chamfer_mesh_ref.npz")))
     sc = synth.make_dtu_scan(int(g["scan_seed"]))
     vertices, triangles = synth.make_dtu_mesh(int(g["mesh_seed"]))
-    cloud = eval_dtu.sample_mesh(vertices, triangles, 0.2).cpu().numpy()
+    cloud = clouds.sample_mesh(vertices, triangles, 0.2).cpu().numpy()
     want, per_tri = corc.sample_mesh(vertices, triangles, 0.2)
     np.testing.assert_array_equal(cloud, want)                                   # HIP == oracle, bit for bit
     new_pts = cloud[len(vertices):]
@@ -91,22 +92,22 @@ def test_mesh_mode_matches_reference_script(dev, golden_dir, tmp_path):
 def test_mesh_sampler_vs_oracle(dev, seed, n_tri, thresh):
     """Random triangle soups (slivers, tiny and large triangles, some with no sample at all) against the oracle's
     restatement of sample_single_tri: same points, same order, bit for bit."""
-    from evals import eval_dtu
+    from svs_hip import clouds
     rng = np.random.default_rng(seed)
     vertices = rng.normal(0, 1, (n_tri + 2, 3)) * rng.choice([0.05, 0.5, 3.0], (n_tri + 2, 1))
     triangles = np.stack([rng.integers(0, len(vertices), n_tri) for _ in range(3)], 1)
     triangles[::17, 1] = triangles[::17, 0]                                     # degenerate ones in between
     want, per_tri = corc.sample_mesh(vertices, triangles, thresh)
-    got = eval_dtu.sample_mesh(vertices, triangles, thresh).cpu().numpy()
+    got = clouds.sample_mesh(vertices, triangles, thresh).cpu().numpy()
     assert (per_tri == 0).any() and per_tri.max() > 5
     np.testing.assert_array_equal(got, want)
     # no triangle at all: the vertices alone
-    np.testing.assert_array_equal(eval_dtu.sample_mesh(vertices, np.zeros((0, 3), np.int64), thresh).cpu().numpy(), vertices)
+    np.testing.assert_array_equal(clouds.sample_mesh(vertices, np.zeros((0, 3), np.int64), thresh).cpu().numpy(), vertices)
 
 
 @pytest.mark.parametrize("n_ref,n_q,seed", [(5000, 3000, 0), (1, 17, 1), (257, 1, 2), (20000, 20000, 3)])
 def test_nearest_neighbor_vs_sklearn(dev, n_ref, n_q, seed):
-    from evals import eval_dtu
+    from svs_hip import clouds
     rng = np.random.default_rng(seed)
     ref = rng.normal(0, 30, (n_ref, 3))
     q = np.concatenate([ref[rng.integers(0, n_ref, n_q // 2)] + rng.normal(0, 0.5, (n_q // 2, 3)),       # near the cloud
@@ -116,7 +117,7 @@ def test_nearest_neighbor_vs_sklearn(dev, n_ref, n_q, seed):
         q[0] = ref[3]
     want_d, want_i = corc.nn_distance(ref, q, n_jobs=2)
     for cell in (None, 3.0, 11.0):
-        got_d, got_i = eval_dtu.nearest_neighbor(ref, q, max_radius=25.0, cell=cell, return_index=True)
+        got_d, got_i = clouds.nearest_neighbor(ref, q, max_radius=25.0, cell=cell, return_index=True)
         got_d, got_i = got_d.cpu().numpy(), got_i.cpu().numpy()
         near = want_d < 25.0
         np.testing.assert_array_equal(got_d[near], want_d[near])
@@ -125,31 +126,31 @@ def test_nearest_neighbor_vs_sklearn(dev, n_ref, n_q, seed):
         assert ties.all()
     if n_ref > 100:
         assert got_d[0] == 0.0 and got_i[0] == 3
-    assert eval_dtu.nearest_neighbor(ref, np.zeros((0, 3)), 5.0).shape == (0,)
+    assert clouds.nearest_neighbor(ref, np.zeros((0, 3)), 5.0).shape == (0,)
     with pytest.raises(ValueError):
-        eval_dtu.nearest_neighbor(np.zeros((0, 3)), q, 5.0)
+        clouds.nearest_neighbor(np.zeros((0, 3)), q, 5.0)
 
 
 @pytest.mark.parametrize("n,radius,seed", [(4000, 0.2, 0), (9000, 1.5, 1), (1, 0.2, 2), (300, 50.0, 3)])
 def test_radius_downsample_vs_sklearn_greedy(dev, n, radius, seed):
-    from evals import eval_dtu
+    from svs_hip import clouds
     rng = np.random.default_rng(seed)
     base = rng.normal(0, 8, (max(n // 3, 1), 3))
     pts = (base[rng.integers(0, len(base), n)] + rng.normal(0, radius * 0.7, (n, 3)))
     if n > 10:
         pts[5] = pts[2]                       # duplicates: the later one is dropped
     want = corc.radius_downsample(pts, radius, n_jobs=2)
-    got = eval_dtu.radius_downsample(pts, radius).cpu().numpy()
+    got = clouds.radius_downsample(pts, radius).cpu().numpy()
     assert np.array_equal(got, want)
     if n > 1000:
         assert 0.05 < want.mean() < 0.95
-    assert eval_dtu.radius_downsample(np.zeros((0, 3)), radius).shape == (0,)
+    assert clouds.radius_downsample(np.zeros((0, 3)), radius).shape == (0,)
 
 
 def test_obs_filter_plane_mean_and_compact(dev):
     """The elementwise stages against the oracle, with points sitting exactly on the box faces and grid-cell centres."""
     import ctypes
-    from evals import eval_dtu
+    from svs_hip import clouds
     from svs_hip import lib
     from svs_hip.ops import _ptr, _stream
     L = lib.load()
@@ -167,8 +168,8 @@ def test_obs_filter_plane_mean_and_compact(dev):
     lib.check(L.svs_cloud_obs_filter(_ptr(d), len(pts), bb, 2.0, 60.0, _ptr(om), *om.shape, _ptr(inb), _ptr(obs), _stream()), "obs")
     assert np.array_equal(inb.cpu().numpy().astype(bool), want_in) and np.array_equal(obs.cpu().numpy().astype(bool), want_obs)
     assert 0 < want_obs.sum() < want_in.sum() < len(pts)
-    np.testing.assert_array_equal(eval_dtu.compact(d, obs).cpu().numpy(), pts[want_obs])
-    assert eval_dtu.compact(d, torch.zeros_like(obs)).shape == (0, 3)
+    np.testing.assert_array_equal(clouds.compact(d, obs).cpu().numpy(), pts[want_obs])
+    assert clouds.compact(d, torch.zeros_like(obs)).shape == (0, 3)
 
     stl = sc["stl"]
     P = sc["P"]
@@ -181,8 +182,8 @@ def test_obs_filter_plane_mean_and_compact(dev):
 
     dist = torch.from_numpy(np.abs(np.random.default_rng(0).normal(0, 15, 100001))).to(dev)
     dn = dist.cpu().numpy()
-    np.testing.assert_allclose(eval_dtu.mean_below(dist, 20.0), dn[dn < 20.0].mean(), rtol=1e-13)
-    assert np.isnan(eval_dtu.mean_below(dist, -1.0))            # empty selection: numpy's mean gives nan
+    np.testing.assert_allclose(clouds.mean_below(dist, 20.0), dn[dn < 20.0].mean(), rtol=1e-13)
+    assert np.isnan(clouds.mean_below(dist, -1.0))            # empty selection: numpy's mean gives nan
 
 
 def test_large_cloud_properties(dev):
@@ -190,23 +191,23 @@ def test_large_cloud_properties(dev):
     distance 0; against a rigidly shifted copy no distance exceeds the shift; down-sampling leaves no two kept points
     within the radius (down-sampling the result again keeps everything) and every dropped point within the radius of a
     kept one."""
-    from evals import eval_dtu
+    from svs_hip import clouds
     n = 4_000_000
     g = torch.Generator(device="cpu").manual_seed(0)
     d = torch.randn(n, 3, generator=g, dtype=torch.float64)
     d = d / d.norm(dim=1, keepdim=True) * 150.0                  # sphere of radius 150 mm, spacing ~ 0.27 mm
     pts = d.to(dev)
-    dist, idx = eval_dtu.nearest_neighbor(pts, pts, max_radius=20.0, return_index=True)
+    dist, idx = clouds.nearest_neighbor(pts, pts, max_radius=20.0, return_index=True)
     assert float(dist.max()) == 0.0 and bool((idx.long() == torch.arange(n, device=dev)).all())
     shift = torch.tensor([0.3, -0.2, 0.1], dtype=torch.float64, device=dev)
-    dist = eval_dtu.nearest_neighbor(pts, pts + shift, max_radius=20.0)
+    dist = clouds.nearest_neighbor(pts, pts + shift, max_radius=20.0)
     assert float(dist.max()) <= float(shift.norm()) * (1 + 1e-12) and float(dist.min()) >= 0.0
-    keep = eval_dtu.radius_downsample(pts, 0.2)
-    kept = eval_dtu.compact(pts, keep)
+    keep = clouds.radius_downsample(pts, 0.2)
+    kept = clouds.compact(pts, keep)
     assert 0.3 * n < kept.shape[0] < n
-    assert bool(eval_dtu.radius_downsample(kept, 0.2).all())      # no two kept points within the radius: a fixed point
-    dropped = eval_dtu.compact(pts, ~keep)
-    dk = eval_dtu.nearest_neighbor(kept, dropped, 1.0)
+    assert bool(clouds.radius_downsample(kept, 0.2).all())      # no two kept points within the radius: a fixed point
+    dropped = clouds.compact(pts, ~keep)
+    dk = clouds.nearest_neighbor(kept, dropped, 1.0)
     assert float(dk.max()) <= 0.2
 
 
@@ -214,17 +215,17 @@ def test_large_cloud_properties(dev):
 def test_compact_keeps_order_at_any_size(dev, n):
     """The ordered compaction (block-wise mask scan, csrc/svs_scan.h) at sizes around its 16-byte / 4096-byte units, with an
     aligned and an unaligned mask: rows with a non-zero mask byte, in order."""
-    from evals import eval_dtu
+    from svs_hip import clouds
     g = torch.Generator(device="cpu").manual_seed(n)
     pts = torch.randn(n, 3, generator=g, dtype=torch.float64).to(dev)
     raw = (torch.rand(n + 1, generator=g) < 0.37).to(torch.uint8).to(dev)
     raw[raw != 0] = 7                                           # any non-zero byte counts
     for mask in (raw[:n], raw[1:]):                             # raw[1:] starts one byte off a 16-byte boundary
-        got = eval_dtu.compact(pts, mask)
+        got = clouds.compact(pts, mask)
         want = pts[mask != 0]
         assert got.shape == want.shape and torch.equal(got, want)
-    assert eval_dtu.compact(pts, torch.zeros(n, dtype=torch.uint8, device=dev)).shape == (0, 3)
-    assert torch.equal(eval_dtu.compact(pts, torch.ones(n, dtype=torch.uint8, device=dev)), pts)
+    assert clouds.compact(pts, torch.zeros(n, dtype=torch.uint8, device=dev)).shape == (0, 3)
+    assert torch.equal(clouds.compact(pts, torch.ones(n, dtype=torch.uint8, device=dev)), pts)
 
 
 @pytest.mark.parametrize("n", [1, 63, 1000, 3_000_001])

@@ -14,6 +14,7 @@ import bmvs_chamfer_oracle as borc
 import synth
 import synth_bmvs
 from evals import eval_bmvs, eval_dtu
+from svs_hip import clouds
 
 pytestmark = pytest.mark.gpu
 
@@ -49,7 +50,7 @@ def _cloud(n, dtype, seed):
 def test_prepare_scale_mode_vs_oracle(dev, n, dtype):
     pts = _cloud(n, dtype, n)
     for scan, scale in eval_bmvs.RELATIVE_SCALE.items():
-        got = eval_bmvs.prepare_cloud(pts, scale).cpu().numpy()
+        got = clouds.prepare_cloud(pts, scale).cpu().numpy()
         want = borc.prepare(pts, scale)
         assert got.dtype == np.float64 and got.shape == (n, 3)
         assert np.array_equal(_bits(got), _bits(want)), (scan, np.abs(got - want).max())      # signed zeros included
@@ -63,20 +64,20 @@ def test_prepare_matrix_mode_vs_oracle(dev, n, dtype):
     pts = _cloud(n, dtype, 100 + n)
     mat = np.random.default_rng(7).normal(0, 1, (4, 4)); mat[3] = [0, 0, 0, 1]
     for scale in (eval_bmvs.RELATIVE_SCALE[5], 1.0 / 3.0):
-        got = eval_bmvs.prepare_cloud(pts, scale, mat).cpu().numpy()
+        got = clouds.prepare_cloud(pts, scale, mat).cpu().numpy()
         want = borc.prepare(pts, scale, mat)
         assert np.array_equal(_bits(got), _bits(want)), np.abs(got - want).max()
-    got = eval_bmvs.prepare_cloud(torch.from_numpy(pts).to(dev), 0.5, mat).cpu().numpy()      # a device tensor is taken as is
+    got = clouds.prepare_cloud(torch.from_numpy(pts).to(dev), 0.5, mat).cpu().numpy()      # a device tensor is taken as is
     assert np.array_equal(_bits(got), _bits(borc.prepare(pts, 0.5, mat)))
 
 
 def test_prepare_empty_and_bad_arguments(dev):
-    assert eval_bmvs.prepare_cloud(np.zeros((0, 3), np.float32), 0.5).shape == (0, 3)
+    assert clouds.prepare_cloud(np.zeros((0, 3), np.float32), 0.5).shape == (0, 3)
     from svs_hip.lib import SvsError
     with pytest.raises(SvsError):
-        eval_bmvs.prepare_cloud(np.zeros((4, 3)), 0.0)
+        clouds.prepare_cloud(np.zeros((4, 3)), 0.0)
     with pytest.raises(ValueError):
-        eval_bmvs.prepare_cloud(np.zeros((4, 3)), 1.0, np.eye(3))
+        clouds.prepare_cloud(np.zeros((4, 3)), 1.0, np.eye(3))
 
 
 def _distances(n, seed, max_dist=20.0, vis_dist=10.0):
@@ -107,7 +108,7 @@ def test_error_colors_vs_oracle(dev, n):
                     sel = buf[off:off + n]
                     sel.copy_(torch.from_numpy(mask))
                     assert sel.data_ptr() % 16 == 1
-            rgb, u8 = eval_bmvs.error_colors(torch.from_numpy(d).to(dev), max_dist, vis_dist, select=sel)
+            rgb, u8 = clouds.error_colors(torch.from_numpy(d).to(dev), max_dist, vis_dist, select=sel)
             want, want_u8 = borc.error_colors(d, max_dist, vis_dist, select=mask)
             assert rgb.shape == u8.shape == (n, 3) and rgb.dtype == torch.float64 and u8.dtype == torch.uint8
             assert np.array_equal(_bits(rgb.cpu().numpy()), _bits(want)), (k, n)
@@ -117,7 +118,7 @@ def test_error_colors_vs_oracle(dev, n):
 def test_error_colors_edges(dev):
     """inf is green, the thresholds fall on the side the script puts them, nothing evaluated is all blue, bool masks."""
     d = np.array([np.inf, 1e300, 20.0, np.nextafter(20.0, 0), 10.0, 0.0, 3.3])
-    rgb, u8 = eval_bmvs.error_colors(torch.from_numpy(d).to(dev))
+    rgb, u8 = clouds.error_colors(torch.from_numpy(d).to(dev))
     rgb = rgb.cpu().numpy()
     np.testing.assert_array_equal(rgb[:3], [[0, 1, 0]] * 3)
     np.testing.assert_array_equal(rgb[3:5], [[1, 0, 0]] * 2)
@@ -126,13 +127,13 @@ def test_error_colors_edges(dev):
     np.testing.assert_array_equal(rgb[6], [a + (1 - a), 1 - a, 1 - a])
     np.testing.assert_array_equal(u8.cpu().numpy()[:6], [[0, 255, 0]] * 3 + [[255, 0, 0]] * 2 + [[255, 255, 255]])
     for n in (1, 65, 4097):
-        rgb, u8 = eval_bmvs.error_colors(torch.zeros(0, dtype=torch.float64, device=dev), select=torch.zeros(n, dtype=torch.uint8, device=dev))
+        rgb, u8 = clouds.error_colors(torch.zeros(0, dtype=torch.float64, device=dev), select=torch.zeros(n, dtype=torch.uint8, device=dev))
         assert (rgb.cpu().numpy() == [0, 0, 1]).all() and (u8.cpu().numpy() == [0, 0, 255]).all() and len(rgb) == n
     mask = torch.tensor([True, False, True, True, False], device=dev)
     d = np.array([1.0, 25.0, 12.0])
-    rgb, _ = eval_bmvs.error_colors(torch.from_numpy(d).to(dev), select=mask)
+    rgb, _ = clouds.error_colors(torch.from_numpy(d).to(dev), select=mask)
     np.testing.assert_array_equal(rgb.cpu().numpy(), borc.error_colors(d, select=mask.cpu().numpy())[0])
-    assert eval_bmvs.error_colors(torch.zeros(0, dtype=torch.float64, device=dev))[0].shape == (0, 3)
+    assert clouds.error_colors(torch.zeros(0, dtype=torch.float64, device=dev))[0].shape == (0, 3)
 
 
 def _check_u8_classes(u8, classes):
@@ -183,7 +184,7 @@ def test_scan4_matches_reference_script(dev, fx):
         near = want < 20
         np.testing.assert_array_equal(got[near], want[near])
         assert (got[~near] >= 20).all()
-        _check_colors(fx, f"s4_color_{side}", *eval_bmvs.error_colors(d["dist_" + side], 20, 10))
+        _check_colors(fx, f"s4_color_{side}", *clouds.error_colors(d["dist_" + side], 20, 10))
     np.testing.assert_allclose(res, fx["s4_means"], rtol=1e-12)
     assert 'scan{:0>3} {:.2f} {:.2f} {:.2f}'.format(4, *res) == str(fx["s4_row"])
     # the oracle on the same order: the whole prepared cloud, not the stored head only
@@ -203,7 +204,7 @@ def test_scan5_matches_reference_script(dev, fx):
         near = want < 20
         np.testing.assert_allclose(got[near], want[near], rtol=1e-12, atol=0)
         assert (got[~near] >= 20 * (1 - 1e-12)).all()
-        rgb, u8 = eval_bmvs.error_colors(d["dist_" + side], 20, 10)
+        rgb, u8 = clouds.error_colors(d["dist_" + side], 20, 10)
         np.testing.assert_array_equal(borc.color_classes(rgb.cpu().numpy()), fx[f"s5_color_{side}_classes"])
         _check_u8_classes(u8.cpu().numpy(), fx[f"s5_color_{side}_classes"])
     np.testing.assert_allclose(res, fx["s5_means"], rtol=1e-12)
@@ -245,7 +246,7 @@ def _write_ply(fn, pts):
 
 
 def test_file_layout_and_command_line(dev, fx, tmp_path, capsys):
-    from svs_hip.fusion import read_ply_points
+    from svs_hip.ply import read_points
     root, pred = tmp_path / "root" / "BlendedMVS", tmp_path / "pred"
     (root / "stl").mkdir(parents=True); pred.mkdir()
     scans = {}
@@ -267,19 +268,19 @@ def test_file_layout_and_command_line(dev, fx, tmp_path, capsys):
         np.testing.assert_allclose([float(v) for v in vals], fx[f"s{scan}_means"], rtol=0.02)
         np.testing.assert_allclose(res[scan], fx[f"s{scan}_means"], rtol=0.02)
         for side, n in (("d2s", int(fx[f"s{scan}_n_data"])), ("s2d", len(scans[scan]["gt_pcd"]))):
-            pts, rgb = read_ply_points(str(pred / "result" / f"{scan}_{side}.ply"))
+            pts, rgb = read_points(str(pred / "result" / f"{scan}_{side}.ply"))
             assert pts.shape == (n, 3) and rgb.shape == (n, 3) and rgb.dtype == np.uint8
             _check_u8_classes(rgb, fx[f"s{scan}_color_{side}_classes"])
-        gt, _ = read_ply_points(str(pred / "result" / f"{scan}_s2d.ply"))                 # the cloud the search saw
+        gt, _ = read_points(str(pred / "result" / f"{scan}_s2d.ply"))                 # the cloud the search saw
         assert np.array_equal(_bits(gt), _bits(borc.prepare(scans[scan]["gt_pcd"], scans[scan]["relative_scale"])))
     # --no_crop reads scan4.ply (half the ground truth here); the result is a tuple of three again
     r = eval_bmvs.evaluate_scan_files(4, str(pred), str(tmp_path / "root"), no_crop=True, visualize_error=True)
-    assert len(r) == 3 and read_ply_points(str(pred / "result" / "4_s2d.ply"))[0].shape == ((len(scans[4]["gt_pcd"]) + 1) // 2, 3)
+    assert len(r) == 3 and read_points(str(pred / "result" / "4_s2d.ply"))[0].shape == ((len(scans[4]["gt_pcd"]) + 1) // 2, 3)
 
 
 def test_dtu_command_line_writes_error_clouds(dev, dtu_run, fx, tmp_path, capsys):
     from scipy.io import savemat
-    from svs_hip.fusion import read_ply_points
+    from svs_hip.ply import read_points
     sc, _, d = dtu_run
     scan = 24
     ds = tmp_path / "root" / "DTU" / "DTU_MVS_Data"
@@ -293,8 +294,8 @@ def test_dtu_command_line_writes_error_clouds(dev, dtu_run, fx, tmp_path, capsys
     lines = capsys.readouterr().out.strip().splitlines()
     assert lines[0] == "ply_name, accuracy(mm), completeness(mm), overall(mm)" and lines[1].startswith("scan024 ") and \
         lines[2].startswith("mean_err ")
-    stl, rgb = read_ply_points(str(tmp_path / "pred" / "result" / f"vis_{scan:03}_s2d.ply"))
+    stl, rgb = read_points(str(tmp_path / "pred" / "result" / f"vis_{scan:03}_s2d.ply"))
     np.testing.assert_array_equal(stl, sc["stl"])
     np.testing.assert_array_equal(borc.color_classes(rgb)[0], fx["dtu_color_s2d_classes"][0])      # the plane side: order-free
-    pts, rgb = read_ply_points(str(tmp_path / "pred" / "result" / f"vis_{scan:03}_d2s.ply"))
+    pts, rgb = read_points(str(tmp_path / "pred" / "result" / f"vis_{scan:03}_d2s.ply"))
     assert pts.shape == rgb.shape and abs(len(pts) - int(fx["dtu_color_d2s_n"])) <= 0.02 * int(fx["dtu_color_d2s_n"])

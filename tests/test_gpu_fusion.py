@@ -78,6 +78,7 @@ def test_filter_depth_ply_and_edge_cases(dev, tmp_path):
     """filter_depth end to end (all-vs-all pairs, PLY on disk) against the oracle's vertices; no source views; a view
     fused against itself keeps every pixel with positive depth (size-independent property at a DTU-size image)."""
     from svs_hip import fusion
+    from svs_hip.ply import read_points
     views = synth.make_fusion_views(9, hw=(30, 44), n_views=3)
     ids = [0, 1, 2]
     pairs = [(v, [s for s in ids if s != v]) for v in ids]
@@ -90,7 +91,7 @@ def test_filter_depth_ply_and_edge_cases(dev, tmp_path):
         np.testing.assert_allclose(xyz, np.concatenate([w["xyz"] for w in want]), rtol=2e-6, atol=2e-6)
         assert np.array_equal(rgb, np.concatenate([w["rgb"] for w in want]))
         assert open(ply, "rb").read() == forc.ply_bytes(xyz, rgb)
-    pts, col = fusion.read_ply_points(ply)
+    pts, col = read_points(ply)
     assert pts.shape == (len(xyz), 3) and np.array_equal(col, rgb)
     assert sorted(os.listdir(tmp_path / "mask"))[0] == "00000000_final.png"
 
@@ -135,6 +136,7 @@ def test_filter_depth_folder_vs_reference_end_to_end(dev, golden_dir, tmp_path):
     from datasets.data_io import save_pfm
     from PIL import Image
     from svs_hip import fusion
+    from svs_hip.ply import read_points
     from test_fusion_cpu import load_filter_depth
     g, ids, views, conf = load_filter_depth(golden_dir)
     scan, out = tmp_path / "scan24", tmp_path / "out" / "scan24"
@@ -171,7 +173,7 @@ def test_filter_depth_folder_vs_reference_end_to_end(dev, golden_dir, tmp_path):
     assert np.array_equal(rgb[got_rows], g["vertex_rgb"][ref_rows])
     # the file: the reference's record layout (the oracle's ply_bytes is pinned to it by test_fusion_cpu) of OUR vertices
     assert open(ply, "rb").read() == forc.ply_bytes(xyz, rgb)
-    pts, col = fusion.read_ply_points(ply)
+    pts, col = read_points(ply)
     assert pts.shape == (len(xyz), 3) and np.array_equal(col, rgb)
     print(f"filter_depth: {len(xyz)} vertices (reference {len(g['vertex_xyz'])}), {n_diff} mask pixels differ")
     # on this fixture the masks are the reference's pixel for pixel, hence so are the vertex list and the file

@@ -286,8 +286,8 @@ def test_grid_sdf_with_rotation_and_offset(network):
 
 # ---- end to end --------------------------------------------------------------------------------------------------------
 def test_surface_high_res_end_to_end(network, tmp_path):
-    from evals import eval_dtu
-    from svs_hip.fusion import read_ply_mesh
+    from svs_hip import clouds
+    from svs_hip.ply import read_mesh
     with torch.no_grad():
         out = mesh.surface_high_res(network, resolution=32, grid_boundary=(-1.5, 1.5), coarse_resolution=32, n_samples=2000)
     assert out is not None
@@ -302,9 +302,9 @@ def test_surface_high_res_end_to_end(network, tmp_path):
     scale = np.diag([2.0, 2.0, 2.0, 1.0])
     scale[:3, 3] = [1.0, -2.0, 0.5]
     v, ff = mesh.finish_mesh(verts, faces, scale, fn)
-    rv, rf = read_ply_mesh(fn)
+    rv, rf = read_mesh(fn)
     assert np.array_equal(rv, v.astype(np.float64)) and np.array_equal(rf, ff.astype(np.int64))
-    cloud = eval_dtu.sample_mesh(rv, rf, 0.2)
+    cloud = clouds.sample_mesh(rv, rf, 0.2)
     assert cloud.shape[0] >= len(rv) and cloud.shape[1] == 3
 
 
@@ -329,7 +329,7 @@ def test_extract_from_a_checkpoint(dataset, tmp_path):
     eval_vsdf.py:148-150, scale_mat applied, one component; DTU cut by its box (scan 82 reads 83's)."""
     import os
     from svs_hip.evalviews import build_model
-    from svs_hip.fusion import read_ply_mesh
+    from svs_hip.ply import read_mesh
     root, scan = str(tmp_path), 82 if dataset == "DTU" else 1
     torch.manual_seed(0)
     ckpt = _checkpoint(root, build_model(dataset), 7)
@@ -346,7 +346,7 @@ def test_extract_from_a_checkpoint(dataset, tmp_path):
                        seed=a.seed, log=lines.append)
     assert res["file"] == os.path.join(root, "evals", f"t_{scan}", "mesh_7", f"scan{scan}.ply") and res["epoch"] == 7
     assert any(line.startswith("seconds: ") and "sdf" in line and "write" in line for line in lines)
-    v, f = read_ply_mesh(res["file"])
+    v, f = read_mesh(res["file"])
     assert len(v) == res["n_verts"] > 100 and len(f) == res["n_faces"] > 100
     assert len(np.unique(mo.vertex_labels(len(v), f))) == 1
     local = (v - scale[:3, 3]) / 2.0                                        # back to the model's frame

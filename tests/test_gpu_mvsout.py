@@ -222,6 +222,7 @@ def test_save_view_then_filter_depth_folder(dev, golden_dir, tmp_path):
     from helpers.utils import read_camera_parameters, read_img
     from PIL import Image
     from svs_hip import fusion, mvsout
+    from svs_hip.ply import read_points
     views, ids, pairs, hw = _scene(golden_dir)
     H, W = hw
     rng = np.random.default_rng(8)
@@ -255,7 +256,7 @@ def test_save_view_then_filter_depth_folder(dev, golden_dir, tmp_path):
     mem = {v: dict(views[v], confidence=conf[v], img=read_img(str(out / "images" / "{:0>8}.jpg".format(v)))) for v in ids}
     masks = {v: mvsout.eval_mask(read_img(mvsout.eval_mask_path(str(root), "DTU", "scan24", v)), H, W) for v in ids}
     xyz_m, rgb_m, stats_m = fusion.filter_depth(mem, pairs, eval_masks=masks, **kw)
-    pts, col = fusion.read_ply_points(ply)
+    pts, col = read_points(ply)
     assert len(pts) == len(xyz) == len(xyz_m) > 100
     assert np.array_equal(xyz, xyz_m) and np.array_equal(rgb, rgb_m) and np.array_equal(col, rgb)
     # without the new keywords, and with eval_mask_root=None: today's result

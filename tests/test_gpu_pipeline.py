@@ -22,6 +22,7 @@ def test_scan_pipeline(tmp_path, monkeypatch):
     from helpers.utils import write_cam
     from models.CasMVSNet import CascadeMVSNet
     from svs_hip import fusion
+    from svs_hip.ply import read_points
     from svs_hip.stage_loop import StageLoop
     from volsdf.vsdf import VolOpt
     monkeypatch.chdir(tmp_path)
@@ -104,7 +105,7 @@ def test_scan_pipeline(tmp_path, monkeypatch):
     assert sorted(os.listdir(outdir / "mask"))[:3] == ["00000000_final.png", "00000000_geo.png", "00000000_photo.png"]
 
     # ---- Chamfer evaluation of that PLY against a stand-in ground truth (evals/eval_dtu.py) ----
-    pts, col = fusion.read_ply_points(ply)
+    pts, col = read_points(ply)
     assert pts.shape[0] == xyz.shape[0]
     lo, hi = pts.min(0), pts.max(0)
     res = float((hi - lo).max() / 40.0)

@@ -259,7 +259,8 @@ def listed(folder, subs):
 
 def test_run_main_writes_the_scan(scan_run):
     from datasets.data_io import read_pfm
-    from svs_hip import fusion, mvsout
+    from svs_hip import mvsout
+    from svs_hip.ply import read_points
     out, res, text = scan_run["out"], scan_run["res"], scan_run["text"]
     assert sorted(os.listdir(out)) == ["all_scans.yaml", "mvsnet106_l3.ply", "scan106"]
     scan = out / "scan106"
@@ -292,23 +293,23 @@ def test_run_main_writes_the_scan(scan_run):
                   r"render ([\d.]+), save ([\d.]+), fusion ([\d.]+)", text)
     assert m and all(float(x) > 0 for x in m.groups()), text[-600:]
     xyz, rgb, stats = res["clouds"]["scan106"]
-    pts, col = fusion.read_ply_points(str(out / "mvsnet106_l3.ply"))
+    pts, col = read_points(str(out / "mvsnet106_l3.ply"))
     print(f"points {len(xyz)}, masks {stats}")
     assert len(stats) == 3 and pts.shape[0] == xyz.shape[0] > 0 and rgb.shape == xyz.shape
 
 
 def test_filter_only_leaves_the_maps_and_fuses_the_same_cloud(scan_run):
-    from svs_hip import fusion
+    from svs_hip.ply import read_points
     out = scan_run["out"]
     ply = str(out / "mvsnet106_l3.ply")
     pfms = [out / "scan106" / f for f in view_files(out) if f.endswith(".pfm")]
     before = {p: (os.stat(p).st_mtime_ns, open(p, "rb").read()) for p in pfms}
-    pts0, col0 = fusion.read_ply_points(ply)
+    pts0, col0 = read_points(ply)
     os.remove(ply)
     res, text = run_main(scan_run["root"], out, ["filter_only=true"])
     assert res["scans"] == {} and "loading model" not in text and text.count("photo/geo/final-mask:") == 3
     assert {p: (os.stat(p).st_mtime_ns, open(p, "rb").read()) for p in pfms} == before
-    pts1, col1 = fusion.read_ply_points(ply)
+    pts1, col1 = read_points(ply)
     # The fusion's order is fixed -- views in trains_i order, the surviving pixels of a view in row-major order
     # (svs_fuse_points compacts by a prefix sum over the mask, not by arrival) -- so the files would compare equal as they
     # are; sorted rows keep this test about the points, not about that order.

@@ -302,13 +302,13 @@ def scan_folder(tmp_path_factory):
 
 
 def _check_mesh_file(ply, v, f, c, sc, voxel):
-    from evals import eval_dtu
-    from svs_hip import fusion
-    rv, rf = fusion.read_ply_mesh(ply)
+    from svs_hip import clouds
+    from svs_hip.ply import read_mesh, read_points
+    rv, rf = read_mesh(ply)
     assert np.array_equal(rv, v.astype(np.float64)) and np.array_equal(rf, f)
-    assert np.array_equal(fusion.read_ply_points(ply)[1], c)
+    assert np.array_equal(read_points(ply)[1], c)
     assert len(f) > 0 and f.min() >= 0 and f.max() < len(v)
-    pts = eval_dtu.sample_mesh(rv, rf, voxel / 2)
+    pts = clouds.sample_mesh(rv, rf, voxel / 2)
     assert pts.shape[0] > len(v) and pts.shape[1] == 3 and bool(torch.isfinite(pts).all())
     # the averaged depth of a surviving pixel is within filter_diff = 1 % of the view's own, which is exact: the surface moves
     # by at most 0.01 * depth along the ray, on top of the one voxel of the grid (tests/test_tsdf_cpu.py)
@@ -353,8 +353,8 @@ def test_command_raw_bounds_largest(scan_folder):
 
 
 def test_runner_switch(scan_folder):
-    from evals import eval_dtu
-    from svs_hip import fusion, run
+    from svs_hip import clouds, run
+    from svs_hip.ply import read_mesh
     root = scan_folder["root"]
     base = [f"outdir={root}", "filter_only=true", "eval_mask=false", "testlist=scan106"]
     text = io.StringIO()
@@ -369,9 +369,9 @@ def test_runner_switch(scan_folder):
     assert os.path.exists(ply) and open(root / "mvsnet106_l3.ply", "rb").read() == cloud
     assert text.getvalue().count("scan106 tsdf seconds: read ") == 1
     stats = res["meshes"]["scan106"]
-    rv, rf = fusion.read_ply_mesh(str(ply))
+    rv, rf = read_mesh(str(ply))
     assert len(rv) == stats["n_verts"] > 0 and len(rf) == stats["n_faces"] > 0
-    assert eval_dtu.sample_mesh(rv, rf, 0.025).shape[0] > len(rv)
+    assert clouds.sample_mesh(rv, rf, 0.025).shape[0] > len(rv)
 
 
 # ---- errors ----------------------------------------------------------------------------------------------------------------

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 import mesh_oracle as mo
-from svs_hip import mc_table, mesh, scans
+from svs_hip import mc_table, mesh, ply, scans
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -131,13 +131,13 @@ def test_dtu_box_lookup(tmp_path):
 
 
 def test_ply_mesh_round_trip(tmp_path):
-    from svs_hip.fusion import read_ply_mesh
+    from svs_hip.ply import read_mesh
     rng = np.random.default_rng(3)
     verts = rng.standard_normal((37, 3)).astype(np.float32)
     faces = rng.integers(0, 37, size=(51, 3)).astype(np.int32)
     fn = str(tmp_path / "m.ply")
-    mesh.write_ply_mesh(fn, verts, faces)
-    v, f = read_ply_mesh(fn)
+    ply.write(fn, verts, faces=faces)
+    v, f = read_mesh(fn)
     assert v.dtype == np.float64 and np.array_equal(v, verts.astype(np.float64))
     assert np.array_equal(f, faces.astype(np.int64))
     head = open(fn, "rb").read(400).split(b"end_header\n")[0].decode("ascii")

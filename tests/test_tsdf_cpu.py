@@ -92,25 +92,25 @@ def _mesh():
 
 
 def test_coloured_ply_round_trips(tmp_path):
-    from svs_hip import fusion, mesh
+    from svs_hip import ply
     verts, faces, colors = _mesh()
     f = str(tmp_path / "c.ply")
-    mesh.write_ply_mesh(f, verts, faces, colors=colors)
-    v, t = fusion.read_ply_mesh(f)
+    ply.write(f, verts, colors, faces)
+    v, t = ply.read_mesh(f)
     np.testing.assert_array_equal(v, verts.astype(np.float64))
     np.testing.assert_array_equal(t, faces)
-    p, c = fusion.read_ply_points(f)
+    p, c = ply.read_points(f)
     np.testing.assert_array_equal(p, verts.astype(np.float64))
     np.testing.assert_array_equal(c, colors)
     with pytest.raises(ValueError):
-        mesh.write_ply_mesh(f, verts, faces, colors=colors[:3])
+        ply.write(f, verts, colors[:3], faces)
 
 
 def test_ply_without_colours_is_unchanged(tmp_path):
-    from svs_hip import mesh
+    from svs_hip import ply
     verts, faces, _ = _mesh()
     f = str(tmp_path / "m.ply")
-    mesh.write_ply_mesh(f, verts, faces)
+    ply.write(f, verts, faces=faces)
     want = (b"ply\nformat binary_little_endian 1.0\nelement vertex 4\nproperty float x\nproperty float y\nproperty float z\n"
             b"element face 3\nproperty list uchar int vertex_indices\nend_header\n" + verts.astype("<f4").tobytes()
             + b"".join(b"\x03" + row.astype("<i4").tobytes() for row in faces))

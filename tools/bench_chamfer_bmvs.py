@@ -39,8 +39,8 @@ def main(argv=None):
     import numpy as np
     import torch
     import synth_bmvs
-    from evals import eval_bmvs
-    from evals.eval_dtu import mean_below, nearest_neighbor
+    from svs_hip import clouds, ply
+    from svs_hip.clouds import mean_below, nearest_neighbor
     if not torch.cuda.is_available():
         raise SystemExit("bench_chamfer_bmvs needs the GPU")
     max_dist, vis_dist = 20, 10
@@ -64,16 +64,16 @@ def main(argv=None):
                 sec[name] = time.perf_counter() - t0
                 return r
             pred_d, gt_d = phase("upload", lambda: (torch.from_numpy(pred).to(dev), torch.from_numpy(gt).to(dev)))
-            data, ref = phase("prepare", lambda: (eval_bmvs.prepare_cloud(pred_d, rel), eval_bmvs.prepare_cloud(gt_d, rel)))
+            data, ref = phase("prepare", lambda: (clouds.prepare_cloud(pred_d, rel), clouds.prepare_cloud(gt_d, rel)))
             d2s = phase("d2s_search", lambda: nearest_neighbor(ref, data, max_dist))
             if sec["d2s_search"] <= LIMITS["d2s_search"]:
                 s2d = phase("s2d_search", lambda: nearest_neighbor(data, ref, max_dist))
             if all(sec[k] <= LIMITS[k] for k in sec) and "s2d_search" in sec:
                 means = phase("means", lambda: (mean_below(d2s, max_dist), mean_below(s2d, max_dist)))
-                cols = phase("colours", lambda: (eval_bmvs.error_colors(d2s, max_dist, vis_dist), eval_bmvs.error_colors(s2d, max_dist, vis_dist)))
+                cols = phase("colours", lambda: (clouds.error_colors(d2s, max_dist, vis_dist), clouds.error_colors(s2d, max_dist, vis_dist)))
                 host = phase("download", lambda: (data.cpu().numpy(), cols[0][1].cpu().numpy(), ref.cpu().numpy(), cols[1][1].cpu().numpy()))
-                phase("write", lambda: (eval_bmvs.write_vis_pcd(os.path.join(tmp, "d2s.ply"), host[0], host[1]),
-                                        eval_bmvs.write_vis_pcd(os.path.join(tmp, "s2d.ply"), host[2], host[3])))
+                phase("write", lambda: (ply.write(os.path.join(tmp, "d2s.ply"), host[0], host[1], coords="double"),
+                                        ply.write(os.path.join(tmp, "s2d.ply"), host[2], host[3], coords="double")))
             runs.append(sec)
             print(f"run {rep}: " + ", ".join(f"{k} {v * 1e3:.1f} ms" for k, v in sec.items()), flush=True)
             late = [k for k in sec if sec[k] > LIMITS[k]]

@@ -25,8 +25,7 @@ def gpu_time(fn, n=3):
 
 
 def main():
-    from evals import eval_dtu
-    from svs_hip import fusion
+    from svs_hip import clouds, fusion
     import chamfer_oracle, fusion_oracle
     res = {}
     views = synth.make_fusion_views(1, hw=(1200, 1600), n_views=3)
@@ -44,9 +43,9 @@ def main():
     s = rng.normal(0, 1, (n // 2, 3)); s /= np.linalg.norm(s, axis=1, keepdims=True); stl = s * 150.0
     P, Sd = torch.from_numpy(pred).cuda(), torch.from_numpy(stl).cuda()
     res["points_pred"], res["points_stl"] = n, n // 2
-    res["downsample_0.2_ms"] = gpu_time(lambda: eval_dtu.radius_downsample(P, 0.2), 1) * 1e3
-    res["nn_pred_to_stl_ms"] = gpu_time(lambda: eval_dtu.nearest_neighbor(Sd, P, 20.0), 2) * 1e3
-    res["nn_stl_to_pred_ms"] = gpu_time(lambda: eval_dtu.nearest_neighbor(P, Sd, 20.0), 2) * 1e3
+    res["downsample_0.2_ms"] = gpu_time(lambda: clouds.radius_downsample(P, 0.2), 1) * 1e3
+    res["nn_pred_to_stl_ms"] = gpu_time(lambda: clouds.nearest_neighbor(Sd, P, 20.0), 2) * 1e3
+    res["nn_stl_to_pred_ms"] = gpu_time(lambda: clouds.nearest_neighbor(P, Sd, 20.0), 2) * 1e3
     m = 400_000
     t0 = time.perf_counter(); chamfer_oracle.nn_distance(stl, pred[:m]); t1 = time.perf_counter()
     res["nn_cpu_sklearn_ms_scaled"] = (t1 - t0) * (n / m) * 1e3

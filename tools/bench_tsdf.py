@@ -105,7 +105,7 @@ def main(argv=None):
     a = p.parse_args(argv)
     import numpy as np
     import torch
-    from svs_hip import mesh, tsdf
+    from svs_hip import mesh, ply, tsdf
     if not torch.cuda.is_available():
         raise SystemExit("bench_tsdf needs the GPU")
     n = a.resolution
@@ -176,7 +176,7 @@ def main(argv=None):
     ms["download"] = sync_ms(t0)
     with tempfile.TemporaryDirectory() as tmp:
         t0 = time.perf_counter()
-        mesh.write_ply_mesh(os.path.join(tmp, "tsdf.ply"), v, f, colors=c)
+        ply.write(os.path.join(tmp, "tsdf.ply"), v, c, f)
         ms["write"] = (time.perf_counter() - t0) * 1e3
         file_bytes = os.path.getsize(os.path.join(tmp, "tsdf.ply"))
 
