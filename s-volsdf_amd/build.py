@@ -27,6 +27,7 @@ UNITS = {
     "svs_bg_f32.hip": [],
     "svs_sampler.hip": ["-ffp-contract=off"],
     "svs_render.hip": ["-ffp-contract=off"],
+    "svs_composite.hip": ["-ffp-contract=off"],
     "svs_costvol.hip": ["-ffp-contract=off"],
     "svs_conv_mfma.hip": [],
     "svs_conv_pair.hip": [],

@@ -1,9 +1,9 @@
-// Ray set-up and alpha compositing for gfx950.
+// Ray set-up, the MVS prior look-up, the loss and the inverse-sphere points for gfx950 (compositing: svs_composite.hip).
 //
 // Reference: volsdf/utils/rend_util.py:60-95,143-156 (get_camera_params, lift), volsdf/model/network.py:213-222
-// (ray set-up), :281-295 (volume_rendering) and :237-256,270-276 (the weighted reductions).
+// (ray set-up), volsdf/vsdf.py:382-452 (cost_mapping), volsdf/model/loss.py:80-114, volsdf/model/network_bg.py:182-214.
 // Compiled with -ffp-contract=off: same numeric contract as the sampler (svs_sampler.hip).
-#include "svs_common.h"
+#include "svs_ray_scan.h"
 
 namespace svs {
 namespace render {
@@ -64,256 +64,6 @@ __global__ void split_last_kernel(const float* __restrict__ z, int R, int n, flo
   const int r = i / n, c = i - r * n;
   if (c == n - 1) last[r] = z[i];
   else head[r * (n - 1) + c] = z[i];
-}
-
-// ---- a8: compositing ------------------------------------------------------------------------------------
-constexpr int kMaxS = 256;
-
-__device__ __forceinline__ float wave_cumsum_excl_out(const float* in, float* out, int m, int lane) {
-  // canonical inclusive cumsum (see svs_sampler.hip); duplicated here so this file stands alone
-  const int c = (m + 63) >> 6;
-  const int lo = lane * c;
-  const int hi = (lo + c < m) ? lo + c : m;
-  double tot = 0.0;
-  for (int j = lo; j < hi; ++j) tot = tot + (double)in[j];
-  double scan = tot;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const double o = __shfl_up(scan, d);
-    if (lane >= d) scan = scan + o;
-  }
-  double off = __shfl_up(scan, 1);
-  if (lane == 0) off = 0.0;
-  double acc = 0.0;
-  float last = 0.0f;
-  for (int j = lo; j < hi; ++j) {
-    acc = acc + (double)in[j];
-    last = (float)(off + acc);
-    out[j] = last;
-  }
-  return __shfl(last, (m - 1) / c);
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-  return v;
-}
-
-// ---- float64 helpers of the compositing BACKWARD kernels.  The forward kernels follow the bit-exact float32 contract of
-// the sampler; their reverse passes have no such contract (the reference gets these gradients from float32 autograd) and
-// d loss / d beta is a sum with 1 / beta^3 factors and heavy cancellation: in float32 it was 4e-4 off float64 autograd at
-// beta = 0.005.  Everything between the float32 inputs and the float32 outputs of the reverse passes is therefore double.
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-  return v;
-}
-__device__ __forceinline__ double dexp(double x) { return x < -745.0 ? 0.0 : exp(x); }
-// out[j] = sum_{i <= j} in[i] (in place allowed); returns the total
-__device__ __forceinline__ double wave_cumsum_incl(const double* in, double* out, int m, int lane) {
-  const int c = (m + 63) >> 6;
-  const int lo = lane * c;
-  const int hi = (lo + c < m) ? lo + c : m;
-  double tot = 0.0;
-  for (int j = lo; j < hi; ++j) tot += in[j];
-  double scan = tot;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const double o = __shfl_up(scan, d);
-    if (lane >= d) scan += o;
-  }
-  double acc = scan - tot;
-  for (int j = lo; j < hi; ++j) { acc += in[j]; out[j] = acc; }
-  return __shfl(acc, (m - 1) / c);
-}
-// out[j] = sum_{i > j} in[i] (in place allowed), summed from the top down.  Not total - prefix: that difference carries
-// eps times the whole ray's sum, which swamps a suffix behind an opaque surface at beta_min (test_composite_backward_edges
-// [1e-12-2] and test_composite_bg_backward_edges[0.0-2]: d_sdf 5.6x and 2.1x its largest value off).  The last element's
-// suffix is exactly 0 (its interval is 1e10).
-__device__ __forceinline__ void wave_suffix_excl(const double* in, double* out, int m, int lane) {
-  const int c = (m + 63) >> 6;
-  const int lo = lane * c;
-  const int hi = (lo + c < m) ? lo + c : m;
-  double tot = 0.0;
-  for (int j = hi - 1; j >= lo; --j) tot += in[j];
-  double scan = tot;                    // -> sum of the chunks of lanes >= lane
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const double o = __shfl_down(scan, d);
-    if (lane + d < 64) scan += o;
-  }
-  double acc = __shfl_down(scan, 1);    // the chunks of lanes > lane
-  if (lane == 63) acc = 0.0;
-  for (int j = hi - 1; j >= lo; --j) { const double v = in[j]; out[j] = acc; acc += v; }
-}
-// Laplace density and its derivatives in double (density.py:21-30)
-struct DensityD {
-  double sigma, dsig_dsdf, dsig_dbeta;
-  __device__ __forceinline__ DensityD(double s, double beta) {
-    const double as = s < 0.0 ? -s : s;
-    const double e = dexp(-as / beta);
-    const double sgn = s > 0.0 ? 1.0 : (s < 0.0 ? -1.0 : 0.0);
-    // 0.5 + 0.5 * sgn * (e - 1) without its cancellation: formed as written, sigma for sdf / beta > 20 kept only
-    // 1e-16 / e of its relative accuracy, which the last interval (1e10) carries into d_sdf and d beta
-    // (test_composite_backward_edges[0.02-2/63/64/98/256]: d_sdf up to 130x its largest value off, d beta 4x its bound)
-    sigma = (1.0 / beta) * (s > 0.0 ? 0.5 * e : 1.0 - 0.5 * e);
-    // sign(0) = 0 in the reference's density: its gradient w.r.t. sdf vanishes there as well
-    dsig_dsdf = s != 0.0 ? -0.5 * e / (beta * beta) : 0.0;
-    dsig_dbeta = -sigma / beta + 0.5 * sgn * e * as / (beta * beta * beta);
-  }
-};
-
-struct CompositeArgs {
-  int R, S;
-  const float* z;            // (R,S)
-  const float* sdf;          // (R*S)
-  const float* rgb;          // (R*S,3)
-  const float* normals;      // (R*S,3) or nullptr
-  const float* depth_scale;  // (R)
-  const float* beta_param;   // device scalar: density.beta; beta = |beta| + beta_min (density.py:28-30)
-  float beta_min;
-  float* weights;            // (R,S)
-  float* rgb_values;         // (R,3)
-  float* depth_values;       // (R)
-  float* depth_vals;         // (R,S) = z * depth_scale
-  float* normal_map;         // (R,3) or nullptr
-};
-
-__global__ __launch_bounds__(64) void composite_kernel(CompositeArgs a) {
-  __shared__ float zs[kMaxS], fe[kMaxS], sfe[kMaxS];
-  const int r = blockIdx.x, lane = threadIdx.x, S = a.S;
-  const float beta = __builtin_fabsf(*a.beta_param) + a.beta_min;
-  for (int i = lane; i < S; i += 64) zs[i] = a.z[(size_t)r * S + i];
-  __syncthreads();
-  for (int i = lane; i < S; i += 64) {
-    const float dist = i < S - 1 ? zs[i + 1] - zs[i] : 1e10f;
-    fe[i] = dist * laplace_density(a.sdf[(size_t)r * S + i], beta);
-  }
-  __syncthreads();
-  for (int i = lane; i < S; i += 64) sfe[i] = i == 0 ? 0.0f : fe[i - 1];
-  __syncthreads();
-  wave_cumsum_excl_out(sfe, sfe, S, lane);
-  __syncthreads();
-  float sw = 0.0f, swz = 0.0f, c0 = 0.0f, c1 = 0.0f, c2 = 0.0f, n0 = 0.0f, n1 = 0.0f, n2 = 0.0f;
-  const float ds = a.depth_scale[r];
-  for (int i = lane; i < S; i += 64) {
-    const size_t p = (size_t)r * S + i;
-    const float w = (1.0f - sleef_expf(-fe[i])) * sleef_expf(-sfe[i]);
-    a.weights[p] = w;
-    a.depth_vals[p] = zs[i] * ds;
-    sw += w; swz += w * zs[i];
-    c0 += w * a.rgb[3 * p]; c1 += w * a.rgb[3 * p + 1]; c2 += w * a.rgb[3 * p + 2];
-    if (a.normal_map) {
-      const float g0 = a.normals[3 * p], g1 = a.normals[3 * p + 1], g2 = a.normals[3 * p + 2];
-      const float nn = norm3(g0, g1, g2);            // gradients.norm(2, -1)
-      n0 += w * (g0 / nn); n1 += w * (g1 / nn); n2 += w * (g2 / nn);
-    }
-  }
-  sw = wave_sum(sw); swz = wave_sum(swz); c0 = wave_sum(c0); c1 = wave_sum(c1); c2 = wave_sum(c2);
-  if (a.normal_map) { n0 = wave_sum(n0); n1 = wave_sum(n1); n2 = wave_sum(n2); }
-  if (lane == 0) {
-    a.rgb_values[3 * r] = c0; a.rgb_values[3 * r + 1] = c1; a.rgb_values[3 * r + 2] = c2;
-    a.depth_values[r] = ds * (swz / (sw + 1e-8f));
-    if (a.normal_map) { a.normal_map[3 * r] = n0; a.normal_map[3 * r + 1] = n1; a.normal_map[3 * r + 2] = n2; }
-  }
-}
-
-// ---- a8 backward: d(loss)/d(sdf, rgb, beta) from d(loss)/d(rgb_values, weights, depth_values) -----------------
-// Forward (network.py:281-295): fe_i = dist_i * sigma(sdf_i, beta), w_i = (1 - exp(-fe_i)) * exp(-sum_{j<i} fe_j);
-// rgb_values = sum w_i c_i, depth_values = ds * sum(w_i z_i) / (sum w_i + 1e-8).  Hand-derived reverse pass:
-//   dL/dfe_k = dw_k * T_k * exp(-fe_k) - sum_{i>k} dw_i * w_i
-//   dsigma/dsdf = -exp(-|s|/beta) / (2 beta^2),  dsigma/dbeta = -sigma/beta + sgn(s) exp(-|s|/beta) |s| / (2 beta^3)
-struct CompositeBwdArgs {
-  int R, S;
-  const float* z; const float* sdf; const float* rgb; const float* depth_scale;
-  const float* beta_param; float beta_min;
-  const float* d_rgb_values;   // (R,3)
-  const float* d_weights;      // (R,S) or nullptr
-  const float* d_depth_values; // (R) or nullptr
-  float* d_sdf;                // (R*S)
-  float* d_rgb;                // (R*S,3)
-  float* d_beta_ray;           // (R): per-ray d loss / d beta (summed by beta_reduce_kernel)
-};
-
-__global__ __launch_bounds__(64) void composite_bwd_kernel(CompositeBwdArgs a) {
-  __shared__ double zs[kMaxS], fe[kMaxS], tr[kMaxS], dw[kMaxS], pre[kMaxS];
-  const int r = blockIdx.x, lane = threadIdx.x, S = a.S;
-  const double beta = (double)(__builtin_fabsf(*a.beta_param) + a.beta_min);
-  for (int i = lane; i < S; i += 64) zs[i] = (double)a.z[(size_t)r * S + i];
-  __syncthreads();
-  for (int i = lane; i < S; i += 64) {
-    const double dist = i < S - 1 ? (double)(float)(zs[i + 1] - zs[i]) : 1e10;      // (the forward's float32 distance)
-    fe[i] = dist * DensityD((double)a.sdf[(size_t)r * S + i], beta).sigma;
-  }
-  __syncthreads();
-  // tr[i] = sum_{j < i} fe_j as the inclusive scan of the shifted sequence: the last free energy (dist = 1e10) must not
-  // enter any partial sum, it would cost the prefixes of its lane's chunk 1e-5 of absolute accuracy
-  for (int i = lane; i < S; i += 64) tr[i] = i == 0 ? 0.0 : fe[i - 1];
-  __syncthreads();
-  wave_cumsum_incl(tr, tr, S, lane);
-  __syncthreads();
-  double sw = 0.0, swz = 0.0;
-  for (int i = lane; i < S; i += 64) {
-    const double T = dexp(-tr[i]);
-    tr[i] = T;
-    const double w = (1.0 - dexp(-fe[i])) * T;
-    pre[i] = w;                         // weights, reused below
-    sw += w; swz += w * zs[i];
-  }
-  sw = wave_sum(sw); swz = wave_sum(swz);
-  __syncthreads();
-  const double ds = (double)a.depth_scale[r];
-  const double g0 = a.d_rgb_values[3 * r], g1 = a.d_rgb_values[3 * r + 1], g2 = a.d_rgb_values[3 * r + 2];
-  const double gd = a.d_depth_values ? (double)a.d_depth_values[r] * ds : 0.0;
-  const double den = sw + 1e-8;
-  for (int i = lane; i < S; i += 64) {
-    const size_t p = (size_t)r * S + i;
-    const double w = pre[i];
-    const double c0 = a.rgb[3 * p], c1 = a.rgb[3 * p + 1], c2 = a.rgb[3 * p + 2];
-    a.d_rgb[3 * p] = (float)(w * g0); a.d_rgb[3 * p + 1] = (float)(w * g1); a.d_rgb[3 * p + 2] = (float)(w * g2);
-    double d = (c0 * g0 + c1 * g1) + c2 * g2;
-    if (a.d_weights) d += (double)a.d_weights[p];
-    d += gd * (zs[i] * den - swz) / (den * den);
-    dw[i] = d;
-    pre[i] = d * w;                     // summand of the suffix sums
-  }
-  __syncthreads();
-  wave_suffix_excl(pre, pre, S, lane);
-  __syncthreads();
-  double dbeta = 0.0;
-  for (int i = lane; i < S; i += 64) {
-    const size_t p = (size_t)r * S + i;
-    const double suffix = pre[i];                                // sum_{j>i} dw_j w_j
-    const double dfe = dw[i] * tr[i] * dexp(-fe[i]) - suffix;
-    const double dist = i < S - 1 ? (double)(float)(zs[i + 1] - zs[i]) : 1e10;
-    const double dsig = dfe * dist;
-    const DensityD dn((double)a.sdf[p], beta);
-    a.d_sdf[p] = (float)(dsig * dn.dsig_dsdf);
-    // exp(-fe) underflows long before dist = 1e10 matters; guard the 0 * inf of the last sample
-    if (dfe != 0.0) dbeta += dsig * dn.dsig_dbeta;
-  }
-  dbeta = wave_sum(dbeta);
-  if (lane == 0) a.d_beta_ray[r] = (float)dbeta;
-}
-
-// d loss / d density.beta = sign(beta_param) * sum over rays (float64, fixed order -> reproducible)
-__global__ __launch_bounds__(256) void beta_reduce_kernel(const float* __restrict__ d_beta_ray, int R,
-                                                          const float* __restrict__ beta_param, float* __restrict__ out,
-                                                          int accumulate) {
-  __shared__ double sh[4];
-  double acc = 0.0;
-  for (int i = threadIdx.x; i < R; i += 256) acc += (double)d_beta_ray[i];
-  for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const double t = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-    const float bp = *beta_param;
-    const float sg = bp > 0.0f ? 1.0f : (bp < 0.0f ? -1.0f : 0.0f);
-    const float v = sg * (float)t;
-    out[0] = accumulate ? out[0] + v : v;
-  }
 }
 
 // ---- a10: MVS prior lookup (VolOpt.cost_mapping, volsdf/vsdf.py:382-452) --------------------------------
@@ -543,12 +293,6 @@ __global__ __launch_bounds__(256) void loss_reduce_kernel(LossArgs a, const doub
 }
 
 // ---- a9 (BG model): inverted-sphere samples and fg/bg compositing (volsdf/model/network_bg.py) --------------------
-// torch.linspace(start,end,n)[i] in float32 (see svs_sampler.hip)
-__device__ __forceinline__ float linspace_at_r(float start, float end, int n, int i) {
-  const float step = (end - start) / (float)(n - 1);
-  return i < n / 2 ? __builtin_fmaf(step, (float)i, start) : __builtin_fmaf(-step, (float)(n - 1 - i), end);
-}
-
 struct BgPointsArgs {
   int R, N;                 // rays, inverse-sphere samples per ray (32)
   const float* cam; int cam_stride;
@@ -567,7 +311,7 @@ __global__ void bg_points_kernel(BgPointsArgs a) {
   if (idx >= a.R * a.N) return;
   const int r = idx / a.N, k = idx % a.N;
   const int i = a.N - 1 - k;                              // position before the flip
-  auto zu = [&](int j) { const float t = linspace_at_r(0.0f, 1.0f, a.N, j); return 0.0f * (1.0f - t) + 1.0f * t; };
+  auto zu = [&](int j) { const float t = linspace_at(0.0f, 1.0f, a.N, j); return 0.0f * (1.0f - t) + 1.0f * t; };
   float z = zu(i);
   if (a.jitter) {
     const float upper = i < a.N - 1 ? 0.5f * (zu(i + 1) + zu(i)) : zu(a.N - 1);
@@ -605,231 +349,6 @@ __global__ void bg_points_kernel(BgPointsArgs a) {
   const float d1 = -o_dot_d / dd;
   const float ray_d_cos = 1.0f / norm3(d[0], d[1], d[2]);
   a.depth_real[idx] = ((1.0f / (depth + 1e-6f)) * cosf(theta)) * ray_d_cos + d1;
-}
-
-struct CompositeBgArgs {
-  int R, S, Nb;              // rays, fg samples (97), bg samples (32)
-  const float* z;            // (R,S) fg sample distances
-  const float* z_max;        // (R) sphere exit
-  const float* sdf;          // (R*S)
-  const float* rgb;          // (R*S,3)
-  const float* normals;      // (R*S,3) or nullptr
-  const float* depth_scale;  // (R)
-  const float* beta_param; float beta_min;
-  const float* z_bg;         // (R,Nb) descending inverse depths
-  const float* bg_out0;      // (R*Nb) raw bg output[:,0]; density = |.|
-  const float* bg_rgb;       // (R*Nb,3)
-  const float* bg_depth;     // (R,Nb) conventional depths of the bg samples
-  float* weights;            // (R,S)
-  float* bg_trans;           // (R) transmittance behind the last fg sample
-  float* bg_weights;         // (R,Nb)
-  float* rgb_values;         // (R,3)
-  float* depth_values;       // (R)
-  float* depth_values_all;   // (R)
-  float* depth_vals;         // (R,S)
-  float* normal_map;         // (R,3) or nullptr
-};
-
-// VolSDFNetworkBG.volume_rendering / bg_volume_rendering and the composition (network_bg.py:76-125, 147-180)
-__global__ __launch_bounds__(64) void composite_bg_kernel(CompositeBgArgs a) {
-  __shared__ float zs[kMaxS], fe[kMaxS], sfe[kMaxS], bfe[64], bsf[64];
-  const int r = blockIdx.x, lane = threadIdx.x, S = a.S, Nb = a.Nb;
-  const float beta = __builtin_fabsf(*a.beta_param) + a.beta_min;
-  for (int i = lane; i < S; i += 64) zs[i] = a.z[(size_t)r * S + i];
-  for (int i = lane; i < Nb; i += 64) bsf[i] = a.z_bg[(size_t)r * Nb + i];
-  __syncthreads();
-  for (int i = lane; i < S; i += 64) {
-    const float dist = i < S - 1 ? zs[i + 1] - zs[i] : a.z_max[r] - zs[i];
-    fe[i] = dist * laplace_density(a.sdf[(size_t)r * S + i], beta);
-  }
-  for (int i = lane; i < Nb; i += 64) {
-    const float dist = i < Nb - 1 ? bsf[i] - bsf[i + 1] : 1e10f;
-    bfe[i] = dist * __builtin_fabsf(a.bg_out0[(size_t)r * Nb + i]);
-  }
-  __syncthreads();
-  for (int i = lane; i <= S; i += 64) sfe[i] = i == 0 ? 0.0f : fe[i - 1];      // S + 1 entries: the last is the total
-  for (int i = lane; i < Nb; i += 64) bsf[i] = i == 0 ? 0.0f : bfe[i - 1];
-  __syncthreads();
-  wave_cumsum_excl_out(sfe, sfe, S + 1, lane);
-  __syncthreads();
-  wave_cumsum_excl_out(bsf, bsf, Nb, lane);
-  __syncthreads();
-  const float tbg = sleef_expf(-sfe[S]);
-  const float ds = a.depth_scale[r];
-  float sw = 0.0f, swz = 0.0f, c0 = 0.0f, c1 = 0.0f, c2 = 0.0f, n0 = 0.0f, n1 = 0.0f, n2 = 0.0f, swa = 0.0f, swd = 0.0f;
-  for (int i = lane; i < S; i += 64) {
-    const size_t p = (size_t)r * S + i;
-    const float w = (1.0f - sleef_expf(-fe[i])) * sleef_expf(-sfe[i]);
-    a.weights[p] = w;
-    const float dv = zs[i] * ds;
-    a.depth_vals[p] = dv;
-    sw += w; swz += w * dv; swa += w; swd += w * (ds * zs[i]);
-    c0 += w * a.rgb[3 * p]; c1 += w * a.rgb[3 * p + 1]; c2 += w * a.rgb[3 * p + 2];
-    if (a.normal_map) {
-      const float g0 = a.normals[3 * p], g1 = a.normals[3 * p + 1], g2 = a.normals[3 * p + 2];
-      const float nn = norm3(g0, g1, g2);            // gradients.norm(2, -1)
-      n0 += w * (g0 / nn); n1 += w * (g1 / nn); n2 += w * (g2 / nn);
-    }
-  }
-  float b0 = 0.0f, b1 = 0.0f, b2 = 0.0f;
-  for (int i = lane; i < Nb; i += 64) {
-    const size_t p = (size_t)r * Nb + i;
-    const float bw = (1.0f - sleef_expf(-bfe[i])) * sleef_expf(-bsf[i]);
-    a.bg_weights[p] = bw;
-    b0 += bw * a.bg_rgb[3 * p]; b1 += bw * a.bg_rgb[3 * p + 1]; b2 += bw * a.bg_rgb[3 * p + 2];
-    const float wa = tbg * bw;
-    swa += wa; swd += wa * (ds * a.bg_depth[p]);
-  }
-  sw = wave_sum(sw); swz = wave_sum(swz); c0 = wave_sum(c0); c1 = wave_sum(c1); c2 = wave_sum(c2);
-  b0 = wave_sum(b0); b1 = wave_sum(b1); b2 = wave_sum(b2); swa = wave_sum(swa); swd = wave_sum(swd);
-  if (a.normal_map) { n0 = wave_sum(n0); n1 = wave_sum(n1); n2 = wave_sum(n2); }
-  if (lane == 0) {
-    a.bg_trans[r] = tbg;
-    a.rgb_values[3 * r] = c0 + tbg * b0; a.rgb_values[3 * r + 1] = c1 + tbg * b1; a.rgb_values[3 * r + 2] = c2 + tbg * b2;
-    a.depth_values[r] = swz / (sw + 1e-8f);
-    a.depth_values_all[r] = swd / (swa + 1e-8f);
-    if (a.normal_map) { a.normal_map[3 * r] = n0; a.normal_map[3 * r + 1] = n1; a.normal_map[3 * r + 2] = n2; }
-  }
-}
-
-struct CompositeBgBwdArgs {
-  int R, S, Nb;
-  const float* z; const float* z_max; const float* sdf; const float* rgb; const float* depth_scale;
-  const float* beta_param; float beta_min;
-  const float* z_bg; const float* bg_out0; const float* bg_rgb;
-  const float* d_rgb_values;   // (R,3)
-  const float* d_weights;      // (R,S) or nullptr
-  const float* d_depth_values; // (R) or nullptr (the fg depth of network_bg.py:111-112)
-  const float* d_depth_all;    // (R) or nullptr: gradient of depth_values_all (network_bg.py:105-107) -- what the sparsity
-                               // term of the loss reads (loss.py:72-73); needs bg_depth
-  const float* bg_depth;       // (R,Nb) conventional depths of the inverse-sphere samples (with d_depth_all)
-  float* d_sdf;                // (R*S)
-  float* d_rgb;                // (R*S,3)
-  float* d_bg_out0;            // (R*Nb)
-  float* d_bg_rgb;             // (R*Nb,3)
-  float* d_beta_ray;           // (R)
-};
-
-// backward of composite_bg_kernel with respect to sdf, rgb, beta, the bg density logits and the bg colours
-__global__ __launch_bounds__(64) void composite_bg_bwd_kernel(CompositeBgBwdArgs a) {
-  // (float64 throughout, see DensityD)
-  __shared__ double zs[kMaxS], fe[kMaxS], tr[kMaxS], dw[kMaxS], pre[kMaxS], bz[64], bfe[64], btr[64], bdw[64], bpre[64];
-  const int r = blockIdx.x, lane = threadIdx.x, S = a.S, Nb = a.Nb;
-  const double beta = (double)(__builtin_fabsf(*a.beta_param) + a.beta_min);
-  for (int i = lane; i < S; i += 64) zs[i] = (double)a.z[(size_t)r * S + i];
-  for (int i = lane; i < Nb; i += 64) bz[i] = (double)a.z_bg[(size_t)r * Nb + i];
-  __syncthreads();
-  const double zmax = (double)a.z_max[r];
-  auto fg_dist = [&](int i) { return (double)(float)((i < S - 1 ? zs[i + 1] : zmax) - zs[i]); };   // the forward's float32 distances
-  auto bg_dist = [&](int i) { return i < Nb - 1 ? (double)(float)(bz[i] - bz[i + 1]) : 1e10; };
-  for (int i = lane; i < S; i += 64) fe[i] = fg_dist(i) * DensityD((double)a.sdf[(size_t)r * S + i], beta).sigma;
-  for (int i = lane; i < Nb; i += 64) {
-    const double o = (double)a.bg_out0[(size_t)r * Nb + i];
-    bfe[i] = bg_dist(i) * (o < 0.0 ? -o : o);
-  }
-  __syncthreads();
-  // exclusive prefixes as inclusive scans of the shifted sequences (the last background free energy, dist = 1e10, must not
-  // enter any partial sum); tr[S] = the total foreground free energy
-  for (int i = lane; i <= S; i += 64) tr[i] = i == 0 ? 0.0 : fe[i - 1];
-  for (int i = lane; i < Nb; i += 64) btr[i] = i == 0 ? 0.0 : bfe[i - 1];
-  __syncthreads();
-  wave_cumsum_incl(tr, tr, S + 1, lane);
-  __syncthreads();
-  wave_cumsum_incl(btr, btr, Nb, lane);
-  __syncthreads();
-  const double tbg = dexp(-tr[S]);
-  const double ds = (double)a.depth_scale[r];
-  const double g0 = a.d_rgb_values[3 * r], g1 = a.d_rgb_values[3 * r + 1], g2 = a.d_rgb_values[3 * r + 2];
-  // background: weights, colour sums, and the sums of depth_values_all = swd / (swa + 1e-8) over [w_fg, tbg * bw] with
-  // depths ds * [z, bg_depth]
-  const double ga = a.d_depth_all ? (double)a.d_depth_all[r] : 0.0;
-  double bdot = 0.0;       // sum_c g_c * sum_k bw_k cb_kc
-  double swa = 0.0, swd = 0.0;
-  for (int i = lane; i < Nb; i += 64) {
-    const size_t p = (size_t)r * Nb + i;
-    const double T = dexp(-btr[i]);
-    btr[i] = T;
-    const double bw = (1.0 - dexp(-bfe[i])) * T;
-    const double c0 = a.bg_rgb[3 * p], c1 = a.bg_rgb[3 * p + 1], c2 = a.bg_rgb[3 * p + 2];
-    a.d_bg_rgb[3 * p] = (float)((tbg * bw) * g0); a.d_bg_rgb[3 * p + 1] = (float)((tbg * bw) * g1);
-    a.d_bg_rgb[3 * p + 2] = (float)((tbg * bw) * g2);
-    const double cg = (c0 * g0 + c1 * g1) + c2 * g2;
-    bdot += bw * cg;
-    bdw[i] = tbg * cg;                 // d loss / d bw_i (colour term; the depth term follows once the sums are known)
-    bpre[i] = bw;
-    if (a.d_depth_all) { swa += tbg * bw; swd += (tbg * bw) * (ds * (double)a.bg_depth[p]); }
-  }
-  bdot = wave_sum(bdot);
-  // foreground: weights and their sums
-  double sw = 0.0, swz = 0.0;
-  for (int i = lane; i < S; i += 64) {
-    const double T = dexp(-tr[i]);
-    tr[i] = T;
-    const double w = (1.0 - dexp(-fe[i])) * T;
-    pre[i] = w;
-    sw += w; swz += w * (zs[i] * ds);
-  }
-  sw = wave_sum(sw); swz = wave_sum(swz);
-  double dall = 1.0, qnum = 0.0;       // depth_values_all's denominator and numerator
-  if (a.d_depth_all) {
-    swa = wave_sum(swa); swd = wave_sum(swd);
-    dall = (swa + sw) + 1e-8; qnum = swd + swz;
-  }
-  __syncthreads();
-  // d depth_all / d (a weight with depth dv) = (dv * dall - qnum) / dall^2; through tbg it also reaches every fg free energy
-  double bdep = 0.0;        // sum_k bw_k q_k: d depth_all / d tbg
-  for (int i = lane; i < Nb; i += 64) {
-    const double bw = bpre[i];
-    if (a.d_depth_all) {
-      const double q = ((ds * (double)a.bg_depth[(size_t)r * Nb + i]) * dall - qnum) / (dall * dall);
-      bdw[i] += ga * tbg * q;
-      bdep += bw * q;
-    }
-    bpre[i] = bdw[i] * bw;
-  }
-  if (a.d_depth_all) bdot += ga * wave_sum(bdep);
-  __syncthreads();
-  const double gd = a.d_depth_values ? (double)a.d_depth_values[r] : 0.0;
-  const double den = sw + 1e-8;
-  for (int i = lane; i < S; i += 64) {
-    const size_t p = (size_t)r * S + i;
-    const double w = pre[i];
-    const double c0 = a.rgb[3 * p], c1 = a.rgb[3 * p + 1], c2 = a.rgb[3 * p + 2];
-    a.d_rgb[3 * p] = (float)(w * g0); a.d_rgb[3 * p + 1] = (float)(w * g1); a.d_rgb[3 * p + 2] = (float)(w * g2);
-    double d = (c0 * g0 + c1 * g1) + c2 * g2;
-    if (a.d_weights) d += (double)a.d_weights[p];
-    d += gd * ((zs[i] * ds) * den - swz) / (den * den);
-    if (a.d_depth_all) d += ga * ((zs[i] * ds) * dall - qnum) / (dall * dall);
-    dw[i] = d;
-    pre[i] = d * w;
-  }
-  __syncthreads();
-  wave_suffix_excl(pre, pre, S, lane);
-  __syncthreads();
-  wave_suffix_excl(bpre, bpre, Nb, lane);
-  __syncthreads();
-  double dbeta = 0.0;
-  for (int i = lane; i < S; i += 64) {
-    const size_t p = (size_t)r * S + i;
-    const double suffix = pre[i];
-    // every free energy also attenuates the background term: d (tbg * B) / d fe_i = -tbg * B
-    const double dfe = (dw[i] * tr[i] * dexp(-fe[i]) - suffix) - tbg * bdot;
-    const double dsig = dfe * fg_dist(i);
-    const DensityD dn((double)a.sdf[p], beta);
-    a.d_sdf[p] = (float)(dsig * dn.dsig_dsdf);
-    dbeta += dsig * dn.dsig_dbeta;
-  }
-  for (int i = lane; i < Nb; i += 64) {
-    const size_t p = (size_t)r * Nb + i;
-    const double suffix = bpre[i];
-    const double dfe = bdw[i] * btr[i] * dexp(-bfe[i]) - suffix;
-    const float o = a.bg_out0[p];
-    const double sg = o > 0.0f ? 1.0 : (o < 0.0f ? -1.0 : 0.0);
-    // exp(-fe) underflows long before dist = 1e10 matters; guard the 0 * inf of the last sample
-    a.d_bg_out0[p] = dfe != 0.0 ? (float)((dfe * bg_dist(i)) * sg) : 0.0f;
-  }
-  dbeta = wave_sum(dbeta);
-  if (lane == 0) a.d_beta_ray[r] = (float)dbeta;
 }
 
 }  // namespace render
@@ -881,21 +400,6 @@ int svs_eikonal_points(const float* uniform_points, const float* cam_loc, const 
   return check_launch("svs_eikonal_points");
 }
 
-int svs_composite(int n_rays, int n_samples, const float* z, const float* sdf, const float* rgb, const float* normals,
-                  const float* depth_scale, const float* beta_param, float beta_min, float* weights, float* rgb_values,
-                  float* depth_values, float* depth_vals, float* normal_map, void* hip_stream) {
-  if (!z || !sdf || !rgb || !depth_scale || !beta_param || !weights || !rgb_values || !depth_values || !depth_vals ||
-      n_rays <= 0) {
-    set_error("svs_composite: null/invalid argument"); return SVS_EINVAL;
-  }
-  if (n_samples < 2 || n_samples > kMaxS) { set_error("svs_composite: n_samples must be in [2,%d]", kMaxS); return SVS_ESHAPE; }
-  if (normal_map && !normals) { set_error("svs_composite: normal_map needs normals"); return SVS_EINVAL; }
-  CompositeArgs a{n_rays, n_samples, z, sdf, rgb, normals, depth_scale, beta_param, beta_min, weights, rgb_values,
-                  depth_values, depth_vals, normal_map};
-  composite_kernel<<<n_rays, 64, 0, (hipStream_t)hip_stream>>>(a);
-  return check_launch("svs_composite");
-}
-
 // BG model: inverse-sphere samples of a batch of rays (ray_sampler.py:215-216, network_bg.py:79-86).
 // jitter: (n_rays, n_bg) uniform draws in train mode or NULL.  -> z_bg (n_rays,n_bg) descending, pts (n_rays*n_bg,4),
 // depth_real (n_rays,n_bg).
@@ -908,62 +412,6 @@ int svs_bg_points(const float* cam, int cam_stride, const float* dirs, int n_ray
   const int n = n_rays * n_bg;
   bg_points_kernel<<<(n + 255) / 256, 256, 0, (hipStream_t)hip_stream>>>(a);
   return check_launch("svs_bg_points");
-}
-
-// BG model: fg weights with the sphere exit as the last interval end, bg weights, composition (network_bg.py:76-125)
-int svs_composite_bg(int n_rays, int n_samples, int n_bg, const float* z, const float* z_max, const float* sdf,
-                     const float* rgb, const float* normals, const float* depth_scale, const float* beta_param,
-                     float beta_min, const float* z_bg, const float* bg_out0, const float* bg_rgb, const float* bg_depth,
-                     float* weights, float* bg_trans, float* bg_weights, float* rgb_values, float* depth_values,
-                     float* depth_values_all, float* depth_vals, float* normal_map, void* hip_stream) {
-  if (!z || !z_max || !sdf || !rgb || !depth_scale || !beta_param || !z_bg || !bg_out0 || !bg_rgb || !bg_depth || !weights ||
-      !bg_trans || !bg_weights || !rgb_values || !depth_values || !depth_values_all || !depth_vals || n_rays <= 0) {
-    set_error("svs_composite_bg: null/invalid argument"); return SVS_EINVAL;
-  }
-  if (n_samples < 2 || n_samples + 1 > kMaxS || n_bg < 2 || n_bg > 64) { set_error("svs_composite_bg: sample counts out of range"); return SVS_ESHAPE; }
-  if (normal_map && !normals) { set_error("svs_composite_bg: normal_map needs normals"); return SVS_EINVAL; }
-  CompositeBgArgs a{n_rays, n_samples, n_bg, z, z_max, sdf, rgb, normals, depth_scale, beta_param, beta_min, z_bg, bg_out0,
-                    bg_rgb, bg_depth, weights, bg_trans, bg_weights, rgb_values, depth_values, depth_values_all, depth_vals,
-                    normal_map};
-  composite_bg_kernel<<<n_rays, 64, 0, (hipStream_t)hip_stream>>>(a);
-  return check_launch("svs_composite_bg");
-}
-
-// backward of svs_composite_bg with respect to sdf, rgb, density.beta, the bg density logits and the bg colours
-// (d_weights, d_depth_values may be NULL); d_beta_ray (n_rays) is workspace, *d_beta_param receives the sum.
-int svs_composite_bg_bwd(int n_rays, int n_samples, int n_bg, const float* z, const float* z_max, const float* sdf,
-                         const float* rgb, const float* depth_scale, const float* beta_param, float beta_min,
-                         const float* z_bg, const float* bg_out0, const float* bg_rgb, const float* d_rgb_values,
-                         const float* d_weights, const float* d_depth_values, const float* d_depth_all,
-                         const float* bg_depth, float* d_sdf, float* d_rgb,
-                         float* d_bg_out0, float* d_bg_rgb, float* d_beta_ray, float* d_beta_param, void* hip_stream) {
-  if (!z || !z_max || !sdf || !rgb || !depth_scale || !beta_param || !z_bg || !bg_out0 || !bg_rgb || !d_rgb_values || !d_sdf ||
-      !d_rgb || !d_bg_out0 || !d_bg_rgb || !d_beta_ray || !d_beta_param || n_rays <= 0 || (d_depth_all && !bg_depth)) {
-    set_error("svs_composite_bg_bwd: null/invalid argument"); return SVS_EINVAL;
-  }
-  if (n_samples < 2 || n_samples + 1 > kMaxS || n_bg < 2 || n_bg > 64) { set_error("svs_composite_bg_bwd: sample counts out of range"); return SVS_ESHAPE; }
-  CompositeBgBwdArgs a{n_rays, n_samples, n_bg, z, z_max, sdf, rgb, depth_scale, beta_param, beta_min, z_bg, bg_out0, bg_rgb,
-                       d_rgb_values, d_weights, d_depth_values, d_depth_all, bg_depth, d_sdf, d_rgb, d_bg_out0, d_bg_rgb,
-                       d_beta_ray};
-  hipStream_t s = (hipStream_t)hip_stream;
-  composite_bg_bwd_kernel<<<n_rays, 64, 0, s>>>(a);
-  beta_reduce_kernel<<<1, 256, 0, s>>>(d_beta_ray, n_rays, beta_param, d_beta_param, 0);
-  return check_launch("svs_composite_bg_bwd");
-}
-
-int svs_composite_bwd(int n_rays, int n_samples, const float* z, const float* sdf, const float* rgb,
-                      const float* depth_scale, const float* beta_param, float beta_min, const float* d_rgb_values,
-                      const float* d_weights, const float* d_depth_values, float* d_sdf, float* d_rgb,
-                      float* d_beta_ray, float* d_beta_param, void* hip_stream) {
-  if (!z || !sdf || !rgb || !depth_scale || !beta_param || !d_rgb_values || !d_sdf || !d_rgb || !d_beta_ray ||
-      !d_beta_param || n_rays <= 0) { set_error("svs_composite_bwd: null/invalid argument"); return SVS_EINVAL; }
-  if (n_samples < 2 || n_samples > kMaxS) { set_error("svs_composite_bwd: n_samples must be in [2,%d]", kMaxS); return SVS_ESHAPE; }
-  CompositeBwdArgs a{n_rays, n_samples, z, sdf, rgb, depth_scale, beta_param, beta_min, d_rgb_values, d_weights,
-                     d_depth_values, d_sdf, d_rgb, d_beta_ray};
-  hipStream_t s = (hipStream_t)hip_stream;
-  composite_bwd_kernel<<<n_rays, 64, 0, s>>>(a);
-  beta_reduce_kernel<<<1, 256, 0, s>>>(d_beta_ray, n_rays, beta_param, d_beta_param, 0);
-  return check_launch("svs_composite_bwd");
 }
 
 int svs_cost_lookup(const float* xyz, const float* cam, const float* dirs, const float* z, int S, int n_points,

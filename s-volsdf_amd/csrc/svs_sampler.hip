@@ -13,7 +13,7 @@
 // device-side flags: round-A kernels OR the per-ray convergence test into conv_flag[i], round-B kernels read
 // it, decide "up-sample or final" and publish active[i+1] for the next round's kernels (incl. the gated MLP
 // launch).  All rounds are enqueued without a host sync.
-#include "svs_common.h"
+#include "svs_ray_scan.h"
 
 namespace svs {
 namespace sampler {
@@ -29,40 +29,6 @@ struct Ctl {            // device-side control block, one per group of rays (the
 };
 
 __device__ __forceinline__ float fma32(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
-
-// torch.linspace(start,end,n)[i] in float32 (ATen: step=(end-start)/(n-1); fma(step,i,start) for i<n/2,
-// fma(-step, n-1-i, end) otherwise)
-__device__ __forceinline__ float linspace_at(float start, float end, int n, int i) {
-  const float step = (end - start) / (float)(n - 1);
-  return i < n / 2 ? fma32(step, (float)i, start) : fma32(-step, (float)(n - 1 - i), end);
-}
-
-// Canonical inclusive cumsum of m floats held in LDS (in -> out, may alias), float64 accumulation.
-// Returns the total (prefix m-1) rounded to float32, in every lane.  Caller syncs before and after.
-__device__ __forceinline__ float wave_cumsum(const float* in, float* out, int m, int lane) {
-  const int c = (m + 63) >> 6;
-  const int lo = lane * c;
-  const int hi = (lo + c < m) ? lo + c : m;
-  double tot = 0.0;
-  for (int j = lo; j < hi; ++j) tot = tot + (double)in[j];
-  double scan = tot;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const double o = __shfl_up(scan, d);
-    if (lane >= d) scan = scan + o;
-  }
-  double off = __shfl_up(scan, 1);
-  if (lane == 0) off = 0.0;
-  double acc = 0.0;
-  float last = 0.0f;
-  for (int j = lo; j < hi; ++j) {
-    acc = acc + (double)in[j];
-    last = (float)(off + acc);
-    out[j] = last;
-  }
-  const int owner = (m - 1) / c;
-  return __shfl(last, owner);
-}
 
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll

@@ -38,6 +38,25 @@ def _f32(t):
     return t.detach().to(dtype=torch.float32).contiguous()
 
 
+def _beta1(beta_param):
+    """the `density.beta` parameter as the float32 device scalar (1,) the kernels read"""
+    return _f32(beta_param).reshape(1)
+
+
+def _out_tensor(t, shape, dev):
+    """An output tensor of a wrapper: the caller's (checked: shape, float32, contiguous, on the inputs' device) or a new one."""
+    if t is None:
+        return torch.empty(*shape, device=dev)
+    if tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
+        raise ValueError(f"output tensor must be contiguous float32 {shape} on {dev}")
+    return t
+
+
+def _opt_ptr(t):
+    """device address of an optional input, as float32"""
+    return _ptr(_f32(t)) if t is not None else None
+
+
 def _ptr_array(tensors):
     arr = (ctypes.c_void_p * len(tensors))()
     for i, t in enumerate(tensors):
@@ -203,20 +222,32 @@ def composite(z, sdf, rgb, depth_scale, beta_param, beta_min, normals=None):
     L = _lib.load()
     z = _f32(z)
     R, S = z.shape
-    dev = z.device
-    sdf, rgb, depth_scale = _f32(sdf), _f32(rgb), _f32(depth_scale)
-    beta_param = _f32(beta_param).reshape(1)
-    weights = torch.empty(R, S, device=dev)
-    rgb_values = torch.empty(R, 3, device=dev)
-    depth_values = torch.empty(R, 1, device=dev)
-    depth_vals = torch.empty(R, S, device=dev)
-    normal_map = torch.empty(R, 3, device=dev) if normals is not None else None
-    nrm = _f32(normals) if normals is not None else None
-    _lib.check(L.svs_composite(R, S, _ptr(z), _ptr(sdf), _ptr(rgb), _ptr(nrm), _ptr(depth_scale), _ptr(beta_param),
-                               float(beta_min), _ptr(weights), _ptr(rgb_values), _ptr(depth_values), _ptr(depth_vals),
-                               _ptr(normal_map), _stream()), "svs_composite")
+    f = lambda *s: torch.empty(*s, device=z.device)
+    weights, rgb_values, depth_values, depth_vals = f(R, S), f(R, 3), f(R, 1), f(R, S)
+    normal_map = f(R, 3) if normals is not None else None
+    _lib.check(L.svs_composite(R, S, _ptr(z), _ptr(_f32(sdf)), _ptr(_f32(rgb)), _opt_ptr(normals), _ptr(_f32(depth_scale)),
+                               _ptr(_beta1(beta_param)), float(beta_min), _ptr(weights), _ptr(rgb_values), _ptr(depth_values),
+                               _ptr(depth_vals), _ptr(normal_map), _stream()), "svs_composite")
     return dict(weights=weights, rgb_values=rgb_values, depth_values=depth_values, depth_vals=depth_vals,
                 normal_map=normal_map)
+
+
+def composite_bwd(z, sdf, rgb, depth_scale, beta_param, beta_min, d_rgb_values, d_weights=None, d_depth_values=None,
+                  d_sdf_out=None, d_beta_out=None):
+    """Reverse pass of `composite`: -> d_sdf (R*S,1), d_rgb (R*S,3), d_beta_param (1,).  d_sdf_out / d_beta_out: optional
+    preallocated contiguous float32 tensors of those shapes to write into (the fused train step hands in views of its
+    persistent buffers, which saves a fill and two copies per ray group)."""
+    L = _lib.load()
+    z = _f32(z)
+    R, S = z.shape
+    dev = z.device
+    d_sdf, d_beta = _out_tensor(d_sdf_out, (R * S, 1), dev), _out_tensor(d_beta_out, (1,), dev)
+    d_rgb, d_beta_ray = torch.empty(R * S, 3, device=dev), torch.empty(R, device=dev)
+    _lib.check(L.svs_composite_bwd(R, S, _ptr(z), _ptr(_f32(sdf)), _ptr(_f32(rgb)), _ptr(_f32(depth_scale)),
+                                   _ptr(_beta1(beta_param)), float(beta_min), _ptr(_f32(d_rgb_values)), _opt_ptr(d_weights),
+                                   _opt_ptr(d_depth_values), _ptr(d_sdf), _ptr(d_rgb), _ptr(d_beta_ray), _ptr(d_beta),
+                                   _stream()), "svs_composite_bwd")
+    return d_sdf, d_rgb, d_beta
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -298,20 +329,41 @@ def composite_bg(z, z_max, sdf, rgb, depth_scale, beta_param, beta_min, z_bg, bg
     z = _f32(z)
     R, S = z.shape
     Nb = z_bg.shape[1]
-    dev = z.device
-    beta_param = _f32(beta_param).reshape(1)
-    f = lambda *s: torch.empty(*s, device=dev)
+    f = lambda *s: torch.empty(*s, device=z.device)
     weights, bg_trans, bg_w = f(R, S), f(R), f(R, Nb)
     rgb_values, depth_values, depth_all, depth_vals = f(R, 3), f(R, 1), f(R, 1), f(R, S)
     normal_map = f(R, 3) if normals is not None else None
-    _lib.check(L.svs_composite_bg(R, S, Nb, _ptr(z), _ptr(_f32(z_max)), _ptr(_f32(sdf)), _ptr(_f32(rgb)),
-                                  _ptr(_f32(normals)) if normals is not None else None, _ptr(_f32(depth_scale)),
-                                  _ptr(beta_param), float(beta_min), _ptr(_f32(z_bg)), _ptr(_f32(bg_out0)), _ptr(_f32(bg_rgb)),
-                                  _ptr(_f32(bg_depth)), _ptr(weights), _ptr(bg_trans), _ptr(bg_w), _ptr(rgb_values),
-                                  _ptr(depth_values), _ptr(depth_all), _ptr(depth_vals), _ptr(normal_map), _stream()),
-               "svs_composite_bg")
+    _lib.check(L.svs_composite_bg(R, S, Nb, _ptr(z), _ptr(_f32(z_max)), _ptr(_f32(sdf)), _ptr(_f32(rgb)), _opt_ptr(normals),
+                                  _ptr(_f32(depth_scale)), _ptr(_beta1(beta_param)), float(beta_min), _ptr(_f32(z_bg)),
+                                  _ptr(_f32(bg_out0)), _ptr(_f32(bg_rgb)), _ptr(_f32(bg_depth)), _ptr(weights), _ptr(bg_trans),
+                                  _ptr(bg_w), _ptr(rgb_values), _ptr(depth_values), _ptr(depth_all), _ptr(depth_vals),
+                                  _ptr(normal_map), _stream()), "svs_composite_bg")
     return dict(weights=weights, bg_transmittance=bg_trans, bg_weights=bg_w, rgb_values=rgb_values,
                 depth_values=depth_values, depth_values_all=depth_all, depth_vals=depth_vals, normal_map=normal_map)
+
+
+def composite_bg_bwd(z, z_max, sdf, rgb, depth_scale, beta_param, beta_min, z_bg, bg_out0, bg_rgb, d_rgb_values,
+                     d_weights=None, d_depth_values=None, d_depth_values_all=None, bg_depth=None, d_sdf_out=None,
+                     d_beta_out=None):
+    """backward of composite_bg -> d_sdf (R*S,1), d_rgb (R*S,3), d_bg_out0 (R*Nb,1), d_bg_rgb (R*Nb,3), d_beta (1,).
+    d_depth_values: gradient of the foreground depth; d_depth_values_all (with bg_depth (R,Nb)): gradient of
+    depth_values_all, the fg + bg depth the loss's sparsity term reads (network_bg.py:105-110, loss.py:72-73).
+    d_sdf_out / d_beta_out: optional contiguous float32 device tensors the two results are written into (as composite_bwd)."""
+    L = _lib.load()
+    z = _f32(z)
+    R, S = z.shape
+    Nb = z_bg.shape[1]
+    dev = z.device
+    f = lambda *s: torch.empty(*s, device=dev)
+    d_sdf, d_beta = _out_tensor(d_sdf_out, (R * S, 1), dev), _out_tensor(d_beta_out, (1,), dev)
+    d_rgb, d_bo, d_brgb, d_beta_ray = f(R * S, 3), f(R * Nb, 1), f(R * Nb, 3), f(R)
+    _lib.check(L.svs_composite_bg_bwd(R, S, Nb, _ptr(z), _ptr(_f32(z_max)), _ptr(_f32(sdf)), _ptr(_f32(rgb)),
+                                      _ptr(_f32(depth_scale)), _ptr(_beta1(beta_param)), float(beta_min),
+                                      _ptr(_f32(z_bg)), _ptr(_f32(bg_out0)), _ptr(_f32(bg_rgb)), _ptr(_f32(d_rgb_values)),
+                                      _opt_ptr(d_weights), _opt_ptr(d_depth_values), _opt_ptr(d_depth_values_all),
+                                      _opt_ptr(bg_depth), _ptr(d_sdf), _ptr(d_rgb), _ptr(d_bo), _ptr(d_brgb),
+                                      _ptr(d_beta_ray), _ptr(d_beta), _stream()), "svs_composite_bg_bwd")
+    return d_sdf, d_rgb, d_bo, d_brgb, d_beta
 
 
 def stage_in(dev_tensor, pinned_tensor):
@@ -344,63 +396,6 @@ def eikonal_points(uniform_points, cam_loc, z_eik, ray_dirs):
     _lib.check(_lib.load().svs_eikonal_points(_ptr(_f32(uniform_points)), _ptr(_f32(cam_loc)), _ptr(_f32(z_eik)),
                                               _ptr(_f32(ray_dirs)), R, _ptr(out), _stream()), "svs_eikonal_points")
     return out
-
-
-def composite_bg_bwd(z, z_max, sdf, rgb, depth_scale, beta_param, beta_min, z_bg, bg_out0, bg_rgb, d_rgb_values,
-                     d_weights=None, d_depth_values=None, d_depth_values_all=None, bg_depth=None, d_sdf_out=None,
-                     d_beta_out=None):
-    """backward of composite_bg -> d_sdf (R*S,1), d_rgb (R*S,3), d_bg_out0 (R*Nb,1), d_bg_rgb (R*Nb,3), d_beta (1,).
-    d_depth_values: gradient of the foreground depth; d_depth_values_all (with bg_depth (R,Nb)): gradient of
-    depth_values_all, the fg + bg depth the loss's sparsity term reads (network_bg.py:105-110, loss.py:72-73).
-    d_sdf_out / d_beta_out: optional contiguous float32 device tensors the two results are written into (as composite_bwd)."""
-    L = _lib.load()
-    z = _f32(z)
-    R, S = z.shape
-    Nb = z_bg.shape[1]
-    dev = z.device
-    f = lambda *s: torch.empty(*s, device=dev)
-    for t, shape in ((d_sdf_out, (R * S, 1)), (d_beta_out, (1,))):
-        if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev):
-            raise ValueError(f"output tensor must be contiguous float32 {shape} on {dev}")
-    d_sdf = d_sdf_out if d_sdf_out is not None else f(R * S, 1)
-    d_rgb, d_bo, d_brgb = f(R * S, 3), f(R * Nb, 1), f(R * Nb, 3)
-    d_beta_ray = f(R)
-    d_beta = d_beta_out if d_beta_out is not None else f(1)
-    opt = lambda t: _ptr(_f32(t)) if t is not None else None
-    _lib.check(L.svs_composite_bg_bwd(R, S, Nb, _ptr(z), _ptr(_f32(z_max)), _ptr(_f32(sdf)), _ptr(_f32(rgb)),
-                                      _ptr(_f32(depth_scale)), _ptr(_f32(beta_param).reshape(1)), float(beta_min),
-                                      _ptr(_f32(z_bg)), _ptr(_f32(bg_out0)), _ptr(_f32(bg_rgb)), _ptr(_f32(d_rgb_values)),
-                                      opt(d_weights), opt(d_depth_values), opt(d_depth_values_all), opt(bg_depth),
-                                      _ptr(d_sdf), _ptr(d_rgb), _ptr(d_bo), _ptr(d_brgb),
-                                      _ptr(d_beta_ray), _ptr(d_beta), _stream()), "svs_composite_bg_bwd")
-    return d_sdf, d_rgb, d_bo, d_brgb, d_beta
-
-
-def composite_bwd(z, sdf, rgb, depth_scale, beta_param, beta_min, d_rgb_values, d_weights=None, d_depth_values=None,
-                  d_sdf_out=None, d_beta_out=None):
-    """Reverse pass of `composite`: -> d_sdf (R*S,1), d_rgb (R*S,3), d_beta_param (1,).  d_sdf_out / d_beta_out: optional
-    preallocated contiguous float32 tensors of those shapes to write into (the fused train step hands in views of its
-    persistent buffers, which saves a fill and two copies per ray group)."""
-    L = _lib.load()
-    z = _f32(z)
-    R, S = z.shape
-    dev = z.device
-    sdf, rgb, depth_scale = _f32(sdf), _f32(rgb), _f32(depth_scale)
-    beta_param = _f32(beta_param).reshape(1)
-    g_rgb = _f32(d_rgb_values)
-    g_w = _f32(d_weights) if d_weights is not None else None
-    g_d = _f32(d_depth_values).reshape(-1) if d_depth_values is not None else None
-    for t, shape in ((d_sdf_out, (R * S, 1)), (d_beta_out, (1,))):
-        if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous()):
-            raise ValueError("composite_bwd: output tensor must be contiguous float32 of shape %s" % (shape,))
-    d_sdf = d_sdf_out if d_sdf_out is not None else torch.empty(R * S, 1, device=dev)
-    d_rgb = torch.empty(R * S, 3, device=dev)
-    ws = torch.empty(R, device=dev)
-    d_beta = d_beta_out if d_beta_out is not None else torch.empty(1, device=dev)
-    _lib.check(L.svs_composite_bwd(R, S, _ptr(z), _ptr(sdf), _ptr(rgb), _ptr(depth_scale), _ptr(beta_param),
-                                   float(beta_min), _ptr(g_rgb), _ptr(g_w), _ptr(g_d), _ptr(d_sdf), _ptr(d_rgb),
-                                   _ptr(ws), _ptr(d_beta), _stream()), "svs_composite_bwd")
-    return d_sdf, d_rgb, d_beta
 
 
 _HOST_COPIES = {}
@@ -573,7 +568,7 @@ def sample_rays(packed, cam, dirs, beta_param, *, beta_min=1e-4, near, scene_bou
     rng = rng or {}
     if not torch.is_tensor(beta_param):
         beta_param = torch.tensor(float(beta_param), device=dev)
-    beta_param = _f32(beta_param).reshape(1)
+    beta_param = _beta1(beta_param)
     max_iters = fast if fast >= 0 else max_total_iters
     if training and max_iters > 1 and "perm" in rng:
         raise NotImplementedError("train-mode extras for more than one round need the bin count on the host")

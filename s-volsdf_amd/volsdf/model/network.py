@@ -191,6 +191,47 @@ class VolSDFBase(nn.Module):
         R % 32 == 0 for the fg + background model (S = 97)."""
         return 32 // math.gcd(self.samples_per_ray(), 32)
 
+    # ---- the foreground networks of a forward, the start of a backward ----------------------------------------------
+    def _fg_networks(self, input, pk, cam_loc, ray_dirs, z_vals, z_samples_eik, rng, keep, sphere_radius, view_dirs):
+        """network.py:224-236, 258-268: the SDF network on the ray samples cam + z * dir (clamped at sphere_radius; 0: not
+        clamped) and the radiance network on them, seen from view_dirs (R,3).  keep: dict that receives what the backward
+        kernels need.  -> sdf (R*S,1), gradients (R*S,3), grad_theta (the eikonal points' gradients; empty in eval mode),
+        rgb_flat (R*S,3)."""
+        n_main = z_vals.numel()
+        eikonal_points = None
+        if self.training:
+            # eikonal samples (network.py:258-266) ride in the same launch as the ray samples; they
+            # differentiate the raw network output (ImplicitNetwork.gradient), the ray samples the clamped sdf
+            # [uniform points in the bounding sphere ; one point per ray at the sampler's extra depth]: one launch straight
+            # into the launch's point list
+            eikonal_points = ops.eikonal_points(rng["eik_points"], cam_loc, z_samples_eik, ray_dirs)
+        src = ops.PointSource(points=eikonal_points, cam=cam_loc, dirs=ray_dirs, z=z_vals)
+        sdf, gradients, feat_tiles, _, _ = ops.sdf_outputs(pk, src, sphere_radius, self.implicit_network.sphere_scale,
+                                                           clamp_n=n_main, keep=keep)
+        grad_theta = gradients[n_main:]
+        sdf, gradients = sdf[:n_main], gradients[:n_main]
+        src_main = ops.PointSource(cam=cam_loc, dirs=ray_dirs, z=z_vals)
+        hook = input.get("_before_rgb")              # (trainer: the radiance weight stream is packed on another stream)
+        if hook is not None:
+            hook()
+        rgb_flat = ops.rgb_eval(pk, src_main, gradients, view_dirs, feat_tiles, keep=keep)
+        return sdf, gradients, grad_theta, rgb_flat
+
+    def _backward_inputs(self, keep, g_rgb_values, g_grad_theta):
+        """The start of backward_from_output_grads: builds the backward objects (self._mlp_bwd, and self._bg_bwd of the
+        background model) on first use, and returns the two gradients with zeros for those the caller left out."""
+        from svs_hip.train import BgBackward, MlpBackward
+        dev = keep["z_vals"].device
+        if getattr(self, "_mlp_bwd", None) is None or self._mlp_bwd.dev != dev:
+            self._mlp_bwd = MlpBackward(dev)
+            self._bg_bwd = BgBackward(dev) if self.ray_sampler.inverse_sphere_bg else None
+        if g_rgb_values is None:
+            g_rgb_values = torch.zeros(keep["z_vals"].shape[0], 3, device=dev)
+        n_extra = keep["src"].n - keep["rgb"].shape[0]
+        if g_grad_theta is None and n_extra:
+            g_grad_theta = torch.zeros(n_extra, 3, device=dev)
+        return g_rgb_values, g_grad_theta
+
     # ---- train-mode random draws ----------------------------------------------------------------------------
     def draw_train_rng(self, R, dev, out=None, stream=None):
         """All train-mode random draws of one forward for R rays, in the reference's order (sampler draws, then the
@@ -270,7 +311,6 @@ class VolSDFNetwork(VolSDFBase):
         intrinsics, uv, pose = input["intrinsics"], input["uv"], input["pose"]
         if uv.shape[0] != 1:
             raise NotImplementedError("batch_size 1 only (runner.py:166)")
-        net = self.implicit_network
         pk = self.packed_mlp()
         ray_dirs, cam_loc, depth_scale = ops.rays_from_uv(uv[0], pose[0], intrinsics[0])       # network.py:213-217
         num_pixels = ray_dirs.shape[0]
@@ -279,25 +319,8 @@ class VolSDFNetwork(VolSDFBase):
             rng = self.draw_rays(input.get("_valid_rays", num_pixels), num_pixels, ray_dirs.device)
         z_vals, z_samples_eik = self.ray_sampler.get_z_vals(ray_dirs, cam_loc, self, fast=fast,
                                                             iter_step=input.get("iter_step", 1), rng=rng)
-        N_samples = z_vals.shape[1]
-        n_main = num_pixels * N_samples
-        eikonal_points = None
-        if self.training:
-            # eikonal samples (network.py:258-266) ride in the same launch as the ray samples; they
-            # differentiate the raw network output (ImplicitNetwork.gradient), the ray samples the clamped sdf
-            # [uniform points in the bounding sphere ; one point per ray at the sampler's extra depth]: one launch straight
-            # into the launch's point list
-            eikonal_points = ops.eikonal_points(rng["eik_points"], cam_loc, z_samples_eik, ray_dirs)
-        src = ops.PointSource(points=eikonal_points, cam=cam_loc, dirs=ray_dirs, z=z_vals)
-        sdf, gradients, feat_tiles, _, _ = ops.sdf_outputs(pk, src, net.sdf_bounding_sphere, net.sphere_scale,
-                                                           clamp_n=n_main, keep=keep)
-        grad_theta = gradients[n_main:]
-        sdf, gradients = sdf[:n_main], gradients[:n_main]
-        src_main = ops.PointSource(cam=cam_loc, dirs=ray_dirs, z=z_vals)
-        hook = input.get("_before_rgb")              # (trainer: the radiance weight stream is packed on another stream)
-        if hook is not None:
-            hook()
-        rgb_flat = ops.rgb_eval(pk, src_main, gradients, ray_dirs, feat_tiles, keep=keep)
+        sdf, gradients, grad_theta, rgb_flat = self._fg_networks(input, pk, cam_loc, ray_dirs, z_vals, z_samples_eik, rng, keep,
+                                                                 self.implicit_network.sdf_bounding_sphere, ray_dirs)
         comp = ops.composite(z_vals, sdf, rgb_flat, depth_scale, self.density.beta, self.density.beta_min_value,
                              normals=None if self.training else gradients)
         if keep is not None:
@@ -323,20 +346,11 @@ class VolSDFNetwork(VolSDFBase):
                                    out=None):
         """d loss / d parameters from d loss / d (rgb_values, weights, depth_values, grad_theta): compositing
         backward, then the fused MLP backward.  Returns (sdf_grads, rgb_grads, d_beta)."""
-        from svs_hip.train import MlpBackward
-        dev = keep["z_vals"].device
-        if getattr(self, "_mlp_bwd", None) is None or self._mlp_bwd.dev != dev:
-            self._mlp_bwd = MlpBackward(dev)
-        R = keep["z_vals"].shape[0]
-        if g_rgb_values is None:
-            g_rgb_values = torch.zeros(R, 3, device=dev)
+        g_rgb_values, g_grad_theta = self._backward_inputs(keep, g_rgb_values, g_grad_theta)
         g_weights = self.white_bkgd_weight_grad(g_rgb_values, g_weights, keep["z_vals"].shape[1])
         d_sdf, d_rgb, d_beta = ops.composite_bwd(keep["z_vals"], keep["sdf"], keep["rgb_flat"], keep["depth_scale"],
                                                  self.density.beta, self.density.beta_min_value, g_rgb_values,
                                                  g_weights, g_depth_values)
-        n_extra = keep["src"].n - keep["rgb"].shape[0]
-        if g_grad_theta is None and n_extra:
-            g_grad_theta = torch.zeros(n_extra, 3, device=dev)
         sdf_p, rgb_p = self.mlp_params()
         sdf_g, rgb_g = self._mlp_bwd.run(sdf_p, rgb_p, keep, d_rgb, d_sdf, g_grad_theta, out=out)
         return sdf_g, rgb_g, d_beta

@@ -1,7 +1,7 @@
 """VolSDFNetworkBG with the reference's class name, constructor, state-dict keys and forward() contract
 (volsdf/model/network_bg.py): the foreground VolSDF model plus the NeRF++ inverted-sphere background, evaluated by
 the fused HIP kernels (svs_mlp_h2.hip for the foreground networks, svs_bg_h2.hip for the background networks,
-svs_render.hip for the inverse-sphere points and the fg/bg compositing).
+svs_render.hip for the inverse-sphere points, svs_composite.hip for the fg/bg compositing).
 
 `train.model_class: volsdf.model.network_bg.VolSDFNetworkBG` (config/vol/bmvs.yaml:4).  Checkpoint keys:
 `implicit_network.*`, `rendering_network.*`, `density.beta`, `bg_implicit_network.lin{0..8}.{weight,bias}`,
@@ -85,20 +85,12 @@ class VolSDFNetworkBG(VolSDFBase):
                                    g_grad_theta=None):
         """d loss / d parameters (in _flat_param_list() order) from d loss / d (rgb_values, weights, depth_values,
         depth_values_all, grad_theta): fg / bg compositing backward, then the fused MLP backwards of all four networks."""
-        from svs_hip.train import BgBackward, MlpBackward, finalize
-        dev = keep["z_vals"].device
-        if getattr(self, "_mlp_bwd", None) is None or self._mlp_bwd.dev != dev:
-            self._mlp_bwd, self._bg_bwd = MlpBackward(dev), BgBackward(dev)
-        R = keep["z_vals"].shape[0]
-        if g_rgb_values is None:
-            g_rgb_values = torch.zeros(R, 3, device=dev)
+        from svs_hip.train import finalize
+        g_rgb_values, g_grad_theta = self._backward_inputs(keep, g_rgb_values, g_grad_theta)
         d_sdf, d_rgb, d_bo, d_brgb, d_beta = ops.composite_bg_bwd(
             keep["z_vals"], keep["z_max"], keep["sdf"], keep["rgb_flat"], keep["depth_scale"], self.density.beta,
             self.density.beta_min_value, keep["z_bg"], keep["bg_out0"], keep["bg_rgb"], g_rgb_values, g_weights,
             g_depth_values, d_depth_values_all=g_depth_values_all, bg_depth=keep["bg_depth"])
-        n_extra = keep["src"].n - keep["rgb"].shape[0]
-        if g_grad_theta is None and n_extra:
-            g_grad_theta = torch.zeros(n_extra, 3, device=dev)
         sdf_p, rgb_p = self.mlp_params()
         bg_sdf_wb, bg_rgb_wb = self.bg_params()
         bw, bgb = self._mlp_bwd, self._bg_bwd
@@ -124,7 +116,6 @@ class VolSDFNetworkBG(VolSDFBase):
         intrinsics, uv, pose = input["intrinsics"], input["uv"], input["pose"]
         if uv.shape[0] != 1:
             raise NotImplementedError("batch_size 1 only (runner.py:166)")
-        net = self.implicit_network
         pk, pkb = self.packed_mlp(), self.packed_bg()
         ray_dirs, cam_loc, depth_scale = ops.rays_from_uv(uv[0], pose[0], intrinsics[0])
         R = ray_dirs.shape[0]
@@ -138,11 +129,7 @@ class VolSDFNetworkBG(VolSDFBase):
             self.ray_sampler.return_bg_ascending = True
         z_bg, bg_pts, bg_depth = self.ray_sampler._bg_last
         z_vals, z_max = ops.split_last(z_all)
-        S, Nb = z_vals.shape[1], z_bg.shape[1]
-        n_main = R * S
-        eikonal_points = None
-        if self.training:
-            eikonal_points = ops.eikonal_points(rng["eik_points"], cam_loc, z_samples_eik, ray_dirs)
+        Nb = z_bg.shape[1]
         view_dirs = ray_dirs
         if not self.training:
             # nearest training view's directions (network_bg.py:69-74)
@@ -173,15 +160,8 @@ class VolSDFNetworkBG(VolSDFBase):
                 bs.wait_event(fork)
                 bg_out0, bg_rgb = background()
                 bg_join = torch.cuda.Event(); bg_join.record(bs)
-        src = ops.PointSource(points=eikonal_points, cam=cam_loc, dirs=ray_dirs, z=z_vals)
-        sdf, gradients, feat_tiles, _, _ = ops.sdf_outputs(pk, src, 0.0, net.sphere_scale, clamp_n=n_main, keep=keep)
-        grad_theta = gradients[n_main:]
-        sdf, gradients = sdf[:n_main], gradients[:n_main]
-        src_main = ops.PointSource(cam=cam_loc, dirs=ray_dirs, z=z_vals)
-        hook = input.get("_before_rgb")              # (trainer: the radiance weight stream is packed on another stream)
-        if hook is not None:
-            hook()
-        rgb_flat = ops.rgb_eval(pk, src_main, gradients, view_dirs, feat_tiles, keep=keep)
+        sdf, gradients, grad_theta, rgb_flat = self._fg_networks(input, pk, cam_loc, ray_dirs, z_vals, z_samples_eik, rng, keep,
+                                                                 0.0, view_dirs)
         if bg_join is not None:
             torch.cuda.current_stream().wait_event(bg_join)
         else:

@@ -116,3 +116,32 @@ def test_argument_errors_come_back_as_codes():
     assert L.svs_split_last(dummy, 4, 1, dummy, dummy, None) < 0 and L.svs_split_last(None, 4, 3, dummy, dummy, None) < 0
     assert L.svs_stage_in(None, dummy, 64, None) < 0 and L.svs_stage_in(dummy, dummy, 6, None) < 0
     assert L.svs_stage_in(ctypes.c_void_p(68), dummy, 64, None) < 0            # not 16-byte aligned
+
+
+def test_composite_entry_points_validate_sample_counts():
+    """The four compositing entry points share one argument check: sample counts outside what the kernels hold and a normal
+    map without normals come back with the documented codes and messages (dummy pointers, nothing is launched)."""
+    import ctypes
+    from svs_hip import lib
+    L = lib.load()
+    d = ctypes.c_void_p(64)
+    EINVAL, ESHAPE = -1, -2
+    calls = {
+        "svs_composite": lambda S, Nb, normals=d: L.svs_composite(4, S, d, d, d, normals, d, d, 1e-4, d, d, d, d, d, None),
+        "svs_composite_bwd": lambda S, Nb: L.svs_composite_bwd(4, S, d, d, d, d, d, 1e-4, d, d, d, d, d, d, d, None),
+        "svs_composite_bg": lambda S, Nb, normals=d: L.svs_composite_bg(4, S, Nb, d, d, d, d, normals, d, d, 1e-4, d, d, d, d,
+                                                                        d, d, d, d, d, d, d, d, None),
+        "svs_composite_bg_bwd": lambda S, Nb: L.svs_composite_bg_bwd(4, S, Nb, d, d, d, d, d, d, 1e-4, d, d, d, d, d, d, d, d,
+                                                                     d, d, d, d, d, d, None),
+    }
+    for name in ("svs_composite", "svs_composite_bwd"):
+        for S in (1, 257):
+            assert calls[name](S, 0) == ESHAPE
+            assert L.svs_last_error_string() == b"%s: n_samples must be in [2,256]" % name.encode()
+    for name in ("svs_composite_bg", "svs_composite_bg_bwd"):
+        for S, Nb in ((1, 32), (256, 32), (97, 1), (97, 65)):
+            assert calls[name](S, Nb) == ESHAPE
+            assert L.svs_last_error_string() == b"%s: sample counts out of range" % name.encode()
+    for name in ("svs_composite", "svs_composite_bg"):
+        assert calls[name](97, 32, normals=None) == EINVAL
+        assert L.svs_last_error_string() == b"%s: normal_map needs normals" % name.encode()

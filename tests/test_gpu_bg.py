@@ -95,6 +95,43 @@ def test_bg_pieces(dev, golden_dir, tag, precision, monkeypatch):
     np.testing.assert_allclose(comp["rgb_values"].cpu().numpy(), rgb_ref, atol=2e-6)
 
 
+@pytest.mark.parametrize("Nb", [2, 32, 64])
+@pytest.mark.parametrize("S", [2, 64, 65, 255])
+def test_composite_bg_forward_edges(dev, S, Nb):
+    """The fg + background forward kernel where the S + 1 prefixes and the lane-strided loops cross a multiple of 64 and at
+    the limits the entry point accepts: both sequences' weights and the transmittance behind the foreground bit for bit the
+    oracle's, the reduced outputs within the float32 summation bound of the float64 sums over the weights the kernel
+    returned (tests/test_gpu_parity.py::assert_f32_reduction)."""
+    from svs_hip import ops
+    from test_gpu_parity import assert_f32_reduction, forward_edge_scene
+    z, sdf, rgb, nrm, ds = forward_edge_scene(S, seed=1000 * Nb + S)
+    R = z.shape[0]
+    rs = np.random.default_rng(S * 100 + Nb)
+    z_max = (z[:, -1] + F32(0.3)).astype(F32)
+    z_bg = np.sort(rs.uniform(0.01, 1.0, (R, Nb)), -1)[:, ::-1].astype(F32)
+    bg_out0 = rs.normal(0, 1, (R, Nb)).astype(F32)
+    bg_rgb = rs.uniform(0, 1, (R, Nb, 3)).astype(F32)
+    bg_depth = (1.0 / z_bg).astype(F32)
+    out = ops.composite_bg(G(z, dev), G(z_max, dev), G(sdf.reshape(-1, 1), dev), G(rgb.reshape(-1, 3), dev), G(ds, dev),
+                           torch.tensor(0.02, device=dev), 1e-4, G(z_bg, dev), G(bg_out0.reshape(-1, 1), dev),
+                           G(bg_rgb.reshape(-1, 3), dev), G(bg_depth, dev), normals=G(nrm.reshape(-1, 3), dev))
+    out = {k: v.cpu().numpy() for k, v in out.items()}
+    w_ref, t_ref, _ = orc.fg_weights_bg_model(z, z_max, sdf, orc.get_beta(0.02))
+    np.testing.assert_array_equal(out["weights"], w_ref)
+    np.testing.assert_array_equal(out["bg_transmittance"], t_ref)
+    np.testing.assert_array_equal(out["bg_weights"], orc.bg_weights(z_bg, np.abs(bg_out0)))
+    w, T, bw, ds64, n64 = (a.astype(np.float64) for a in (out["weights"], out["bg_transmittance"], out["bg_weights"], ds, nrm))
+    dv, wa, da = z * ds64, T[:, None] * bw, bg_depth * ds64          # fg depths; composed bg weights and their depths
+    assert_f32_reduction("rgb_values", out["rgb_values"],
+                         (w[:, :, None] * rgb).sum(1) + T[:, None] * (bw[:, :, None] * bg_rgb).sum(1), S + Nb)
+    assert_f32_reduction("depth_values", out["depth_values"], (w * dv).sum(1) / (w.sum(1) + 1e-8), S)
+    assert_f32_reduction("depth_values_all", out["depth_values_all"],
+                         ((w * dv).sum(1) + (wa * da).sum(1)) / (w.sum(1) + wa.sum(1) + 1e-8), S + Nb)
+    nhat = n64 / np.sqrt((n64 * n64).sum(-1, keepdims=True))
+    assert_f32_reduction("normal_map", out["normal_map"], (w[:, :, None] * nhat).sum(1), S,
+                         scale=(w[:, :, None] * np.abs(nhat)).sum(1))
+
+
 @pytest.mark.parametrize("tag,precision", [("eval_b0.1", None), ("eval_b0.01", None), ("train", None), ("eval_b0.1", "f32"),
                                            ("train", "f32")])
 def test_bg_model_forward_golden(dev, golden_dir, tag, precision, monkeypatch):

@@ -228,6 +228,51 @@ def test_composite_golden(dev, ops, golden_dir):
         np.testing.assert_allclose(out[k].cpu().numpy(), ref[k], atol=2e-6, err_msg=k)
 
 
+def forward_edge_scene(S, seed, R=3):
+    """Inputs of test_composite_forward_edges / test_composite_bg_forward_edges (beta parameter 0.02): z sorted in [0.5, 5],
+    sdf ~ N(0, 0.2), colours in [0, 1], normals, depth_scale in [0.8, 1]."""
+    rs = np.random.default_rng(seed)
+    z = np.sort(rs.uniform(0.5, 5.0, (R, S)), -1).astype(F32)
+    sdf = rs.normal(0, 0.2, (R, S)).astype(F32)
+    rgb = rs.uniform(0, 1, (R, S, 3)).astype(F32)
+    nrm = rs.normal(0, 1, (R, S, 3)).astype(F32)
+    ds = rs.uniform(0.8, 1.0, (R, 1)).astype(F32)
+    return z, sdf, rgb, nrm, ds
+
+
+def assert_f32_reduction(name, got, want, n, scale=None):
+    """A float32 sum of n terms (or a quotient of two) against its float64 value `want`, formed from the same float32 terms:
+    every term carries at most a few roundings of its own (products, the normalisation of a normal: the + 4) and every
+    addition one more on the partial sum, so |got - want| <= (n + 4) 2^-23 scale with scale = sum |term|: `want` itself
+    where no term is negative, handed in where the terms change sign."""
+    scale = np.abs(want) if scale is None else scale
+    err = np.abs(got.astype(np.float64).reshape(want.shape) - want)
+    bound = (n + 4) * 2.0 ** -23 * scale
+    print(f"{name}: max err / bound {np.max(err / np.maximum(bound, 1e-300)):.3f} (n = {n})")
+    assert (err <= bound).all(), (name, err.max(), bound[err > bound].min())
+
+
+@pytest.mark.parametrize("S", [2, 63, 64, 65, 256])
+def test_composite_forward_edges(dev, ops, S):
+    """The forward kernel where its lane-strided loops cross a multiple of 64 and at the limits the entry point accepts: the
+    weights bit for bit the oracle's, depth_vals bit for bit z * depth_scale, and the reduced outputs within the float32
+    summation bound of the float64 sums over the weights the kernel returned."""
+    z, sdf, rgb, nrm, ds = forward_edge_scene(S, seed=S)
+    out = ops.composite(G(z, dev), G(sdf.reshape(-1, 1), dev), G(rgb.reshape(-1, 3), dev), G(ds, dev),
+                        torch.tensor(0.02, device=dev), 1e-4, normals=G(nrm.reshape(-1, 3), dev))
+    out = {k: v.cpu().numpy() for k, v in out.items()}
+    ref = orc.composite(z, sdf, rgb, orc.get_beta(0.02), ds, normals=nrm)
+    assert np.array_equal(out["weights"].view(np.uint32), ref["weights"].view(np.uint32))
+    assert np.array_equal(out["depth_vals"].view(np.uint32), (z * ds).astype(F32).view(np.uint32))
+    w, z64, ds64, n64 = (a.astype(np.float64) for a in (out["weights"], z, ds, nrm))
+    assert_f32_reduction("rgb_values", out["rgb_values"], (w[:, :, None] * rgb).sum(1), S)
+    assert_f32_reduction("depth_values", out["depth_values"], ds64 * ((w * z64).sum(1, keepdims=True) /
+                                                                      (w.sum(1, keepdims=True) + 1e-8)), S)
+    nhat = n64 / np.sqrt((n64 * n64).sum(-1, keepdims=True))
+    assert_f32_reduction("normal_map", out["normal_map"], (w[:, :, None] * nhat).sum(1), S,
+                         scale=(w[:, :, None] * np.abs(nhat)).sum(1))
+
+
 def _oracle_sampler(params, dirs, cam, beta_param, fast, training=False, rng=None):
     layers = orc.effective_weights(params, "implicit_network", 9)
     trace = []

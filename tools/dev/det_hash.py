@@ -1,5 +1,6 @@
 """tools/dev/det_hash.py [steps]: SHA-256 of the gradients and parameters after a few DETERMINISTIC optimisation steps (both
-models) and of a 1024-ray forward's outputs -- two builds of the library that claim bit-identical arithmetic (SVS_LIB_PATH
+models) and of the outputs of an eval-mode forward with the stepped parameters (1024 rays, 256 for the background model:
+the path that composites the normals) -- two builds of the library that claim bit-identical arithmetic (SVS_LIB_PATH
 selects one) must print the same lines.  Dev aid, GPU only."""
 import hashlib, os, sys
 import numpy as np, torch
@@ -48,6 +49,11 @@ def run(kind, R):
         print(f"{kind} R={R} step {i}: grad {sha(ts.fp.grad)} rgb {sha(out['rgb_values'])} loss {float(lo['loss']).hex()}")
     torch.cuda.synchronize()
     print(f"{kind} R={R} params {sha(ts.fp.flat)}")
+    m.invalidate_packed()
+    m.eval()
+    with torch.no_grad():
+        out = m(dict(inp, near_pose=inp["pose"]))
+    print(f"{kind} R={R} forward: " + " ".join(f"{k} {sha(out[k])}" for k in ("rgb_values", "depth_values", "weights", "normal_map")))
 
 
 L = _lib.load()
