@@ -959,6 +959,61 @@ int svs_tsdf_face_keep(const float* weight, int n0, int n1, int n2, const int* c
 int svs_tsdf_vertex_colors(const float* rgb, const float* weight, int n0, int n1, int n2, const float* verts, int n_verts,
                            float* out, void* hip_stream);
 
+/* ---- a mesh seen from a scan's cameras (svs_hip.meshview; csrc/svs_meshview.hip) -----------------------------------------
+ * Depth, face ids, normals and a shaded picture of a triangle mesh per view, and the per-vertex visibility that cuts a mesh
+ * to what the cameras and the evaluation masks see.  The reference has no such step; the arithmetic below is this
+ * project's (tests/meshview_oracle.py restates it in numpy float64).  Cameras as svs_tsdf_integrate takes them: mats DEVICE
+ * double[n_views][21] = K row-major, then the top three rows of E; n_views <= 16 per call.  Per vertex p, in float64 without
+ * contraction: cam = E (p,1), z = cam.z, pix = K cam, x = pix.x / pix.z, y = pix.y / pix.z.  Pixel (ix, iy) has its centre
+ * at x = ix, y = iy, so the nearest pixel of a point is floor(x + 0.5): the TSDF rule.
+ *
+ * svs_mesh_raster: verts DEVICE float[n_verts][3], faces DEVICE int[n_faces][3], zbuf DEVICE uint64 (n_views,H,W), which
+ *   the CALLER fills with all-ones bits first: calls (chunks of faces, several meshes) compose into one buffer.  Per view
+ *   and face f, in this order:
+ *   1. skipped if a vertex index is outside [0, n_verts);
+ *   2. skipped if a vertex has z <= near or a z, x or y that is not finite (no near-plane clipping: a documented limit);
+ *   3. A = (x1-x0)(y2-y0) - (y1-y0)(x2-x0); skipped if A == 0 or A is not finite.  Both orientations are drawn;
+ *   4. candidate pixels: the integer points of the bounding box, ceil(min) .. floor(max) per axis,
+ *   5. clamped to [0, W-1] x [0, H-1] in float64, before any conversion to int;
+ *   6. centre c is covered iff s * e_k(c) >= 0 for k = 0, 1, 2, with e_k(c) = (x_q-x_p)(c.y-y_p) - (y_q-y_p)(c.x-x_p),
+ *      (p,q) = (k+1,k+2) mod 3, s = sign(A): inclusive, no top-left rule;
+ *   7. b_k = e_k / A, zc = 1 / (b_0/z_0 + b_1/z_1 + b_2/z_2) (summed left to right); a pixel whose float32(zc) is not a
+ *      positive finite number is skipped;
+ *   8. key = (bits of float32(zc)) << 32 | (face_base + f);
+ *   9. zbuf holds the minimum key per pixel (64-bit unsigned atomic minimum): the smallest float32 depth wins, the smaller
+ *      id at equal depth; the result does not depend on the order of faces, threads or launches.
+ *   A clamped box of at most svs_mesh_raster_small_box() pixels is walked by the lane that set the face up; larger ones go
+ *   through a device list to a second kernel whose waves stride one box each.  work: DEVICE int[work_ints], work_ints >=
+ *   4 + n_views * n_faces (n_views * n_faces < 2^31: chunk the faces); the call zeroes work[0..3] and leaves work[0] = the
+ *   list's length (the (view, face) pairs on the large path).  An empty mesh or no views: nothing is touched,
+ *   work included.  flags: 0; for measurements 1 = also count work[1] = the pairs
+ *   walked by the small path and the uint64 at work[2] = atomics issued, 2 = the list is built but not drawn, 4 = only the
+ *   list is drawn.  face_base >= 0, face_base + n_faces < 2^31.
+ * svs_mesh_raster_resolve: per pixel depth DEVICE float (n_views,H,W) = the key's high word as float32, 0 where empty;
+ *   face DEVICE int (n_views,H,W) = the low word, -1 where empty.  normal DEVICE float (n_views,H,W,3) or NULL: the unit
+ *   normal cross(P1-P0, P2-P0) of the winner's camera-space corners in float64, flipped so that n.z <= 0, 0 where empty.
+ *   shade DEVICE uint8 (n_views,H,W,3) or NULL: g = 0.2 + 0.8 |n.z|, code = floor(255 g colour + 0.5) clamped to [0,255],
+ *   colour = sum_k (b_k / z_k * zc) * vert_rgb[i_k] / 255 with b_k, zc of the winner at this pixel in float64, or 1 when
+ *   vert_rgb (DEVICE uint8[n_verts][3]) is NULL; 255 where empty.  The winner is faces[id - face_base]; ids outside
+ *   [face_base, face_base + n_faces) belong to another call's mesh: their normal and shade are left untouched.
+ * svs_mesh_vertex_visibility: depth DEVICE float (n_views,H,W); masks: HOST array of n_views DEVICE uint8 (H,W) pointers,
+ *   NULL or NULL entries = no mask.  seen, off_mask DEVICE int[n_verts] are ACCUMULATED (the caller zeroes them; more than
+ *   16 views: several calls).  Per vertex and view: skipped if z <= near, z, x or y is not finite, or (iu, iv) =
+ *   (floor(x+0.5), floor(y+0.5)) is outside the image; off_mask += 1 if the mask is 0 there; otherwise, with d =
+ *   depth[iv,iu], seen += 1 iff d == 0 or z <= d * (1 + rel) + abs_tol.
+ * SVS_ESHAPE for more than 16 views or H * W == 0, SVS_EINVAL for near <= 0 or a negative tolerance; an empty mesh is not
+ * an error.  Bad input (indices out of range, NaN vertices, faces behind the camera) is skipped, never dereferenced. */
+int svs_mesh_raster_small_box(void);
+int svs_mesh_raster(const float* verts, int n_verts, const int* faces, int n_faces, const double* mats, int n_views, int H,
+                    int W, double near, int face_base, unsigned long long* zbuf, int* work, long long work_ints, int flags,
+                    void* hip_stream);
+int svs_mesh_raster_resolve(const unsigned long long* zbuf, const float* verts, int n_verts, const int* faces, int n_faces,
+                            const double* mats, int n_views, int H, int W, int face_base, const uint8_t* vert_rgb, float* depth,
+                            int* face, float* normal, uint8_t* shade, void* hip_stream);
+int svs_mesh_vertex_visibility(const float* verts, int n_verts, const double* mats, int n_views, int H, int W, double near,
+                               const float* depth, const uint8_t* const* masks, double rel, double abs_tol, int* seen,
+                               int* off_mask, void* hip_stream);
+
 /* ---- numeric-contract self tests (used by tests/test_gpu_parity.py) --------------------------------------- */
 int svs_selftest_exp(const float* x, float* y_exp, float* y_expm1, int n, void* hip_stream);
 int svs_selftest_arith(const float* a, const float* b, float* quotient, float* sqrt_abs_a, int n, void* hip_stream);

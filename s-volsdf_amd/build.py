@@ -53,6 +53,7 @@ UNITS = {
     "svs_mvsdata.hip": ["-ffp-contract=off"],
     "svs_mesh.hip": ["-ffp-contract=off"],
     "svs_tsdf.hip": ["-ffp-contract=off"],
+    "svs_meshview.hip": ["-ffp-contract=off"],
     "svs_plan.hip": [],
 }
 BASE_FLAGS = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function", "-x", "hip"]

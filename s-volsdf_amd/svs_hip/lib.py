@@ -206,6 +206,15 @@ SIGNATURES.update({
     "svs_tsdf_vertex_colors": (c_int, [_P, _P, c_int, c_int, c_int, _P, c_int, _P, _P]),
 })
 
+# svs_hip.meshview (csrc/svs_meshview.hip)
+SIGNATURES.update({
+    "svs_mesh_raster_small_box": (c_int, []),
+    "svs_mesh_raster": (c_int, [_P, c_int, _P, c_int, _P, c_int, c_int, c_int, c_double, c_int, _P, _P, c_longlong, c_int, _P]),
+    "svs_mesh_raster_resolve": (c_int, [_P, _P, c_int, _P, c_int, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P]),
+    "svs_mesh_vertex_visibility": (c_int, [_P, c_int, _P, c_int, c_int, c_int, c_double, _P, _PP, c_double, c_double, _P, _P,
+                                           _P]),
+})
+
 # svs_hip.lpips (csrc/svs_lpips.hip)
 SIGNATURES.update({
     "svs_conv3x3_mfma_supported": (c_int, [c_int, c_int]),

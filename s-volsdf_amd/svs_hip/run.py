@@ -15,6 +15,8 @@ filter_depth_folder`) -> {outdir}/mvsnet{scan:03}_l3.ply.
     save_depth / save_scene_depth / pcd_filter / create_scenes / main
     +tsdf_voxel=V [+tsdf_trunc=T]   after the point clouds, every scan's depth maps meshed by `svs_hip.tsdf` into
                              {outdir}/tsdf/mvsnet{scan:03}_l3.ply (`python -m evals.eval_dtu --datadir {outdir}/tsdf --mode mesh`)
+    +tsdf_views=true         with +tsdf_voxel: every scan's TSDF mesh rendered into its training views by `svs_hip.meshview`,
+                             {outdir}/tsdf/scanNNN/mesh_depth/{id:08}.pfm and mesh_shade/{id:08}.png
 
 Differences from the reference, all deliberate: `gpu: auto` keeps the current device (there is no GPUtil probe) and an
 integer selects it with torch.cuda.set_device; `prevent_oom` is taken as given; the five-second sleep before the first
@@ -387,6 +389,24 @@ def tsdf_meshes(args, testlist):
     return out
 
 
+def tsdf_views(args, testlist):
+    """+tsdf_views=true: every scan's TSDF mesh (`tsdf_meshes`) rendered into that scan's training views by
+    `meshview.view_folder`, under {outdir}/tsdf/{scan}/; one time line per scan.  -> {scene: view_folder's stats}"""
+    from . import meshview
+    from .scans import get_trains_ids
+    data_dir = args["vol"]["dataset"]["data_dir"]
+    out = OrderedDict()
+    for scan in testlist:
+        folder = os.path.join(args["outdir"], scan)
+        stats = meshview.view_folder(tsdf_ply_name(args["outdir"], scan), folder, os.path.join(args["outdir"], "tsdf", scan),
+                                     get_trains_ids(data_dir, scan, args["num_view"]))[1]
+        info(f"saving the TSDF mesh's views to {os.path.dirname(stats['files']['depth'][0])} and "
+             f"{os.path.dirname(stats['files']['shade'][0])}")
+        info(f"{scan} tsdf views seconds: " + ", ".join(f"{k} {v:.3f}" for k, v in stats["seconds"].items()))
+        out[scan] = stats
+    return out
+
+
 def create_scenes(args, testlist):
     """runner.py:74-108, 447-452: the folder of cameras and images that image-based rendering reads, per scan"""
     from . import mvsdata
@@ -430,6 +450,8 @@ def main(argv=None, scan_fn=None):
         info(f"{scene} seconds: " + ", ".join(f"{k} {v:.3f}" for k, v in clock.s.items()))
     if args.get("tsdf_voxel"):
         result["meshes"] = tsdf_meshes(args, testlist)
+        if args.get("tsdf_views"):
+            result["mesh_views"] = tsdf_views(args, testlist)
     return result
 
 
