@@ -23,10 +23,30 @@
 extern "C" {
 #endif
 
-/* ABI version.  101 (round 6): svs_set_deterministic / svs_get_deterministic, svs_conv2d_mfma*, svs_featurenet_fpn2 added.  100 -> 101 also marks the argument
- * lists that changed during round 5 without a version signal: svs_sdf_bwd_a lost `a2max`, svs_sdf_bwd_b gained `ubuf`, and in
+/* This file is the one declaration of the ABI: every translation unit of the library is compiled against it
+ * (csrc/svs_common.h includes it), and the Python binding (svs_hip/lib.py) derives its ctypes table, its two Structure
+ * classes and its constants from this text.  It therefore keeps to a small subset of C: #define of an integer, one enum,
+ * typedef struct, and prototypes over int, float, double, size_t, long long and pointers. */
+
+/* Return codes (see "Conventions"): 0, a HIP error code (> 0), or one of these. */
+#define SVS_EINVAL (-1)    /* an argument: a null pointer, a misaligned buffer, a count or a setting out of range */
+#define SVS_ESHAPE (-2)    /* a size the kernels do not handle */
+#define SVS_ENOCONV (-3)   /* an iteration did not settle within its round limit (svs_mesh_components) */
+#define SVS_EOVERFLOW (-4) /* an operand of the fp16x2 3x3 convolution does not fit fp16 (svs_conv3x3_mfma, svs_lpips_score) */
+
+/* Marks a pointer parameter as host memory read or written during the call -- a small array of parameters, a table of
+ * device pointers, a result the host reads at once.  Unmarked pointers follow the convention above: device memory, or an
+ * address the call only hands on.  (Eight pointer tables that are host memory too travel unmarked: `weights`, `biases` and
+ * `wfrags` of svs_featurenet_fpn / _fpn2 / _unet, which bindings pass as plain addresses.)  Expands to nothing. */
+#define SVS_HOST
+
+/* ABI version: svs_version() returns SVS_ABI_VERSION.  101 (round 6): svs_set_deterministic / svs_get_deterministic,
+ * svs_conv2d_mfma*, svs_featurenet_fpn2 added.  100 -> 101 also marks the argument lists that changed during round 5
+ * without a version signal: svs_sdf_bwd_a lost `a2max`, svs_sdf_bwd_b gained `ubuf`, and in
  * fp16x2 svs_sdf_outputs writes records BEHIND gbuf's 8 blocks -- size gbuf with svs_sdf_gbuf_bytes(), not svs_sdf_hbuf_bytes().
- * A host binding should refuse a library whose version differs from the one it was written against (svs_hip/lib.py does). */
+ * A host binding should refuse a library whose version differs from the one it was written against (svs_hip/lib.py, which
+ * reads the macro from this file, does). */
+#define SVS_ABI_VERSION 101
 int svs_version(void);
 const char* svs_last_error_string(void);
 
@@ -85,8 +105,9 @@ int svs_split_last(const float* z, int n_rays, int n, float* head, float* last, 
  * Stream sizes do not depend on the precision. */
 enum { SVS_MMA_F32 = 0, SVS_MMA_F16X2 = 1, SVS_MMA_F16X2_HALF = 2 };
 size_t svs_stream_bytes(int which);
-int svs_pack_stream(int which, int precision, const float* const* weight_v, const float* const* weight_g,
-                    const float* const* bias, float* workspace, float* stream_out, void* hip_stream);
+int svs_pack_stream(int which, int precision, const float* const SVS_HOST* weight_v,
+                    const float* const SVS_HOST* weight_g, const float* const SVS_HOST* bias, float* workspace,
+                    float* stream_out, void* hip_stream);
 size_t svs_pack_workspace_bytes(void);
 
 /* ---- a5  SDF MLP ------------------------------------------------------------------------------------
@@ -329,8 +350,9 @@ int svs_clip_guard_adam(float* params, float* grads, float* exp_avg, float* exp_
  * (hipGraph) can be replayed for another rendered view.
  * -> pj (n_points), pi (n_points), valid (n_points, uint8) */
 int svs_cost_lookup(const float* xyz, const float* cam, const float* dirs, const float* z, int S, int n_points,
-                    int n_views, int same_view, int inverse_depth, float img_w, float img_h, const float* view_params,
-                    const float* const* cost, const float* const* z_near, const float* const* z_far, const int* dims,
+                    int n_views, int same_view, int inverse_depth, float img_w, float img_h,
+                    const float SVS_HOST* view_params, const float* const SVS_HOST* cost,
+                    const float* const SVS_HOST* z_near, const float* const SVS_HOST* z_far, const int SVS_HOST* dims,
                     float* pj, float* pi, unsigned char* valid, const int* same_view_dev, void* hip_stream);
 
 /* ---- a11  loss ----------------------------------------------------------------------------------------
@@ -395,9 +417,9 @@ int svs_featurenet_fpn2(const float* image, int H, int W, int base_channels, con
  * proj = K[:3,:3] @ E[:3,:4] (:622-625).  depth_values (D,H,W) per-pixel hypotheses.  C in {8,16,32}.
  * raw_warp != 0: write the warped volume of source 0 instead (homo_warping on its own). */
 int svs_chw_to_hwc(const float* in, float* out, int C, int H, int W, void* hip_stream);
-int svs_warp_variance(const float* ref_feature, const float* const* src_features_hwc, const float* rot_trans, int n_src,
-                      int C, int D, int H, int W, const float* depth_values, float* variance, int raw_warp,
-                      void* hip_stream);
+int svs_warp_variance(const float* ref_feature, const float* const SVS_HOST* src_features_hwc,
+                      const float SVS_HOST* rot_trans, int n_src, int C, int D, int H, int W, const float* depth_values,
+                      float* variance, int raw_warp, void* hip_stream);
 
 /* ---- a15  3-D regularisation blocks ----------------------------------------------------------------------------
  * Conv3d / Deconv3d blocks of CostRegNet (models/CasMVSNet.py:107-186,441-472) with BatchNorm(eval) folded:
@@ -429,15 +451,15 @@ int svs_conv3d_mfma(const float* in, const void* wfrag, const float* bias, const
  *     wfrag (svs_conv3d_pair_wfrag_bytes(Cin)): [k-step s][piece][lane][8] fp16, row m = lane & 15 = (channel m & 7,
  *     position m >> 3), k = 32 s + 8 (lane >> 4) + j = (((kd*3 + kh)*4 + t)*(Cin/8) + g)*8 + c8: the folded weight of
  *     tap (kd, kh, kw = t - (m >> 3)) and input channel 8 g + c8, zero if kw is outside 0..2 or m & 7 >= Cout. */
-size_t svs_split_volume_dims(int C, int D, int H, int W, int* dims);
+size_t svs_split_volume_dims(int C, int D, int H, int W, int SVS_HOST* dims);
 /* The final `prob` layer (Cin -> 1, CasMVSNet.py:458,471): float32 fused multiply-adds on the vector ALUs (a one-row
  * matrix-core tile would be 1/16 full).  weight [Cin][27][1]. */
 int svs_conv3d_c1(const float* in, const float* weight, const float* bias, const float* skip, float* out, int Cin, int D,
                   int H, int W, int relu, void* hip_stream);
 int svs_split_volume_pack(const float* in, void* split, int C, int D, int H, int W, void* hip_stream);
-int svs_warp_variance_split(const float* ref_feature, const float* const* src_features_hwc, const float* rot_trans,
-                            int n_src, int C, int D, int H, int W, const float* depth_values, void* split,
-                            void* hip_stream);
+int svs_warp_variance_split(const float* ref_feature, const float* const SVS_HOST* src_features_hwc,
+                            const float SVS_HOST* rot_trans, int n_src, int C, int D, int H, int W,
+                            const float* depth_values, void* split, void* hip_stream);
 size_t svs_conv3d_pair_wfrag_bytes(int Cin);
 int svs_conv3d_pair(const void* split, const void* wfrag, const float* bias, float* out, int Cin, int Cout, int D, int H,
                     int W, int relu, void* hip_stream);
@@ -551,12 +573,13 @@ int svs_deform_conv2d(const float* in, const float* offset_mask, const float* we
  *   Z = 1 / (Q . Ksum + 1e-6) per head, attention, out-projection, LayerNorm1(x + .), 32 -> 64 -> 32 with ReLU, LayerNorm2
  *   (eps 1e-5).  weights: HOST array of 12 device pointers: query_projection.{weight,bias}, out_projection.{weight,bias},
  *   linear1.{weight,bias}, linear2.{weight,bias}, norm1.{weight,bias}, norm2.{weight,bias}. */
-int svs_fmt_tokens_in(const float* chw, int H, int W, const float* div_term, float* tokens, void* hip_stream);
+int svs_fmt_tokens_in(const float* chw, int H, int W, const float SVS_HOST* div_term, float* tokens, void* hip_stream);
 int svs_fmt_tokens_out(const float* tokens, int H, int W, float* chw, void* hip_stream);
 size_t svs_fmt_kv_workspace_bytes(int S);
 int svs_fmt_kv(const float* source, int S, const float* k_w, const float* k_b, const float* v_w, const float* v_b, float* workspace,
                float* kvsum, void* hip_stream);
-int svs_fmt_layer(const float* x, int L, const float* kvsum, const float* const* weights, float* out, void* hip_stream);
+int svs_fmt_layer(const float* x, int L, const float* kvsum, const float* const SVS_HOST* weights, float* out,
+                  void* hip_stream);
 /* _upsample_add(dim_reduction(x), y) of the pathway (models/FMT.py:196-223): out (Cin/2,2h,2w) = bilinear_x2(conv1x1(x (Cin,h,w)))
  * + y, align_corners=False, the reduction before the up-sampling as in the reference.  weight (Cin/2,Cin), Cin 32 or 16. */
 int svs_pathway_step(const float* x, const float* weight, const float* y, float* out, int Cin, int h, int w, void* hip_stream);
@@ -569,9 +592,10 @@ int svs_pathway_step(const float* x, const float* weight, const float* y, float*
  * prev_weights (n_src,H/2,W/2) is read at (y/2, x/2), the nearest x2 of :208 (H and W even).  weights_out (n_src,H,W) receives
  * the weights at this stage's size either way.  workspace: svs_warp_similarity_workspace_bytes (the per-view similarities). */
 size_t svs_warp_similarity_workspace_bytes(int n_src, int D, int H, int W);
-int svs_warp_similarity(const float* ref_feature, const float* const* src_features_hwc, const float* rot_trans, int n_src, int C,
-                        int D, int H, int W, const float* depth_values, const float* prev_weights, const float* net,
-                        float* workspace, float* similarity, float* weights_out, void* hip_stream);
+int svs_warp_similarity(const float* ref_feature, const float* const SVS_HOST* src_features_hwc,
+                        const float SVS_HOST* rot_trans, int n_src, int C, int D, int H, int W, const float* depth_values,
+                        const float* prev_weights, const float* net, float* workspace, float* similarity,
+                        float* weights_out, void* hip_stream);
 /* TransMVSNet's tail (models/TransMVSNet.py:100-109, 225-227), the device code of svs_prob_depth_conf with a flag
  * (csrc/svs_costvol.hip): prob is bit-identical to that entry's; index = the first plane that holds the maximum logit
  * (torch.argmax's rule on exact ties), depth = depth_values[index], conf = prob[index]. */
@@ -592,8 +616,8 @@ int svs_prob_wta(const float* reg, const float* depth_values, int D, int H, int 
  * float32 in [0,1]) is given, uint8 colours (count,3) = trunc(img * 255).  mats: inv(K_ref) (9), inv(E_ref) (16).
  * offset_ws: H*W ints; xyz / rgb sized for H*W points; *count (device int) receives the number written. */
 int svs_fuse_mats_per_src(void);
-int svs_fuse_view(const float* ref_depth, const float* confidence, const float* const* src_depths, const double* mats,
-                  int n_src, int H, int W, float conf, double filter_dist, float filter_diff, int thres_view,
+int svs_fuse_view(const float* ref_depth, const float* confidence, const float* const SVS_HOST* src_depths,
+                  const double* mats, int n_src, int H, int W, float conf, double filter_dist, float filter_diff, int thres_view,
                   const uint8_t* extra_mask, double* depth_avg, uint8_t* photo_mask, uint8_t* geo_mask, uint8_t* final_mask,
                   uint8_t* src_mask, float* src_depth_reproj, float* src_x, float* src_y, void* hip_stream);
 int svs_fuse_points(const double* depth_avg, const uint8_t* final_mask, const float* ref_img, const double* mats, int H, int W,
@@ -616,8 +640,8 @@ int svs_fuse_points(const double* depth_avg, const uint8_t* final_mask, const fl
  *   cv2.pyrDown (levels 1..3), per level sum_j m_jl (g_jl - pyrUp(g_j,l+1)) (the coarsest: sum_j m_j3 g_j3),
  *   reconstruction out_l = pyrUp(out_l+1) + LS_l, clip(0, 1).  -> out (H,W,3). */
 size_t svs_ibr_workspace_bytes(int n_src, int H, int W);
-int svs_ibr_weights(const float* const* src_imgs, const float* const* src_dirs, const float* ref_dir, const float* pred_img,
-                    const uint8_t* geo_mask, const float* map_x, const float* map_y, int n_src, int H, int W,
+int svs_ibr_weights(const float* const SVS_HOST* src_imgs, const float* const SVS_HOST* src_dirs, const float* ref_dir,
+                    const float* pred_img, const uint8_t* geo_mask, const float* map_x, const float* map_y, int n_src, int H, int W,
                     void* workspace, float* fill, float* masks, void* hip_stream);
 int svs_ibr_laplacian_blend(const float* fill, const float* masks, int n_src, int H, int W, void* workspace, float* out,
                             void* hip_stream);
@@ -662,7 +686,6 @@ int svs_nvs_score(const uint8_t* pred, const uint8_t* gt, const uint8_t* mask, i
  *   aligned; svs_lpips_net_offset(what, index) is the byte offset of (what 0) the packed weights of convolution index
  *   0..12, (1) its float32 bias, (2) the float32 lin weights of tap index 0..4; (size_t)-1 otherwise.  workspace:
  *   svs_lpips_workspace_bytes() (0: rejected sizes), 16-byte aligned.  Bit-identical run to run. */
-#define SVS_EOVERFLOW (-4)
 int svs_conv3x3_mfma_supported(int Cin, int Cout);
 size_t svs_conv3x3_mfma_wfrag_bytes(int Cin, int Cout);
 int svs_conv3x3_mfma_pack(const float* weight, int Cin, int Cout, void* wfrag, void* hip_stream);
@@ -776,8 +799,8 @@ int svs_mvs_confidence(const float* conf1, int H1, int W1, const int* xofs1, con
  *   divides by zero and casts NaN to uint8, which is platform-defined; here every code is 0.  One launch.  Unused maps
  *   may be null. */
 size_t svs_select_workspace_bytes(void);
-int svs_select_sorted_pairs(const float* x, long long n, const long long* ranks, int n_ranks, void* workspace, float* values,
-                            unsigned int* counts, void* hip_stream);
+int svs_select_sorted_pairs(const float* x, long long n, const long long SVS_HOST* ranks, int n_ranks, void* workspace,
+                            float* values, unsigned int* counts, void* hip_stream);
 int svs_depth_preview(const float* map0, int n0, uint8_t* out0, const float* map1, int n1, uint8_t* out1, const float* map2,
                       int n2, uint8_t* out2, int n_maps, float lo, float hi, int direct, const uint8_t* table,
                       void* hip_stream);
@@ -826,15 +849,15 @@ int svs_view_depth_colors(const float* depth, const float* acc, int n_pixels, in
  * svs_cloud_mean_below: mean of dist[dist < max_dist] (:153,:176) -> mean_count[0], and the number of terms
  *   -> mean_count[1]; deterministic two-level sum.  workspace: svs_cloud_mean_workspace_bytes(). */
 size_t svs_cloud_grid_bytes(int n_points);
-int svs_cloud_nn(const double* ref, int n_ref, const double* query, int n_query, const double* origin, double cell,
+int svs_cloud_nn(const double* ref, int n_ref, const double* query, int n_query, const double SVS_HOST* origin, double cell,
                  double max_radius, void* grid_ws, double* dist, int* idx, void* hip_stream);
-int svs_cloud_downsample_begin(const double* pts, int n, const double* origin, double radius, void* grid_ws, uint8_t* state,
+int svs_cloud_downsample_begin(const double* pts, int n, const double SVS_HOST* origin, double radius, void* grid_ws, uint8_t* state,
                                void* hip_stream);
-int svs_cloud_downsample_round(const double* origin, int n, double radius, void* grid_ws, uint8_t* state, int* undecided,
+int svs_cloud_downsample_round(const double SVS_HOST* origin, int n, double radius, void* grid_ws, uint8_t* state, int* undecided,
                                void* hip_stream);
-int svs_cloud_obs_filter(const double* pts, int n, const float* bb, double res, double patch, const uint8_t* obs_mask,
+int svs_cloud_obs_filter(const double* pts, int n, const float SVS_HOST* bb, double res, double patch, const uint8_t* obs_mask,
                          int d0, int d1, int d2, uint8_t* inbound, uint8_t* in_obs, void* hip_stream);
-int svs_cloud_plane_side(const double* pts, int n, const double* plane, uint8_t* above, void* hip_stream);
+int svs_cloud_plane_side(const double* pts, int n, const double SVS_HOST* plane, uint8_t* above, void* hip_stream);
 int svs_cloud_compact(const double* pts, const uint8_t* mask, int n, int* offset_ws, double* out, int* count, void* hip_stream);
 size_t svs_cloud_mean_workspace_bytes(void);
 /* svs_cloud_bounds: lo_hi[0..2] = per-axis minimum, lo_hi[3..5] = per-axis maximum of pts (n >= 1; DEVICE double[6]) -- the
@@ -860,7 +883,8 @@ int svs_cloud_mean_below(const double* dist, int n, double max_dist, double* wor
  *   (0,1,0); else a = min(d, vis_dist) / vis_dist and the colour is (a + (1 - a), 1 - a, 1 - a) in float64 -- numpy's
  *   R * a + W * (1 - a).  rgb_f64: (n_full,3) float64; rgb_u8: (n_full,3) = (uint8) rint(min(1, max(0, c)) * 255), what the
  *   PLY stores; either may be NULL. */
-int svs_cloud_prepare(const void* pts, int is_f64, int n, const double* matrix, double scale, double* out, void* hip_stream);
+int svs_cloud_prepare(const void* pts, int is_f64, int n, const double SVS_HOST* matrix, double scale, double* out,
+                      void* hip_stream);
 int svs_cloud_error_colors(const double* dist, int n_dist, const uint8_t* select, const int* rank, int n_full, double max_dist,
                            double vis_dist, double* rgb_f64, uint8_t* rgb_u8, void* hip_stream);
 
@@ -895,12 +919,12 @@ int svs_mesh_sample_points(const double* tri, int n_tri, const long long* offset
  *   index * spacing with the crossing at p0 + t * spacing, t = (level - v0) / (v1 - v0) in float32, and faces as int32
  *   triples: node order, then axis / table order, no atomics.  spacing: HOST float[3]. */
 int svs_grid_points(const float* x, const float* y, const float* z, int nx, int ny, int nz, long long start, int count,
-                    const float* rotation, const float* shift, float* out, void* hip_stream);
-int svs_mc_tile(int* tile);
+                    const float SVS_HOST* rotation, const float SVS_HOST* shift, float* out, void* hip_stream);
+int svs_mc_tile(int SVS_HOST* tile);
 int svs_mc_classify(const float* volume, int n0, int n1, int n2, long long stride0, long long stride1, float level,
                     short* cell, void* hip_stream);
 int svs_mc_emit(const float* volume, int n0, int n1, int n2, long long stride0, long long stride1, float level,
-                const float* spacing, const short* cell, const int* active, int n_active, const int* vert_base,
+                const float SVS_HOST* spacing, const short* cell, const int* active, int n_active, const int* vert_base,
                 const int* tri_base, float* verts, int* faces, void* hip_stream);
 /* trimesh's slice_plane without a cap (plots.py:278-285: six calls for the DTU box), one half-space n . x + d >= 0
  * (plane: HOST double[4]), in two steps around a weld the caller does (unique of the int64 keys):
@@ -910,7 +934,7 @@ int svs_mc_emit(const float* volume, int n0, int n1, int n2, long long stride0, 
  *   = index of the face's keys among the n_cut unique cut_keys.  out_verts: the n_kept kept vertices unchanged, then one
  *   vertex per cut edge (interpolated in float64 from the edge's ordered ends, rounded once); out_faces: triangles wholly
  *   inside copied (re-indexed), crossing ones as one or two triangles of the same orientation. */
-int svs_mesh_clip_count(const float* verts, int n_verts, const int* faces, int n_faces, const double* plane, double* dist,
+int svs_mesh_clip_count(const float* verts, int n_verts, const int* faces, int n_faces, const double SVS_HOST* plane, double* dist,
                         uint8_t* inside, int* counts, long long* keys, void* hip_stream);
 int svs_mesh_clip_emit(const float* verts, int n_verts, const int* faces, int n_faces, const double* dist,
                        const uint8_t* inside, const int* vert_remap, const int* offsets, const int* cut_index,
@@ -921,10 +945,9 @@ int svs_mesh_clip_emit(const float* verts, int n_verts, const int* faces, int n_
  * the labels still change after max_rounds, or the HIP error code (positive), as every entry point does.  Synchronises the
  * stream.
  * svs_mesh_face_areas: area[f] in float64; face_label[f] = labels[first corner] (both may be NULL together). */
-#define SVS_ENOCONV (-3)
 size_t svs_mesh_components_workspace_bytes(void);
 int svs_mesh_components(const int* faces, int n_faces, int n_verts, int max_rounds, int* labels, int* workspace,
-                        int* rounds, void* hip_stream);
+                        int SVS_HOST* rounds, void* hip_stream);
 int svs_mesh_face_areas(const float* verts, const int* faces, int n_faces, const int* labels, double* area, int* face_label,
                         void* hip_stream);
 
@@ -951,9 +974,9 @@ int svs_mesh_face_areas(const float* verts, const int* faces, int n_faces, const
  * svs_tsdf_vertex_colors: verts DEVICE float[n_verts][3] in volume index units -> out DEVICE float[n_verts][3]: trilinear
  *   over the eight nodes around the vertex in float64 (base index clamped to [0, n-2]), over the nodes with weight > 0 only,
  *   normalised by the sum of their trilinear weights; 0 where that sum is 0. */
-int svs_tsdf_integrate(float* tsdf, float* weight, float* rgb, int n0, int n1, int n2, const double* origin, double voxel,
-                       double trunc, const float* const* depths, const uint8_t* const* masks, const float* const* images,
-                       const double* mats, int n_views, int H, int W, void* hip_stream);
+int svs_tsdf_integrate(float* tsdf, float* weight, float* rgb, int n0, int n1, int n2, const double SVS_HOST* origin, double voxel,
+                       double trunc, const float* const SVS_HOST* depths, const uint8_t* const SVS_HOST* masks,
+                       const float* const SVS_HOST* images, const double* mats, int n_views, int H, int W, void* hip_stream);
 int svs_tsdf_face_keep(const float* weight, int n0, int n1, int n2, const int* cells, int n_faces, float min_weight,
                        uint8_t* keep, void* hip_stream);
 int svs_tsdf_vertex_colors(const float* rgb, const float* weight, int n0, int n1, int n2, const float* verts, int n_verts,
@@ -1011,7 +1034,7 @@ int svs_mesh_raster_resolve(const unsigned long long* zbuf, const float* verts, 
                             const double* mats, int n_views, int H, int W, int face_base, const uint8_t* vert_rgb, float* depth,
                             int* face, float* normal, uint8_t* shade, void* hip_stream);
 int svs_mesh_vertex_visibility(const float* verts, int n_verts, const double* mats, int n_views, int H, int W, double near,
-                               const float* depth, const uint8_t* const* masks, double rel, double abs_tol, int* seen,
+                               const float* depth, const uint8_t* const SVS_HOST* masks, double rel, double abs_tol, int* seen,
                                int* off_mask, void* hip_stream);
 
 /* ---- numeric-contract self tests (used by tests/test_gpu_parity.py) --------------------------------------- */
@@ -1045,7 +1068,7 @@ int svs_randperm_prefix(unsigned char* rng_state, size_t state_bytes, long long 
  * before the call returns -- and does not synchronise.  The graph is never instantiated or launched; it must outlive the
  * plan (the kernel arguments stay in its nodes).  svs_plan_info: counts[8] = nodes, kernels, copies, memsets, empty
  * nodes, streams, events, side streams that start at the entry. */
-int svs_plan_build(void* hip_graph, void* const* side_streams, int n_side_streams, void** plan_out);
+int svs_plan_build(void* hip_graph, void* const SVS_HOST* side_streams, int n_side_streams, void* SVS_HOST* plan_out);
 int svs_plan_run(void* plan, void* hip_stream);
 int svs_plan_info(void* plan, int* counts);
 /* one line per node in issue order: "<position> s<stream> kernel <name> grid .. | memcpy .. | memset .. | empty", followed by

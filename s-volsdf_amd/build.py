@@ -12,6 +12,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
+HEADER = os.path.join(os.path.dirname(HERE), "include", "svolsdf_hip.h")   # csrc/svs_common.h includes it: every unit sees it
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libsvolsdf_hip.so")
 ARCH = "gfx950"
@@ -68,9 +69,9 @@ def _hipcc():
 
 def _stamp():
     h = hashlib.sha256()
-    for name in sorted(os.listdir(CSRC)):
-        with open(os.path.join(CSRC, name), "rb") as f:
-            h.update(name.encode()); h.update(f.read())
+    for path in [HEADER] + [os.path.join(CSRC, name) for name in sorted(os.listdir(CSRC))]:
+        with open(path, "rb") as f:
+            h.update(os.path.basename(path).encode()); h.update(f.read())
     h.update(repr(sorted(UNITS.items())).encode())
     h.update(repr(BASE_FLAGS).encode())
     return h.hexdigest()

@@ -119,7 +119,7 @@ int svs_randperm_prefix(unsigned char* rng_state, size_t state_bytes, long long 
   return SVS_OK;
 }
 
-int svs_version(void) { return 101; }
+int svs_version(void) { return SVS_ABI_VERSION; }
 // deterministic accumulation of the weight gradients (csrc/svs_ticket.h): process-wide switch, off by default
 int svs_set_deterministic(int on) { const int was = svs::g_deterministic.load(); svs::g_deterministic.store(on ? 1 : 0); return was; }
 int svs_get_deterministic(void) { return svs::g_deterministic.load(); }

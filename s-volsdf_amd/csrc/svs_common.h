@@ -3,11 +3,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+// The C-ABI every entry point is defined against: prototypes, job structs, error codes, version.  A definition that
+// disagrees with its declaration there does not compile.
+#include "../../include/svolsdf_hip.h"
+
 #define SVS_OK 0
-#define SVS_EINVAL (-1)
-#define SVS_ESHAPE (-2)
-#define SVS_ENOCONV (-3)   // an iteration did not settle within its round limit (include/svolsdf_hip.h)
-#define SVS_EOVERFLOW (-4) // an operand of the fp16x2 3x3 convolution does not fit fp16 (include/svolsdf_hip.h)
 
 // Activation blocks are written once and read once by a later kernel: non-temporal stores keep them from evicting the
 // packed weight stream (2-4.6 MB per network, re-read by every workgroup) from the 4 MB L2 of an XCD.

@@ -437,13 +437,6 @@ int set_lds_b(K kernel, int bytes, const char* who) {
 }
 }  // namespace
 
-struct svs_unpack_job {          // include/svolsdf_hip.h
-  const float *dWk, *dbk;
-  int ldw, map, rows, cols, row_off;
-  const float *weight_v, *weight_g, *row0;
-  float *grad_v, *grad_g, *grad_b;
-};
-
 extern "C" {
 
 // blocks_per_tile slots of kBlockF floats per wave tile, followed by one 64-float record per slot (the per-point scales and

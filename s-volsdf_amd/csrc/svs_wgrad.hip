@@ -576,17 +576,6 @@ namespace h2 = svs::wgrad::h2;
 
 extern "C" {
 
-// the C-ABI job record (include/svolsdf_hip.h)
-struct svs_wgrad_job {
-  const float *a0, *b0; long long sa0, sb0;
-  const float *a1, *b1; long long sa1, sb1;
-  const float* b_extra; long long s_extra;
-  int n_points, ldw;
-  float *dW, *db;
-  const float* absmax;
-  const float *rec0, *rec1;     // fp16x2: records [tile][64] of the scaled operands (a0's; b1's), required with absmax
-};
-
 // Weight gradients of several layers in one call.  Per job: dW[256][ldw] += sum_p A(p) B(p)^T over one or two
 // operand pairs; db[256] += row sums of A of pair 0.  fp16x2: one launch for all jobs; float32: one launch per job.
 int svs_wgrad_multi(const svs_wgrad_job* jobs, int n_jobs, int precision, void* hip_stream) {

@@ -82,7 +82,7 @@ def rays_from_uv(uv, pose, intrinsics):
 
 
 # MFMA precision of the MLP kernels (include/svolsdf_hip.h: SVS_MMA_F32 / SVS_MMA_F16X2 / SVS_MMA_F16X2_HALF)
-F32, F16X2, F16X2_HALF = 0, 1, 2
+F32, F16X2, F16X2_HALF = _lib.MMA_F32, _lib.MMA_F16X2, _lib.MMA_F16X2_HALF
 _PRECISIONS = {"f32": F32, "f16x2": F16X2, "f16x2_half": F16X2_HALF}
 
 

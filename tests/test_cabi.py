@@ -1,26 +1,47 @@
-"""CPU-side checks of the C-ABI: the library builds for gfx950, loads, and exports exactly what
-include/svolsdf_hip.h declares with the argument counts the ctypes table uses (no compute calls)."""
+"""CPU-side checks of the C-ABI: include/svolsdf_hip.h stands alone as C and C++, the library builds for gfx950 against it,
+loads, and exports exactly what it declares, and the ctypes table svs_hip/lib.py derives from it is the one its rules
+promise (no compute calls)."""
+import ctypes
 import os
 import re
+import shutil
+import subprocess
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_longlong, c_size_t, c_void_p
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, "include", "svolsdf_hip.h")
+_P, _PP = c_void_p, POINTER(c_void_p)
 
 
-@pytest.fixture(scope="module")
-def lib():
+def _build_module():
     import importlib.util
     spec = importlib.util.spec_from_file_location("svs_build", os.path.join(ROOT, "s-volsdf_amd", "build.py"))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
-    mod.build(verbose=False)
+    return mod
+
+
+@pytest.fixture(scope="module")
+def lib():
+    _build_module().build(verbose=False)
     from svs_hip import lib as L
     return L
 
 
+def _llvm_tool(name):
+    """A tool of the LLVM toolchain the library was built with: the one hipcc belongs to."""
+    rocm = os.path.dirname(os.path.dirname(os.path.realpath(shutil.which(_build_module()._hipcc()))))
+    for d in (os.path.join(rocm, "lib", "llvm", "bin"), os.path.join(rocm, "llvm", "bin")):
+        if os.path.exists(os.path.join(d, name)):
+            return os.path.join(d, name)
+    raise AssertionError(f"{name} not found under {rocm}")
+
+
 def _header_decls():
-    src = open(os.path.join(ROOT, "include", "svolsdf_hip.h")).read()
+    """Name -> argument count by a regular expression of this file's own (no code shared with the binding's parser)."""
+    src = open(HEADER).read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
     decls = {}
     for m in re.finditer(r"\b(?:int|size_t|const char\*)\s+(svs_\w+)\s*\(([^;]*?)\)\s*;", src, flags=re.S):
@@ -30,13 +51,129 @@ def _header_decls():
 
 
 def test_header_matches_library_and_ctypes_table(lib):
+    """The header's functions = the library's dynamic svs_ symbols = the derived table, and load() has set that table's
+    types on every one of them."""
     decls = _header_decls()
     L = lib.load()
     assert set(decls) == set(lib.SIGNATURES), set(decls) ^ set(lib.SIGNATURES)
+    out = subprocess.run([_llvm_tool("llvm-readelf"), "--dyn-syms", "--wide", lib.LIB_PATH], check=True, capture_output=True,
+                         text=True).stdout
+    exported = {f[7].split("@")[0] for f in (line.split() for line in out.splitlines())
+                if len(f) == 8 and f[6] != "UND" and f[7].startswith("svs_")}
+    assert exported == set(lib.SIGNATURES), exported ^ set(lib.SIGNATURES)
     for name, nargs in decls.items():
         assert hasattr(L, name), f"{name} declared in the header but not exported"
-        assert len(lib.SIGNATURES[name][1]) == nargs, name
-    assert L.svs_version() == 101
+        res, args = lib.SIGNATURES[name]
+        assert len(args) == nargs, name
+        fn = getattr(L, name)
+        assert fn.restype is res, name
+        assert len(fn.argtypes) == nargs and all(a is b for a, b in zip(fn.argtypes, args)), name
+    assert L.svs_version() == lib.ABI_VERSION == 101
+
+
+def test_parser_rules_on_header_snippets(lib):
+    """Every rule of the binding's header parser on literal C text, and its refusal of what it cannot classify."""
+    consts, structs, sigs = lib.parse_header("""
+        #ifndef X_H
+        #define X_H
+        #include <stddef.h>
+        #ifdef __cplusplus
+        extern "C" {
+        #endif
+        #define SVS_HOST
+        #define SVS_ABI_VERSION 7
+        #define SVS_EBAD (-9)   /* with a comment */
+        enum { SVS_A = 0, SVS_B = 2 };
+        /* a declaration
+         * spread over three lines */
+        int svs_three(const float* x, int n,
+                      float scale,   // one per line
+                      void* hip_stream);
+        int svs_none(void);
+        const char* svs_text(void);
+        size_t svs_bytes(size_t n, double d, long long k);
+        int svs_tables(const float* const* unmarked, const float* const SVS_HOST* marked, void* SVS_HOST* out,
+                       void* const SVS_HOST* in);
+        int svs_host(unsigned char* state, const long long SVS_HOST* ranks, const float SVS_HOST* f,
+                     double SVS_HOST* d, int SVS_HOST* i, char* buf, const char* name, const uint8_t* const* masks);
+        typedef struct svs_job {
+          const float *a0, *b0; long long sa0, sb0;
+          int n, ldw;
+          float* dW;
+          size_t bytes; double x; float y;
+        } svs_job;
+        int svs_jobs(const svs_job* jobs, int n);
+        #ifdef __cplusplus
+        }
+        #endif
+        #endif
+    """)
+    assert consts == {"SVS_ABI_VERSION": 7, "SVS_EBAD": -9, "SVS_A": 0, "SVS_B": 2}
+    assert sigs == {
+        "svs_three": (c_int, [_P, c_int, c_float, _P]),
+        "svs_none": (c_int, []),
+        "svs_text": (c_char_p, []),
+        "svs_bytes": (c_size_t, [c_size_t, c_double, c_longlong]),
+        "svs_tables": (c_int, [_P, _PP, _PP, _PP]),
+        "svs_host": (c_int, [_P, POINTER(c_longlong), POINTER(c_float), POINTER(c_double), POINTER(c_int), c_char_p, c_char_p, _P]),
+        "svs_jobs": (c_int, [_P, c_int]),
+    }
+    assert structs == {"svs_job": [("a0", _P), ("b0", _P), ("sa0", c_longlong), ("sb0", c_longlong), ("n", c_int),
+                                   ("ldw", c_int), ("dW", _P), ("bytes", c_size_t), ("x", c_double), ("y", c_float)]}
+    refused = {
+        "int svs_f(const float* x, half y);": "svs_f",                       # a parameter of an unknown type
+        "int svs_g(long n);": "svs_g",
+        "int svs_h(float SVS_HOST x);": "svs_h",                             # the marker on a value
+        "int svs_i(const unsigned char SVS_HOST* s);": "svs_i",              # a host pointer to a type with no rule
+        "int svs_j(float*** p);": "svs_j",
+        "int svs_k(int (*callback)(int));": "svs_k",
+        "short svs_l(int n);": "svs_l",                                      # a return type with no rule
+        "typedef struct svs_s { float a[4]; } svs_s;": "svs_s",              # an unparsable struct field
+        "typedef struct svs_t { int a : 3; } svs_t;": "svs_t",
+        "typedef struct svs_u { struct svs_u* next; } svs_u;": "svs_u",
+        "typedef struct svs_v { int a; } svs_w;": "svs_v",
+        "#define SVS_MAX(a, b) ((a) > (b) ? (a) : (b))": "SVS_MAX",
+        "enum { SVS_C = 1 << 3 };": "SVS_C",
+        "static inline int svs_m(int n) { return n; }": "svs_m",
+    }
+    for text, named in refused.items():
+        with pytest.raises(lib.SvsError, match=named):
+            lib.parse_header(text)
+
+
+def test_three_real_signatures(lib):
+    """The rules on the real header: the list INTEGRATION.md prints, five doubles and a long long, a pointer table and a
+    host float array."""
+    assert lib.SIGNATURES["svs_sdf_vals"] == (c_int, [_P, c_int, _P, c_int, _P, _P, c_int, c_int, _P, c_int, c_float, c_float,
+                                                      c_int, _P, _P, c_int, c_int, _P])
+    assert lib.SIGNATURES["svs_clip_guard_adam"] == (c_int, [_P, _P, _P, _P, c_longlong, c_int, _P, c_double, c_double,
+                                                             c_double, c_double, c_double, _P, _P, _P])
+    assert lib.SIGNATURES["svs_warp_variance"] == (c_int, [_P, _PP, POINTER(c_float), c_int, c_int, c_int, c_int, c_int, _P, _P,
+                                                           c_int, _P])
+
+
+def test_header_stands_alone(lib, tmp_path):
+    """The header compiles as C99 and as C++17 with nothing else on the include path, and the C compiler lays the two job
+    structs out as ctypes lays out the classes derived from them."""
+    clang = _llvm_tool("clang")
+    subprocess.run([clang, "-std=c99", "-x", "c", "-fsyntax-only", "-Wall", "-Werror", HEADER], check=True)
+    subprocess.run([clang, "-std=c++17", "-x", "c++", "-fsyntax-only", "-Wall", "-Werror", HEADER], check=True)
+    classes = {"svs_wgrad_job": lib.WGradJob, "svs_unpack_job": lib.UnpackJob}
+    lines = ['#include <stdio.h>', '#include "svolsdf_hip.h"', "int main(void) {"]
+    for c_name, cls in classes.items():
+        lines.append(f'  printf("{c_name} %zu\\n", sizeof({c_name}));')
+        lines += [f'  printf("{c_name}.{f} %zu\\n", offsetof({c_name}, {f}));' for f, _ in cls._fields_]
+    lines += ["  return 0;", "}"]
+    (tmp_path / "layout.c").write_text("\n".join(lines) + "\n")
+    exe = str(tmp_path / "layout")
+    subprocess.run([clang, "-std=c99", "-I", os.path.dirname(HEADER), str(tmp_path / "layout.c"), "-o", exe], check=True)
+    got = dict(line.split() for line in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.splitlines())
+    want = {}
+    for c_name, cls in classes.items():
+        want[c_name] = str(ctypes.sizeof(cls))
+        want.update({f"{c_name}.{f}": str(getattr(cls, f).offset) for f, _ in cls._fields_})
+    assert got == want
+    assert len(want) == 2 + 17 + 13
 
 
 def test_size_queries(lib):
