@@ -429,10 +429,11 @@ int svs_conv3d(const float* in, const float* weight, const float* bias, const fl
                int Di, int Hi, int Wi, int stride, int transposed, int relu, void* hip_stream);
 /* The stride-1 convolutions with Cin in {8,16,32} and Cout <= 16 (conv0, conv2, prob: 79 % of the U-Net's MACs at
  * stage 1) on the fp16 matrix cores with two-piece split operands (float32-class accuracy).
- * wfrag (svs_conv3d_mfma_wfrag_bytes(Cin)): the folded weights as fp16 hi / mid A fragments of
- * v_mfma_f32_16x16x32_f16: [k-step s][piece][lane][8]: output channel lane & 15, k = 32 s + 8 (lane >> 4) + j =
- * tap * Cin + cin (zero for tap > 26 and channels >= Cout). */
+ * wfrag (svs_conv3d_mfma_wfrag_bytes(Cin)): the folded [Cin][27][Cout] weights (float32, on the device) as fp16 hi / mid A
+ * fragments of v_mfma_f32_16x16x32_f16, written by svs_conv3d_mfma_pack (asynchronous, allocates nothing; the layout:
+ * convmfma::WeightMap, csrc/svs_conv_mfma.hip). */
 size_t svs_conv3d_mfma_wfrag_bytes(int Cin);
+int svs_conv3d_mfma_pack(const float* weight, int Cin, int Cout, void* wfrag, void* hip_stream);
 int svs_conv3d_mfma(const float* in, const void* wfrag, const float* bias, const float* skip, float* out, int Cin,
                     int Cout, int D, int H, int W, int relu, void* hip_stream);
 
@@ -448,9 +449,8 @@ int svs_conv3d_mfma(const float* in, const void* wfrag, const float* bias, const
  *   svs_conv3d_pair          = relu?(conv3d(volume, 3x3x3, stride 1, padding 1) + bias), Cin in {8,16,32}, Cout <= 8:
  *     the 16 rows of v_mfma_f32_16x16x32_f16 are 8 output channels x 2 neighbouring x positions, a column is that pair
  *     of positions, K = 3 kd x 3 kh x 4 input columns x Cin (27 of 36 products useful; 27 of 54 with channels only).
- *     wfrag (svs_conv3d_pair_wfrag_bytes(Cin)): [k-step s][piece][lane][8] fp16, row m = lane & 15 = (channel m & 7,
- *     position m >> 3), k = 32 s + 8 (lane >> 4) + j = (((kd*3 + kh)*4 + t)*(Cin/8) + g)*8 + c8: the folded weight of
- *     tap (kd, kh, kw = t - (m >> 3)) and input channel 8 g + c8, zero if kw is outside 0..2 or m & 7 >= Cout. */
+ *     wfrag (svs_conv3d_pair_wfrag_bytes(Cin)): written by svs_conv3d_pair_pack from the folded [Cin][27][Cout] weights
+ *     (the layout: convpair::PairMap, csrc/svs_conv_pair.hip). */
 size_t svs_split_volume_dims(int C, int D, int H, int W, int SVS_HOST* dims);
 /* The final `prob` layer (Cin -> 1, CasMVSNet.py:458,471): float32 fused multiply-adds on the vector ALUs (a one-row
  * matrix-core tile would be 1/16 full).  weight [Cin][27][1]. */
@@ -461,6 +461,7 @@ int svs_warp_variance_split(const float* ref_feature, const float* const SVS_HOS
                             const float SVS_HOST* rot_trans, int n_src, int C, int D, int H, int W,
                             const float* depth_values, void* split, void* hip_stream);
 size_t svs_conv3d_pair_wfrag_bytes(int Cin);
+int svs_conv3d_pair_pack(const float* weight, int Cin, int Cout, void* wfrag, void* hip_stream);
 int svs_conv3d_pair(const void* split, const void* wfrag, const float* bias, float* out, int Cin, int Cout, int D, int H,
                     int W, int relu, void* hip_stream);
 
@@ -469,7 +470,7 @@ int svs_conv3d_pair(const void* split, const void* wfrag, const float* bias, flo
  * (svs_conv3d_gemm_supported).  One wave = 16 output voxels along x times all output channels; the transposed form
  * runs as 8 GEMMs, one per output parity class, over only the taps that class uses.
  * wfrag: svs_conv3d_gemm_wfrag_bytes(Cin, Cout, transposed), filled once per layer by svs_conv3d_gemm_pack from the
- * folded [Cin][27][Cout] weights (layout [class][k-step][m-tile][hi,mid][lane][8 fp16], k = tap-in-class * Cin + cin). */
+ * folded [Cin][27][Cout] weights (the layout: convgemm::GemmMap, csrc/svs_conv_gemm.hip). */
 int svs_conv3d_gemm_supported(int Cin, int Cout);
 size_t svs_conv3d_gemm_wfrag_bytes(int Cin, int Cout, int transposed);
 int svs_conv3d_gemm_pack(const float* weight, int Cin, int Cout, int transposed, void* wfrag, void* hip_stream);
@@ -477,19 +478,19 @@ int svs_conv3d_gemm(const float* in, const void* wfrag, const float* bias, const
                     int Di, int Hi, int Wi, int stride, int transposed, int relu, void* hip_stream);
 /* conv1 of CostRegNet (8 -> 2b channels, stride 2, from the full-resolution volume: CasMVSNet.py:445,461): a lane group
  * owns whole (kz,ky) input rows, one 8-byte load per (row, channel) serves the taps kx = 1, 2 and the neighbour lane's
- * value the tap kx = 0.  Cout <= 16, Wi even.  wfrag (svs_conv3d_s2c8_wfrag_bytes()): [9 k-steps][piece][lane][8] fp16,
- * row lane & 15 = output channel, k = 32 s + 8 g + j with s = kx*3 + q, g = lane >> 4: tap ((g+4q)/3, (g+4q)%3, kx),
- * input channel j; zero for g + 4q > 8. */
+ * value the tap kx = 0.  Cout <= 16, Wi even.  wfrag (svs_conv3d_s2c8_wfrag_bytes()): written by svs_conv3d_s2c8_pack from the
+ * folded [8][27][Cout] weights (the layout: convgemm::S2c8Map, csrc/svs_conv_gemm.hip). */
 size_t svs_conv3d_s2c8_wfrag_bytes(void);
+int svs_conv3d_s2c8_pack(const float* weight, int Cout, void* wfrag, void* hip_stream);
 /* split_out != NULL (Cout = 16, no skip): the output leaves as a split volume (svs_split_volume_dims(16, Do, Ho, Wo)) instead
  * of float32 to `out` -- the input form of svs_conv3d_rows (conv2). */
 int svs_conv3d_s2c8(const float* in, const void* wfrag, const float* bias, const float* skip, float* out, void* split_out,
                     int Cout, int Di, int Hi, int Wi, int relu, void* hip_stream);
 /* conv2 of CostRegNet (2b -> 2b at half resolution, CasMVSNet.py:446,462) from a split volume: slice ring + LDS-DMA as
  * svs_conv3d_pair, the 16 MFMA rows = output channels.  Cin = 16, Cout <= 16.  wfrag (svs_conv3d_rows_wfrag_bytes(Cin)):
- * [k-step s][piece][lane][8] fp16, row lane & 15 = output channel, k-step s / lane group lane >> 4 = combination
- * 4 s + (lane >> 4) = tap * (Cin/8) + g of the (kd,kh,kw)-major tap list: weight of that tap, input channel 8 g + c8. */
+ * written by svs_conv3d_rows_pack from the folded [16][27][Cout] weights (the layout: convpair::RowsMap, csrc/svs_conv_pair.hip). */
 size_t svs_conv3d_rows_wfrag_bytes(int Cin);
+int svs_conv3d_rows_pack(const float* weight, int Cin, int Cout, void* wfrag, void* hip_stream);
 int svs_conv3d_rows(const void* split, const void* wfrag, const float* bias, float* out, int Cin, int Cout, int D, int H,
                     int W, int relu, void* hip_stream);
 

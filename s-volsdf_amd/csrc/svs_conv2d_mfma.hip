@@ -11,14 +11,15 @@
 // first in global memory) into channel-last fp16 hi / mid pieces in LDS, then every wave computes one output row: 2 N tiles
 // x MT M tiles x KS k-steps x 3 MFMAs, the B fragments (16-byte channel vectors of one input pixel) read from LDS one k-step
 // ahead.  Pixel pitch in LDS: an odd multiple of 16 bytes (conflict-free 16-byte reads at pixel stride 1; stride 2: two-way).
-#include "svs_common.h"
+#include "svs_conv_frag.h"
 #include "svs_conv2d_api.h"
 
 namespace svs {
 namespace conv2dmfma {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
+using frag::f16x8;
+using frag::f32x4v;
+using frag::pitch;
 
 constexpr int kWaves = 4, kTX = 32;            // a workgroup's output window: RW * 4 rows (RW rows per wave) x 32 columns
 
@@ -39,12 +40,26 @@ struct Args {
 };
 
 template <int CIN, int K, int S> constexpr int k_steps() { return (K * K * CIN + 31) / 32; }
-template <int CIN> constexpr int pitch() { return CIN == 8 ? 16 : (CIN == 16 ? 48 : 80); }
 template <int K, int S, int RW> constexpr int halo_y() { return (kWaves * RW - 1) * S + K; }
 template <int K, int S> constexpr int halo_x() { return (kTX - 1) * S + K; }
 template <int CIN, int K, int S, int RW> constexpr int lds_bytes() {
   return 2 * halo_y<K, S, RW>() * halo_x<K, S>() * pitch<CIN>() + (CIN * 8 + CIN) * 4;      // + the lateral weights of LAT instances
 }
+
+// The A fragments of conv2d_mfma_kernel (svs_conv2d_mfma_pack) from (Cout, Cin, K, K) float32: fragment pairs [M tile mt]
+// [k-step s]; lane l holds output channel 16 mt + (l & 15) and, for j = 0..7, k = 32 s + 8 (l >> 4) + j = (kh * K + kw) * Cin +
+// ci, ci fastest -- the kernel's `boff`.  Zero beyond the K * K taps and beyond Cout.
+struct WeightMap {
+  int Cin, Cout, K;
+  __host__ __device__ int k_steps() const { return (K * K * Cin + 31) / 32; }
+  __host__ __device__ int n_fragments() const { return (Cout > 16 ? 2 : 1) * k_steps(); }
+  __device__ float source(const float* w, int f, int lane, int j) const {
+    const int s = f % k_steps(), mt = f / k_steps();
+    const int co = 16 * mt + (lane & 15), k = 32 * s + 8 * (lane >> 4) + j;
+    const int tap = k / Cin, ci = k - tap * Cin;
+    return (tap < K * K && co < Cout) ? w[((size_t)co * Cin + ci) * K * K + tap] : 0.0f;
+  }
+};
 
 // RW: output rows per wave (2: an 8 x 32 window -- 1.33 instead of 1.6 input pixels converted per output pixel at 3x3 --
 // for the layers at full image resolution, where the conversion of the halo is most of the kernel)
@@ -103,12 +118,7 @@ __global__ __launch_bounds__(256, 1) void conv2d_mfma_kernel(Args a) {
       unsigned char* ph = smem + p * PITCH;
       auto put = [&](int c8, const float (&v)[8]) {
         f16x8 h, m;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const _Float16 hh = (_Float16)v[j];
-          h[j] = hh;
-          m[j] = (_Float16)(v[j] - (float)hh);
-        }
+        frag::split(v, h, m);
         *reinterpret_cast<f16x8*>(ph + 16 * c8) = h;
         *reinterpret_cast<f16x8*>(ph + PIECE + 16 * c8) = m;
       };
@@ -226,29 +236,11 @@ __global__ __launch_bounds__(256, 1) void conv2d_mfma_kernel(Args a) {
   }
 }
 
-// (Cout, Cin, K, K) float32 -> A fragments: element j of fragment [mt][s][piece][lane] is the hi / mid part of
-// W[16 mt + (lane & 15)][ci][kh][kw] with k = 32 s + 8 (lane >> 4) + j = (kh * K + kw) * Cin + ci; zero beyond K * K taps and Cout
-__global__ void pack_kernel(const float* __restrict__ w, int Cout, int Cin, int K, int KS, int MT, _Float16* __restrict__ frag) {
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= MT * KS * 64 * 8) return;
-  const int j = e & 7, lane = (e >> 3) & 63, s = (e >> 9) % KS, mt = (e >> 9) / KS;
-  const int co = 16 * mt + (lane & 15), k = 32 * s + 8 * (lane >> 4) + j;
-  const int tap = k / Cin, ci = k - tap * Cin;
-  float v = 0.0f;
-  if (tap < K * K && co < Cout) v = w[((size_t)co * Cin + ci) * K * K + tap];
-  const _Float16 h = (_Float16)v;
-  const size_t base = (((size_t)(mt * KS + s) * 2) * 64 + lane) * 8 + j;
-  frag[base] = h;
-  frag[base + 64 * 8] = (_Float16)(v - (float)h);
-}
-
 template <int CIN, int K, int S, int MT, int RW, bool LAT = false>
 int launch(Args a, hipStream_t s) {
   constexpr int lds = lds_bytes<CIN, K, S, RW>();
   a.tiles = a.tiles_x * ((a.Ho + kWaves * RW - 1) / (kWaves * RW));
-  static hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv2d_mfma_kernel<CIN, K, S, MT, RW, LAT>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  if (e != hipSuccess) { set_error("svs_conv2d_mfma: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
+  if (const int rc = frag::opt_in_lds<conv2d_mfma_kernel<CIN, K, S, MT, RW, LAT>>(lds, "svs_conv2d_mfma")) return rc;
   // two workgroups per CU where the registers allow it; a workgroup walks its windows with the weights in registers
   const int grid = a.tiles < 512 ? a.tiles : 512;
   conv2d_mfma_kernel<CIN, K, S, MT, RW, LAT><<<grid, 256, lds, s>>>(a);
@@ -313,15 +305,13 @@ int svs_conv2d_mfma_supported(int Cin, int Cout, int k, int stride) { return con
 
 // bytes of the packed A fragments of a layer: [Cout <= 16 ? 1 : 2][ceil(k k Cin / 32)][2][64][16 B]
 size_t svs_conv2d_mfma_wfrag_bytes(int Cin, int Cout, int k) {
-  return (size_t)(Cout > 16 ? 2 : 1) * ((k * k * Cin + 31) / 32) * 2 * 64 * 16;
+  return (size_t)conv2dmfma::WeightMap{Cin, Cout, k}.n_fragments() * 2 * 64 * 16;
 }
 
 // weight (Cout,Cin,k,k) float32 on the device (BatchNorm folded) -> wfrag (svs_conv2d_mfma_wfrag_bytes)
 int svs_conv2d_mfma_pack(const float* weight, int Cin, int Cout, int k, void* wfrag, void* hip_stream) {
   if (!weight || !wfrag || Cin < 1 || Cout < 1 || Cout > 32 || (k != 3 && k != 5)) { set_error("svs_conv2d_mfma_pack: bad argument"); return SVS_EINVAL; }
-  const int KS = (k * k * Cin + 31) / 32, MT = Cout > 16 ? 2 : 1, n = MT * KS * 64 * 8;
-  conv2dmfma::pack_kernel<<<(n + 255) / 256, 256, 0, (hipStream_t)hip_stream>>>(weight, Cout, Cin, k, KS, MT, static_cast<_Float16*>(wfrag));
-  return check_launch("svs_conv2d_mfma_pack");
+  return frag::pack_fragments(weight, conv2dmfma::WeightMap{Cin, Cout, k}, wfrag, (hipStream_t)hip_stream, "svs_conv2d_mfma_pack");
 }
 
 // out (Cout,Ho,Wo) = relu?(conv2d(in (Cin,H,W), k x k, padding k / 2, stride) + bias) on the fp16x2 matrix-core path:

@@ -18,14 +18,14 @@
 // the two x-parities of a (pz,py) class share one GEMM: output rows [0,Cout) are the even-x outputs, rows
 // [Cout,2Cout) the odd-x ones, over the same B fragments (input voxels xi and xi+1) -- one third fewer input loads,
 // full M tiles for Cout = 8, and the even/odd outputs of a channel leave in the same store instruction.
-#include "svs_common.h"
+#include "svs_conv_frag.h"
 #include "svs_split_volume.h"
 #include <cstdlib>
 
 namespace svs {
 namespace convgemm {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+using frag::f16x8;
 
 struct Args {
   const float* in;      // (Cin, Di, Hi, Wi)
@@ -49,68 +49,64 @@ __host__ __device__ inline void deconv_tap(int parity, int idx, int* k, int* d) 
 __host__ __device__ constexpr int ksteps(int cin, int ntaps) { return (ntaps * cin + 31) / 32; }
 __host__ __device__ constexpr int ksteps_max(int cin, bool transposed) { return ksteps(cin, transposed ? 8 : 27); }
 
-// ---- weight packing: [Cin][27][Cout] float32 -> fp16 hi / mid A fragments ------------------------------------------------------
-// transposed: 0 convolution, 1 transposed (8 classes), 2 transposed with the x-parities paired (4 classes, M = 2 Cout)
-__global__ void pack_kernel(const float* __restrict__ w, int Cin, int Cout, int transposed, int MT, f16x8* __restrict__ frag) {
-  const int KS = ksteps_max(Cin, transposed != 0);
-  const int n_class = transposed == 1 ? 8 : (transposed >= 2 ? 4 : 1);
-  const long long total = (long long)n_class * KS * MT * 64;
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= total) return;
-  const int lane = (int)(i % 64), mt = (int)((i / 64) % MT), s = (int)((i / (64 * MT)) % KS), c = (int)(i / ((long long)64 * MT * KS));
-  int co = 16 * mt + (lane & 15);
-  const int k0 = 32 * s + 8 * (lane >> 4);
-  const int t = k0 / Cin, ci0 = k0 % Cin;
-  int tap = -1;
-  if (!transposed) {
-    if (t < 27) tap = t;
-  } else if (transposed == 3) {
-    // all classes share the B operand: slot t = (dz*2 + dy)*2 + dxs of the 8 input voxels a 2x2x2 output cell touches;
-    // class c = (pz,py) takes offset d along an axis with kernel index {parity 0: d=0 -> 1; parity 1: d=1 -> 0, d=0 -> 2}
-    const int pz = (c >> 1) & 1, py = c & 1;
-    // row r of the 16: channel 2 (r >> 2) + ((r >> 1) & 1), x parity r & 1 -- a lane's four accumulator rows are then the
-    // even / odd outputs of two channels: both parities of a channel leave (and their skip values arrive) as one float2
-    const int px = co & 1;
-    co = 2 * (co >> 2) + ((co >> 1) & 1);
-    const int dz = t >> 2, dy = (t >> 1) & 1, dxs = t & 1;
-    const int kz = pz == 0 ? (dz == 0 ? 1 : -1) : (dz == 1 ? 0 : 2);
-    const int ky = py == 0 ? (dy == 0 ? 1 : -1) : (dy == 1 ? 0 : 2);
-    const int kx = px == 0 ? (dxs == 0 ? 1 : -1) : (dxs == 0 ? 2 : 0);
-    if (t < 8 && kz >= 0 && ky >= 0 && kx >= 0) tap = (kz * 3 + ky) * 3 + kx;
-  } else if (transposed == 2) {
-    // slot t = (a * ny + b) * 2 + dxs: input offset (dz(a), dy(b), dxs); row block px = co / Cout
-    const int pz = (c >> 1) & 1, py = c & 1;
-    const int ny = 1 + py, nz = 1 + pz;
-    const int px = co >= Cout ? 1 : 0;
-    co -= px * Cout;
-    if (px == 1 && co >= Cout) co = 1 << 20;                 // rows beyond 2 * Cout: zero
-    if (t < nz * ny * 2) {
-      const int dxs = t & 1, ab = t >> 1;
-      int kz, ky, d;
-      deconv_tap(pz, ab / ny, &kz, &d); deconv_tap(py, ab % ny, &ky, &d);
-      // even x (px = 0): kernel index 1 on input xi; odd x: index 2 on xi, index 0 on xi + 1
+// ---- the A fragments of conv_gemm_kernel / deconv_cell_kernel (svs_conv3d_gemm_pack): [Cin][27][Cout] float32 -> fragment
+// pairs [class c][k-step s][M tile mt]; lane l holds row 16 mt + (l & 15) and k = 32 s + 8 (l >> 4) + j = t * Cin + cin,
+// where t counts the taps (or input offsets) of the class in the order the kernels' B-operand decode walks them.
+// mode: 0 convolution, 1 transposed (8 classes), 2 transposed with the x-parities paired (4 classes, M = 2 Cout),
+// 3 transposed, whole 2x2x2 cells (deconv_cell_kernel: 4 classes over one set of B fragments)
+struct GemmMap {
+  int Cin, Cout, mode, MT;
+  __host__ __device__ int n_classes() const { return mode == 1 ? 8 : (mode >= 2 ? 4 : 1); }
+  __host__ __device__ int n_fragments() const { return n_classes() * ksteps_max(Cin, mode != 0) * MT; }
+  __device__ float source(const float* w, int f, int lane, int j) const {
+    const int KS = ksteps_max(Cin, mode != 0);
+    const int mt = f % MT, s = (f / MT) % KS, c = f / (MT * KS);
+    int co = 16 * mt + (lane & 15);
+    const int k = 32 * s + 8 * (lane >> 4) + j;
+    const int t = k / Cin, ci = k % Cin;
+    int tap = -1;
+    if (mode == 0) {
+      if (t < 27) tap = t;
+    } else if (mode == 3) {
+      // all classes share the B operand: slot t = (dz*2 + dy)*2 + dxs of the 8 input voxels a 2x2x2 output cell touches;
+      // class c = (pz,py) takes offset d along an axis with kernel index {parity 0: d=0 -> 1; parity 1: d=1 -> 0, d=0 -> 2}
+      const int pz = (c >> 1) & 1, py = c & 1;
+      // row r of the 16: channel 2 (r >> 2) + ((r >> 1) & 1), x parity r & 1 -- a lane's four accumulator rows are then the
+      // even / odd outputs of two channels: both parities of a channel leave (and their skip values arrive) as one float2
+      const int px = co & 1;
+      co = 2 * (co >> 2) + ((co >> 1) & 1);
+      const int dz = t >> 2, dy = (t >> 1) & 1, dxs = t & 1;
+      const int kz = pz == 0 ? (dz == 0 ? 1 : -1) : (dz == 1 ? 0 : 2);
+      const int ky = py == 0 ? (dy == 0 ? 1 : -1) : (dy == 1 ? 0 : 2);
       const int kx = px == 0 ? (dxs == 0 ? 1 : -1) : (dxs == 0 ? 2 : 0);
-      if (kx >= 0) tap = (kz * 3 + ky) * 3 + kx;
+      if (t < 8 && kz >= 0 && ky >= 0 && kx >= 0) tap = (kz * 3 + ky) * 3 + kx;
+    } else if (mode == 2) {
+      // slot t = (a * ny + b) * 2 + dxs: input offset (dz(a), dy(b), dxs); row block px = co / Cout
+      const int pz = (c >> 1) & 1, py = c & 1;
+      const int ny = 1 + py, nz = 1 + pz;
+      const int px = co >= Cout ? 1 : 0;
+      co -= px * Cout;
+      if (px == 1 && co >= Cout) co = 1 << 20;                 // rows beyond 2 * Cout: zero
+      if (t < nz * ny * 2) {
+        const int dxs = t & 1, ab = t >> 1;
+        int kz, ky, d;
+        deconv_tap(pz, ab / ny, &kz, &d); deconv_tap(py, ab % ny, &ky, &d);
+        // even x (px = 0): kernel index 1 on input xi; odd x: index 2 on xi, index 0 on xi + 1
+        const int kx = px == 0 ? (dxs == 0 ? 1 : -1) : (dxs == 0 ? 2 : 0);
+        if (kx >= 0) tap = (kz * 3 + ky) * 3 + kx;
+      }
+    } else {
+      const int pz = (c >> 2) & 1, py = (c >> 1) & 1, px = c & 1;
+      const int nx = 1 + px, ny = 1 + py, nz = 1 + pz;
+      if (t < nx * ny * nz) {
+        int kz, ky, kx, d;
+        deconv_tap(pz, t / (nx * ny), &kz, &d); deconv_tap(py, (t / nx) % ny, &ky, &d); deconv_tap(px, t % nx, &kx, &d);
+        tap = (kz * 3 + ky) * 3 + kx;
+      }
     }
-  } else {
-    const int pz = (c >> 2) & 1, py = (c >> 1) & 1, px = c & 1;
-    const int nx = 1 + px, ny = 1 + py, nz = 1 + pz;
-    if (t < nx * ny * nz) {
-      int kz, ky, kx, d;
-      deconv_tap(pz, t / (nx * ny), &kz, &d); deconv_tap(py, (t / nx) % ny, &ky, &d); deconv_tap(px, t % nx, &kx, &d);
-      tap = (kz * 3 + ky) * 3 + kx;
-    }
+    return (tap >= 0 && co < Cout) ? w[((size_t)ci * 27 + tap) * Cout + co] : 0.0f;
   }
-  f16x8 hi, mid;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const float v = (tap >= 0 && co < Cout) ? w[((size_t)(ci0 + j) * 27 + tap) * Cout + co] : 0.0f;
-    const _Float16 h = (_Float16)v;
-    hi[j] = h; mid[j] = (_Float16)(v - (float)h);
-  }
-  const size_t o = (((size_t)c * KS + s) * MT + mt) * 2 * 64 + lane;
-  frag[o] = hi; frag[o + 64] = mid;
-}
+};
 
 // MODE 0: convolution (stride 1 or 2); MODE 1: transposed convolution, 8 classes; MODE 2: transposed, x-parities paired
 // KSPLIT: the four waves of a workgroup share ONE tile, wave w takes the k-steps s = w (mod 4) and the partial sums meet in
@@ -196,6 +192,8 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(Args a) {
       for (int m = 0; m < MT; ++m) { ahn[m] = wn[m * 128]; amn[m] = wn[m * 128 + 64]; }
     }
     f16x8 bh, bm;
+    // (frag::split spelled out, here and in the two kernels below: through the helper the operand arrays are promoted to
+    // registers in another order and the register allocation moves, and these kernels' machine code is pinned)
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const _Float16 h = (_Float16)xc[j];
@@ -266,7 +264,7 @@ __global__ __launch_bounds__(256) void deconv_cell_kernel(Args a) {
   const int zi = row / a.Hi, yi = row - zi * a.Hi, xi = 16 * xt + n;
   const bool col_ok = xi < a.Wi;
   const size_t chan_in = (size_t)a.Di * a.Hi * a.Wi, chan_out = (size_t)a.Do * a.Ho * a.Wo;
-  // accumulator rows 4 g + j of a lane in M tile mt: (channel 8 mt + 2 g + (j >> 1), x = 2 xi + (j & 1)) -- pack_kernel, mode 3
+  // accumulator rows 4 g + j of a lane in M tile mt: (channel 8 mt + 2 g + (j >> 1), x = 2 xi + (j & 1)) -- GemmMap, mode 3
   // ---- skip values of the cell (8 MTC float2 per lane), requested first
   float2 sk[4][MTC][2];
   size_t obase[4];
@@ -347,6 +345,19 @@ __global__ __launch_bounds__(256) void deconv_cell_kernel(Args a) {
 // time as a full gather: the cost is per line touched).  K order: k-step s = kx*3 + q carries rows g + 4q (g = lane
 // group; rows 9..11: zero weights), 8 channels each: 9 k-steps instead of 7, 24 loads per lane instead of 56, all
 // issued up front.
+//
+// The A fragments (svs_conv3d_s2c8_pack): fragment pair s = kx*3 + q; lane l holds row l & 15 = output channel and, for input
+// channel j = 0..7, the folded weight of tap (kz, ky, kx) with 3 kz + ky = (l >> 4) + 4 q -- zero for rows 9..11 and for
+// channels >= Cout.
+struct S2c8Map {
+  int Cout;
+  __host__ __device__ int n_fragments() const { return 9; }
+  __device__ float source(const float* w, int s, int lane, int j) const {
+    const int kx = s / 3, row = (lane >> 4) + 4 * (s % 3), co = lane & 15;
+    return (row < 9 && co < Cout) ? w[((size_t)j * 27 + row * 3 + kx) * Cout + co] : 0.0f;
+  }
+};
+
 __global__ __launch_bounds__(256) void conv_s2c8_kernel(Args a) {
   const int lane = threadIdx.x & 63;
   const long long tile = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -401,8 +412,7 @@ __global__ __launch_bounds__(256) void conv_s2c8_kernel(Args a) {
   if (a.split) {
     // the next layer (conv2, svs_conv3d_rows) reads fp16 hi / mid pieces, 8 channels per 16-byte unit: this lane's four
     // channels 4g .. 4g+3 are one half of unit g >> 1 (Cout = 16: rows beyond Cout hold zeros, their weights being zero)
-    typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-    f16x4 h, m;
+    frag::f16x4 h, m;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       float r = acc[j] + ((a.bias && 4 * g + j < a.Cout) ? a.bias[4 * g + j] : 0.0f);
@@ -463,6 +473,10 @@ static int deconv_mode(int Cin, int Cout) {
   if ((Cin == 16 && Cout == 8) || (Cin == 32 && Cout == 16)) return 3;     // whole 2x2x2 cells per wave (deconv_cell_kernel)
   return (Cout <= 32 && Cout % 4 == 0) ? 2 : 1;
 }
+static GemmMap gemm_map(int Cin, int Cout, int transposed) {
+  const int mode = transposed ? deconv_mode(Cin, Cout) : 0;
+  return GemmMap{Cin, Cout, mode, m_tiles(mode >= 2 ? 2 * Cout : Cout)};
+}
 
 }  // namespace convgemm
 }  // namespace svs
@@ -476,17 +490,12 @@ int svs_conv3d_gemm_supported(int Cin, int Cout) { return (Cin == 8 || Cin == 16
 
 size_t svs_conv3d_gemm_wfrag_bytes(int Cin, int Cout, int transposed) {
   if (!svs_conv3d_gemm_supported(Cin, Cout)) return 0;
-  const int mode = transposed ? deconv_mode(Cin, Cout) : 0;
-  return (size_t)(mode == 1 ? 8 : (mode >= 2 ? 4 : 1)) * ksteps_max(Cin, mode != 0) * m_tiles(mode >= 2 ? 2 * Cout : Cout) * 128 * sizeof(f16x8);
+  return (size_t)gemm_map(Cin, Cout, transposed).n_fragments() * 128 * sizeof(f16x8);
 }
 
 int svs_conv3d_gemm_pack(const float* weight, int Cin, int Cout, int transposed, void* wfrag, void* hip_stream) {
   if (!weight || !wfrag || !svs_conv3d_gemm_supported(Cin, Cout)) { set_error("svs_conv3d_gemm_pack: bad argument"); return SVS_EINVAL; }
-  const int mode = transposed ? deconv_mode(Cin, Cout) : 0;
-  const int MT = m_tiles(mode >= 2 ? 2 * Cout : Cout);
-  const long long total = (long long)(mode == 1 ? 8 : (mode >= 2 ? 4 : 1)) * ksteps_max(Cin, mode != 0) * MT * 64;
-  pack_kernel<<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)hip_stream>>>(weight, Cin, Cout, mode, MT, (f16x8*)wfrag);
-  return check_launch("svs_conv3d_gemm_pack");
+  return frag::pack_fragments(weight, gemm_map(Cin, Cout, transposed), wfrag, (hipStream_t)hip_stream, "svs_conv3d_gemm_pack");
 }
 
 int svs_conv3d_gemm(const float* in, const void* wfrag, const float* bias, const float* skip, float* out, int Cin, int Cout,
@@ -517,10 +526,13 @@ int svs_conv3d_gemm(const float* in, const void* wfrag, const float* bias, const
 }
 
 // The stride-2 convolution from 8 channels (conv1) with whole input rows per lane group (conv_s2c8_kernel): Cout <= 16,
-// Wi even.  wfrag: 9 k-steps x 2 pieces x 64 lanes x 16 B: row = lane & 15 (output channel), k = 32 s + 8 g + j with
-// s = kx*3 + q, g = lane >> 4: the folded weight of tap ((g + 4q) / 3, (g + 4q) % 3, kx) and input channel j (zero for
-// g + 4q > 8).
-size_t svs_conv3d_s2c8_wfrag_bytes(void) { return (size_t)9 * 2 * 64 * 16; }
+// Wi even.  wfrag: 9 k-steps x 2 pieces x 64 lanes x 16 B, S2c8Map.
+size_t svs_conv3d_s2c8_wfrag_bytes(void) { return (size_t)S2c8Map{1}.n_fragments() * 2 * 64 * 16; }
+// weight [8][27][Cout] float32 on the device (BatchNorm folded) -> wfrag (svs_conv3d_s2c8_wfrag_bytes())
+int svs_conv3d_s2c8_pack(const float* weight, int Cout, void* wfrag, void* hip_stream) {
+  if (!weight || !wfrag || Cout < 1 || Cout > 16) { set_error("svs_conv3d_s2c8_pack: bad argument (Cout <= 16)"); return SVS_EINVAL; }
+  return frag::pack_fragments(weight, S2c8Map{Cout}, wfrag, (hipStream_t)hip_stream, "svs_conv3d_s2c8_pack");
+}
 // split_out: not null = the output (Cout = 16 channels) leaves as a split volume (svs_split_volume_dims(16, Do, Ho, Wo)
 // bytes, zero-filled by the caller before its first use) instead of float32 to `out` -- the form svs_conv3d_rows reads.
 int svs_conv3d_s2c8(const float* in, const void* wfrag, const float* bias, const float* skip, float* out, void* split_out,

@@ -9,20 +9,36 @@
 // 16-byte channel vectors read from a four-slot z ring in LDS.  A workgroup (4 waves) owns a 4 (y) x 32 (x) output
 // window and marches along z: per step it converts one new input slice (6 x 34 voxels x Cin, float32 channel-first in
 // global memory) into channel-last fp16 hi / mid pieces in LDS while the MFMAs of the previous step run.
-#include "svs_common.h"
+#include "svs_conv_frag.h"
 
 namespace svs {
 namespace convmfma {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
+using frag::f16x8;
+using frag::f32x4v;
 
 constexpr int kTY = 4, kTX = 32;               // output window of a workgroup
 constexpr int kHY = kTY + 2, kHX = kTX + 2;    // with halo
 
+// one piece (hi or mid) of one z slice of the halo window in LDS; the ring holds four slices of two pieces
+template <int CIN> constexpr int piece_bytes() { return kHY * kHX * frag::pitch<CIN>(); }
+template <int CIN> constexpr int lds_bytes() { return 4 * 2 * piece_bytes<CIN>(); }
+
+// The A fragments (svs_conv3d_mfma_pack): fragment pair s = k-step s; lane l holds, for output channel l & 15 and j = 0..7,
+// the weight of k = 32 s + 8 (l >> 4) + j = tap * Cin + cin, cin fastest, tap = (kd*3 + kh)*3 + kw -- the order in which
+// conv3d_mfma_kernel's `boff` / `bkd` address the B operand.  Zero for tap > 26 (the padded end of K) and channels >= Cout.
+struct WeightMap {
+  int Cin, Cout;
+  __host__ __device__ int n_fragments() const { return (27 * Cin + 31) / 32; }
+  __device__ float source(const float* w, int s, int lane, int j) const {
+    const int k = 32 * s + 8 * (lane >> 4) + j, tap = k / Cin, ci = k % Cin, co = lane & 15;
+    return (tap < 27 && co < Cout) ? w[((size_t)ci * 27 + tap) * Cout + co] : 0.0f;
+  }
+};
+
 struct Args {
   const float* in;      // (Cin, D, H, W)
-  const uint4* wfrag;   // [KS][2 pieces][64 lanes] 16-byte A fragments (packed by the host)
+  const uint4* wfrag;   // [KS][2 pieces][64 lanes] 16-byte A fragments (WeightMap)
   const float* bias;    // [Cout] or nullptr
   const float* skip;    // (Cout, D, H, W) added after the ReLU, or nullptr
   float* out;           // (Cout, D, H, W)
@@ -33,8 +49,8 @@ struct Args {
 template <int CIN>
 __global__ __launch_bounds__(256, 1) void conv3d_mfma_kernel(Args a) {
   constexpr int KS = (27 * CIN + 31) / 32;                 // k-steps of 32
-  constexpr int PITCH = CIN == 8 ? 16 : (CIN == 16 ? 48 : 80);   // bytes per voxel and piece: odd multiple of 16
-  constexpr int PIECE = kHY * kHX * PITCH;                 // one piece of one slice
+  constexpr int PITCH = frag::pitch<CIN>();                // bytes per voxel and piece
+  constexpr int PIECE = piece_bytes<CIN>();                // one piece of one slice
   constexpr int SLICE = 2 * PIECE;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -84,7 +100,7 @@ __global__ __launch_bounds__(256, 1) void conv3d_mfma_kernel(Args a) {
     unsigned char* ph = smem + slot * SLICE + lcol + 16 * c8;
     f16x8 h, m;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
+    for (int j = 0; j < 8; ++j) {                  // frag::split spelled out: through the helper the schedule of CIN = 32 moves
       const float v = stage[8 * c8 + j];
       const _Float16 hh = (_Float16)v;
       h[j] = hh;
@@ -175,16 +191,9 @@ __global__ __launch_bounds__(256, 1) void conv3d_mfma_kernel(Args a) {
 }
 
 template <int CIN>
-constexpr int lds_bytes() {
-  return 4 * 2 * kHY * kHX * (CIN == 8 ? 16 : (CIN == 16 ? 48 : 80));
-}
-
-template <int CIN>
 int launch(const Args& a, hipStream_t s) {
   constexpr int lds = lds_bytes<CIN>();
-  static hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3d_mfma_kernel<CIN>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  if (e != hipSuccess) { set_error("svs_conv3d_mfma: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
+  if (const int rc = frag::opt_in_lds<conv3d_mfma_kernel<CIN>>(lds, "svs_conv3d_mfma")) return rc;
   dim3 grid((a.W + kTX - 1) / kTX, (a.H + kTY - 1) / kTY, (a.D + a.z_per_wg - 1) / a.z_per_wg);
   conv3d_mfma_kernel<CIN><<<grid, 256, lds, s>>>(a);
   return check_launch("svs_conv3d_mfma");
@@ -198,12 +207,18 @@ using namespace svs;
 extern "C" {
 
 // bytes of the packed A fragments of a layer: [ceil(27 Cin / 32)][2][64][16 B]
-size_t svs_conv3d_mfma_wfrag_bytes(int Cin) { return (size_t)((27 * Cin + 31) / 32) * 2 * 64 * 16; }
+size_t svs_conv3d_mfma_wfrag_bytes(int Cin) { return (size_t)convmfma::WeightMap{Cin, 1}.n_fragments() * 2 * 64 * 16; }
+
+// weight [Cin][27][Cout] float32 on the device (BatchNorm folded) -> wfrag (svs_conv3d_mfma_wfrag_bytes(Cin)), convmfma::WeightMap
+int svs_conv3d_mfma_pack(const float* weight, int Cin, int Cout, void* wfrag, void* hip_stream) {
+  if (!weight || !wfrag || Cout < 1 || Cout > 16 || (Cin != 8 && Cin != 16 && Cin != 32)) {
+    set_error("svs_conv3d_mfma_pack: bad argument (Cin in {8,16,32}, Cout <= 16)"); return SVS_EINVAL;
+  }
+  return frag::pack_fragments(weight, convmfma::WeightMap{Cin, Cout}, wfrag, (hipStream_t)hip_stream, "svs_conv3d_mfma_pack");
+}
 
 // out (Cout,D,H,W) = [relu](conv3d(in (Cin,D,H,W), 3x3x3, stride 1, padding 1) + bias) [+ skip]; Cin in {8,16,32},
-// Cout <= 16.  wfrag: the folded weights as fp16 hi / mid A fragments of v_mfma_f32_16x16x32_f16: fragment
-// [k-step s][piece][lane] holds, for output channel lane & 15 and j = 0..7, the weight of k = 32 s + 8 (lane >> 4) + j
-// = tap * Cin + cin (tap = (kd*3+kh)*3+kw; zero for tap > 26 and for channels >= Cout).
+// Cout <= 16.  wfrag: the folded weights as svs_conv3d_mfma_pack writes them.
 int svs_conv3d_mfma(const float* in, const void* wfrag, const float* bias, const float* skip, float* out, int Cin,
                     int Cout, int D, int H, int W, int relu, void* hip_stream) {
   if (!in || !wfrag || !out || Cout < 1 || Cout > 16 || D < 1 || H < 1 || W < 1 || (Cin != 8 && Cin != 16 && Cin != 32)) {

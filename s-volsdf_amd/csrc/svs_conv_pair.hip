@@ -26,16 +26,15 @@
 // layout of a slice: [row][piece][g][35] units -- the copy is contiguous on both sides, and the odd row-segment
 // length puts the two channel groups (or x taps) a ds_read_b128 lane group mixes on opposite 16-byte slot parities:
 // conflict-free (SQ_LDS_BANK_CONFLICT = 0).
-#include "svs_common.h"
+#include "svs_conv_frag.h"
 #include "svs_split_volume.h"
 #include <type_traits>
 
 namespace svs {
 namespace convpair {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
+using frag::f16x8;
+using frag::f32x4v;
 
 constexpr int kTY = 4, kTX = 32, kHY = kTY + 2;
 constexpr int kRS = 35;                            // units per row segment: x0-1 .. x0+33 (one more than needed: odd)
@@ -50,6 +49,22 @@ struct Args {
   float* out;           // (Cout, D, H, W) float32
   int Cout, D, H, W, relu;
   int z_per_wg;
+};
+
+// The A fragments of conv3d_pair_kernel (svs_conv3d_pair_pack): fragment pair s = k-step s; lane l holds row m = l & 15 =
+// (output channel m & 7, x position parity m >> 3) and, for j = 0..7, k = 32 s + 8 (l >> 4) + j =
+// (((kd*3 + kh)*4 + t)*G + g)*8 + c8 with G = Cin / 8: k multiplies input column 2n - 1 + t, channel 8 g + c8 (the kernel's
+// `frag` / `lane_off`), so the row of parity p carries the folded weight of tap (kd, kh, kw = t - p) there -- zero where kw
+// falls outside 0..2 or m & 7 >= Cout.
+struct PairMap {
+  int Cin, Cout;
+  __host__ __device__ int n_fragments() const { return 9 * (Cin / 8); }
+  __device__ float source(const float* w, int s, int lane, int j) const {
+    const int G = Cin / 8, k = 32 * s + 8 * (lane >> 4) + j, m = lane & 15;
+    const int c8 = k % 8, g = (k / 8) % G, t = (k / (8 * G)) % 4, row9 = k / (32 * G);
+    const int co = m & 7, kw = t - (m >> 3);
+    return (kw >= 0 && kw <= 2 && co < Cout) ? w[((size_t)(8 * g + c8) * 27 + row9 * 3 + kw) * Cout + co] : 0.0f;
+  }
 };
 
 // KSPLIT = 2: eight waves, waves w and w + 4 share output row w and each takes half of the k-steps (and keeps only
@@ -196,9 +211,7 @@ __global__ __launch_bounds__(256 * KSPLIT, 1) void conv3d_pair_kernel(Args a) {
 template <int CIN, int KSPLIT>
 int launch(const Args& a, hipStream_t s) {
   constexpr int lds = 4 * kHY * 2 * (CIN / 8) * kRS * 16 + (KSPLIT == 2 ? 2 * 4 * 64 * 16 : 0);
-  static hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3d_pair_kernel<CIN, KSPLIT>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  if (e != hipSuccess) { set_error("svs_conv3d_pair: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
+  if (const int rc = frag::opt_in_lds<conv3d_pair_kernel<CIN, KSPLIT>>(lds, "svs_conv3d_pair")) return rc;
   dim3 grid((a.W + kTX - 1) / kTX, (a.H + kTY - 1) / kTY, (a.D + a.z_per_wg - 1) / a.z_per_wg);
   conv3d_pair_kernel<CIN, KSPLIT><<<grid, 256 * KSPLIT, lds, s>>>(a);
   return check_launch("svs_conv3d_pair");
@@ -216,6 +229,18 @@ struct RowsArgs {
   float* out;           // (Cout, D, H, W) float32
   int Cout, D, H, W, relu;
   int z_per_wg;
+};
+
+// The A fragments of conv3d_rows_kernel (svs_conv3d_rows_pack): fragment pair s = k-step s; lane l holds row l & 15 = output
+// channel and, for c8 = 0..7, input channel 8 g + c8 of combination c = 4 s + (l >> 4) = tap * G + g, G = Cin / 8,
+// tap = (kd*3 + kh)*3 + kw -- the kernel's `boff` / `bkd`.  Zero for tap > 26 and channels >= Cout.
+struct RowsMap {
+  int Cin, Cout;
+  __host__ __device__ int n_fragments() const { return (27 * (Cin / 8) + 3) / 4; }
+  __device__ float source(const float* w, int s, int lane, int c8) const {
+    const int G = Cin / 8, c = 4 * s + (lane >> 4), tap = c / G, g = c % G, co = lane & 15;
+    return (tap < 27 && co < Cout) ? w[((size_t)(8 * g + c8) * 27 + tap) * Cout + co] : 0.0f;
+  }
 };
 
 template <int CIN>
@@ -360,10 +385,9 @@ __global__ __launch_bounds__(256) void split_pack_kernel(const float* __restrict
   f16x8 h, m;
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
-    const float v = in[(size_t)(8 * g + j) * DHW + (size_t)z * HW + (size_t)y * W + x];
-    const _Float16 hh = (_Float16)v;
-    h[j] = hh;
-    m[j] = (_Float16)(v - (float)hh);
+    _Float16 hh, mm;
+    frag::split(in[(size_t)(8 * g + j) * DHW + (size_t)z * HW + (size_t)y * W + x], hh, mm);
+    h[j] = hh; m[j] = mm;
   }
   const size_t u = splitvol::unit(z, y, 0, g, x, G, Hp, Wp);
   out[u] = __builtin_bit_cast(uint4, h);
@@ -397,13 +421,18 @@ int svs_split_volume_pack(const float* in, void* split, int C, int D, int H, int
 }
 
 // bytes of the packed A fragments of a layer: [9 Cin / 8][2][64][16 B]
-size_t svs_conv3d_pair_wfrag_bytes(int Cin) { return (size_t)(9 * Cin / 8) * 2 * 64 * 16; }
+size_t svs_conv3d_pair_wfrag_bytes(int Cin) { return (size_t)convpair::PairMap{Cin, 1}.n_fragments() * 2 * 64 * 16; }
+
+// weight [Cin][27][Cout] float32 on the device (BatchNorm folded) -> wfrag (svs_conv3d_pair_wfrag_bytes(Cin)), convpair::PairMap
+int svs_conv3d_pair_pack(const float* weight, int Cin, int Cout, void* wfrag, void* hip_stream) {
+  if (!weight || !wfrag || Cout < 1 || Cout > 8 || (Cin != 8 && Cin != 16 && Cin != 32)) {
+    set_error("svs_conv3d_pair_pack: bad argument (Cin in {8,16,32}, Cout <= 8)"); return SVS_EINVAL;
+  }
+  return frag::pack_fragments(weight, convpair::PairMap{Cin, Cout}, wfrag, (hipStream_t)hip_stream, "svs_conv3d_pair_pack");
+}
 
 // out (Cout,D,H,W) = [relu](conv3d(split volume of (Cin,D,H,W), 3x3x3, stride 1, padding 1) + bias); Cin in {8,16,32},
-// Cout <= 8.  wfrag: fp16 hi / mid A fragments, fragment [k-step s][piece][lane] = for row m = lane & 15 (output
-// channel m & 7 at x position parity m >> 3) and j = 0..7 the weight of k = 32 s + 8 (lane >> 4) + j, where
-// k = (((kd*3 + kh)*4 + t)*G + g)*8 + c8 (G = Cin/8) multiplies input column 2n-1+t, channel 8g + c8: the folded
-// weight of tap (kd, kh, kw = t - (m >> 3)), zero if kw is outside 0..2 or m & 7 >= Cout.
+// Cout <= 8.  wfrag: as svs_conv3d_pair_pack writes it.
 int svs_conv3d_pair(const void* split, const void* wfrag, const float* bias, float* out, int Cin, int Cout, int D, int H,
                     int W, int relu, void* hip_stream) {
   if (!split || !wfrag || !out || Cout < 1 || Cout > 8 || D < 1 || H < 1 || W < 1 || (Cin != 8 && Cin != 16 && Cin != 32)) {
@@ -430,12 +459,18 @@ int svs_conv3d_pair(const void* split, const void* wfrag, const float* bias, flo
 }
 
 // bytes of the packed A fragments of svs_conv3d_rows: [ceil(27 Cin / 32)][2][64][16 B]
-size_t svs_conv3d_rows_wfrag_bytes(int Cin) { return (size_t)((27 * (Cin / 8) + 3) / 4) * 2 * 64 * 16; }
+size_t svs_conv3d_rows_wfrag_bytes(int Cin) { return (size_t)convpair::RowsMap{Cin, 1}.n_fragments() * 2 * 64 * 16; }
+
+// weight [16][27][Cout] float32 on the device (BatchNorm folded) -> wfrag (svs_conv3d_rows_wfrag_bytes(Cin)), convpair::RowsMap
+int svs_conv3d_rows_pack(const float* weight, int Cin, int Cout, void* wfrag, void* hip_stream) {
+  if (!weight || !wfrag || Cout < 1 || Cout > 16 || Cin != 16) {
+    set_error("svs_conv3d_rows_pack: bad argument (Cin = 16, Cout <= 16)"); return SVS_EINVAL;
+  }
+  return frag::pack_fragments(weight, convpair::RowsMap{Cin, Cout}, wfrag, (hipStream_t)hip_stream, "svs_conv3d_rows_pack");
+}
 
 // out (Cout,D,H,W) = [relu](conv3d(split volume of (Cin,D,H,W), 3x3x3, stride 1, padding 1) + bias); Cin = 16, Cout <= 16
-// (conv2 of CostRegNet).  wfrag: fragment [k-step s][piece][lane]: row lane & 15 = output channel, k = 32 s + 8 (lane >> 4)
-// + c8 with combination 4 s + (lane >> 4) = tap * (Cin/8) + g (tap = (kd*3+kh)*3+kw): the folded weight of that tap and
-// input channel 8 g + c8; zero for tap > 26 and channels >= Cout.
+// (conv2 of CostRegNet).  wfrag: as svs_conv3d_rows_pack writes it.
 int svs_conv3d_rows(const void* split, const void* wfrag, const float* bias, float* out, int Cin, int Cout, int D, int H,
                     int W, int relu, void* hip_stream) {
   if (!split || !wfrag || !out || Cout < 1 || Cout > 16 || D < 1 || H < 1 || W < 1 || Cin != 16) {
@@ -455,9 +490,7 @@ int svs_conv3d_rows(const void* split, const void* wfrag, const float* bias, flo
   }
   a.z_per_wg = (D + best - 1) / best;
   constexpr int lds = 4 * convpair::kHY * 2 * 2 * convpair::kRS * 16;
-  static hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(convpair::conv3d_rows_kernel<16>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  if (e != hipSuccess) { set_error("svs_conv3d_rows: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
+  if (const int rc = frag::opt_in_lds<convpair::conv3d_rows_kernel<16>>(lds, "svs_conv3d_rows")) return rc;
   dim3 grid((W + convpair::kTX - 1) / convpair::kTX, (H + convpair::kTY - 1) / convpair::kTY, (D + a.z_per_wg - 1) / a.z_per_wg);
   convpair::conv3d_rows_kernel<16><<<grid, 256, lds, (hipStream_t)hip_stream>>>(a);
   return check_launch("svs_conv3d_rows");

@@ -797,7 +797,6 @@ __global__ __launch_bounds__(256, 4) void conv3d_c1_flat_kernel(const float* __r
   }
 }
 
-template <bool VEC>
 __global__ __launch_bounds__(256, 4) void conv3d_c1_kernel(C1Args a) {
   constexpr int VX = kC1VX, VZ = kC1VZ;
   const int tx = threadIdx.x % kC1TX, ty = threadIdx.x / kC1TX;
@@ -838,16 +837,10 @@ __global__ __launch_bounds__(256, 4) void conv3d_c1_kernel(C1Args a) {
         const float l = row[xl], rr = row[xr];
         r[kh][0] = (ok && lok) ? l : 0.0f;
         r[kh][VX + 1] = (ok && rok) ? rr : 0.0f;
-        if (VEC) {
-          const f32x4 m = *reinterpret_cast<const f32x4*>(row + x0);
 #pragma unroll
-          for (int v = 0; v < VX; ++v) r[kh][1 + v] = ok ? m[v] : 0.0f;
-        } else {
-#pragma unroll
-          for (int v = 0; v < VX; ++v) {
-            const float t = row[x0 + v < W ? x0 + v : W - 1];
-            r[kh][1 + v] = (ok && x0 + v < W) ? t : 0.0f;
-          }
+        for (int v = 0; v < VX; ++v) {
+          const float t = row[x0 + v < W ? x0 + v : W - 1];
+          r[kh][1 + v] = (ok && x0 + v < W) ? t : 0.0f;
         }
       }
       auto taps = [&](int kd, float (&acc)[VX]) {
@@ -874,11 +867,8 @@ __global__ __launch_bounds__(256, 4) void conv3d_c1_kernel(C1Args a) {
         if (a.skip && x0 + v < W) t += a.skip[o + v];
         res[v] = t;
       }
-      if (VEC) *reinterpret_cast<f32x4*>(a.out + o) = f32x4{res[0], res[1], res[2], res[3]};
-      else {
 #pragma unroll
-        for (int v = 0; v < VX; ++v) if (x0 + v < W) a.out[o + v] = res[v];
-      }
+      for (int v = 0; v < VX; ++v) if (x0 + v < W) a.out[o + v] = res[v];
     }
 #pragma unroll
     for (int v = 0; v < VX; ++v) { a0[v] = a1[v]; a1[v] = a2[v]; a2[v] = 0.0f; }
@@ -1240,7 +1230,7 @@ int svs_conv3d_c1(const float* in, const float* weight, const float* bias, const
     conv3d_c1_flat_kernel<<<grid, 256, 0, s>>>(in, weight, bias, skip, out, Cin, D, H, W, relu);
   } else {
     dim3 grid((W + kC1VX * kC1TX - 1) / (kC1VX * kC1TX), (H + kC1TY - 1) / kC1TY, (D + kC1VZ - 1) / kC1VZ);
-    conv3d_c1_kernel<false><<<grid, 256, 0, s>>>(a);
+    conv3d_c1_kernel<<<grid, 256, 0, s>>>(a);
   }
   return check_launch("svs_conv3d_c1");
 }

@@ -26,15 +26,16 @@
 // Head: per pixel one wave forms both channel norms, the weighted squared difference of the unit vectors and adds it to the
 // wave's float64 sum; workgroups write partial sums, one finishing launch adds them in a fixed order.  No atomics anywhere:
 // a run is bit-identical to the next.
-#include "svs_common.h"
+#include "svs_conv_frag.h"
 #include <mutex>
 
 namespace svs {
 namespace lpips {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
+using frag::f16x8;
+using frag::f16x4;
+using frag::f32x4v;
+using frag::split;
 
 constexpr int kTY = 8, kTX = 16;                         // output window of a workgroup
 constexpr int kHY = kTY + 2, kHX = kTX + 2, kHP = kHY * kHX;
@@ -71,11 +72,6 @@ struct ConvArgs {
   size_t in_stride, out_stride;   // bytes between the images of a launch (blockIdx.z)
   int* status;           // raised when an operand does not fit fp16
 };
-
-__device__ __forceinline__ void split(float v, _Float16& h, _Float16& m) {
-  h = (_Float16)v;
-  m = (_Float16)(v - (float)h);
-}
 
 template <int CS, bool IN_F32, bool OUT_F32>
 __global__ __launch_bounds__(256) void conv3x3_kernel(ConvArgs a) {
@@ -426,9 +422,7 @@ __global__ void finish_kernel(const double* __restrict__ partial, FinishArgs f, 
 template <int CS, bool IN_F32, bool OUT_F32>
 int launch_conv(const ConvArgs& a, int images, hipStream_t s) {
   constexpr int lds = lds_bytes<CS>();
-  static hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_kernel<CS, IN_F32, OUT_F32>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  if (e != hipSuccess) { set_error("svs_conv3x3_mfma: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
+  if (const int rc = frag::opt_in_lds<conv3x3_kernel<CS, IN_F32, OUT_F32>>(lds, "svs_conv3x3_mfma")) return rc;
   const dim3 grid((unsigned)(a.tiles_x * ((a.H + kTY - 1) / kTY)), (unsigned)(a.Cout / kMB), (unsigned)images);
   conv3x3_kernel<CS, IN_F32, OUT_F32><<<grid, 256, lds, s>>>(a);
   return check_launch("svs_conv3x3_mfma");

@@ -19,16 +19,17 @@
 // OPERAND RANGE (the split is not scaled): |value| < 65504 for activations and folded weights, or the hi piece is inf (and inf
 // times the zero weights of the padded k-step is NaN); a mid piece below 2^-14 (|value| < 0.125) is an fp16 subnormal, good to
 // 3e-8 absolute: weights of 1e-2 carry 3e-6 relative instead of 2e-7.  Within [0.125, 65504) both operands have 22 bits.
-#include "svs_common.h"
+#include "svs_conv_frag.h"
 #include "svs_conv2d_api.h"
 #include <cstdint>
 
 namespace svs {
 namespace ucsnet {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-typedef float f32x2v __attribute__((ext_vector_type(2)));
+using frag::f16x8;
+using frag::f32x4v;
+using frag::f32x2v;
+using frag::pitch;
 
 constexpr int kWaves = 4, kRW = 2, kTX = 32, kTY = kWaves * kRW;      // a window: 8 x 32 input positions
 constexpr int kHY = kTY + 1, kHX = kTX + 1;                           // + the row below and the column to the right
@@ -44,12 +45,34 @@ struct DeconvArgs {
   int tiles_x, tiles;
 };
 
-constexpr int class_taps(int c) { return (1 + (c >> 1)) * (1 + (c & 1)); }
+__host__ __device__ constexpr int class_taps(int c) { return (1 + (c >> 1)) * (1 + (c & 1)); }
 template <int CIN> constexpr int class_ks(int c) { return (class_taps(c) * CIN + 31) / 32; }
 template <int CIN> constexpr int class_s0(int c) { int o = 0; for (int i = 0; i < c; ++i) o += class_ks<CIN>(i); return o; }
 template <int CIN> constexpr int total_ks() { return class_s0<CIN>(4); }
-template <int CIN> constexpr int pitch() { return CIN == 16 ? 48 : 80; }
 template <int CIN> constexpr int lds_bytes() { return 2 * kHY * kHX * pitch<CIN>(); }
+
+// the weight tap (ky or kx) that output parity p takes from the input at offset d (d <= p)
+__host__ __device__ constexpr int tap_of(int p, int d) { return p ? (d ? 0 : 2) : 1; }
+
+// The A fragments of deconv2d_mfma_kernel (svs_deconv2d_mfma_pack) from (Cin, Cout, 3, 3) float32: fragment pairs [class c =
+// 2 py + px][k-step s of the class]; lane l holds output channel l & 15 and, for j = 0..7, k = 32 s + 8 (l >> 4) + j =
+// t * Cin + ci with t = tdy * (1 + px) + tdx the input offset (the kernel's `boff`): W[ci][co][tap_of(py, tdy)][tap_of(px, tdx)].
+// Zero beyond the class's taps and beyond Cout.
+struct DeconvMap {
+  int Cin, Cout;
+  __host__ __device__ int class_ks(int c) const { return (class_taps(c) * Cin + 31) / 32; }
+  __host__ __device__ int n_fragments() const { return class_ks(0) + class_ks(1) + class_ks(2) + class_ks(3); }
+  __device__ float source(const float* w, int si, int lane, int j) const {
+    int c = 0, s = si;
+    while (s >= class_ks(c)) s -= class_ks(c++);
+    const int py = c >> 1, px = c & 1;
+    const int co = lane & 15, k = 32 * s + 8 * (lane >> 4) + j;
+    const int t = k / Cin, ci = k - t * Cin;
+    if (t >= class_taps(c) || co >= Cout) return 0.0f;
+    const int tdy = t / (1 + px), tdx = t - tdy * (1 + px);
+    return w[(((size_t)ci * Cout + co) * 3 + tap_of(py, tdy)) * 3 + tap_of(px, tdx)];
+  }
+};
 
 template <int CIN>
 __global__ __launch_bounds__(256, 2) void deconv2d_mfma_kernel(DeconvArgs a) {
@@ -98,13 +121,7 @@ __global__ __launch_bounds__(256, 2) void deconv2d_mfma_kernel(DeconvArgs a) {
 #pragma unroll
       for (int c8 = 0; c8 < CIN / 8; ++c8) {
         f16x8 h, m;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const float f = v[8 * c8 + j];
-          const _Float16 hh = (_Float16)f;
-          h[j] = hh;
-          m[j] = (_Float16)(f - (float)hh);
-        }
+        frag::split(v + 8 * c8, h, m);
         *reinterpret_cast<f16x8*>(ph + 16 * c8) = h;
         *reinterpret_cast<f16x8*>(ph + PIECE + 16 * c8) = m;
       }
@@ -158,34 +175,6 @@ __global__ __launch_bounds__(256, 2) void deconv2d_mfma_kernel(DeconvArgs a) {
     }
     __syncthreads();                  // everyone is done reading the window before the next one is converted
   }
-}
-
-// the weight tap (ky or kx) that output parity p takes from the input at offset d (d <= p)
-__host__ __device__ constexpr int tap_of(int p, int d) { return p ? (d ? 0 : 2) : 1; }
-
-// (Cin, Cout, 3, 3) float32 -> A fragments: element j of fragment [class][s][piece][lane] is the hi / mid part of
-// W[ci][lane & 15][ky][kx] with k = 32 s + 8 (lane >> 4) + j = t * Cin + ci; zero beyond the class's taps and beyond Cout
-__global__ void deconv_pack_kernel(const float* __restrict__ w, int Cin, int Cout, _Float16* __restrict__ frag) {
-  int ks[4], s0[5];
-  s0[0] = 0;
-  for (int c = 0; c < 4; ++c) { ks[c] = (class_taps(c) * Cin + 31) / 32; s0[c + 1] = s0[c] + ks[c]; }
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= s0[4] * 64 * 8) return;
-  const int j = e & 7, lane = (e >> 3) & 63, si = e >> 9;
-  int c = 0;
-  while (si >= s0[c + 1]) ++c;
-  const int s = si - s0[c], py = c >> 1, px = c & 1;
-  const int co = lane & 15, k = 32 * s + 8 * (lane >> 4) + j;
-  const int t = k / Cin, ci = k - t * Cin;
-  float v = 0.0f;
-  if (t < class_taps(c) && co < Cout) {
-    const int tdy = t / (1 + px), tdx = t - tdy * (1 + px);
-    v = w[(((size_t)ci * Cout + co) * 3 + tap_of(py, tdy)) * 3 + tap_of(px, tdx)];
-  }
-  const _Float16 h = (_Float16)v;
-  const size_t base = (((size_t)si * 2) * 64 + lane) * 8 + j;
-  frag[base] = h;
-  frag[base + 64 * 8] = (_Float16)(v - (float)h);
 }
 
 // ---- the float32 vector path: one thread = one input position = a 2 x 2 output quad x 8 output channels; the weights of a
@@ -248,9 +237,7 @@ bool deconv_args(DeconvArgs& a, const char* what, const float* in, const float* 
 template <int CIN>
 int launch_mfma(const DeconvArgs& a, hipStream_t s) {
   constexpr int lds = lds_bytes<CIN>();
-  static hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(deconv2d_mfma_kernel<CIN>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  if (e != hipSuccess) { set_error("svs_deconv2d_mfma: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
+  if (const int rc = frag::opt_in_lds<deconv2d_mfma_kernel<CIN>>(lds, "svs_deconv2d_mfma")) return rc;
   const int grid = a.tiles < 512 ? a.tiles : 512;
   deconv2d_mfma_kernel<CIN><<<grid, 256, lds, s>>>(a);
   return check_launch("svs_deconv2d_mfma");
@@ -345,16 +332,12 @@ int svs_deconv2d_mfma_supported(int Cin, int Cout) { return deconv_supported(Cin
 // bytes of the packed A fragments: [sum over the four classes of ceil(taps Cin / 32)][2][64][16 B]
 size_t svs_deconv2d_mfma_wfrag_bytes(int Cin, int Cout) {
   if (!deconv_supported(Cin, Cout)) return 0;
-  size_t ks = 0;
-  for (int c = 0; c < 4; ++c) ks += (class_taps(c) * Cin + 31) / 32;
-  return ks * 2 * 64 * 16;
+  return (size_t)DeconvMap{Cin, Cout}.n_fragments() * 2 * 64 * 16;
 }
 
 int svs_deconv2d_mfma_pack(const float* weight, int Cin, int Cout, void* wfrag, void* hip_stream) {
   if (!weight || !wfrag || !deconv_supported(Cin, Cout)) { set_error("svs_deconv2d_mfma_pack: bad argument"); return SVS_EINVAL; }
-  const int n = (int)(svs_deconv2d_mfma_wfrag_bytes(Cin, Cout) / 2 / 2);       // fp16 elements of one piece
-  deconv_pack_kernel<<<(n + 255) / 256, 256, 0, (hipStream_t)hip_stream>>>(weight, Cin, Cout, static_cast<_Float16*>(wfrag));
-  return check_launch("svs_deconv2d_mfma_pack");
+  return frag::pack_fragments(weight, DeconvMap{Cin, Cout}, wfrag, (hipStream_t)hip_stream, "svs_deconv2d_mfma_pack");
 }
 
 int svs_deconv2d_mfma(const float* in, const void* wfrag, const float* bias, float* out, long long out_channel_stride, int Cin,

@@ -1,6 +1,5 @@
 """torch-tensor wrappers for the CasMVSNet cost-volume kernels (csrc/svs_costvol.hip)."""
 import ctypes
-import functools
 import os
 import weakref
 
@@ -218,59 +217,53 @@ def homo_warp(src_fea, src_rel, depth_values):
     return out
 
 
-def _cached_fragments(tag):
-    """a fragment builder f(weight), cached per weight tensor in _WFRAG_CACHE"""
-    def wrap(build):
-        @functools.wraps(build)
-        def cached(weight):
-            return _WFRAG_CACHE.get(weight, lambda: build(weight), tag=tag)
-        return cached
-    return wrap
+def _packed_fragments(weight, cache, tag, nbytes, pack, what):
+    """The MFMA A fragments of a weight tensor, packed on the device by the library and cached per tensor (address + version)
+    under `tag`: nbytes(L) -> the buffer's size, pack(L, w, frag, stream) -> the library's return code, `what` names the call.
+    The float32 copy the packer reads asynchronously is kept with the buffer."""
+    def make():
+        L = _lib.load()
+        w = _f32(weight.detach())
+        frag = torch.empty(nbytes(L), dtype=torch.uint8, device=weight.device)
+        _lib.check(pack(L, _ptr(w), _ptr(frag), _stream()), what)
+        return frag, w
+    return cache.get(weight, make, tag=tag)[0]
 
 
-def _hi_mid(w, ok):
-    """float32 fragment values (zero where not ok) -> (KS, 2, 64, 8) fp16: the hi piece and what it leaves, stacked per k-step"""
-    w = torch.where(ok, w, torch.zeros_like(w)).float()
-    hi = w.half()
-    return torch.stack([hi, (w - hi.float()).half()], 1).contiguous()
-
-
-@_cached_fragments("mfma")
 def mfma_weight_fragments(weight):
-    """[Cin][27][Cout] folded float32 weights -> the fp16 hi / mid A fragments of svs_conv3d_mfma
-    ([k-step][piece][lane][8] fp16, see include/svolsdf_hip.h).  One-time repacking per layer (cached)."""
+    """[Cin][27][Cout] folded float32 weights -> the A fragments of svs_conv3d_mfma"""
     Cin, _, Cout = weight.shape
-    dev = weight.device
-    KS = (27 * Cin + 31) // 32
-    s = torch.arange(KS, device=dev).view(KS, 1, 1)
-    lane = torch.arange(64, device=dev).view(1, 64, 1)
-    j = torch.arange(8, device=dev).view(1, 1, 8)
-    kk = 32 * s + 8 * (lane >> 4) + j
-    tap, ci, co = kk // Cin, kk % Cin, (lane & 15).expand(KS, 64, 8)
-    ok = (tap < 27) & (co < Cout)
-    w = weight[ci.clamp(max=Cin - 1), tap.clamp(max=26), co.clamp(max=Cout - 1)]
-    return _hi_mid(w, ok)
+    return _packed_fragments(weight, _WFRAG_CACHE, "mfma", lambda L: L.svs_conv3d_mfma_wfrag_bytes(Cin),
+                             lambda L, w, f, s: L.svs_conv3d_mfma_pack(w, Cin, Cout, f, s), "svs_conv3d_mfma_pack")
 
 
-@_cached_fragments("pair")
 def pair_weight_fragments(weight):
-    """[Cin][27][Cout <= 8] folded float32 weights -> the fp16 hi / mid A fragments of svs_conv3d_pair
-    ([k-step][piece][lane][8] fp16, include/svolsdf_hip.h): row m = (channel m & 7, x parity m >> 3),
-    k = (((kd*3+kh)*4 + t)*G + g)*8 + c8 carries the weight of tap (kd, kh, kw = t - parity)."""
+    """[Cin][27][Cout <= 8] folded float32 weights -> the A fragments of svs_conv3d_pair"""
     Cin, _, Cout = weight.shape
-    dev = weight.device
-    G = Cin // 8
-    KS = 9 * G
-    s = torch.arange(KS, device=dev).view(KS, 1, 1)
-    lane = torch.arange(64, device=dev).view(1, 64, 1)
-    j = torch.arange(8, device=dev).view(1, 1, 8)
-    kk = 32 * s + 8 * (lane >> 4) + j
-    c8, g, t, row9 = kk % 8, (kk // 8) % G, (kk // (8 * G)) % 4, kk // (32 * G)
-    m = (lane & 15).expand(KS, 64, 8)
-    co, kw = m & 7, t - (m >> 3)
-    ok = (kw >= 0) & (kw <= 2) & (co < Cout)
-    w = weight[8 * g + c8, (row9 * 3 + kw.clamp(0, 2)), co.clamp(max=Cout - 1)]
-    return _hi_mid(w, ok)
+    return _packed_fragments(weight, _WFRAG_CACHE, "pair", lambda L: L.svs_conv3d_pair_wfrag_bytes(Cin),
+                             lambda L, w, f, s: L.svs_conv3d_pair_pack(w, Cin, Cout, f, s), "svs_conv3d_pair_pack")
+
+
+def rows_weight_fragments(weight):
+    """[16][27][Cout <= 16] folded float32 weights -> the A fragments of svs_conv3d_rows"""
+    Cin, _, Cout = weight.shape
+    return _packed_fragments(weight, _WFRAG_CACHE, "rows", lambda L: L.svs_conv3d_rows_wfrag_bytes(Cin),
+                             lambda L, w, f, s: L.svs_conv3d_rows_pack(w, Cin, Cout, f, s), "svs_conv3d_rows_pack")
+
+
+def s2c8_weight_fragments(weight):
+    """[8][27][Cout <= 16] folded float32 weights -> the A fragments of svs_conv3d_s2c8"""
+    Cout = weight.shape[2]
+    return _packed_fragments(weight, _WFRAG_CACHE, "s2c8", lambda L: L.svs_conv3d_s2c8_wfrag_bytes(),
+                             lambda L, w, f, s: L.svs_conv3d_s2c8_pack(w, Cout, f, s), "svs_conv3d_s2c8_pack")
+
+
+def gemm_weight_fragments(weight, transposed):
+    """[Cin][27][Cout] folded float32 weights -> the A fragments of svs_conv3d_gemm"""
+    Cin, _, Cout = weight.shape
+    t = int(bool(transposed))
+    return _packed_fragments(weight, _WFRAG_CACHE, ("gemm", bool(transposed)), lambda L: L.svs_conv3d_gemm_wfrag_bytes(Cin, Cout, t),
+                             lambda L, w, f, s: L.svs_conv3d_gemm_pack(w, Cin, Cout, t, f, s), "svs_conv3d_gemm_pack")
 
 
 def conv2d_pack(weight):
@@ -314,16 +307,10 @@ def conv2d_mfma_supported(Cin, Cout, k, stride):
 
 
 def conv2d_mfma_frag(weight):
-    """(Cout,Cin,k,k) float32 -> the fp16 hi / mid MFMA A fragments svs_conv2d_mfma reads (packed on the device by
-    svs_conv2d_mfma_pack; cached per weight tensor: address + version)."""
-    def make():
-        L = _lib.load()
-        Cout, Cin, k, _ = weight.shape
-        w = _f32(weight.detach())
-        frag = torch.empty(L.svs_conv2d_mfma_wfrag_bytes(Cin, Cout, k) // 2, dtype=torch.float16, device=weight.device)
-        _lib.check(L.svs_conv2d_mfma_pack(_ptr(w), Cin, Cout, k, _ptr(frag), _stream()), "svs_conv2d_mfma_pack")
-        return frag, w
-    return _W2D_MFMA_CACHE.get(weight, make)[0]
+    """(Cout,Cin,k,k) float32 -> the A fragments of svs_conv2d_mfma"""
+    Cout, Cin, k, _ = weight.shape
+    return _packed_fragments(weight, _W2D_MFMA_CACHE, None, lambda L: L.svs_conv2d_mfma_wfrag_bytes(Cin, Cout, k),
+                             lambda L, w, f, s: L.svs_conv2d_mfma_pack(w, Cin, Cout, k, f, s), "svs_conv2d_mfma_pack")
 
 
 def conv2d_mfma(x, weight, bias=None, stride=1, relu=False):
@@ -445,16 +432,10 @@ def deconv2d_mfma_supported(Cin, Cout):
 
 
 def deconv2d_mfma_frag(weight):
-    """(Cin,Cout,3,3) float32 -> the fp16 hi / mid MFMA A fragments of svs_deconv2d_mfma (packed on the device, cached per
-    weight tensor: address + version)."""
-    def make():
-        L = _lib.load()
-        Cin, Cout = weight.shape[:2]
-        w = _f32(weight.detach())
-        frag = torch.empty(L.svs_deconv2d_mfma_wfrag_bytes(Cin, Cout) // 2, dtype=torch.float16, device=weight.device)
-        _lib.check(L.svs_deconv2d_mfma_pack(_ptr(w), Cin, Cout, _ptr(frag), _stream()), "svs_deconv2d_mfma_pack")
-        return frag, w
-    return _DECONV_FRAG_CACHE.get(weight, make)[0]
+    """(Cin,Cout,3,3) float32 -> the A fragments of svs_deconv2d_mfma"""
+    Cin, Cout = weight.shape[:2]
+    return _packed_fragments(weight, _DECONV_FRAG_CACHE, None, lambda L: L.svs_deconv2d_mfma_wfrag_bytes(Cin, Cout),
+                             lambda L, w, f, s: L.svs_deconv2d_mfma_pack(w, Cin, Cout, f, s), "svs_deconv2d_mfma_pack")
 
 
 def deconv2d(x, weight, bias=None, relu=False, out=None, mfma=None):
@@ -698,55 +679,6 @@ def gemm_enabled(on=None):
     if on is not None:
         _GEMM_ON[0] = bool(on)
     return _GEMM_ON[0]
-
-
-@_cached_fragments("rows")
-def rows_weight_fragments(weight):
-    """[16][27][Cout <= 16] folded float32 weights -> the fp16 hi / mid A fragments of svs_conv3d_rows
-    ([k-step][piece][lane][8], include/svolsdf_hip.h): k-step s, lane group kg = combination 4 s + kg = tap * G + g."""
-    Cin, _, Cout = weight.shape
-    dev = weight.device
-    G = Cin // 8
-    KS = (27 * G + 3) // 4
-    s = torch.arange(KS, device=dev).view(KS, 1, 1)
-    lane = torch.arange(64, device=dev).view(1, 64, 1)
-    j = torch.arange(8, device=dev).view(1, 1, 8)
-    c = 4 * s + (lane >> 4)
-    tap, g = (c // G).expand(KS, 64, 8), (c % G).expand(KS, 64, 8)
-    co = (lane & 15).expand(KS, 64, 8)
-    ok = (tap < 27) & (co < Cout)
-    w = weight[8 * g + j, tap.clamp(max=26), co.clamp(max=Cout - 1)]
-    return _hi_mid(w, ok)
-
-
-@_cached_fragments("s2c8")
-def s2c8_weight_fragments(weight):
-    """[8][27][Cout <= 16] folded float32 weights -> the fp16 hi / mid A fragments of svs_conv3d_s2c8
-    ([9 k-steps][piece][lane][8], include/svolsdf_hip.h)."""
-    Cin, _, Cout = weight.shape
-    dev = weight.device
-    s = torch.arange(9, device=dev).view(9, 1, 1)
-    lane = torch.arange(64, device=dev).view(1, 64, 1)
-    j = torch.arange(8, device=dev).view(1, 1, 8).expand(9, 64, 8)
-    kx, q = s // 3, s % 3
-    row = (lane >> 4) + 4 * q
-    co = (lane & 15).expand(9, 64, 8)
-    ok = ((row < 9) & (co < Cout)).expand(9, 64, 8)
-    tap = (row.clamp(max=8) * 3 + kx).expand(9, 64, 8)
-    w = weight[j, tap, co.clamp(max=Cout - 1)]
-    return _hi_mid(w, ok)
-
-
-def gemm_weight_fragments(weight, transposed):
-    """[Cin][27][Cout] folded float32 weights -> the A fragments of svs_conv3d_gemm (packed on the device, cached)."""
-    def make():
-        L = _lib.load()
-        Cin, _, Cout = weight.shape
-        w = _f32(weight)
-        frag = torch.empty(L.svs_conv3d_gemm_wfrag_bytes(Cin, Cout, int(transposed)), dtype=torch.uint8, device=weight.device)
-        _lib.check(L.svs_conv3d_gemm_pack(_ptr(w), Cin, Cout, int(transposed), _ptr(frag), _stream()), "svs_conv3d_gemm_pack")
-        return frag
-    return _WFRAG_CACHE.get(weight, make, tag=("gemm", bool(transposed)))
 
 
 def rows_supported(Cin, Cout):

@@ -282,3 +282,33 @@ def test_composite_entry_points_validate_sample_counts():
     for name in ("svs_composite", "svs_composite_bg"):
         assert calls[name](97, 32, normals=None) == EINVAL
         assert L.svs_last_error_string() == b"%s: normal_map needs normals" % name.encode()
+
+
+def test_fragment_packers_validate_before_any_launch():
+    """The four packers of the cost-regularisation U-Net's A fragments accept what the kernel they pack for accepts: a null
+    pointer or another (Cin, Cout) is SVS_EINVAL with the entry point named, on a machine without a GPU; their buffers have
+    the sizes the queries report."""
+    from svs_hip import lib
+    L = lib.load()
+    EINVAL = -1
+    p = 4096                                                       # never dereferenced: the checks come first
+    packers = {
+        "svs_conv3d_mfma_pack": (lambda w, f, cin, cout: L.svs_conv3d_mfma_pack(w, cin, cout, f, None), (8, 16), [(12, 8), (8, 17), (8, 0), (64, 8)]),
+        "svs_conv3d_pair_pack": (lambda w, f, cin, cout: L.svs_conv3d_pair_pack(w, cin, cout, f, None), (32, 8), [(12, 8), (8, 9), (8, 0), (64, 8)]),
+        "svs_conv3d_rows_pack": (lambda w, f, cin, cout: L.svs_conv3d_rows_pack(w, cin, cout, f, None), (16, 16), [(8, 16), (32, 16), (16, 17), (16, 0)]),
+        "svs_conv3d_s2c8_pack": (lambda w, f, cin, cout: L.svs_conv3d_s2c8_pack(w, cout, f, None), (8, 16), [(8, 17), (8, 0)]),
+    }
+    for name, (call, good, unsupported) in packers.items():
+        for w, f in ((None, p), (p, None)):
+            assert call(w, f, *good) == EINVAL, name
+            assert L.svs_last_error_string().startswith(name.encode() + b": bad argument")
+        for cin, cout in unsupported:
+            assert call(p, p, cin, cout) == EINVAL, (name, cin, cout)
+            assert L.svs_last_error_string().startswith(name.encode() + b": bad argument")
+    # [fragment pairs][2 pieces][64 lanes][16 B]
+    assert [L.svs_conv3d_mfma_wfrag_bytes(c) for c in (8, 16, 32)] == [7 * 2048, 14 * 2048, 27 * 2048]
+    assert [L.svs_conv3d_pair_wfrag_bytes(c) for c in (8, 16, 32)] == [9 * 2048, 18 * 2048, 36 * 2048]
+    assert L.svs_conv3d_rows_wfrag_bytes(16) == 14 * 2048 and L.svs_conv3d_s2c8_wfrag_bytes() == 9 * 2048
+    assert L.svs_conv2d_mfma_wfrag_bytes(16, 20, 5) == 2 * 13 * 2048 and L.svs_deconv2d_mfma_wfrag_bytes(32, 16) == 9 * 2048
+    assert L.svs_conv3d_gemm_wfrag_bytes(64, 64, 0) == 54 * 4 * 2048 and L.svs_conv3d_gemm_wfrag_bytes(16, 8, 1) == 4 * 4 * 2048
+    assert L.svs_version() == 101

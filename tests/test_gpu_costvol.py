@@ -250,6 +250,47 @@ def test_conv3d_rows_from_split_volume(dev, cout, shape):
     assert torch.equal(a, costvol.SplitVolume.pack(f).buf)
 
 
+def test_device_packers_match_the_torch_layouts(dev, golden_dir):
+    """Every A-fragment buffer the library packs, bit for bit (raw int16, a condition and not a tolerance).  svs_conv3d_mfma /
+    _pair / _rows / _s2c8: against the torch index arithmetic that built them before (tests/wfrag_oracle.py), evaluated on the
+    CPU copy and on the device copy of the weight, over the whole supported (Cin, Cout) set; the weights carry zeros of both
+    signs, 1, values at both ends of fp16's range and one below it.  svs_conv2d_mfma / svs_deconv2d_mfma / svs_conv3d_gemm:
+    against tests/golden/convfrag_packed.npz, written by the kernels each of the three had of its own
+    (tests/golden/make_convfrag_fixture.py)."""
+    import wfrag_oracle as wo
+    from svs_hip import costvol
+    raw = lambda t: t.contiguous().view(torch.int16).reshape(-1).cpu()
+    layouts = {
+        "mfma": (costvol.mfma_weight_fragments, wo.mfma_weight_fragments, [(ci, co) for ci in (8, 16, 32) for co in (1, 5, 16)]),
+        "pair": (costvol.pair_weight_fragments, wo.pair_weight_fragments, [(ci, co) for ci in (8, 16, 32) for co in (1, 5, 8)]),
+        "rows": (costvol.rows_weight_fragments, wo.rows_weight_fragments, [(16, co) for co in (1, 11, 16)]),
+        "s2c8": (costvol.s2c8_weight_fragments, wo.s2c8_weight_fragments, [(8, co) for co in (1, 12, 16)]),
+    }
+    bad = []
+    for m, (name, (packed, oracle, shapes)) in enumerate(layouts.items()):
+        for n, (cin, cout) in enumerate(shapes):
+            w = wo.make_weight((cin, 27, cout), 100 * m + n)
+            assert all((w == v).any() for v in wo.SPECIALS) and torch.signbit(w[w == 0]).any()
+            wd = w.to(dev)
+            got, on_cpu, on_dev = raw(packed(wd)), raw(oracle(w)), raw(oracle(wd))
+            assert got.numel() == on_cpu.numel() == on_dev.numel() > 0
+            if not torch.equal(on_cpu, on_dev):
+                bad.append(f"{name} {cin}->{cout}: the oracle differs between CPU and device in {(on_cpu != on_dev).sum()} elements")
+            if not torch.equal(got, on_dev):
+                bad.append(f"{name} {cin}->{cout}: {(got != on_dev).sum()} of {got.numel()} elements differ from the device oracle")
+            if not torch.equal(got, on_cpu):
+                bad.append(f"{name} {cin}->{cout}: {(got != on_cpu).sum()} of {got.numel()} elements differ from the CPU oracle")
+    golden = load(golden_dir, "convfrag_packed")
+    assert set(golden) == set(wo.PACKED_CASES)
+    pack = {"conv2d": lambda w, _: costvol.conv2d_mfma_frag(w), "deconv2d": lambda w, _: costvol.deconv2d_mfma_frag(w),
+            "gemm": costvol.gemm_weight_fragments}
+    for key, (kind, _, arg) in wo.PACKED_CASES.items():
+        got, want = raw(pack[kind](wo.packed_case_weight(key).to(dev), arg)), torch.from_numpy(golden[key])
+        if got.shape != want.shape or not torch.equal(got, want):
+            bad.append(f"{key}: differs from the recorded buffer ({got.numel()} against {want.numel()} elements)")
+    assert not bad, "\n".join(bad)
+
+
 @pytest.mark.parametrize("cin,shape", [(8, (5, 7, 37)), (8, (11, 33, 40)), (16, (3, 5, 6)), (8, (24, 40, 64))])
 def test_conv3d_one_output_channel(dev, cin, shape):
     """The `prob` layer's kernel (Cout = 1, float32 FMAs on the vector ALUs) against a float64 torch convolution:
