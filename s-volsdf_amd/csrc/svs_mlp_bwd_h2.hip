@@ -48,10 +48,8 @@ struct RgbBwdEpi {
       split8(v8, out->h[2 * tp + (rr >> 3)], out->m[2 * tp + (rr >> 3)]);
       pin(out->h[2 * tp + (rr >> 3)], out->m[2 * tp + (rr >> 3)]);
     }
-    // stores behind the LDS-DMA pieces: k-step 9 (the piece split at element 7) and 15
-    if (rr == 9) store_piece(zblk, 2 * tp, lane, out->h[2 * tp], 0);
-    if (GP && rr == 11) store_piece(zblk, 2 * tp, lane, out->m[2 * tp], 1);
-    if (rr == 15) store_grad<GP>(zblk, 2 * tp + 1, lane, out->h[2 * tp + 1], out->m[2 * tp + 1]);
+    // the tile's kTileStores<GP> stores behind the LDS-DMA pieces: k-steps 9, 11 (the fragment split at element 7) and 15
+    store_tile_late<GP>(zblk, tp, lane, rr, &out->h[2 * tp], &out->m[2 * tp]);
   }
   __device__ __forceinline__ void all(int tp) {
 #pragma unroll
@@ -83,8 +81,8 @@ __device__ __forceinline__ void rgb_bwd_layer_h2(Stream& st, const Pieces2& in, 
     if (t == 0) acc = tile_mma_h2_pf<16, kChunkF4>(st, in, lane, NoEpi(), NoEpi(), rload);
     else acc = tile_mma_h2_pf<16, kChunkF4>(st, in, lane, NoEpi(), [&](int s) { ep.b(t - 1, s); }, rload);
     ep.prev = acc; ep.r = rcur;
-    // in flight across the barrier: the 2 r loads (t < 7) and the zbuf stores of tile t-1's epilogue (2, with GP 4)
-    constexpr int kSt = GP ? 4 : 2;
+    // in flight across the barrier: the 2 r loads (t < 7) and the zbuf stores of tile t-1's epilogue
+    constexpr int kSt = kTileStores<GP>;
     if (t == 0) st.advance_keep<2>();
     else if (t < 7) st.advance_keep<2 + kSt>();
     else st.advance_keep<kSt>();
@@ -92,6 +90,30 @@ __device__ __forceinline__ void rgb_bwd_layer_h2(Stream& st, const Pieces2& in, 
   ep.all(7);
   ps.next();
 }
+
+// fbar (the feature rows of W_0^T zbar_0) for one tile: its maximum, then value * s_f as the stored fragments of a scaled block
+template <bool GP>
+struct FeatBarEpi {
+  f32x16 prev;
+  float v8[8];
+  f16x8 fh[2], fm[2];  // the fragments being stored (fm: mid, GP)
+  float* fblk;
+  float inv_in, s_f;   // s_f: the scale predicted from zbar_0's maximum (see rgb_bwd_h2_kernel)
+  float fmax;
+  int lane;
+  __device__ __forceinline__ void b(int tp, int r) {
+    float v = prev[r] * inv_in;
+    pin(v);
+    fmax = __builtin_fmaxf(fmax, __builtin_fabsf(v));
+    v8[r & 7] = v * s_f;
+    if ((r & 7) == 7) {
+      if (GP) { split8(v8, fh[r >> 3], fm[r >> 3]); pin(fh[r >> 3], fm[r >> 3]); }
+      else { fh[r >> 3] = hi8(v8, 1.0f); pin(fh[r >> 3]); }
+    }
+    // the tile's kTileStores<GP> stores behind the LDS-DMA pieces (k-steps 9, 11, 15)
+    store_tile_late<GP>(fblk, tp, lane, r, fh, fm);
+  }
+};
 
 template <bool GP>
 __global__ __launch_bounds__(kThreads, 1) void rgb_bwd_h2_kernel(RgbBwdArgs a) {
@@ -110,12 +132,25 @@ __global__ __launch_bounds__(kThreads, 1) void rgb_bwd_h2_kernel(RgbBwdArgs a) {
   auto zrec = [&](int l) { return record_ptr(a.zbuf, 5, T, l, wtile); };
 
   st.prefetch<kW4TF4>();
+  // The hi pieces of all eight r_4 tiles (only their sign is needed, below), requested here: the forward launch wrote the
+  // block, so every request goes to HBM, and the sixteen of them share ONE round trip with the W4T chunk and the loads of
+  // rgb / d_rgb -- the first advance() below waits for them all.  (Requested tile by tile in the loop that consumes them, each
+  // was a round trip of its own with nothing else for the wave to do: eight in a row.)  The LDS-DMA statements above and the
+  // barrier below keep the compiler from moving the requests; the pin behind the barrier keeps them from being re-formed later.
+  TilePieces r4t[8];
+#pragma unroll
+  for (int t = 0; t < 8; ++t) load_tile_hi(rb + 3 * LS, t, lane, r4t[t]);
+  // (all six requested before the first is used: left to hipcc, each channel's pair was a round trip of its own)
+  float o3[3], g3[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) { o3[c] = a.rgb[3 * pc + c]; g3[c] = a.d_rgb[3 * pc + c]; }
+  __builtin_amdgcn_sched_barrier(0);
   float dz[3];
   float m0 = 0.0f;
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
-    const float o = a.rgb[3 * pc + c];
-    dz[c] = (livep && half == 0) ? a.d_rgb[3 * pc + c] * o * (1.0f - o) : 0.0f;   // through the sigmoid (network.py:189)
+    const float o = o3[c];
+    dz[c] = (livep && half == 0) ? g3[c] * o * (1.0f - o) : 0.0f;   // through the sigmoid (network.py:189)
     m0 = __builtin_fmaxf(m0, __builtin_fabsf(dz[c]));
   }
   m0 = __builtin_fmaxf(m0, __shfl_xor(m0, 32));
@@ -127,18 +162,18 @@ __global__ __launch_bounds__(kThreads, 1) void rgb_bwd_h2_kernel(RgbBwdArgs a) {
     store_record(zrec(4), lane, ps.s_in, m0);
   }
   st.advance();
+#pragma unroll
+  for (int t = 0; t < 8; ++t) pin(r4t[t].h[0], r4t[t].h[1]);
   Pieces2 pa, pb;
   // rbar_4 = W_4^T zbar_4 (K = 3: float32 MFMA from the short W4T chunk), masked by r_4 > 0 -> zbar_3
   st.prefetch<kChunkF4>();
   {
     const f32x4* c = st.cur_buf();
-    const float* r4 = rb + 3 * LS;
     float* z3 = zb + 3 * LS;
     store_record(zrec(3), lane, ps.s_out, 0.0f);
 #pragma unroll
     for (int t = 0; t < 8; ++t) {
-      TilePieces r;
-      load_tile_hi(r4, t, lane, r);
+      const TilePieces& r = r4t[t];
       const f32x4 w = c[t * 64 + lane];
       f32x16 acc = (f32x16)(0.0f);
       acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w[0], dz[0], acc, 0, 0, 0);
@@ -147,12 +182,13 @@ __global__ __launch_bounds__(kThreads, 1) void rgb_bwd_h2_kernel(RgbBwdArgs a) {
 #pragma unroll
       for (int i = 0; i < 16; ++i) { acc[i] = hi_at(r, i) > 0.0f ? acc[i] : 0.0f; ps.track(acc[i]); }
       split_tile_scaled(acc, t, pa, ps.s_out);
-      store_grad<GP>(z3, 2 * t, lane, pa.h[2 * t], pa.m[2 * t]);
-      store_grad<GP>(z3, 2 * t + 1, lane, pa.h[2 * t + 1], pa.m[2 * t + 1]);
+      store_tile_pieces<GP>(z3, t, lane, &pa.h[2 * t], &pa.m[2 * t]);
     }
   }
   ps.next();
-  st.advance();
+  // The zbar_3 stores of all eight tiles are younger than the chunk's LDS-DMA (issued in front of the loop) and stay in
+  // flight into layer 3: nothing here reads them back.  (The record store is not counted: waiting for it too is harmless.)
+  st.advance_keep<8 * kTileStores<GP>>();
   // layers 3..1
   rgb_bwd_layer_h2<GP>(st, pa, pb, rb + 2 * LS, zb + 2 * LS, zrec(2), ps, lane);
   rgb_bwd_layer_h2<GP>(st, pb, pa, rb + 1 * LS, zb + 1 * LS, zrec(1), ps, lane);
@@ -160,34 +196,30 @@ __global__ __launch_bounds__(kThreads, 1) void rgb_bwd_h2_kernel(RgbBwdArgs a) {
   // layer 0: the input gradients from zbar_0 (feature rows: tiles 0..7, extras: tile 8).  fbar is stored as a scaled block
   // under the scale predicted from zbar_0's maximum (ps.s_out, as between any two layers); its record -- pass B takes
   // the scale and the maximum from it -- is written once the maximum is known
-  float* fb = a.feat_bar + (size_t)wtile * kBlockF;
-  float fmax = 0.0f;
-  const float s_f = ps.s_out;
+  FeatBarEpi<GP> ep;
+  ep.fblk = a.feat_bar + (size_t)wtile * kBlockF; ep.inv_in = ps.inv_in; ep.s_f = ps.s_out; ep.fmax = 0.0f; ep.lane = lane;
   {
-    f32x16 prev;
-    float v8[8];
-    auto slice = [&](int tp, int r) {
-      const float v = prev[r] * ps.inv_in;
-      fmax = __builtin_fmaxf(fmax, __builtin_fabsf(v));
-      v8[r & 7] = v * s_f;
-      if ((r & 7) == 7) store_grad8<GP>(fb, 2 * tp + (r >> 3), lane, v8);
-    };
+    // Per tile, as in rgb_bwd_layer_h2: the next chunk's 9 LDS-DMA pieces behind k-steps 0..8, then the fbar stores of tile
+    // t-1's epilogue, which the barrier leaves in flight.  The extras tile (8) is the last chunk: it fetches nothing.
 #pragma unroll
     for (int t = 0; t < 9; ++t) {
-      if (t < 8) st.prefetch<kChunkF4>();
       f32x16 acc;
-      if (t == 0) acc = tile_mma_h2<16>(st.cur_buf(), pb, lane);
-      else acc = tile_mma_h2<16>(st.cur_buf(), pb, lane, NoEpi(), [&](int s) { slice(t - 1, s); });
-      if (t < 8) { prev = acc; st.advance(); }
-      else if (half == 1 && livep) {
+      if (t == 0) acc = tile_mma_h2_pf<16, kChunkF4>(st, pb, lane, NoEpi(), NoEpi());
+      else if (t < 8) acc = tile_mma_h2_pf<16, kChunkF4>(st, pb, lane, NoEpi(), [&](int s) { ep.b(t - 1, s); });
+      else acc = tile_mma_h2<16>(st.cur_buf(), pb, lane, NoEpi(), [&](int s) { ep.b(t - 1, s); });
+      if (t < 8) {
+        ep.prev = acc;
+        if (t == 0) st.advance();      // (older than the pieces: the zbar_0 stores of layer 1's last epilogue)
+        else st.advance_keep<kTileStores<GP>>();
+      } else if (half == 1 && livep) {
         // extra rows 12,13,14 (normals, network.py:175) = local rows rho(4..6)+4 of the extras tile
         a.d_normals[3 * p] = acc[4] * ps.inv_in; a.d_normals[3 * p + 1] = acc[5] * ps.inv_in;
         a.d_normals[3 * p + 2] = acc[6] * ps.inv_in;
       }
     }
   }
-  fmax = __builtin_fmaxf(fmax, __shfl_xor(fmax, 32));
-  store_record(record_ptr(a.feat_bar, 1, T, 0, wtile), lane, s_f, fmax);
+  const float fmax = __builtin_fmaxf(ep.fmax, __shfl_xor(ep.fmax, 32));
+  store_record(record_ptr(a.feat_bar, 1, T, 0, wtile), lane, ep.s_f, fmax);
   publish_max(a.absmax + 1, ps.gmax);
   publish_max(a.absmax + 2, fmax);
 }
@@ -304,7 +336,7 @@ __device__ __forceinline__ void pass_a_layer_h2(Stream& st, const Pieces2& in, P
     ep.prev = acc; ep.h = hload;
     if (fetch) {
       if (t == 0) st.advance();
-      else st.advance_keep<GP ? 4 : 2>();
+      else st.advance_keep<kTileStores<GP>>();
     }
   }
   if (ep.l3) { ep.all(6); ep.splice_tile7(); }
@@ -519,7 +551,7 @@ __device__ __forceinline__ void pass_b_stage_h2(Stream& st, const Pieces2& in, P
   if (kG) load_tile_grad<GP>(gblk, 0, lane, gnext);
   constexpr int kPer = GP ? 4 : 2;
   constexpr int kLoads = kPer * (1 + (A2 ? 1 : 0) + (kG ? 1 : 0));
-  constexpr int kStores = GP ? 4 : 2;
+  constexpr int kStores = kTileStores<GP>;
 #pragma unroll
   for (int t = 0; t < 8; ++t) {
     const TilePieces hcur = hnext, ucur = unext, gcur = gnext;

@@ -50,6 +50,43 @@ __device__ __forceinline__ void publish_max(float* slot, float v) {
   if ((threadIdx.x & 63) == 0) atomicMax(reinterpret_cast<unsigned*>(slot), __float_as_uint(v));
 }
 
+// ---- the stores of one tile of a scaled block, and how many of them a barrier may leave in flight
+// A tile is two fragments (k-steps 2 tp, 2 tp + 1) of the hi plane and, with GP, of the mid plane: kTileStores<GP> vector
+// stores, numbered i = 0 .. kTileStores - 1 in issue order (fragment 0: hi, mid; fragment 1: hi, mid).  The radiance sweep
+// (rgb_bwd_h2_kernel) issues a tile's stores through store_tile_piece() alone -- a loop of kTileStores trips -- and gives
+// the SAME constant to Stream::advance_keep<N>: what the epilogue issues and what the barrier leaves in flight cannot
+// drift apart (a too-large N would let the barrier pass before the chunk's LDS-DMA has landed -- silently).
+// The SDF sweeps (PassAEpi / PassBEpi::store_slot) take their N from the constant too, but keep their store lines written
+// out: routed through the loop, hipcc allocates the registers of their GP instances differently, and those launches are the
+// step's HBM phase, whose machine code this header has no business changing.
+template <bool GP>
+constexpr int kTileStores = GP ? 4 : 2;
+template <bool GP>
+__device__ __forceinline__ void store_tile_piece(float* blk, int tp, int lane, int i, const f16x8* h, const f16x8* m) {
+  const int f = GP ? i >> 1 : i;
+  if (GP && (i & 1)) store_piece(blk, 2 * tp + f, lane, m[f], 1);
+  else store_piece(blk, 2 * tp + f, lane, h[f], 0);
+}
+// all of them at once (an epilogue that is not spread over MFMA gaps)
+template <bool GP>
+__device__ __forceinline__ void store_tile_pieces(float* blk, int tp, int lane, const f16x8* h, const f16x8* m) {
+#pragma unroll
+  for (int i = 0; i < kTileStores<GP>; ++i) store_tile_piece<GP>(blk, tp, lane, i, h, m);
+}
+// Spread behind the LDS-DMA pieces of a 16-k-step tile (Stream::prefetch_step issues the 9 pieces in k-steps 0..8): store i
+// goes out in k-step late_store_step(i) >= 9, so every store is younger than every piece, as advance_keep<N> requires.
+// Fragment 0 is complete at k-step 7 (hi at 9, mid at 11: one store per MFMA gap), fragment 1 at k-step 15.
+template <bool GP>
+__device__ __forceinline__ constexpr int late_store_step(int i) {
+  return (GP ? i >> 1 : i) ? 15 : ((GP && (i & 1)) ? 11 : 9);
+}
+template <bool GP>
+__device__ __forceinline__ void store_tile_late(float* blk, int tp, int lane, int s, const f16x8* h, const f16x8* m) {
+#pragma unroll
+  for (int i = 0; i < kTileStores<GP>; ++i)
+    if (s == late_store_step<GP>(i)) store_tile_piece<GP>(blk, tp, lane, i, h, m);
+}
+
 __device__ __forceinline__ void split_tile_scaled(const f32x16& y, int t, Pieces2& p, float s) {
   f32x16 v;
 #pragma unroll

@@ -39,6 +39,7 @@ __device__ __forceinline__ void split8(const float* v, f16x8& h, f16x8& m) {
 // LLVM sinks pure arithmetic past the scheduling barriers of the k-loop; pinning a value makes it (and what it
 // depends on) stay in the slot it was written in.
 __device__ __forceinline__ void pin(float& v) { asm volatile("" : "+v"(v)); }
+__device__ __forceinline__ void pin(f16x8& a) { asm volatile("" : "+v"(a)); }
 __device__ __forceinline__ void pin(f16x8& a, f16x8& b) { asm volatile("" : "+v"(a), "+v"(b)); }
 
 // accumulator tile t (16 registers) -> k-steps 2t, 2t+1 of p
