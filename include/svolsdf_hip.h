@@ -1038,6 +1038,61 @@ int svs_mesh_vertex_visibility(const float* verts, int n_verts, const double* ma
                                const float* depth, const uint8_t* const SVS_HOST* masks, double rel, double abs_tol, int* seen,
                                int* off_mask, void* hip_stream);
 
+/* ---- a mesh painted from a scan's photographs (svs_hip.meshpaint; csrc/svs_meshpaint.hip) --------------------------------
+ * Vertex colours for a mesh that has none: every view projects into it, the depth maps of svs_mesh_raster_resolve decide
+ * occlusion, views are weighted by viewing angle, vertices no view sees are filled from their neighbours over the mesh's
+ * edges.  The reference has no such step; the arithmetic below is this project's (tests/meshpaint_oracle.py restates it in
+ * numpy float64).  Cameras, projection, pixel convention, near and the 16 views per call are those of
+ * svs_mesh_vertex_visibility; all arithmetic is float64 without contraction.
+ *
+ * svs_mesh_vertex_normals: accum DEVICE double[n_verts][3], which the CALLER zeroes first: calls (chunks of faces) compose.
+ *   Per face with indices inside [0, n_verts) and finite corners, the unnormalised cross(P1-P0, P2-P0) in float64 (area
+ *   weighting) is added to accum of each of its three vertices with float64 atomic adds (the last bits of the sum depend
+ *   on their order).  Then, unless normals (DEVICE float[n_verts][3]) is NULL, normals = float32(accum / |accum|),
+ *   |accum| = sqrt(x x + y y + z z); (0,0,0) where the sum is zero or not finite.  accum is left for the caller.
+ * svs_mesh_paint: acc DEVICE double[n_verts][4] = (r, g, b, w), ACCUMULATED (the caller zeroes it; more than 16 views:
+ *   several calls).  normals DEVICE float[n_verts][3] or NULL; depth DEVICE float (n_views,H,W) as svs_mesh_raster_resolve
+ *   writes it; images: HOST array of n_views DEVICE uint8 (H,W,3) pointers, all required; masks: as in visibility.
+ *   cos_min in [0,1], power in [0,8], flags: SVS_PAINT_BEST | SVS_PAINT_ONE_SIDED.  Per vertex p, the views in index
+ *   order (one thread walks them: no atomics, one fixed order of the sum, the same bits in every run):
+ *   1. projected as visibility does; skipped if z <= near or z, x or y is not finite;
+ *   2. skipped unless 0 <= x <= W-1 and 0 <= y <= H-1: the bilinear footprint lies inside the image;
+ *   3. (iu, iv) = (floor(x+0.5), floor(y+0.5)); skipped if the mask is 0 there;
+ *   4. d = depth[iv,iu]; skipped unless d == 0 or z <= d * (1 + rel) + abs_tol: the visibility rule;
+ *   5. with normals: eye_k = -(E[0][k] E[0][3] + E[1][k] E[1][3] + E[2][k] E[2][3]) once per view, t = eye - p,
+ *      c = (n.x t.x + n.y t.y + n.z t.z) / sqrt(t.x t.x + t.y t.y + t.z t.z), c = |c| unless SVS_PAINT_ONE_SIDED; a vertex
+ *      whose normal is zero or not finite is skipped in every view, a view with c < cos_min (or NaN) is skipped;
+ *      w = 1 * c * c ... (power factors, multiplied left to right; no pow; power 0: w = 1).  Without normals w = 1;
+ *   6. x0 = floor(x), x1 = min(x0+1, W-1), fx = x - x0, likewise y; per channel on the uint8 codes as float64
+ *      colour = ((1-fx) I[y0,x0] + fx I[y0,x1]) (1-fy) + ((1-fx) I[y1,x0] + fx I[y1,x1]) fy, in exactly that order;
+ *   7. blend (default): acc.rgb += w colour, acc.w += w.  SVS_PAINT_BEST: acc = (colour, w) iff w > acc.w (strict: the
+ *      earlier view wins a tie, across calls too).
+ * svs_mesh_paint_finish: where acc.w > 0, rgb (DEVICE uint8[n_verts][3]) = floor(acc.c / acc.w + 0.5) per channel (blend)
+ *   or floor(acc.c + 0.5) (SVS_PAINT_BEST), clamped to [0,255], and painted (DEVICE int[n_verts]) = 1; elsewhere rgb is left
+ *   as the caller filled it and painted = 0.
+ * svs_mesh_paint_spread: one Jacobi round of hole filling in integers; round counts from 1.  work DEVICE int[n_verts][4]
+ *   and changed DEVICE int[1] are zeroed by the call.  For every face with indices inside [0, n_verts) and each ordered
+ *   pair (a, b) of two different corners of it: if 0 < painted[a] <= round and painted[b] == 0, rgb[a] (three ints) and 1
+ *   are added to work[b] atomically.  An edge shared by two faces is met in both and COUNTS TWICE, a boundary edge once:
+ *   that is the rule, not an accident.  Then per vertex with count = work[b][3] > 0:
+ *   rgb = (2 sum + count) / (2 count) by integer division (the rounded mean), painted = round + 1, *changed = 1.
+ *   Integer sums do not depend on their order: the result is exact and the same in every run.  An empty mesh (no vertices
+ *   or no faces): nothing is touched, changed included.
+ * SVS_ESHAPE for more than 16 views, H * W == 0 or a negative count; SVS_EINVAL for near <= 0, a negative tolerance,
+ * cos_min outside [0,1], power outside [0,8], an unknown flag, round < 1 or a null required pointer, with the entry's name
+ * in the message; every check comes before any HIP call.  An empty mesh is not an error.  Bad input (indices out of range,
+ * NaN or infinite vertices or normals) is skipped, never dereferenced. */
+#define SVS_PAINT_BEST 1
+#define SVS_PAINT_ONE_SIDED 2
+int svs_mesh_vertex_normals(const float* verts, int n_verts, const int* faces, int n_faces, double* accum, float* normals,
+                            void* hip_stream);
+int svs_mesh_paint(const float* verts, int n_verts, const float* normals, const double* mats, int n_views, int H, int W,
+                   double near, const float* depth, const uint8_t* const SVS_HOST* images, const uint8_t* const SVS_HOST* masks,
+                   double rel, double abs_tol, double cos_min, int power, int flags, double* acc, void* hip_stream);
+int svs_mesh_paint_finish(const double* acc, int n_verts, int flags, uint8_t* rgb, int* painted, void* hip_stream);
+int svs_mesh_paint_spread(const int* faces, int n_faces, int n_verts, int round, uint8_t* rgb, int* painted, int* work,
+                          int* changed, void* hip_stream);
+
 /* ---- numeric-contract self tests (used by tests/test_gpu_parity.py) --------------------------------------- */
 int svs_selftest_exp(const float* x, float* y_exp, float* y_expm1, int n, void* hip_stream);
 int svs_selftest_arith(const float* a, const float* b, float* quotient, float* sqrt_abs_a, int n, void* hip_stream);

@@ -1,0 +1,263 @@
+// A mesh's vertices coloured from a scan's photographs, for gfx950 (svs_hip.meshpaint): area-weighted vertex normals, the
+// per-vertex blend (or best view) of the photographs' bilinear taps behind the occlusion test of svs_mesh_vertex_visibility,
+// the conversion to codes, and the hole filling over the mesh's edges.  The reference has no such step; the arithmetic is
+// this project's, fixed in include/svolsdf_hip.h and restated in tests/meshpaint_oracle.py.
+//
+// paint_kernel is a gather: one lane per vertex walks the launch's views in index order with its four accumulators in
+// registers, so the sum has one fixed order and needs no atomics; two runs give the same bits.  The per-view eye
+// (-R^T t) is worked out once per workgroup into LDS.  The normals are a scatter of float64 atomic adds (their last bits
+// depend on arrival order: they only weight the views); the hole filling is a scatter of integer atomic adds, which is exact
+// in any order.  All camera arithmetic is float64 without contraction, as svs_meshview.hip does it.
+#include "svs_common.h"
+#include "svs_mesh_camera.h"
+
+namespace svs {
+namespace meshpaint {
+
+using meshview::Corner;
+using meshview::kMatsPerView;
+using meshview::kMaxViews;
+using meshview::project;
+
+constexpr int kMaxPower = 8;
+constexpr double kBig = 1.7976931348623157e308;
+
+__device__ __forceinline__ bool finite3(double a, double b, double c) {
+  return __builtin_fabs(a) <= kBig && __builtin_fabs(b) <= kBig && __builtin_fabs(c) <= kBig;      // NaN fails
+}
+
+// ---- normals ---------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void normal_accumulate_kernel(const float* __restrict__ verts, int n_verts,
+                                                                const int* __restrict__ faces, int n_faces, double* accum) {
+  const long long f = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= n_faces) return;
+  const int idx[3] = {faces[f * 3], faces[f * 3 + 1], faces[f * 3 + 2]};
+  if (idx[0] < 0 || idx[0] >= n_verts || idx[1] < 0 || idx[1] >= n_verts || idx[2] < 0 || idx[2] >= n_verts) return;
+  double p[3][3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) p[k][c] = (double)verts[(size_t)idx[k] * 3 + c];
+    if (!finite3(p[k][0], p[k][1], p[k][2])) return;
+  }
+  const double ux = p[1][0] - p[0][0], uy = p[1][1] - p[0][1], uz = p[1][2] - p[0][2];
+  const double vx = p[2][0] - p[0][0], vy = p[2][1] - p[0][1], vz = p[2][2] - p[0][2];
+  const double n[3] = {uy * vz - uz * vy, uz * vx - ux * vz, ux * vy - uy * vx};
+#pragma unroll
+  for (int k = 0; k < 3; ++k)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) atomicAdd(accum + (size_t)idx[k] * 3 + c, n[c]);
+}
+
+__global__ __launch_bounds__(256) void normal_finish_kernel(const double* __restrict__ accum, int n_verts,
+                                                            float* __restrict__ normals) {
+  const int v = blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= n_verts) return;
+  const double x = accum[(size_t)v * 3], y = accum[(size_t)v * 3 + 1], z = accum[(size_t)v * 3 + 2];
+  const double len = __builtin_sqrt(x * x + y * y + z * z);
+  const bool unit = finite3(x, y, z) && len > 0.0 && len <= kBig;
+  normals[(size_t)v * 3] = unit ? (float)(x / len) : 0.0f;
+  normals[(size_t)v * 3 + 1] = unit ? (float)(y / len) : 0.0f;
+  normals[(size_t)v * 3 + 2] = unit ? (float)(z / len) : 0.0f;
+}
+
+// ---- paint -----------------------------------------------------------------------------------------------------------
+struct PaintArgs {
+  const float* verts;
+  const float* normals;
+  const double* mats;
+  const float* depth;
+  const uint8_t* image[kMaxViews];
+  const uint8_t* mask[kMaxViews];
+  double* acc;
+  double near, rel, abs_tol, cos_min;
+  int n_verts, n_views, H, W, power, flags;
+};
+
+__global__ __launch_bounds__(256) void paint_kernel(PaintArgs a) {
+  __shared__ double eye[kMaxViews][3];
+  if (threadIdx.x < (unsigned)a.n_views) {                   // eye = -R^T t, once per view
+    const double* __restrict__ E = a.mats + (size_t)threadIdx.x * kMatsPerView + 9;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) eye[threadIdx.x][k] = -(E[k] * E[3] + E[4 + k] * E[7] + E[8 + k] * E[11]);
+  }
+  __syncthreads();
+  const int v = blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= a.n_verts) return;
+  const float* __restrict__ p = a.verts + (size_t)v * 3;
+  double n[3] = {0.0, 0.0, 0.0};
+  bool lit = true;
+  if (a.normals) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) n[k] = (double)a.normals[(size_t)v * 3 + k];
+    lit = finite3(n[0], n[1], n[2]) && !(n[0] == 0.0 && n[1] == 0.0 && n[2] == 0.0);
+  }
+  double r = a.acc[(size_t)v * 4], g = a.acc[(size_t)v * 4 + 1], b = a.acc[(size_t)v * 4 + 2], wsum = a.acc[(size_t)v * 4 + 3];
+  const bool best = a.flags & SVS_PAINT_BEST;
+  const size_t hw = (size_t)a.H * (size_t)a.W;
+  for (int view = 0; lit && view < a.n_views; ++view) {
+    Corner c;
+    if (!project(a.mats + (size_t)view * kMatsPerView, p, a.near, c)) continue;                      // 1
+    if (!(c.x >= 0.0 && c.x <= (double)(a.W - 1) && c.y >= 0.0 && c.y <= (double)(a.H - 1))) continue;   // 2
+    const size_t pix = (size_t)(int)__builtin_floor(c.y + 0.5) * (size_t)a.W + (size_t)(int)__builtin_floor(c.x + 0.5);
+    const uint8_t* __restrict__ mask = a.mask[view];
+    if (mask && mask[pix] == 0) continue;                                                            // 3
+    const double d = (double)a.depth[(size_t)view * hw + pix];
+    if (!(d == 0.0 || c.cz <= d * (1.0 + a.rel) + a.abs_tol)) continue;                              // 4
+    double w = 1.0;
+    if (a.normals) {                                                                                 // 5
+      const double tx = eye[view][0] - (double)p[0], ty = eye[view][1] - (double)p[1], tz = eye[view][2] - (double)p[2];
+      double cs = (n[0] * tx + n[1] * ty + n[2] * tz) / __builtin_sqrt(tx * tx + ty * ty + tz * tz);
+      if (!(a.flags & SVS_PAINT_ONE_SIDED)) cs = __builtin_fabs(cs);
+      if (!(cs >= a.cos_min)) continue;                      // NaN too
+      for (int k = 0; k < a.power; ++k) w = w * cs;
+    }
+    const double x0 = __builtin_floor(c.x), y0 = __builtin_floor(c.y);                               // 6
+    const double fx = c.x - x0, fy = c.y - y0;
+    const int ix0 = (int)x0, iy0 = (int)y0;
+    const int ix1 = ix0 + 1 < a.W ? ix0 + 1 : a.W - 1, iy1 = iy0 + 1 < a.H ? iy0 + 1 : a.H - 1;
+    const uint8_t* __restrict__ img = a.image[view];
+    const uint8_t* __restrict__ t00 = img + ((size_t)iy0 * a.W + ix0) * 3;
+    const uint8_t* __restrict__ t01 = img + ((size_t)iy0 * a.W + ix1) * 3;
+    const uint8_t* __restrict__ t10 = img + ((size_t)iy1 * a.W + ix0) * 3;
+    const uint8_t* __restrict__ t11 = img + ((size_t)iy1 * a.W + ix1) * 3;
+    double col[3];
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch)
+      col[ch] = ((1.0 - fx) * (double)t00[ch] + fx * (double)t01[ch]) * (1.0 - fy) +
+                ((1.0 - fx) * (double)t10[ch] + fx * (double)t11[ch]) * fy;
+    if (best) {                                                                                      // 7
+      if (w > wsum) { r = col[0]; g = col[1]; b = col[2]; wsum = w; }
+    } else {
+      r = r + w * col[0]; g = g + w * col[1]; b = b + w * col[2]; wsum = wsum + w;
+    }
+  }
+  a.acc[(size_t)v * 4] = r; a.acc[(size_t)v * 4 + 1] = g; a.acc[(size_t)v * 4 + 2] = b; a.acc[(size_t)v * 4 + 3] = wsum;
+}
+
+__global__ __launch_bounds__(256) void paint_finish_kernel(const double* __restrict__ acc, int n_verts, int flags,
+                                                           uint8_t* __restrict__ rgb, int* __restrict__ painted) {
+  const int v = blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= n_verts) return;
+  const double w = acc[(size_t)v * 4 + 3];
+  if (!(w > 0.0)) { painted[v] = 0; return; }
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) {
+    const double c = acc[(size_t)v * 4 + ch];
+    double code = __builtin_floor(((flags & SVS_PAINT_BEST) ? c : c / w) + 0.5);
+    code = code >= 0.0 ? code : 0.0;                         // NaN too
+    code = code > 255.0 ? 255.0 : code;
+    rgb[(size_t)v * 3 + ch] = (uint8_t)(int)code;
+  }
+  painted[v] = 1;
+}
+
+// ---- spread ----------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void spread_gather_kernel(const int* __restrict__ faces, int n_faces, int n_verts, int round,
+                                                            const uint8_t* __restrict__ rgb, const int* __restrict__ painted,
+                                                            int* work) {
+  const long long f = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= n_faces) return;
+  const int idx[3] = {faces[f * 3], faces[f * 3 + 1], faces[f * 3 + 2]};
+  if (idx[0] < 0 || idx[0] >= n_verts || idx[1] < 0 || idx[1] >= n_verts || idx[2] < 0 || idx[2] >= n_verts) return;
+  const int state[3] = {painted[idx[0]], painted[idx[1]], painted[idx[2]]};
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    if (!(state[i] > 0 && state[i] <= round)) continue;
+    const uint8_t* __restrict__ c = rgb + (size_t)idx[i] * 3;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      if (j == i || state[j] != 0) continue;
+      int* at = work + (size_t)idx[j] * 4;
+      atomicAdd(at, (int)c[0]); atomicAdd(at + 1, (int)c[1]); atomicAdd(at + 2, (int)c[2]); atomicAdd(at + 3, 1);
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void spread_apply_kernel(const int* __restrict__ work, int n_verts, int round,
+                                                           uint8_t* __restrict__ rgb, int* __restrict__ painted, int* changed) {
+  const int v = blockIdx.x * blockDim.x + threadIdx.x;
+  bool filled = false;
+  if (v < n_verts) {
+    const int count = work[(size_t)v * 4 + 3];
+    if (count > 0) {
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) rgb[(size_t)v * 3 + ch] = (uint8_t)((2 * work[(size_t)v * 4 + ch] + count) / (2 * count));
+      painted[v] = round + 1;
+      filled = true;
+    }
+  }
+  if (__ballot(filled) && (threadIdx.x & 63) == 0) *changed = 1;          // every writer stores the same value
+}
+
+}  // namespace meshpaint
+}  // namespace svs
+
+using namespace svs;
+using namespace svs::meshpaint;
+
+extern "C" {
+
+int svs_mesh_vertex_normals(const float* verts, int n_verts, const int* faces, int n_faces, double* accum, float* normals,
+                            void* hip_stream) {
+  if (n_verts < 0 || n_faces < 0) { set_error("svs_mesh_vertex_normals: negative count"); return SVS_ESHAPE; }
+  if (n_verts == 0) return SVS_OK;
+  if (!verts || !accum || (n_faces > 0 && !faces)) { set_error("svs_mesh_vertex_normals: null argument"); return SVS_EINVAL; }
+  hipStream_t s = (hipStream_t)hip_stream;
+  if (n_faces > 0) normal_accumulate_kernel<<<(unsigned)((n_faces + 255) / 256), 256, 0, s>>>(verts, n_verts, faces, n_faces, accum);
+  if (normals) normal_finish_kernel<<<(unsigned)((n_verts + 255) / 256), 256, 0, s>>>(accum, n_verts, normals);
+  return check_launch("svs_mesh_vertex_normals");
+}
+
+int svs_mesh_paint(const float* verts, int n_verts, const float* normals, const double* mats, int n_views, int H, int W,
+                   double near, const float* depth, const uint8_t* const* images, const uint8_t* const* masks, double rel,
+                   double abs_tol, double cos_min, int power, int flags, double* acc, void* hip_stream) {
+  if (int rc = meshview::check_views("svs_mesh_paint", n_views, H, W)) return rc;
+  if (!(near > 0.0) || !(rel >= 0.0) || !(abs_tol >= 0.0)) {
+    set_error("svs_mesh_paint: near must be positive, rel and abs_tol not negative"); return SVS_EINVAL;
+  }
+  if (!(cos_min >= 0.0 && cos_min <= 1.0) || power < 0 || power > kMaxPower) {
+    set_error("svs_mesh_paint: cos_min in [0,1] and power in [0,%d], got %g and %d", kMaxPower, cos_min, power); return SVS_EINVAL;
+  }
+  if (flags & ~(SVS_PAINT_BEST | SVS_PAINT_ONE_SIDED)) { set_error("svs_mesh_paint: unknown flags %d", flags); return SVS_EINVAL; }
+  if (n_verts < 0) { set_error("svs_mesh_paint: negative count"); return SVS_ESHAPE; }
+  if (!images) { set_error("svs_mesh_paint: null argument (images)"); return SVS_EINVAL; }
+  if (n_verts == 0 || n_views == 0) return SVS_OK;
+  if (!verts || !mats || !depth || !acc) { set_error("svs_mesh_paint: null argument"); return SVS_EINVAL; }
+  PaintArgs a;
+  for (int v = 0; v < kMaxViews; ++v) {
+    a.image[v] = v < n_views ? images[v] : nullptr;
+    a.mask[v] = (masks && v < n_views) ? masks[v] : nullptr;
+    if (v < n_views && !a.image[v]) { set_error("svs_mesh_paint: view %d has no image", v); return SVS_EINVAL; }
+  }
+  a.verts = verts; a.normals = normals; a.mats = mats; a.depth = depth; a.acc = acc;
+  a.near = near; a.rel = rel; a.abs_tol = abs_tol; a.cos_min = cos_min;
+  a.n_verts = n_verts; a.n_views = n_views; a.H = H; a.W = W; a.power = power; a.flags = flags;
+  paint_kernel<<<(n_verts + 255) / 256, 256, 0, (hipStream_t)hip_stream>>>(a);
+  return check_launch("svs_mesh_paint");
+}
+
+int svs_mesh_paint_finish(const double* acc, int n_verts, int flags, uint8_t* rgb, int* painted, void* hip_stream) {
+  if (n_verts < 0) { set_error("svs_mesh_paint_finish: negative count"); return SVS_ESHAPE; }
+  if (flags & ~(SVS_PAINT_BEST | SVS_PAINT_ONE_SIDED)) { set_error("svs_mesh_paint_finish: unknown flags %d", flags); return SVS_EINVAL; }
+  if (n_verts == 0) return SVS_OK;
+  if (!acc || !rgb || !painted) { set_error("svs_mesh_paint_finish: null argument"); return SVS_EINVAL; }
+  paint_finish_kernel<<<(n_verts + 255) / 256, 256, 0, (hipStream_t)hip_stream>>>(acc, n_verts, flags, rgb, painted);
+  return check_launch("svs_mesh_paint_finish");
+}
+
+int svs_mesh_paint_spread(const int* faces, int n_faces, int n_verts, int round, uint8_t* rgb, int* painted, int* work,
+                          int* changed, void* hip_stream) {
+  if (n_verts < 0 || n_faces < 0) { set_error("svs_mesh_paint_spread: negative count"); return SVS_ESHAPE; }
+  if (round < 1 || round > 0x7ffffffe) { set_error("svs_mesh_paint_spread: round %d (rounds count from 1)", round); return SVS_EINVAL; }
+  if (n_verts == 0 || n_faces == 0) return SVS_OK;          // nothing is touched, changed included
+  if (!faces || !rgb || !painted || !work || !changed) { set_error("svs_mesh_paint_spread: null argument"); return SVS_EINVAL; }
+  hipStream_t s = (hipStream_t)hip_stream;
+  if (hipMemsetAsync(changed, 0, sizeof(int), s) != hipSuccess || hipMemsetAsync(work, 0, (size_t)n_verts * 4 * sizeof(int), s) != hipSuccess)
+    return check_launch("svs_mesh_paint_spread");
+  spread_gather_kernel<<<(unsigned)((n_faces + 255) / 256), 256, 0, s>>>(faces, n_faces, n_verts, round, rgb, painted, work);
+  spread_apply_kernel<<<(unsigned)((n_verts + 255) / 256), 256, 0, s>>>(work, n_verts, round, rgb, painted, changed);
+  return check_launch("svs_mesh_paint_spread");
+}
+
+}  // extern "C"
