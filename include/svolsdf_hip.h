@@ -900,6 +900,47 @@ int svs_cloud_error_colors(const double* dist, int n_dist, const uint8_t* select
 int svs_mesh_sample_count(const double* tri, int n_tri, long long* counts, void* hip_stream);
 int svs_mesh_sample_points(const double* tri, int n_tri, const long long* offsets, double* out, void* hip_stream);
 
+/* ---- f4c  cleaning a fused cloud: k nearest neighbours, statistical outliers, oriented normals (csrc/svs_cloudknn.hip) ----
+ * This project's own arithmetic, after the common remove_statistical_outlier / PCA-normal recipe (svs_hip/clouds.py,
+ * svs_hip/cloudclean.py; restated in float64 numpy by tests/cloudclean_oracle.py).  Clouds are (n,3) float64 as in f4.
+ * svs_cloud_knn: for every query the k nearest reference points, 1 <= k <= 32, over the grid of f4 (built here, in
+ *   grid_ws: svs_cloud_grid_bytes(n_ref); origin: HOST double[3], <= every coordinate of both clouds, (max - origin)/cell
+ *   < 2^21; cell > 0: the grid's cell size).
+ *   dist (n_query,k) float64, ascending; idx (n_query,k) int32, original indices.  Neighbours are ordered by (d2, index),
+ *   d2 = ex*ex + ey*ey + ez*ez in float64 without contraction (svs_cloud_nn's expression: k = 1 returns its bits wherever
+ *   its result is below max_radius), so ties go to the lower index; dist = sqrt(d2).  A slot whose neighbour is not strictly
+ *   closer than max_radius holds +inf / -1, and so does a slot that does not exist (fewer than k candidates): the output is
+ *   a function of the inputs alone.  0 < max_radius <= 4096 cells (SVS_ESHAPE otherwise): the search walks rings of cells
+ *   outwards until the list is full and its k-th entry is <= (ring * cell + margin to the home cell's walls)^2, or
+ *   through ring ceil(max_radius / cell) + 1.
+ *   exclude_same_index: 0, every reference counts; e > 0, reference (e - 1) + j is skipped for query j -- 1 when the query
+ *   cloud is the reference cloud, 1 + first row when it is a range of the reference's rows.
+ *   mean_dist (n_query) float64: the mean of the finite slots of the row, summed in ascending slot order, +inf if there
+ *   are none.  Each of dist, idx, mean_dist may be NULL, not all three.  With query == ref and n_query == n_ref the queries
+ *   are walked in the grid's sorted order (neighbouring lanes, neighbouring cells); the rows written are the same.
+ *   n_query == 0 returns 0; n_ref == 0 fills the outputs.
+ * svs_cloud_outlier_stats: over the finite entries of mean_dist (n), one fixed two-level summation order, no atomics:
+ *   out[0] = their number, out[1] = their mean (0 if there are none), out[2] = their sample standard deviation
+ *   (denominator count - 1, two passes: the deviations are taken about out[1]; 0 when count < 2).  out: DEVICE double[3];
+ *   workspace: svs_cloud_outlier_workspace_bytes().
+ * svs_cloud_outlier_mask: keep[i] = mean_dist[i] <= threshold, 0 for an entry that is not finite; keep (n) uint8.
+ * svs_cloud_normals: for point i the set S = {pts[j] : j = idx[i, s], 0 <= j < n} (idx (n,k) int32, 1 <= k <= 32: what
+ *   svs_cloud_knn wrote, -1 = no neighbour) plus pts[i] itself when include_self != 0.  The float64 covariance of S about
+ *   its centroid, its eigenvectors by cyclic Jacobi (8 sweeps, rotations in the order (0,1), (0,2), (1,2)); the normal is
+ *   the eigenvector of the smallest eigenvalue l0, curvature = l0 / (l0 + l1 + l2) (0 for a zero trace).
+ *   centres (n_views,3) float64 DEVICE or NULL: NULL leaves the normal as the solver gave it; otherwise it is negated when
+ *   n . (c - p) < 0, c = centres[view_index[i]] (view_index (n) int32, clamped to [0, n_views)) or, with view_index NULL,
+ *   the centre nearest to the point (the lowest index on a tie).  normals (n,3) float32, unit length; curvature (n)
+ *   float32, may be NULL.  Fewer than 3 points in S: normal (0,0,0), curvature 0. */
+int svs_cloud_knn(const double* ref, int n_ref, const double* query, int n_query, const double SVS_HOST* origin, double cell, int k,
+                  double max_radius, int exclude_same_index, void* grid_ws, double* dist, int* idx, double* mean_dist,
+                  void* hip_stream);
+size_t svs_cloud_outlier_workspace_bytes(void);
+int svs_cloud_outlier_stats(const double* mean_dist, int n, double* workspace, double* out, void* hip_stream);
+int svs_cloud_outlier_mask(const double* mean_dist, int n, double threshold, uint8_t* keep, void* hip_stream);
+int svs_cloud_normals(const double* pts, int n, const int* idx, int k, int include_self, const int* view_index,
+                      const double* centres, int n_views, float* normals, float* curvature, void* hip_stream);
+
 /* ---- surface mesh of a checkpoint (svs_hip.mesh; eval_vsdf.py:111-154 --eval_mesh, volsdf/utils/plots.py:108-333) ------
  * What scikit-image's marching_cubes and trimesh do for the reference on the host.  The case table is generated
  * (csrc/svs_mc_table.h, tools/gen_mc_table.py): scikit-image's vertex set (one vertex per sign-changing grid edge, without

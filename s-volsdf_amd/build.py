@@ -43,6 +43,7 @@ UNITS = {
     "svs_optim.hip": ["-ffp-contract=off"],
     "svs_fusion.hip": ["-ffp-contract=off"],
     "svs_cloud.hip": ["-ffp-contract=off"],
+    "svs_cloudknn.hip": ["-ffp-contract=off"],
     "svs_chamfer.hip": ["-ffp-contract=off"],
     "svs_ibr.hip": ["-ffp-contract=off"],
     "svs_nvs.hip": ["-ffp-contract=off"],

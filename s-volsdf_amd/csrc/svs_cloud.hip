@@ -4,55 +4,20 @@
 // cloud, observation-mask / bounding-box filtering, and the two nearest-neighbour passes (data -> STL accuracy,
 // STL -> data completeness) that the reference runs through sklearn's kd-tree on the CPU.
 //
-// Here both neighbour problems use one structure: points sorted by the key of their cell in a uniform grid
+// Here both neighbour problems use one structure (svs_cloud_grid.h, shared with svs_cloudknn.hip; built here): points
+// sorted by the key of their cell in a uniform grid
 // (rocPRIM radix sort -- the only library call) plus an open-addressing hash from cell key to the [begin, end) run
 // in the sorted order.  Neighbour candidates are the runs of the cells around the query, scanned in float64 with
 // the kd-tree's arithmetic (dx*dx + dy*dy + dz*dz, no fused multiply-add), so distances agree with sklearn's to the
 // last bit.  This is latency / HBM-bound gather work: no matrix cores.
 #include <hipcub/hipcub.hpp>
 
+#include "svs_cloud_grid.h"
 #include "svs_common.h"
 #include "svs_scan.h"
 
 namespace svs {
 namespace cloud {
-
-typedef unsigned long long u64;
-constexpr u64 kEmpty = ~0ull;
-constexpr int kCellBits = 21;                     // per-axis cell index range [0, 2^21)
-
-struct Grid {
-  double ox, oy, oz, inv_h, h;                    // cell = floor((p - origin) * inv_h)
-  const double* pts;                              // (n,3) points in SORTED order
-  const unsigned* perm;                           // sorted position -> original index
-  const u64* hkey;                                // hash table (capacity = mask + 1)
-  const uint2* hrun;                              //   [begin, end) of the cell's run
-  unsigned mask;
-  int n;
-};
-
-__device__ __forceinline__ int cell_coord(double p, double o, double inv_h) {
-  const double c = __builtin_floor((p - o) * inv_h);
-  return c < 0.0 ? 0 : (c > (double)((1 << kCellBits) - 1) ? (1 << kCellBits) - 1 : (int)c);
-}
-__device__ __forceinline__ u64 cell_key(int ix, int iy, int iz) {
-  return (u64)ix | ((u64)iy << kCellBits) | ((u64)iz << (2 * kCellBits));
-}
-__device__ __forceinline__ unsigned hash_slot(u64 k, unsigned mask) {
-  k ^= k >> 33; k *= 0xff51afd7ed558ccdull; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull; k ^= k >> 33;
-  return (unsigned)k & mask;
-}
-__device__ __forceinline__ uint2 find_run(const Grid& g, int ix, int iy, int iz) {
-  if ((unsigned)ix >= (1u << kCellBits) || (unsigned)iy >= (1u << kCellBits) || (unsigned)iz >= (1u << kCellBits)) return make_uint2(0, 0);
-  const u64 k = cell_key(ix, iy, iz);
-  unsigned s = hash_slot(k, g.mask);
-  while (true) {
-    const u64 hk = g.hkey[s];
-    if (hk == k) return g.hrun[s];
-    if (hk == kEmpty) return make_uint2(0, 0);
-    s = (s + 1) & g.mask;
-  }
-}
 
 __global__ void keys_kernel(const double* __restrict__ pts, int n, double ox, double oy, double oz, double inv_h,
                             u64* __restrict__ keys, unsigned* __restrict__ idx) {
@@ -279,29 +244,6 @@ GridLayout grid_layout(int n) {
   return L;
 }
 
-// Builds the grid of `pts` in `ws`; returns the device-side view.
-int build_grid(const double* pts, int n, const double* origin, double h, void* ws, hipStream_t s, Grid* g) {
-  const GridLayout L = grid_layout(n);
-  char* base = (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-  u64* keys = (u64*)(base + L.keys); u64* skeys = (u64*)(base + L.skeys);
-  unsigned* idx = (unsigned*)(base + L.idx); unsigned* sidx = (unsigned*)(base + L.sidx);
-  double* spts = (double*)(base + L.spts);
-  u64* hkey = (u64*)(base + L.hkey); uint2* hrun = (uint2*)(base + L.hrun);
-  const int nb = (n + 255) / 256;
-  clear_hash_kernel<<<(L.cap + 255) / 256, 256, 0, s>>>(hkey, L.cap);
-  if (n > 0) {
-    keys_kernel<<<nb, 256, 0, s>>>(pts, n, origin[0], origin[1], origin[2], 1.0 / h, keys, idx);
-    size_t tmp = L.sort_bytes;
-    hipError_t e = hipcub::DeviceRadixSort::SortPairs(base + L.sort_tmp, tmp, keys, skeys, idx, sidx, n, 0, 3 * kCellBits, s);
-    if (e != hipSuccess) { set_error("cell sort: %s", hipGetErrorString(e)); return (int)e; }
-    heads_kernel<<<nb, 256, 0, s>>>(skeys, sidx, pts, n, hkey, hrun, L.cap - 1, spts);
-    tails_kernel<<<nb, 256, 0, s>>>(skeys, n, hkey, hrun, L.cap - 1);
-  }
-  g->ox = origin[0]; g->oy = origin[1]; g->oz = origin[2]; g->inv_h = 1.0 / h; g->h = h;
-  g->pts = spts; g->perm = sidx; g->hkey = hkey; g->hrun = hrun; g->mask = L.cap - 1; g->n = n;
-  return check_launch("cell grid");
-}
-
 // ---- bounding box of a cloud (the grids' origin): per-block minima / maxima, then one block ---------------------------------
 constexpr int kBoundsBlocks = 512;
 __global__ __launch_bounds__(256) void bounds_partial_kernel(const double* __restrict__ pts, int n, double* __restrict__ part) {
@@ -376,6 +318,29 @@ __global__ __launch_bounds__(256) void mesh_sample_kernel(const double* __restri
 }
 
 }  // namespace
+
+// Builds the grid of `pts` in `ws`; returns the device-side view (declared in svs_cloud_grid.h).
+int svs::cloud::build_grid(const double* pts, int n, const double* origin, double h, void* ws, hipStream_t s, Grid* g) {
+  const GridLayout L = grid_layout(n);
+  char* base = (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+  u64* keys = (u64*)(base + L.keys); u64* skeys = (u64*)(base + L.skeys);
+  unsigned* idx = (unsigned*)(base + L.idx); unsigned* sidx = (unsigned*)(base + L.sidx);
+  double* spts = (double*)(base + L.spts);
+  u64* hkey = (u64*)(base + L.hkey); uint2* hrun = (uint2*)(base + L.hrun);
+  const int nb = (n + 255) / 256;
+  clear_hash_kernel<<<(L.cap + 255) / 256, 256, 0, s>>>(hkey, L.cap);
+  if (n > 0) {
+    keys_kernel<<<nb, 256, 0, s>>>(pts, n, origin[0], origin[1], origin[2], 1.0 / h, keys, idx);
+    size_t tmp = L.sort_bytes;
+    hipError_t e = hipcub::DeviceRadixSort::SortPairs(base + L.sort_tmp, tmp, keys, skeys, idx, sidx, n, 0, 3 * kCellBits, s);
+    if (e != hipSuccess) { set_error("cell sort: %s", hipGetErrorString(e)); return (int)e; }
+    heads_kernel<<<nb, 256, 0, s>>>(skeys, sidx, pts, n, hkey, hrun, L.cap - 1, spts);
+    tails_kernel<<<nb, 256, 0, s>>>(skeys, n, hkey, hrun, L.cap - 1);
+  }
+  g->ox = origin[0]; g->oy = origin[1]; g->oz = origin[2]; g->inv_h = 1.0 / h; g->h = h;
+  g->pts = spts; g->perm = sidx; g->hkey = hkey; g->hrun = hrun; g->mask = L.cap - 1; g->n = n;
+  return check_launch("cell grid");
+}
 
 extern "C" {
 

@@ -1,7 +1,8 @@
 """Every PLY byte this project reads or writes: one header parser, the point and mesh readers the Chamfer evaluators take
 their clouds from (what open3d.io.read_point_cloud / read_triangle_mesh give the reference, evals/eval_dtu.py:65-68,96-97,
 139-140), and the one writer behind the fused cloud (runner.py:389-400 through plyfile), the error clouds
-(evals/eval_bmvs.py:241,246) and the meshes of `svs_hip.mesh` and `svs_hip.tsdf`.  Host code only.
+(evals/eval_bmvs.py:241,246), the meshes of `svs_hip.mesh` and `svs_hip.tsdf` and the cleaned cloud with normals of
+`svs_hip.cloudclean`.  Host code only.
 """
 import numpy as np
 import torch
@@ -107,6 +108,14 @@ def read_points(filename):
     return pts, rgb
 
 
+def read_point_normals(filename):
+    """-> (n,3) float32: the nx, ny, nz of the vertex element, or None for a file without them"""
+    cols, _ = _read(filename, faces=False)
+    if not all("n" + k in cols for k in "xyz"):
+        return None
+    return np.stack([np.asarray(cols["n" + k], np.float32) for k in "xyz"], 1)
+
+
 def read_mesh(filename):
     """-> (vertices (n,3) float64, triangles (m,3) int64) of an ascii / binary PLY with a face element whose list property
     is vertex_indices or vertex_index.  Faces with more than three corners are fanned around their first corner, as
@@ -120,24 +129,36 @@ def _host(a, dtype):
     return np.asarray(a.detach().cpu() if torch.is_tensor(a) else a, dtype).reshape(-1, 3)
 
 
-def write(filename, xyz, rgb=None, faces=None, coords="float"):
-    """Binary little-endian PLY.  xyz (n,3) as `coords` ("float" or "double") x, y, z; rgb: optional (n,3), uchar red,
-    green, blue after them (ValueError when their count differs); faces: optional (m,3), a second element of
-    `list uchar int vertex_indices` records (no normals, as trimesh's export).  Arrays, host or device tensors.
-    A float cloud with colours is the file of runner.py:389-400, a double one the error cloud of both evaluators."""
+def write(filename, xyz, rgb=None, faces=None, coords="float", normals=None):
+    """Binary little-endian PLY.  xyz (n,3) as `coords` ("float" or "double") x, y, z; normals: optional (n,3), float nx,
+    ny, nz after them (the order MeshLab and Open3D read); rgb: optional (n,3), uchar red, green, blue last (ValueError when
+    either count differs from the vertices'); faces: optional (m,3), a second element of `list uchar int vertex_indices`
+    records (as trimesh's export).  Arrays, host or device tensors.  A float cloud with colours is the file of
+    runner.py:389-400, a double one the error cloud of both evaluators, one with normals the cleaned cloud of
+    `svs_hip.cloudclean`."""
     t = {"float": "<f4", "double": "<f8"}.get(coords)
     if t is None:
         raise ValueError(f"coords: 'float' or 'double', got {coords!r}")
     v = np.ascontiguousarray(_host(xyz, t))
     head = "ply\nformat binary_little_endian 1.0\nelement vertex %d\n" % len(v) + "".join(f"property {coords} {k}\n" for k in "xyz")
+    fields, cols = [("p", t, (3,))], [v]
+    if normals is not None:
+        nrm = _host(normals, "<f4")
+        if len(nrm) != len(v):
+            raise ValueError(f"{len(nrm)} normals for {len(v)} vertices")
+        fields.append(("n", "<f4", (3,))); cols.append(nrm)
+        head += "".join(f"property float n{k}\n" for k in "xyz")
     if rgb is not None:
         c = _host(rgb, np.uint8)
         if len(c) != len(v):
             raise ValueError(f"{len(c)} colours for {len(v)} vertices")
-        rec = np.empty(len(v), dtype=[("p", t, (3,)), ("c", "u1", (3,))])
-        rec["p"], rec["c"] = v, c
-        v = rec
+        fields.append(("c", "u1", (3,))); cols.append(c)
         head += "".join(f"property uchar {k}\n" for k in _RGB)
+    if len(fields) > 1:
+        rec = np.empty(len(v), dtype=fields)
+        for f_, col in zip(fields, cols):
+            rec[f_[0]] = col
+        v = rec
     if faces is not None:
         f = _host(faces, None)
         corner = np.empty(len(f), dtype=[("n", "u1"), ("v", "<i4", (3,))])

@@ -12,11 +12,14 @@ filter_depth_folder`) -> {outdir}/mvsnet{scan:03}_l3.ply.
                              restated here as a plain nested dict (what `VolOpt` takes); the two loaders are this project's
     apply_overrides(a, argv) hydra's command-line form: key=value, dotted keys, +key=value, vol=dtu|bmvs
     run_help(args)           derived values, the six assertions (ValueError naming the key), all_scans.yaml, the device
-    save_depth / save_scene_depth / pcd_filter / create_scenes / main
+    save_depth / save_scene_depth / pcd_filter / clean_clouds / create_scenes / main
     +tsdf_voxel=V [+tsdf_trunc=T]   after the point clouds, every scan's depth maps meshed by `svs_hip.tsdf` into
                              {outdir}/tsdf/mvsnet{scan:03}_l3.ply (`python -m evals.eval_dtu --datadir {outdir}/tsdf --mode mesh`)
     +tsdf_views=true         with +tsdf_voxel: every scan's TSDF mesh rendered into its training views by `svs_hip.meshview`,
                              {outdir}/tsdf/scanNNN/mesh_depth/{id:08}.pfm and mesh_shade/{id:08}.png
+    +cloud_clean=true [+cloud_k=20 +cloud_std_ratio=2.0 +cloud_normal_k=16]   after the point clouds, every scan's cloud
+                             without its statistical outliers and with oriented normals (`svs_hip.cloudclean`), in
+                             {outdir}/clean/mvsnet{scan:03}_l3.ply (`python -m evals.eval_dtu --datadir {outdir}/clean`)
 
 Differences from the reference, all deliberate: `gpu: auto` keeps the current device (there is no GPUtil probe) and an
 integer selects it with torch.cuda.set_device; `prevent_oom` is taken as given; the five-second sleep before the first
@@ -407,6 +410,35 @@ def tsdf_views(args, testlist):
     return out
 
 
+def clean_ply_name(outdir, scan):
+    """the cleaned cloud of a scan: the point cloud's name one folder down, where `evals.eval_dtu --datadir` finds it"""
+    return ply_name(os.path.join(outdir, "clean"), scan)
+
+
+def clean_clouds(args, testlist):
+    """+cloud_clean=true [+cloud_k=20 +cloud_std_ratio=2.0 +cloud_normal_k=16]: every scan's views fused with the settings
+    and evaluation masks of `pcd_filter`, cleaned by `cloudclean.clean_folder` into {outdir}/clean/mvsnet{scan:03}_l3.ply; one
+    time line per scan.  -> {scene: clean_folder's stats}"""
+    from . import cloudclean
+    from .scans import get_trains_ids
+    data_dir = args["vol"]["dataset"]["data_dir"]
+    out = OrderedDict()
+    for scan in testlist:
+        folder, ply = os.path.join(args["outdir"], scan), clean_ply_name(args["outdir"], scan)
+        os.makedirs(os.path.dirname(ply), exist_ok=True)
+        masks = dict(eval_mask_root=args["data_dir_root"], dataset=data_dir) if args["eval_mask"] else {}
+        stats = cloudclean.clean_folder(folder, folder, get_trains_ids(data_dir, scan, args["num_view"]), ply,
+                                        k=int(args.get("cloud_k", 20)), std_ratio=float(args.get("cloud_std_ratio", 2.0)),
+                                        normal_k=int(args.get("cloud_normal_k", 16)), conf=args["conf"],
+                                        filter_dist=args["filter_dist"], filter_diff=args["filter_diff"],
+                                        thres_view=args["thres_view"], **masks)["stats"]
+        info(f"saving the cleaned cloud to {ply} ({stats['points_kept']} of {stats['points_in']} points, "
+             f"threshold {stats['threshold']:.6g})")
+        info(f"{scan} cloud clean seconds: " + ", ".join(f"{k} {v:.3f}" for k, v in stats["seconds"].items()))
+        out[scan] = stats
+    return out
+
+
 def create_scenes(args, testlist):
     """runner.py:74-108, 447-452: the folder of cameras and images that image-based rendering reads, per scan"""
     from . import mvsdata
@@ -452,6 +484,8 @@ def main(argv=None, scan_fn=None):
         result["meshes"] = tsdf_meshes(args, testlist)
         if args.get("tsdf_views"):
             result["mesh_views"] = tsdf_views(args, testlist)
+    if args.get("cloud_clean"):
+        result["clean"] = clean_clouds(args, testlist)
     return result
 
 
