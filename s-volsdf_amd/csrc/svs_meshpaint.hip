@@ -7,32 +7,24 @@
 // registers, so the sum has one fixed order and needs no atomics; two runs give the same bits.  The per-view eye
 // (-R^T t) is worked out once per workgroup into LDS.  The normals are a scatter of float64 atomic adds (their last bits
 // depend on arrival order: they only weight the views); the hole filling is a scatter of integer atomic adds, which is exact
-// in any order.  All camera arithmetic is float64 without contraction, as svs_meshview.hip does it.
+// in any order.  All camera arithmetic is float64 without contraction; its rules are those of svs_views.h.
 #include "svs_common.h"
-#include "svs_mesh_camera.h"
+#include "svs_views.h"
 
 namespace svs {
 namespace meshpaint {
 
-using meshview::Corner;
-using meshview::kMatsPerView;
-using meshview::kMaxViews;
-using meshview::project;
+using namespace views;
 
 constexpr int kMaxPower = 8;
-constexpr double kBig = 1.7976931348623157e308;
-
-__device__ __forceinline__ bool finite3(double a, double b, double c) {
-  return __builtin_fabs(a) <= kBig && __builtin_fabs(b) <= kBig && __builtin_fabs(c) <= kBig;      // NaN fails
-}
 
 // ---- normals ---------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void normal_accumulate_kernel(const float* __restrict__ verts, int n_verts,
                                                                 const int* __restrict__ faces, int n_faces, double* accum) {
   const long long f = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (f >= n_faces) return;
-  const int idx[3] = {faces[f * 3], faces[f * 3 + 1], faces[f * 3 + 2]};
-  if (idx[0] < 0 || idx[0] >= n_verts || idx[1] < 0 || idx[1] >= n_verts || idx[2] < 0 || idx[2] >= n_verts) return;
+  int idx[3];
+  if (!face_indices(faces, f, n_verts, idx)) return;
   double p[3][3];
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
@@ -96,14 +88,11 @@ __global__ __launch_bounds__(256) void paint_kernel(PaintArgs a) {
   const bool best = a.flags & SVS_PAINT_BEST;
   const size_t hw = (size_t)a.H * (size_t)a.W;
   for (int view = 0; lit && view < a.n_views; ++view) {
-    Corner c;
+    Corner c; size_t pix;
     if (!project(a.mats + (size_t)view * kMatsPerView, p, a.near, c)) continue;                      // 1
     if (!(c.x >= 0.0 && c.x <= (double)(a.W - 1) && c.y >= 0.0 && c.y <= (double)(a.H - 1))) continue;   // 2
-    const size_t pix = (size_t)(int)__builtin_floor(c.y + 0.5) * (size_t)a.W + (size_t)(int)__builtin_floor(c.x + 0.5);
-    const uint8_t* __restrict__ mask = a.mask[view];
-    if (mask && mask[pix] == 0) continue;                                                            // 3
-    const double d = (double)a.depth[(size_t)view * hw + pix];
-    if (!(d == 0.0 || c.cz <= d * (1.0 + a.rel) + a.abs_tol)) continue;                              // 4
+    if (!nearest_pixel(c, a.H, a.W, pix, true) || masked_out(a.mask[view], pix)) continue;           // 3 (inside after 2)
+    if (!not_hidden((double)a.depth[(size_t)view * hw + pix], c.cz, a.rel, a.abs_tol)) continue;     // 4
     double w = 1.0;
     if (a.normals) {                                                                                 // 5
       const double tx = eye[view][0] - (double)p[0], ty = eye[view][1] - (double)p[1], tz = eye[view][2] - (double)p[2];
@@ -144,10 +133,7 @@ __global__ __launch_bounds__(256) void paint_finish_kernel(const double* __restr
 #pragma unroll
   for (int ch = 0; ch < 3; ++ch) {
     const double c = acc[(size_t)v * 4 + ch];
-    double code = __builtin_floor(((flags & SVS_PAINT_BEST) ? c : c / w) + 0.5);
-    code = code >= 0.0 ? code : 0.0;                         // NaN too
-    code = code > 255.0 ? 255.0 : code;
-    rgb[(size_t)v * 3 + ch] = (uint8_t)(int)code;
+    rgb[(size_t)v * 3 + ch] = code_u8((flags & SVS_PAINT_BEST) ? c : c / w);
   }
   painted[v] = 1;
 }
@@ -158,8 +144,8 @@ __global__ __launch_bounds__(256) void spread_gather_kernel(const int* __restric
                                                             int* work) {
   const long long f = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (f >= n_faces) return;
-  const int idx[3] = {faces[f * 3], faces[f * 3 + 1], faces[f * 3 + 2]};
-  if (idx[0] < 0 || idx[0] >= n_verts || idx[1] < 0 || idx[1] >= n_verts || idx[2] < 0 || idx[2] >= n_verts) return;
+  int idx[3];
+  if (!face_indices(faces, f, n_verts, idx)) return;
   const int state[3] = {painted[idx[0]], painted[idx[1]], painted[idx[2]]};
 #pragma unroll
   for (int i = 0; i < 3; ++i) {
@@ -212,7 +198,7 @@ int svs_mesh_vertex_normals(const float* verts, int n_verts, const int* faces, i
 int svs_mesh_paint(const float* verts, int n_verts, const float* normals, const double* mats, int n_views, int H, int W,
                    double near, const float* depth, const uint8_t* const* images, const uint8_t* const* masks, double rel,
                    double abs_tol, double cos_min, int power, int flags, double* acc, void* hip_stream) {
-  if (int rc = meshview::check_views("svs_mesh_paint", n_views, H, W)) return rc;
+  if (int rc = check_views("svs_mesh_paint", n_views, H, W)) return rc;
   if (!(near > 0.0) || !(rel >= 0.0) || !(abs_tol >= 0.0)) {
     set_error("svs_mesh_paint: near must be positive, rel and abs_tol not negative"); return SVS_EINVAL;
   }
@@ -225,11 +211,10 @@ int svs_mesh_paint(const float* verts, int n_verts, const float* normals, const 
   if (n_verts == 0 || n_views == 0) return SVS_OK;
   if (!verts || !mats || !depth || !acc) { set_error("svs_mesh_paint: null argument"); return SVS_EINVAL; }
   PaintArgs a;
-  for (int v = 0; v < kMaxViews; ++v) {
-    a.image[v] = v < n_views ? images[v] : nullptr;
-    a.mask[v] = (masks && v < n_views) ? masks[v] : nullptr;
-    if (v < n_views && !a.image[v]) { set_error("svs_mesh_paint: view %d has no image", v); return SVS_EINVAL; }
-  }
+  view_pointers(images, n_views, a.image);
+  view_pointers(masks, n_views, a.mask);
+  for (int v = 0; v < n_views; ++v)
+    if (!a.image[v]) { set_error("svs_mesh_paint: view %d has no image", v); return SVS_EINVAL; }
   a.verts = verts; a.normals = normals; a.mats = mats; a.depth = depth; a.acc = acc;
   a.near = near; a.rel = rel; a.abs_tol = abs_tol; a.cos_min = cos_min;
   a.n_verts = n_verts; a.n_views = n_views; a.H = H; a.W = W; a.power = power; a.flags = flags;

@@ -15,12 +15,14 @@
 // pixels; larger boxes are appended to a device list, one atomic add per wave (ballot, popcount, rank).
 // raster_large_kernel: a fixed grid of waves strides that list (its length is read on the device: no host round trip),
 // the 64 lanes of a wave stride one box.  Views are the grid's y dimension.
-// All camera arithmetic is float64 without contraction, as svs_tsdf.hip does it.
+// All camera arithmetic is float64 without contraction; projection, pixel rule and face helpers are those of svs_views.h.
 #include "svs_common.h"
-#include "svs_mesh_camera.h"
+#include "svs_views.h"
 
 namespace svs {
 namespace meshview {
+
+using namespace views;
 
 constexpr int kSmallBox = 64;        // pixels of a clamped box the setting-up lane walks itself
 constexpr int kLargeBlocks = 2048;   // raster_large_kernel: 256 CUs x 8 workgroups of four waves
@@ -37,9 +39,8 @@ struct Face {
 // rules 1-5 of the header.  false: the face is skipped or its box holds no pixel.
 __device__ __forceinline__ bool setup_face(const float* __restrict__ verts, int n_verts, const int* __restrict__ faces, int f,
                                            const double* __restrict__ M, double near, int H, int W, Face& s) {
-  const int i0 = faces[(size_t)f * 3], i1 = faces[(size_t)f * 3 + 1], i2 = faces[(size_t)f * 3 + 2];
-  if (i0 < 0 || i0 >= n_verts || i1 < 0 || i1 >= n_verts || i2 < 0 || i2 >= n_verts) return false;
-  const int idx[3] = {i0, i1, i2};
+  int idx[3];
+  if (!face_indices(faces, f, n_verts, idx)) return false;
   bool ok = true;
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
@@ -49,7 +50,7 @@ __device__ __forceinline__ bool setup_face(const float* __restrict__ verts, int 
   }
   if (!ok) return false;
   s.A = (s.x[1] - s.x[0]) * (s.y[2] - s.y[0]) - (s.y[1] - s.y[0]) * (s.x[2] - s.x[0]);
-  if (!(__builtin_fabs(s.A) <= 1.7976931348623157e308) || s.A == 0.0) return false;
+  if (!finite(s.A) || s.A == 0.0) return false;
   // the box, clamped while still float64: every coordinate is finite here, the clamped ones are in [0, W-1] x [0, H-1]
   double lx = __builtin_ceil(__builtin_fmin(s.x[0], __builtin_fmin(s.x[1], s.x[2])));
   double hx = __builtin_floor(__builtin_fmax(s.x[0], __builtin_fmax(s.x[1], s.x[2])));
@@ -64,23 +65,10 @@ __device__ __forceinline__ bool setup_face(const float* __restrict__ verts, int 
   return true;
 }
 
-// rules 6-7: the barycentrics b_k = e_k / A and the float64 depth of pixel centre (ix, iy); false: not covered
-__device__ __forceinline__ bool cover(const Face& s, int ix, int iy, double* b, double& zc) {
-  const double cx = (double)ix, cy = (double)iy;
-  const double e0 = (s.x[2] - s.x[1]) * (cy - s.y[1]) - (s.y[2] - s.y[1]) * (cx - s.x[1]);
-  const double e1 = (s.x[0] - s.x[2]) * (cy - s.y[2]) - (s.y[0] - s.y[2]) * (cx - s.x[2]);
-  const double e2 = (s.x[1] - s.x[0]) * (cy - s.y[0]) - (s.y[1] - s.y[0]) * (cx - s.x[0]);
-  const bool in = s.A > 0.0 ? (e0 >= 0.0 && e1 >= 0.0 && e2 >= 0.0) : (e0 <= 0.0 && e1 <= 0.0 && e2 <= 0.0);
-  if (!in) return false;
-  b[0] = e0 / s.A; b[1] = e1 / s.A; b[2] = e2 / s.A;
-  zc = 1.0 / (b[0] / s.z[0] + b[1] / s.z[1] + b[2] / s.z[2]);
-  return true;
-}
-
-// rules 8-9 -> 1 when an atomic was issued
+// rules 6-9 -> 1 when an atomic was issued
 __device__ __forceinline__ int pixel(const Face& s, int ix, int iy, unsigned id, unsigned long long* __restrict__ zview, int W) {
   double b[3], zc;
-  if (!cover(s, ix, iy, b, zc)) return 0;
+  if (!barycentrics(s.x, s.y, s.z, s.A, ix, iy, b, zc)) return 0;
   const float zf = (float)zc;
   if (!(zf > 0.0f) || zf == __builtin_inff()) return 0;    // NaN, <= 0 (an underflow), inf: no key
   const unsigned long long key = ((unsigned long long)__float_as_uint(zf) << 32) | id;
@@ -198,14 +186,13 @@ __global__ __launch_bounds__(256) void resolve_kernel(ResolveArgs a) {
   if (!a.normal && !a.shade) return;
   const long long f = (long long)id - (long long)a.face_base;
   if (f < 0 || f >= a.n_faces) return;                       // another call's mesh: left untouched
-  const int i0 = a.faces[f * 3], i1 = a.faces[f * 3 + 1], i2 = a.faces[f * 3 + 2];
-  if (i0 < 0 || i0 >= a.n_verts || i1 < 0 || i1 >= a.n_verts || i2 < 0 || i2 >= a.n_verts) return;
+  int idx[3];
+  if (!face_indices(a.faces, f, a.n_verts, idx)) return;
   const long long hw = (long long)a.H * a.W;
   const int view = (int)(p / hw);
   const long long q = p - (long long)view * hw;
   const int iy = (int)(q / a.W), ix = (int)(q - (long long)iy * a.W);
   const double* __restrict__ M = a.mats + (size_t)view * kMatsPerView;
-  const int idx[3] = {i0, i1, i2};
   Corner c[3];
   Face s;
 #pragma unroll
@@ -218,7 +205,7 @@ __global__ __launch_bounds__(256) void resolve_kernel(ResolveArgs a) {
   const double vx = c[2].cx - c[0].cx, vy = c[2].cy - c[0].cy, vz = c[2].cz - c[0].cz;
   double nx = uy * vz - uz * vy, ny = uz * vx - ux * vz, nz = ux * vy - uy * vx;
   const double len = __builtin_sqrt(nx * nx + ny * ny + nz * nz);
-  const bool unit = len > 0.0 && len <= 1.7976931348623157e308;
+  const bool unit = len > 0.0 && len <= kBig;
   nx = unit ? nx / len : 0.0; ny = unit ? ny / len : 0.0; nz = unit ? nz / len : 0.0;
   if (nz > 0.0) { nx = -nx; ny = -ny; nz = -nz; }
   if (a.normal) { a.normal[p * 3] = (float)nx; a.normal[p * 3 + 1] = (float)ny; a.normal[p * 3 + 2] = (float)nz; }
@@ -228,25 +215,16 @@ __global__ __launch_bounds__(256) void resolve_kernel(ResolveArgs a) {
   if (a.vert_rgb) {
     s.A = (s.x[1] - s.x[0]) * (s.y[2] - s.y[0]) - (s.y[1] - s.y[0]) * (s.x[2] - s.x[0]);
     // b_k and zc again, whether or not float64 noise still calls the pixel covered (svs_mesh_raster did)
-    const double cx = (double)ix, cy = (double)iy;
-    const double e0 = (s.x[2] - s.x[1]) * (cy - s.y[1]) - (s.y[2] - s.y[1]) * (cx - s.x[1]);
-    const double e1 = (s.x[0] - s.x[2]) * (cy - s.y[2]) - (s.y[0] - s.y[2]) * (cx - s.x[2]);
-    const double e2 = (s.x[1] - s.x[0]) * (cy - s.y[0]) - (s.y[1] - s.y[0]) * (cx - s.x[0]);
-    const double b[3] = {e0 / s.A, e1 / s.A, e2 / s.A};
-    const double zc = 1.0 / (b[0] / s.z[0] + b[1] / s.z[1] + b[2] / s.z[2]);
+    double b[3], zc;
+    barycentrics(s.x, s.y, s.z, s.A, ix, iy, b, zc);
     const double w0 = b[0] / s.z[0] * zc, w1 = b[1] / s.z[1] * zc, w2 = b[2] / s.z[2] * zc;
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch)
-      col[ch] = w0 * ((double)a.vert_rgb[(size_t)i0 * 3 + ch] / 255.0) + w1 * ((double)a.vert_rgb[(size_t)i1 * 3 + ch] / 255.0) +
-                w2 * ((double)a.vert_rgb[(size_t)i2 * 3 + ch] / 255.0);
+      col[ch] = w0 * ((double)a.vert_rgb[(size_t)idx[0] * 3 + ch] / 255.0) + w1 * ((double)a.vert_rgb[(size_t)idx[1] * 3 + ch] / 255.0) +
+                w2 * ((double)a.vert_rgb[(size_t)idx[2] * 3 + ch] / 255.0);
   }
 #pragma unroll
-  for (int ch = 0; ch < 3; ++ch) {
-    double code = __builtin_floor(255.0 * (g * col[ch]) + 0.5);
-    code = code >= 0.0 ? code : 0.0;                         // NaN too
-    code = code > 255.0 ? 255.0 : code;
-    a.shade[p * 3 + ch] = (uint8_t)(int)code;
-  }
+  for (int ch = 0; ch < 3; ++ch) a.shade[p * 3 + ch] = code_u8(255.0 * (g * col[ch]));
 }
 
 struct VisibilityArgs {
@@ -265,15 +243,11 @@ __global__ __launch_bounds__(256) void visibility_kernel(VisibilityArgs a) {
   if (v >= a.n_verts) return;
   int seen = 0, off = 0;
   for (int view = 0; view < a.n_views; ++view) {
-    Corner c;
-    if (!project(a.mats + (size_t)view * kMatsPerView, a.verts + (size_t)v * 3, a.near, c)) continue;
-    const double fu = __builtin_floor(c.x + 0.5), fv = __builtin_floor(c.y + 0.5);
-    if (!(fu >= 0.0 && fu < (double)a.W && fv >= 0.0 && fv < (double)a.H)) continue;
-    const size_t pix = (size_t)(int)fv * (size_t)a.W + (size_t)(int)fu;
-    const uint8_t* __restrict__ mask = a.mask[view];
-    if (mask && mask[pix] == 0) { ++off; continue; }
+    Corner c; size_t pix;
+    if (!project(a.mats + (size_t)view * kMatsPerView, a.verts + (size_t)v * 3, a.near, c) || !nearest_pixel(c, a.H, a.W, pix)) continue;
+    if (masked_out(a.mask[view], pix)) { ++off; continue; }
     const double d = (double)a.depth[(size_t)view * (size_t)a.H * (size_t)a.W + pix];
-    if (d == 0.0 || c.cz <= d * (1.0 + a.rel) + a.abs_tol) ++seen;
+    if (not_hidden(d, c.cz, a.rel, a.abs_tol)) ++seen;
   }
   a.seen[v] += seen;
   a.off_mask[v] += off;
@@ -345,7 +319,7 @@ int svs_mesh_vertex_visibility(const float* verts, int n_verts, const double* ma
   if (!verts || !mats || !depth || !seen || !off_mask) { set_error("svs_mesh_vertex_visibility: null argument"); return SVS_EINVAL; }
   VisibilityArgs a;
   a.verts = verts; a.mats = mats; a.depth = depth; a.seen = seen; a.off_mask = off_mask;
-  for (int v = 0; v < kMaxViews; ++v) a.mask[v] = (masks && v < n_views) ? masks[v] : nullptr;
+  view_pointers(masks, n_views, a.mask);
   a.near = near; a.rel = rel; a.abs_tol = abs_tol; a.n_verts = n_verts; a.n_views = n_views; a.H = H; a.W = W;
   visibility_kernel<<<(n_verts + 255) / 256, 256, 0, (hipStream_t)hip_stream>>>(a);
   return check_launch("svs_mesh_vertex_visibility");

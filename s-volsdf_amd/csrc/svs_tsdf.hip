@@ -8,14 +8,14 @@
 // (a group may run over a row end; every voxel carries its own (i,j,k)), a scalar group at the end.  The camera matrices
 // are read with a view index that is uniform over the wave (scalar loads), the depth maps and images are gathers that
 // neighbouring voxels share.  40 B of volume traffic per observed voxel with colours, 16 B without; no LDS, no atomics.
-// All camera arithmetic is float64 without contraction, as svs_fusion.hip does it.
+// All camera arithmetic is float64 without contraction; the projection and the pixel rule are those of svs_views.h.
 #include "svs_common.h"
+#include "svs_views.h"
 
 namespace svs {
 namespace tsdf {
 
-constexpr int kMaxViews = 16;
-constexpr int kMatsPerView = 21;     // K(9) row-major, then rows 0..2 of E(12), float64
+using namespace views;
 constexpr int kGroup = 4;            // voxels per lane
 
 struct IntegrateArgs {
@@ -80,27 +80,17 @@ __global__ __launch_bounds__(256) void integrate_kernel(IntegrateArgs a) {
 
   for (int v = 0; v < a.n_views; ++v) {
     const double* __restrict__ M = a.mats + (size_t)v * kMatsPerView;      // uniform over the wave
-    const double* __restrict__ E = M + 9;
     const float* __restrict__ depth = a.depth[v];
     const uint8_t* __restrict__ mask = a.mask[v];
     const float* __restrict__ img = a.img[v];
 #pragma unroll
     for (int e = 0; e < kGroup; ++e) {
       if (e >= count) continue;
-      const double cx = E[0] * px[e] + E[1] * py[e] + E[2] * pz[e] + E[3];
-      const double cy = E[4] * px[e] + E[5] * py[e] + E[6] * pz[e] + E[7];
-      const double cz = E[8] * px[e] + E[9] * py[e] + E[10] * pz[e] + E[11];
-      if (!(cz > 0.0)) continue;
-      const double qx = M[0] * cx + M[1] * cy + M[2] * cz;
-      const double qy = M[3] * cx + M[4] * cy + M[5] * cz;
-      const double qz = M[6] * cx + M[7] * cy + M[8] * cz;
-      const double fu = __builtin_floor(qx / qz + 0.5), fv = __builtin_floor(qy / qz + 0.5);
-      if (!(fu >= 0.0 && fu < (double)a.W && fv >= 0.0 && fv < (double)a.H)) continue;       // NaN fails too
-      const size_t pix = (size_t)(int)fv * (size_t)a.W + (size_t)(int)fu;
-      if (mask && mask[pix] == 0) continue;
+      Corner c; size_t pix;
+      if (!project(M, px[e], py[e], pz[e], 0.0, c) || !nearest_pixel(c, a.H, a.W, pix) || masked_out(mask, pix)) continue;
       const float d = depth[pix];
       if (!(d > 0.0f) || d == __builtin_inff()) continue;                                     // NaN, <= 0, inf
-      const double sdf = (double)d - cz;
+      const double sdf = (double)d - c.cz;
       if (sdf < -a.trunc) continue;
       const double t = sdf / a.trunc;
       st[e] += t < 1.0 ? t : 1.0;
@@ -228,13 +218,11 @@ int svs_tsdf_integrate(float* tsdf_vol, float* weight, float* rgb, int n0, int n
   if (n_views == 0) return SVS_OK;
   IntegrateArgs a;
   a.tsdf = tsdf_vol; a.weight = weight; a.rgb = rgb; a.mats = mats;
-  for (int v = 0; v < kMaxViews; ++v) { a.depth[v] = nullptr; a.mask[v] = nullptr; a.img[v] = nullptr; }
-  for (int v = 0; v < n_views; ++v) {
-    if (!depths[v] || (rgb && !images[v])) { set_error("svs_tsdf_integrate: null depth map or image of view %d", v); return SVS_EINVAL; }
-    a.depth[v] = depths[v];
-    a.mask[v] = masks ? masks[v] : nullptr;
-    a.img[v] = rgb ? images[v] : nullptr;
-  }
+  view_pointers(depths, n_views, a.depth);
+  view_pointers(masks, n_views, a.mask);
+  view_pointers(rgb ? images : nullptr, n_views, a.img);
+  for (int v = 0; v < n_views; ++v)
+    if (!a.depth[v] || (rgb && !a.img[v])) { set_error("svs_tsdf_integrate: null depth map or image of view %d", v); return SVS_EINVAL; }
   a.n1 = n1; a.n2 = n2; a.total = (long long)n0 * n1 * n2;
   a.n_views = n_views; a.H = H; a.W = W;
   a.vec_tw = (((uintptr_t)tsdf_vol | (uintptr_t)weight) & 15u) == 0;

@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from . import clouds, ply
-from .images import tick, to_device
+from .images import seconds_line, tick, to_device
 
 PHASES = ("read", "fuse", "outliers", "compact", "normals", "download", "write")
 
@@ -156,7 +156,7 @@ def main(argv=None):
         res = clean_folder(a.scan_folder, a.out_folder, a.views, a.ply_out, eval_mask_root=a.data_dir_root, dataset=a.dataset, **kw)
     s = res["stats"]
     print(f"points in {s['points_in']}, points kept {s['points_kept']}, threshold {s['threshold']:.6g}", flush=True)
-    print("seconds: " + ", ".join(f"{k_} {v:.3f}" for k_, v in s["seconds"].items()), flush=True)
+    print(seconds_line(s["seconds"]), flush=True)
     print(f"saving the cleaned cloud to {s['file']}", flush=True)
     return res
 

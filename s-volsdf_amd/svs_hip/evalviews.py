@@ -27,7 +27,7 @@ import torch
 
 from . import lib as _lib
 from . import scene as _scene
-from .images import device
+from .images import device, seconds_line
 from .ops import _f32, _ptr, _stream
 from .renderer import render_image
 from .scans import DATASETS, IMG_RES, get_eval_ids, get_trains_ids
@@ -296,7 +296,7 @@ def evaluate(ckpt, data_dir_root, dataset, scan, img_res=IMG_RES, evals_folder="
     log(f"{len(views)} images (including train)")
     written = render_views(model, ds, views, folder, split_n_pixels=split_n_pixels, fast=fast, rank=rank, world=world,
                            seconds=sec)
-    log("seconds: " + ", ".join(f"{k} {v:.3f}" for k, v in sec.items()))
+    log(seconds_line(sec))
     res = dict(folder=folder, epoch=epoch, views=views, written=written, seconds=sec, scores=None)
     if rank != 0:
         return res

@@ -51,8 +51,11 @@ class Phases:
         return time.perf_counter()
 
     def summary(self, total):
-        return ("seconds: " + ", ".join(f"{k} {v:.3f}" for k, v in self.s.items()) + f", total {total:.3f}; "
-                f"{self.bytes_up / 1e6:.1f} MB up, {self.bytes_down / 1e6:.1f} MB down")
+        return seconds_line(self.s) + f", total {total:.3f}; {self.bytes_up / 1e6:.1f} MB up, {self.bytes_down / 1e6:.1f} MB down"
+
+
+def seconds_line(timers):
+    return "seconds: " + ", ".join(f"{k} {v:.3f}" for k, v in timers.items())
 
 
 def tick(timers, name, t0):

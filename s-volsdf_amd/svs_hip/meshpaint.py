@@ -27,10 +27,11 @@ import torch
 from . import lib as _lib
 from . import meshview as _mv
 from . import ply as _ply
-from .images import read_rgb8, tick, to_device
+from .images import seconds_line, tick, to_device
 from .ops import _ptr, _ptr_array, _stream
+from .views import (MAX_VIEWS, add_eval_mask_args, check_eval_mask_args, chunks, device_masks, folder_cameras, folder_images,
+                    folder_masks, launches_since, mesh_args)
 
-MAX_VIEWS = _mv.MAX_VIEWS
 FACE_CHUNK = 1 << 24                 # faces per call of svs_mesh_vertex_normals
 ENTRY_CALLS = {"normals": 0, "paint": 0, "finish": 0, "spread": 0}  # C entry points called, not kernels
 RULES = dict(cos_min=0.1, power=2, one_sided=False, use_normals=True, rel=0.01, abs_tol=0.0, near=1e-6)
@@ -54,7 +55,7 @@ def vertex_normals(verts, faces, chunk=FACE_CHUNK, accum=None):
     """verts (V,3), faces (F,3): arrays or device tensors -> (V,3) float32 device tensor: the area-weighted unit normal of
     every vertex, (0,0,0) where no valid face meets it.  The faces go in chunks of `chunk`; accum: a zeroed (V,3) float64
     device tensor that keeps the unnormalised sums."""
-    verts, faces, _ = _mv._mesh_args(verts, faces)
+    verts, faces, _ = mesh_args(verts, faces)
     if accum is None:
         accum = torch.zeros((verts.shape[0], 3), dtype=torch.float64, device=verts.device)
     normals = torch.zeros((verts.shape[0], 3), dtype=torch.float32, device=verts.device)
@@ -93,28 +94,13 @@ def _images(images, n_views):
     return out
 
 
-def _masks(masks, n_views, H, W, dev):
-    if masks is None:
-        return None
-    out = []
-    for m in masks:
-        if m is not None:
-            m = (torch.as_tensor(m).to(dev) != 0).to(torch.uint8).contiguous()
-            if tuple(m.shape) != (H, W):
-                raise ValueError(f"svs_mesh_paint: a mask of {tuple(m.shape)} for views of {(H, W)}")
-        out.append(m)
-    if len(out) != n_views:
-        raise ValueError(f"svs_mesh_paint: {len(out)} masks for {n_views} views")
-    return out
-
-
 def accumulate(verts, faces, views, images, masks=None, *, normals=None, flags=0, cos_min=0.1, power=2, rel=0.01, abs_tol=0.0,
                near=1e-6, depth=None, seen=None, timers=None):
     """The views in chunks of MAX_VIEWS: each chunk is rasterised (`meshview.rasterize`, unless depth (n_views,H,W) is
     given) and painted before the next, so the device holds MAX_VIEWS z-buffers at a time.  normals: (V,3) float32 or
     None (every view weighs 1).  seen: a zeroed (V,) int32 tensor that gets `meshview.visibility`'s count of the views
     that pass the mask and the depth test.  -> acc (V,4) float64: (r, g, b, w) as svs_mesh_paint leaves them."""
-    verts, faces, _ = _mv._mesh_args(verts, faces)
+    verts, faces, _ = mesh_args(verts, faces)
     views = list(views)
     _check_rules(cos_min, power, rel, abs_tol, near)
     if not views:
@@ -122,7 +108,7 @@ def accumulate(verts, faces, views, images, masks=None, *, normals=None, flags=0
     dev = verts.device
     images = _images(images, len(views))
     H, W = int(images[0].shape[0]), int(images[0].shape[1])
-    masks = _masks(masks, len(views), H, W, dev)
+    masks = device_masks(masks, len(views), H, W, dev, "svs_mesh_paint")
     if depth is not None:
         depth = to_device(depth, torch.float32, "meshpaint", "depth", ndim=(3,))
         if tuple(depth.shape) != (len(views), H, W):
@@ -133,11 +119,9 @@ def accumulate(verts, faces, views, images, masks=None, *, normals=None, flags=0
             raise ValueError(f"svs_mesh_paint: normals of {tuple(normals.shape)} for {verts.shape[0]} vertices")
     acc = torch.zeros((verts.shape[0], 4), dtype=torch.float64, device=dev)
     t0 = time.perf_counter()
-    for at in range(0, len(views), MAX_VIEWS):
-        to = min(at + MAX_VIEWS, len(views))
+    for at, to, mats in chunks(views, dev):
         part = depth[at:to] if depth is not None else _mv.rasterize(verts, faces, views[at:to], H, W, near=near)["depth"]
         t0 = tick(timers, "raster", t0)
-        mats = _mv._mats(views[at:to], dev)
         part_masks = masks[at:to] if masks is not None else None
         _lib.check(paint_raw(verts, normals, mats, to - at, H, W, part, images[at:to], part_masks, acc, near, rel, abs_tol,
                              cos_min, power, flags), "svs_mesh_paint")
@@ -189,7 +173,7 @@ def paint(verts, faces, views, images, masks=None, *, mode="blend", cos_min=0.1,
     hole filling, 0 = never reached (its colour is `fill`).
     stats: a dict that gets acc (V,4) float64, normals, seen (V,) int32 (views that pass the mask and depth test),
     rounds, and seconds per phase (which makes every phase wait for the device)."""
-    verts, faces, _ = _mv._mesh_args(verts, faces)
+    verts, faces, _ = mesh_args(verts, faces)
     flags = flags_of(mode, one_sided)
     _check_rules(cos_min, power, rel, abs_tol, near)
     timers = None
@@ -218,7 +202,7 @@ def consistency(verts, faces, colors, views, images, masks=None, *, cos_min=0.1,
     """How well `colors` (V,3) uint8 agree with views they were not painted from: those views are blended into fresh
     accumulators by the same rules, and over the vertices they see (acc.w > 0), channels pooled:
     -> dict(n = those vertices, mad = mean |colors - acc.rgb / acc.w| in codes, psnr = 10 log10(255^2 / mean square))"""
-    verts, faces, colors = _mv._mesh_args(verts, faces, colors)
+    verts, faces, colors = mesh_args(verts, faces, colors)
     if colors is None:
         raise ValueError("svs_mesh_paint: consistency needs colours")
     normals = vertex_normals(verts, faces) if use_normals else None
@@ -231,15 +215,6 @@ def consistency(verts, faces, colors, views, images, masks=None, *, cos_min=0.1,
     diff = colors[at].to(torch.float64) - acc[at, :3] / acc[at, 3:4]
     mse = float((diff * diff).mean())
     return dict(n=n, mad=float(diff.abs().mean()), psnr=float("inf") if mse == 0 else float(10.0 * np.log10(255.0 ** 2 / mse)))
-
-
-def folder_images(scan_folder, view_ids):
-    """[(H,W,3) uint8] from images/{id:08}.jpg at their own size; ValueError when the sizes differ"""
-    out = [read_rgb8(os.path.join(scan_folder, "images/{:0>8}.jpg".format(v))) for v in view_ids]
-    sizes = sorted({im.shape[:2] for im in out})
-    if len(sizes) > 1:
-        raise ValueError(f"svs_mesh_paint: the views have different sizes {sizes}")
-    return out
 
 
 def paint_folder(ply, scan_folder, view_ids, ply_out, holdout=(), *, mode="blend", cos_min=0.1, power=2, one_sided=False,
@@ -257,18 +232,13 @@ def paint_folder(ply, scan_folder, view_ids, ply_out, holdout=(), *, mode="blend
     rules = dict(cos_min=cos_min, power=power, one_sided=one_sided, use_normals=use_normals, rel=rel, abs_tol=abs_tol, near=near)
     t0 = time.perf_counter()
     verts, faces = _ply.read_mesh(ply)
-    views = _mv.folder_cameras(scan_folder, view_ids + holdout)
+    views = folder_cameras(scan_folder, view_ids + holdout)
     images = folder_images(scan_folder, view_ids + holdout)
     H, W = images[0].shape[:2]
-    masks = None
-    if eval_mask_root is not None:
-        from . import mvsout
-        scan_name = os.path.normpath(scan_folder).split(os.sep)[-1]
-        by_view = mvsout.folder_eval_masks(eval_mask_root, dataset, scan_name, view_ids + holdout,
-                                           {v: (H, W) for v in view_ids + holdout}, radius=eval_mask_radius)
-        masks = [by_view[v] for v in view_ids + holdout]
+    masks = folder_masks(eval_mask_root, dataset, os.path.normpath(scan_folder).split(os.sep)[-1], view_ids + holdout,
+                         H, W, eval_mask_radius)
     t0 = tick(sec, "read", t0)
-    verts_d, faces_d, _ = _mv._mesh_args(verts, faces)
+    verts_d, faces_d, _ = mesh_args(verts, faces)
     images_d = [to_device(im, torch.uint8, "meshpaint", "image") for im in images]
     t0 = tick(sec, "upload", t0)
     n = len(view_ids)
@@ -290,7 +260,7 @@ def paint_folder(ply, scan_folder, view_ids, ply_out, holdout=(), *, mode="blend
         stats.pop(k)
     stats.update(files=dict(ply=ply_out), n_verts=len(verts), n_faces=len(faces), painted=np.bincount(host_p)[1:].tolist(),
                  unpainted=int((host_p == 0).sum()), views=np.bincount(host_seen, minlength=n + 1).tolist(), holdout=score,
-                 launches={k: ENTRY_CALLS[k] - calls[k] for k in ENTRY_CALLS})
+                 launches=launches_since(ENTRY_CALLS, calls))
     if log is not None:
         log(f"meshpaint: {ply} ({len(verts)} vertices, {len(faces)} faces) from {n} views of {H} x {W}: painted per round "
             + " ".join(map(str, stats["painted"])) + f", {stats['unpainted']} never reached; seen by k views: "
@@ -298,7 +268,7 @@ def paint_folder(ply, scan_folder, view_ids, ply_out, holdout=(), *, mode="blend
         if score is not None:
             log(f"held-out views {' '.join(map(str, holdout))}: {score['n']} vertices, mean |difference| {score['mad']:.3f} codes, "
                 f"PSNR {score['psnr']:.2f} dB")
-        log("seconds: " + ", ".join(f"{k} {s:.3f}" for k, s in sec.items()))
+        log(seconds_line(sec))
     return colors, painted, stats
 
 
@@ -319,11 +289,9 @@ def parse_args(argv=None):
     p.add_argument("--abs-tol", type=float, default=RULES["abs_tol"], help="absolute depth tolerance of the visibility test")
     p.add_argument("--spread-rounds", type=int, default=None, help="rounds of hole filling (default: until nothing changes; 0: none)")
     p.add_argument("--fill", type=int, nargs=3, default=[128, 128, 128], metavar=("R", "G", "B"), help="the colour of what is never reached")
-    p.add_argument("--data-dir-root", default=None, help="with --dataset: the evaluation masks cut the photographs")
-    p.add_argument("--dataset", default=None, choices=("DTU", "BlendedMVS"))
+    add_eval_mask_args(p, "the evaluation masks cut the photographs")
     a = p.parse_args(argv)
-    if (a.data_dir_root is None) != (a.dataset is None):
-        p.error("--data-dir-root and --dataset come together")
+    check_eval_mask_args(p, a)
     if not (0 <= a.cos_min <= 1) or not (0 <= a.power <= 8):
         p.error("--cos-min lies in [0,1] and --power in [0,8]")
     if a.rel < 0 or a.abs_tol < 0 or (a.spread_rounds is not None and a.spread_rounds < 0) or not all(0 <= c <= 255 for c in a.fill):

@@ -24,12 +24,11 @@ import torch
 from . import lib as _lib
 from . import mesh as _mesh
 from . import ply as _ply
-from .images import device as _device
-from .images import tick, to_device
+from .images import device as _device, seconds_line, tick, to_device
 from .ops import _ptr, _ptr_array, _stream
-from .tsdf import view_matrices
+from .views import (MAX_VIEWS, add_eval_mask_args, check_eval_mask_args, chunks, device_masks, folder_cameras, folder_masks,
+                    folder_size, launches_since, mesh_args)
 
-MAX_VIEWS = 16                       # views per launch (csrc/svs_meshview.hip kMaxViews)
 FACE_CHUNK = 1 << 22                 # faces per call of svs_mesh_raster: bounds the list of the large path (256 MiB at 16 views)
 WORK_HEAD = 4                        # ints of the work buffer in front of that list
 FLAG_COUNT, FLAG_SMALL_ONLY, FLAG_LARGE_ONLY = 1, 2, 4
@@ -45,10 +44,6 @@ def new_zbuf(n_views, H, W, device=None):
     """(n_views,H,W) int64 device tensor of all-ones bits: the empty buffer svs_mesh_raster folds faces into"""
     dev = _device("meshview") if device is None else torch.device(device)
     return torch.full((int(n_views), int(H), int(W)), -1, dtype=torch.int64, device=dev)
-
-
-def _mats(views, dev):
-    return torch.from_numpy(np.ascontiguousarray(np.stack([view_matrices(v["K"], v["E"]) for v in views]))).to(dev)
 
 
 def raster_raw(zbuf, verts, faces, mats, n_views, H, W, near=1e-6, face_base=0, work=None, flags=0):
@@ -100,32 +95,18 @@ def resolve(zbuf, verts, faces, mats, face_base=0, colors=None, normals=False, s
     return res
 
 
-def _mesh_args(verts, faces, colors=None):
-    verts = to_device(verts, torch.float32, "meshview", "verts")
-    faces = to_device(faces, torch.int32, "meshview", "faces")
-    if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
-        raise ValueError(f"meshview: a mesh is verts (V,3) and faces (F,3), got {tuple(verts.shape)} and {tuple(faces.shape)}")
-    if colors is not None:
-        colors = to_device(colors, torch.uint8, "meshview", "colors")
-        if tuple(colors.shape) != (verts.shape[0], 3):
-            raise ValueError(f"svs_mesh_raster_resolve: {tuple(colors.shape)} colours for {verts.shape[0]} vertices")
-    return verts, faces, colors
-
-
 def rasterize(verts, faces, views, H, W, near=1e-6, colors=None, normals=False, shade=False, stats=None):
     """verts (V,3), faces (F,3), colors (V,3) uint8 or None: arrays or device tensors; views: dicts of K (3,3), E (4,4).
     -> dict of device tensors: depth (n,H,W) float32 (camera z, 0 where empty), face (n,H,W) int32 (-1 where empty)
     [, normal (n,H,W,3) float32 towards the camera, shade (n,H,W,3) uint8].  MAX_VIEWS views per launch."""
-    verts, faces, colors = _mesh_args(verts, faces, colors)
+    verts, faces, colors = mesh_args(verts, faces, colors)
     views = list(views)
     if not (near > 0):
         raise ValueError(f"svs_mesh_raster: near must be positive, got {near}")
     H, W = int(H), int(W)
     parts = []
-    for at in range(0, len(views), MAX_VIEWS):
-        chunk = views[at:at + MAX_VIEWS]
-        mats = _mats(chunk, verts.device)
-        zbuf = raster_into(new_zbuf(len(chunk), H, W, verts.device), verts, faces, mats, near, stats=stats)
+    for at, to, mats in chunks(views, verts.device):
+        zbuf = raster_into(new_zbuf(to - at, H, W, verts.device), verts, faces, mats, near, stats=stats)
         parts.append(resolve(zbuf, verts, faces, mats, colors=colors, normals=normals, shade=shade))
     if not parts:
         raise ValueError("svs_mesh_raster: no views")
@@ -153,23 +134,12 @@ def visibility(verts, views, depth, masks=None, rel=0.01, abs_tol=0.0, near=1e-6
     if rel < 0 or abs_tol < 0 or not (near > 0):
         raise ValueError(f"svs_mesh_vertex_visibility: near must be positive, rel and abs_tol not negative, got {near}, {rel}, {abs_tol}")
     H, W = int(depth.shape[1]), int(depth.shape[2])
-    dev_masks = None
-    if masks is not None:
-        dev_masks = []
-        for m in masks:
-            if m is not None:
-                m = (torch.as_tensor(m).to(verts.device) != 0).to(torch.uint8).contiguous()
-                if tuple(m.shape) != (H, W):
-                    raise ValueError(f"svs_mesh_vertex_visibility: a mask of {tuple(m.shape)} for views of {(H, W)}")
-            dev_masks.append(m)
-        if len(dev_masks) != len(views):
-            raise ValueError(f"svs_mesh_vertex_visibility: {len(dev_masks)} masks for {len(views)} views")
+    dev_masks = device_masks(masks, len(views), H, W, verts.device, "svs_mesh_vertex_visibility")
     seen = torch.zeros(verts.shape[0], dtype=torch.int32, device=verts.device)
     off_mask = torch.zeros_like(seen)
-    for at in range(0, len(views), MAX_VIEWS):
-        to = min(at + MAX_VIEWS, len(views))
-        rc = visibility_raw(verts, _mats(views[at:to], verts.device), to - at, H, W, depth[at:to],
-                            dev_masks[at:to] if dev_masks is not None else None, rel, abs_tol, seen, off_mask, near)
+    for at, to, mats in chunks(views, verts.device):
+        rc = visibility_raw(verts, mats, to - at, H, W, depth[at:to], dev_masks[at:to] if dev_masks is not None else None,
+                            rel, abs_tol, seen, off_mask, near)
         _lib.check(rc, "svs_mesh_vertex_visibility")
     return seen, off_mask
 
@@ -199,16 +169,6 @@ def cull(verts, faces, seen, off_mask=None, min_views=1, max_off_mask=None, mode
 _cull = cull                         # view_folder's switch has the rule's name
 
 
-def folder_cameras(scan_folder, view_ids):
-    """[dict(K, E)] from cams/{id:08}_cam.txt"""
-    from helpers.utils import read_camera_parameters
-    out = []
-    for v in view_ids:
-        K, E = read_camera_parameters(os.path.join(scan_folder, "cams/{:0>8}_cam.txt".format(v)))
-        out.append(dict(K=K, E=E))
-    return out
-
-
 def view_folder(ply, scan_folder, out_folder, view_ids, size=None, cull=False, min_views=1, max_off_mask=None, mode="all",
                 rel=0.01, abs_tol=0.0, near=1e-6, ply_out=None, *, eval_mask_root=None, dataset=None, eval_mask_radius=12,
                 log=None):
@@ -228,23 +188,12 @@ def view_folder(ply, scan_folder, out_folder, view_ids, size=None, cull=False, m
     colors = _ply.read_points(ply)[1]
     views = folder_cameras(scan_folder, view_ids)
     if size is None:
-        sizes = set()
-        for v in view_ids:
-            with Image.open(os.path.join(scan_folder, "images/{:0>8}.jpg".format(v))) as im:
-                sizes.add((im.height, im.width))
-        if len(sizes) != 1:
-            raise ValueError(f"svs_mesh_raster: the views have different sizes {sorted(sizes)}")
-        size = sizes.pop()
+        size = folder_size(scan_folder, view_ids, "svs_mesh_raster")
     H, W = int(size[0]), int(size[1])
-    masks = None
-    if eval_mask_root is not None:
-        from . import mvsout
-        scan_name = os.path.normpath(out_folder).split(os.sep)[-1]
-        by_view = mvsout.folder_eval_masks(eval_mask_root, dataset, scan_name, view_ids, {v: (H, W) for v in view_ids},
-                                           radius=eval_mask_radius)
-        masks = [by_view[v] for v in view_ids]
+    masks = folder_masks(eval_mask_root, dataset, os.path.normpath(out_folder).split(os.sep)[-1], view_ids, H, W,
+                         eval_mask_radius)
     t0 = tick(sec, "read", t0)
-    verts_d, faces_d, colors_d = _mesh_args(verts, faces, colors)
+    verts_d, faces_d, colors_d = mesh_args(verts, faces, colors)
     t0 = tick(sec, "upload", t0)
     res = rasterize(verts_d, faces_d, views, H, W, near=near, colors=colors_d, shade=True)
     t0 = tick(sec, "raster", t0)
@@ -273,11 +222,11 @@ def view_folder(ply, scan_folder, out_folder, view_ids, size=None, cull=False, m
     tick(sec, "write", t0)
     stats = dict(files=files, n_verts=len(verts), n_faces=len(faces), covered=[int((d > 0).sum()) for d in depth],
                  faces_kept=None if kept is None else len(kept[1]),
-                 launches={k: ENTRY_CALLS[k] - calls[k] for k in ENTRY_CALLS}, seconds=sec)
+                 launches=launches_since(ENTRY_CALLS, calls), seconds=sec)
     if log is not None:
         log(f"meshview: {ply} ({len(verts)} vertices, {len(faces)} faces) into {len(view_ids)} views of {H} x {W}: covered "
             + " ".join(str(c) for c in stats["covered"]) + (f"; {stats['faces_kept']} faces kept -> {files['ply']}" if kept else ""))
-        log("seconds: " + ", ".join(f"{k} {s:.3f}" for k, s in sec.items()))
+        log(seconds_line(sec))
     return res, stats
 
 
@@ -296,11 +245,9 @@ def parse_args(argv=None):
     p.add_argument("--rel", type=float, default=0.01, help="relative depth tolerance of the visibility test")
     p.add_argument("--abs-tol", type=float, default=0.0, help="absolute depth tolerance of the visibility test")
     p.add_argument("--ply-out", default=None, help="the culled mesh (default: {out_folder}/mesh_culled.ply)")
-    p.add_argument("--data-dir-root", default=None, help="with --dataset: the evaluation masks count towards --max-off-mask")
-    p.add_argument("--dataset", default=None, choices=("DTU", "BlendedMVS"))
+    add_eval_mask_args(p, "the evaluation masks count towards --max-off-mask")
     a = p.parse_args(argv)
-    if (a.data_dir_root is None) != (a.dataset is None):
-        p.error("--data-dir-root and --dataset come together")
+    check_eval_mask_args(p, a)
     return a
 
 

@@ -28,23 +28,14 @@ from . import lib as _lib
 from . import fusion
 from . import mesh as _mesh
 from . import ply as _ply
-from .images import device as _device
-from .images import tick, to_device
+from .images import device as _device, seconds_line, tick, to_device
 from .ops import _f32, _ptr, _ptr_array, _stream
+from .views import MAX_VIEWS, add_eval_mask_args, check_eval_mask_args, chunks, device_masks, view_matrices
 
-MAX_VIEWS = 16                       # views per launch (csrc/svs_tsdf.hip kMaxViews)
 TRUNC_VOXELS = 3.0                   # the default truncation distance in voxels
 MAX_VOXELS = 1 << 30
 ENTRY_CALLS = {"integrate": 0, "keep": 0, "colors": 0}      # C entry points called, not kernels
 _D3 = ctypes.c_double * 3
-
-
-def view_matrices(K, E):
-    """(21,) float64: K row-major, then the top three rows of E"""
-    K, E = np.asarray(K, np.float64), np.asarray(E, np.float64)
-    if K.shape != (3, 3) or E.shape != (4, 4):
-        raise ValueError(f"a view has K (3,3) and E (4,4), got {K.shape} and {E.shape}")
-    return np.concatenate([K.reshape(-1), E[:3].reshape(-1)])
 
 
 def integrate_raw(tsdf, weight, rgb, origin, voxel, trunc, depths, masks, images, mats, H, W):
@@ -115,16 +106,10 @@ class Volume:
             return self
         depths = [to_device(v["depth"], torch.float32, "tsdf") for v in views]
         H, W = depths[0].shape
-        masks, images = [], []
+        images = []
         for v, d in zip(views, depths):
             if tuple(d.shape) != (H, W):
                 raise AssertionError("depth map shapes differ between the views")
-            m = v.get("mask")
-            if m is not None:
-                m = (torch.as_tensor(m).to(self.tsdf.device) != 0).to(torch.uint8).contiguous()
-            if m is not None and tuple(m.shape) != (H, W):
-                raise AssertionError("mask shape differs from its depth map's")
-            masks.append(m)
             if self.rgb is not None:
                 if v.get("img") is None:
                     raise ValueError("a volume with colours needs every view's img")
@@ -132,10 +117,9 @@ class Volume:
                 if tuple(img.shape) != (H, W, 3):
                     raise AssertionError("image shape differs from its depth map's")
                 images.append(img)
-        mats = np.stack([view_matrices(v["K"], v["E"]) for v in views])
-        for at in range(0, len(views), MAX_VIEWS):
-            to = min(at + MAX_VIEWS, len(views))
-            mats_d = torch.from_numpy(np.ascontiguousarray(mats[at:to])).to(self.tsdf.device)
+        masks = device_masks([v.get("mask") for v in views], len(views), H, W, self.tsdf.device, "svs_tsdf_integrate",
+                             AssertionError)
+        for at, to, mats_d in chunks(views, self.tsdf.device):
             rc = integrate_raw(self.tsdf, self.weight, self.rgb, self.origin, self.voxel, self.trunc, depths[at:to], masks[at:to],
                                images[at:to] if self.rgb is not None else None, mats_d, H, W)
             _lib.check(rc, "svs_tsdf_integrate")
@@ -238,7 +222,7 @@ def fuse_folder(scan_folder, out_folder, view_ids, voxel, trunc=None, ply=None, 
     stats = dict(file=ply, shape=shape, origin=origin, n_verts=len(v), n_faces=len(f), launches=vol.launches, seconds=sec)
     if log is not None:
         log(f"tsdf: {ply} ({len(v)} vertices, {len(f)} faces, volume {shape[0]} x {shape[1]} x {shape[2]})")
-        log("seconds: " + ", ".join(f"{k} {s:.3f}" for k, s in sec.items()))
+        log(seconds_line(sec))
     return v, f, c, stats
 
 
@@ -257,11 +241,9 @@ def parse_args(argv=None):
     p.add_argument("--largest", action="store_true", help="keep the largest component by area")
     p.add_argument("--ply", default=None, help="output file (default: {out_folder}/tsdf.ply)")
     p.add_argument("--min-weight", type=float, default=1.0, help="a face survives when every node of its cell has this weight")
-    p.add_argument("--data-dir-root", default=None, help="with --dataset: cut every view by its evaluation mask")
-    p.add_argument("--dataset", default=None, choices=("DTU", "BlendedMVS"))
+    add_eval_mask_args(p, "cut every view by its evaluation mask")
     a = p.parse_args(argv)
-    if (a.data_dir_root is None) != (a.dataset is None):
-        p.error("--data-dir-root and --dataset come together")
+    check_eval_mask_args(p, a)
     return a
 
 

@@ -21,6 +21,7 @@ import meshpaint_oracle as mp
 import meshview_oracle as mv
 import tsdf_oracle as to
 from svs_hip import lib, meshpaint, meshview, tsdf
+from svs_hip import views as svs_views
 from svs_hip.lib import SvsError
 from test_gpu_meshview import VIEW_IDS, scan_folder  # noqa: F401  -- the scan folder fixture and its view ids
 
@@ -198,7 +199,7 @@ def test_two_runs_are_bit_identical():
     s = _scene(100, 200)
     views = mv.cameras(17, seed=3)
     images = _noise(17, H, W, seed=8)
-    verts, faces = meshview._mesh_args(s["verts"], s["faces"])[:2]
+    verts, faces = svs_views.mesh_args(s["verts"], s["faces"])[:2]
     normals = meshpaint.vertex_normals(verts, faces)
     depth = meshview.rasterize(verts, faces, views, H, W)["depth"]
     out = []
@@ -388,7 +389,7 @@ def test_errors(scan_folder, tmp_path):
     verts, faces = torch.from_numpy(s["verts"]).to(DEV), torch.from_numpy(s["faces"]).to(DEV)
     views = mv.cameras(17)
     images = [torch.from_numpy(im).to(DEV) for im in _noise(17, H, W)]
-    mats = meshview._mats(views, DEV)
+    mats = svs_views.mats(views, DEV)
     depth = torch.zeros((17, H, W), device=DEV)
     acc = torch.zeros((len(verts), 4), dtype=torch.float64, device=DEV)
     rc = meshpaint.paint_raw(verts, None, mats, 17, H, W, depth, images, None, acc)

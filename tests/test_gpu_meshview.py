@@ -18,6 +18,7 @@ import mesh_oracle as mo
 import meshview_oracle as mv
 import tsdf_oracle as to
 from svs_hip import lib, meshview, tsdf
+from svs_hip import views as svs_views
 from svs_hip.lib import SvsError
 
 pytestmark = pytest.mark.gpu
@@ -129,7 +130,7 @@ def test_boxes_at_the_small_threshold():
     faces = np.array([[0, 1, 2]], np.int32)
     for verts, box, on_list in ((tri64, 64, 0), (tri65, 65, 1)):
         assert mv.box_pixels(verts, faces, view["K"], view["E"], 16, 16)[0] == box
-        mats = meshview._mats([view], DEV)
+        mats = svs_views.mats([view], DEV)
         zbuf = meshview.new_zbuf(1, 16, 16)
         stats = {}
         v_d, f_d = torch.from_numpy(verts).to(DEV), torch.from_numpy(faces).to(DEV)
@@ -205,7 +206,7 @@ def test_image_sizes(size):
 def test_order_independence_and_repeatability():
     s = _scene(100, 200)
     verts, faces = torch.from_numpy(s["verts"]).to(DEV), torch.from_numpy(s["faces"]).to(DEV)
-    mats = meshview._mats(s["views"], DEV)
+    mats = svs_views.mats(s["views"], DEV)
     one = meshview.raster_into(meshview.new_zbuf(3, H, W), verts, faces, mats)
     again = meshview.raster_into(meshview.new_zbuf(3, H, W), verts, faces, mats)
     assert torch.equal(one, again)                              # two runs of the same call are bit-identical
@@ -224,7 +225,7 @@ def test_order_independence_and_repeatability():
 def test_exact_shared_edge():
     view = dict(K=mv.EXACT_K, E=np.eye(4))
     want_d, want_f = mv.exact_case_expectation()
-    mats = meshview._mats([view], DEV)
+    mats = svs_views.mats([view], DEV)
     verts = torch.from_numpy(mv.EXACT_VERTS).to(DEV)
     for faces in (mv.EXACT_FACES, mv.EXACT_FACES[:, [0, 2, 1]]):
         zbuf = meshview.new_zbuf(1, 9, 9)
@@ -251,7 +252,7 @@ def test_resolve_leaves_the_ids_of_another_calls_mesh():
     n_big = 2 * 12 * 24                                        # the large sphere's faces: mesh A; the rest: mesh B
     verts = torch.from_numpy(s["verts"]).to(DEV)
     fa, fb = (torch.from_numpy(np.ascontiguousarray(f)).to(DEV) for f in (s["faces"][:n_big], s["faces"][n_big:]))
-    mats = meshview._mats(s["views"], DEV)
+    mats = svs_views.mats(s["views"], DEV)
     zbuf = meshview.new_zbuf(3, H, W)
     meshview.raster_into(zbuf, verts, fb, mats, face_base=n_big)
     meshview.raster_into(zbuf, verts, fa, mats)
@@ -506,7 +507,7 @@ def test_errors(scan_folder, tmp_path):
     s = _scene(12, 24)
     verts, faces = torch.from_numpy(s["verts"]).to(DEV), torch.from_numpy(s["faces"]).to(DEV)
     views = mv.cameras(17)
-    mats = meshview._mats(views, DEV)
+    mats = svs_views.mats(views, DEV)
     zbuf = meshview.new_zbuf(17, H, W)
     work = torch.zeros(4 + 17 * len(faces), dtype=torch.int32, device=DEV)
     rc, _ = meshview.raster_raw(zbuf, verts, faces, mats, 17, H, W, work=work)

@@ -114,15 +114,16 @@ def main(argv=None):
 
 def bench(a, resolution, np, torch, bmv, lib, mesh, mpt, mvw):
     """one run -> its lines"""
+    from svs_hip import views as svs_views
     if a.views > mvw.MAX_VIEWS:
         raise SystemExit(f"--views: at most {mvw.MAX_VIEWS} (one launch of svs_mesh_paint is what is timed)")
     H, W = bmv.H, bmv.W
     views = bmv.make_views(np, a.views)
     verts, faces = bmv.make_mesh(torch, mesh, resolution)
-    verts, faces, _ = mvw._mesh_args(verts, faces)
+    verts, faces, _ = svs_views.mesh_args(verts, faces)
     V, F = int(verts.shape[0]), int(faces.shape[0])
     images = make_images(torch, a.views, H, W)
-    mats = mvw._mats(views, verts.device)
+    mats = svs_views.mats(views, verts.device)
     rules = dict(near=1e-6, rel=0.01, abs_tol=0.0, cos_min=0.1, power=2)
     lines = [f"svs_hip.meshpaint: marching cubes of a sphere and a floor at {resolution}^3 = {V} vertices, {F} faces; {a.views} views of "
              f"{H} x {W}; warm-up, then the median of {a.repeats} intervals of {a.inner} calls each"]

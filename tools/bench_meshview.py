@@ -87,6 +87,7 @@ def main(argv=None):
 
 def bench(a, resolution, np, torch, Image, save_pfm, mesh, mvw):
     """one run -> its lines"""
+    from svs_hip import views as svs_views
     views = make_views(np, a.views)
     verts, faces = make_mesh(torch, mesh, resolution)
     n_verts, n_faces = int(verts.shape[0]), int(faces.shape[0])
@@ -99,11 +100,11 @@ def bench(a, resolution, np, torch, Image, save_pfm, mesh, mvw):
 
     box = {}
     def upload():
-        box["v"], box["f"], box["c"] = mvw._mesh_args(host_v, host_f, host_c)
+        box["v"], box["f"], box["c"] = svs_views.mesh_args(host_v, host_f, host_c)
     ms["upload"] = median_ms(torch, upload, a.repeats)
     nbytes["upload"] = host_v.nbytes + host_f.nbytes + host_c.nbytes
     v_d, f_d, c_d = box["v"], box["f"], box["c"]
-    mats = mvw._mats(views, v_d.device)
+    mats = svs_views.mats(views, v_d.device)
     n_chunks = (n_faces + mvw.FACE_CHUNK - 1) // mvw.FACE_CHUNK
     zbuf = mvw.new_zbuf(a.views, H, W)
     for name, flags in (("raster small", mvw.FLAG_SMALL_ONLY), ("raster large", mvw.FLAG_LARGE_ONLY), ("raster", 0)):
