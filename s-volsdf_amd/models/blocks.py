@@ -6,6 +6,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from svs_hip import costvol
+from svs_hip.tensor_cache import Derived as CachedFold   # folded weights, remade when a tensor they were folded from changes
 
 
 def fold_bn(bn):
@@ -17,21 +18,6 @@ def fold_bn(bn):
 def bn_tensors(bn):
     """the tensors fold_bn reads"""
     return [bn.weight, bn.bias, bn.running_mean, bn.running_var]
-
-
-class CachedFold:
-    """A value derived from parameters (folded weights), recomputed when one of the tensors it depends on is another tensor or
-    has been written to: the key is every tensor's (data_ptr, _version).  An optimiser step, load_state_dict and .to() all
-    change it."""
-
-    def __init__(self):
-        self._key, self._value = None, None
-
-    def __call__(self, tensors, make):
-        key = tuple((t.data_ptr(), t._version) for t in tensors)
-        if key != self._key:
-            self._value, self._key = make(), key
-        return self._value
 
 
 def _conv_batch(x, w, b, add=None, add_upsample2=False, stride=1, relu=False):

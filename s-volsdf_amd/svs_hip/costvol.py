@@ -8,6 +8,7 @@ import torch
 
 from . import lib as _lib
 from .ops import _f32, _ptr, _ptr_array, _stream
+from .tensor_cache import Derived, TensorCache
 
 
 def relative_projection(src_proj, ref_proj):
@@ -22,47 +23,16 @@ def relative_projection(src_proj, ref_proj):
     return list(rel[:3, :3].reshape(-1)) + list(rel[:3, 3])
 
 
-def _tensor_key(t):
-    return (t.data_ptr(), t._version, t.shape, t.stride(), t.device, t.dtype)
-
-
-class _TensorCache:
-    """Values derived from a tensor, keyed on its storage address and torch version counter (plus shape, strides, device, dtype
-    and an optional tag).  An entry keeps its tensor alive: the storage cannot be handed to another tensor while the key
-    exists.  Bounded by entries and / or bytes, or unbounded; a full cache is emptied (the working set of a scan fits: the
-    bound is a guard against a leak, not an eviction policy)."""
-
-    def __init__(self, entries=None, nbytes=None):
-        self.entries, self.nbytes = entries, nbytes
-        self.clear()
-
-    def clear(self):
-        self._d, self._used = {}, 0
-
-    def get(self, t, make, tag=None, nbytes=0):
-        """the cached make() of tensor t"""
-        key = (tag, _tensor_key(t))
-        hit = self._d.get(key)
-        if hit is None:
-            value = make()
-            if (self.entries is not None and len(self._d) >= self.entries) or (self.nbytes is not None and self._used + nbytes > self.nbytes):
-                self.clear()
-            hit = self._d[key] = (t, value)
-            self._used += nbytes
-        return hit[1]
-
-
-_HOST_CACHE = _TensorCache(entries=64)
-_RT_CACHE = _TensorCache(entries=64)
+_HOST_CACHE = TensorCache(entries=64)
+_RT_CACHE = TensorCache(entries=64)
 # bounded by bytes (a 32 x 1200 x 1600 float32 map and its copy are 490 MB), not by entries; `clear_caches()` drops everything
-# at the end of a scan / stage loop.  The key is (storage address, torch version counter, shape): a producer that rewrites a
-# cached feature map through this library's raw-pointer kernels does not bump the counter -- such buffers must not be recycled
-# while cached (the FeatureNet wrappers hand out fresh tensors).
-_HWC_CACHE = _TensorCache(nbytes=int(os.environ.get("SVS_HWC_CACHE_BYTES", str(1 << 30))))
-_WFRAG_CACHE = _TensorCache()               # the 3-D U-Net's weight fragments: a few MB per model, never dropped
-_W2D_CACHE = _TensorCache(entries=65)
-_W2D_MFMA_CACHE = _TensorCache(entries=65)
-_DECONV_FRAG_CACHE = _TensorCache(entries=65)
+# at the end of a scan / stage loop.  A raw-pointer writer does not bump the version counter (svs_hip/tensor_cache.py): the
+# FeatureNet wrappers hand out fresh tensors.
+_HWC_CACHE = TensorCache(nbytes=int(os.environ.get("SVS_HWC_CACHE_BYTES", str(1 << 30))))
+_WFRAG_CACHE = TensorCache()               # the 3-D U-Net's weight fragments: a few MB per model, never dropped
+_W2D_CACHE = TensorCache(entries=65)
+_W2D_MFMA_CACHE = TensorCache(entries=65)
+_DECONV_FRAG_CACHE = TensorCache(entries=65)
 _EXTRACTORS = weakref.WeakSet()             # live feature-extractor wrappers: clear_caches() drops their tables and workspaces
 
 
@@ -362,7 +332,7 @@ class _FeatureExtractor:
 
     def forget(self):
         self._ws, self._ws_key = None, None
-        self._tables, self._tables_key = None, None
+        self._tables = Derived()
 
     def fragment(self, i, w):
         """the MFMA fragments of layer i, or None: the layer runs on the float32 kernels"""
@@ -379,14 +349,12 @@ class _FeatureExtractor:
     def tables(self, layers):
         """layers: LAYERS (weight, bias or None) pairs in the library's order, convolutions (Cout,Cin,k,k), transposed layers
         (Cin,Cout,3,3) -> pointer tables (cached until a tensor changes)."""
-        key = tuple((w.data_ptr(), w._version, None if b is None else (b.data_ptr(), b._version)) for w, b in layers)
-        if key != self._tables_key:
+        def make():
             packed = [_f32(w.detach()) if i in self.TRANSPOSED else conv2d_pack(w) for i, (w, _) in enumerate(layers)]
             biases = [None if b is None else _f32(b) for _, b in layers]
             frags = [self.fragment(i, w) for i, (w, _) in enumerate(layers)]
-            self._tables = (_ptr_array(packed), _ptr_array(biases), packed, biases, layers, _ptr_array(frags), frags)
-            self._tables_key = key
-        return self._tables
+            return (_ptr_array(packed), _ptr_array(biases), packed, biases, layers, _ptr_array(frags), frags)
+        return self._tables([t for pair in layers for t in pair if t is not None], make)
 
     def __call__(self, image, layers):
         """image (3,H,W) -> stage1 (4b,H/4,W/4), stage2 (2b,H/2,W/2), stage3 (b,H,W)."""

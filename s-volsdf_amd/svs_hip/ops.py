@@ -10,6 +10,7 @@ import os
 import torch
 
 from . import lib as _lib
+from .tensor_cache import Derived, TensorCache
 
 
 def _ptr(t):
@@ -114,6 +115,7 @@ class PackedMlp:
         # one row-norm workspace per stream: the fused train step packs the two on different HIP streams at the same time
         self._ws = torch.empty(L.svs_pack_workspace_bytes() // 4, device=device)
         self._ws_rgb = torch.empty(L.svs_pack_workspace_bytes() // 4, device=device)
+        self.sdf_slot, self.rgb_slot = Derived(), Derived()     # which parameters each stream was packed from (network.py)
 
     def pack_sdf(self, weight_v, weight_g, bias):
         """weight_v/bias: 9 tensors; weight_g: 9 tensors or None (no weight-norm). network.py:64-65."""
@@ -263,6 +265,7 @@ class PackedBg:
         self.sdf_stream = torch.empty(L.svs_stream_bytes(5) // 4, device=device)
         self.rgb_stream = torch.empty(L.svs_stream_bytes(7) // 4, device=device)
         self._ws = torch.empty(L.svs_pack_workspace_bytes() // 4, device=device)
+        self.slot = Derived()              # which parameters the streams were packed from (network_bg.py packed_bg)
 
     def pack(self, sdf_wb, rgb_wb):
         """sdf_wb / rgb_wb: (weights, biases) lists of 9 / 2 tensors."""
@@ -398,24 +401,16 @@ def eikonal_points(uniform_points, cam_loc, z_eik, ray_dirs):
     return out
 
 
-_HOST_COPIES = {}
+_HOST_COPIES = TensorCache(entries=256)
+_LOOKUP_CONSTS = TensorCache(entries=4)            # cost_lookup's per-view constants
 
 
 def _host_f32(t):
-    """float32 host copy of a small camera matrix; copies of DEVICE tensors are cached per (address, version) so that a
-    step launches without a device-to-host synchronisation (and can be captured in a hipGraph)."""
+    """float32 host copy of a small camera matrix; copies of DEVICE tensors are cached (tensor_cache.py) so that a step
+    launches without a device-to-host synchronisation (and can be captured in a hipGraph)."""
     if not (torch.is_tensor(t) and t.is_cuda):
         return torch.as_tensor(t, dtype=torch.float32)
-    key = (t.data_ptr(), t._version, tuple(t.shape))
-    hit = _HOST_COPIES.get(key)
-    if hit is None:
-        if len(_HOST_COPIES) > 256:
-            _HOST_COPIES.clear()
-        hit = _HOST_COPIES[key] = t.detach().to(dtype=torch.float32).cpu()
-    return hit
-
-
-_LOOKUP_CONSTS = {}
+    return _HOST_COPIES.get(t, lambda: t.detach().to(dtype=torch.float32).cpu())
 
 
 def clear_lookup_caches():
@@ -445,18 +440,16 @@ def cost_lookup(views, same_view, img_res, *, xyz=None, cam=None, dirs=None, z=N
         R, S = z.shape
         dev = z.device
     V = len(views)
-    # the per-view constants (camera block, volume pointers and sizes) are the same every step of a stage: cached by the
-    # identity / version / address of what they were built from (51 scalar reads of host tensors per call otherwise: 0.1 ms)
+    # the per-view constants (camera block, volume pointers and sizes) are the same every step of a stage: cached on what they
+    # point into and on the identity / version of the camera matrices (51 scalar reads of host tensors per call otherwise: 0.1 ms)
     ver = lambda t: (id(t), getattr(t, "_version", 0))
-    key = tuple((ver(v["K"]), ver(v["c2w"]), v["cost"].data_ptr(), v["cost"].shape,
-                 (v["z_mvs"].data_ptr(), v["z_mvs"].shape) if "z_mvs" in v else (v["z_near"].data_ptr(), v["z_far"].data_ptr()))
-                for v in views)
-    hit = _LOOKUP_CONSTS.get(key)
-    if hit is None:
+    cams = [v[k] for v in views for k in ("K", "c2w")]
+    volumes = [v[k] for v in views for k in (("cost", "z_mvs") if "z_mvs" in v else ("cost", "z_near", "z_far"))]
+
+    def make():     # -> the launch's constants, what their pointers and the tag's id() name (alive with them), copied
         vp = (ctypes.c_float * (17 * V))()
         dims = (ctypes.c_int * (3 * V))()
-        keep, cost_p, near_p, far_p = [], [], [], []
-        copied = False
+        cost_p, near_p, far_p, copied = [], [], [], False
         for j, v in enumerate(views):
             K, c2w = _host_f32(v["K"]), _host_f32(v["c2w"])
             vals = [K[0, 0], K[1, 1], K[0, 2], K[1, 2], K[0, 1]] + [c2w[i, k] for i in range(3) for k in range(4)]
@@ -470,20 +463,15 @@ def cost_lookup(views, same_view, img_res, *, xyz=None, cam=None, dirs=None, z=N
             else:
                 zn, zf = _f32(v["z_near"]), _f32(v["z_far"])
                 copied = copied or zn.data_ptr() != v["z_near"].data_ptr() or zf.data_ptr() != v["z_far"].data_ptr()
-            # kept alive: the key holds the addresses of the ORIGINAL tensors (v["cost"], z range) -- not only those of the
-            # float32 / contiguous copies _f32 may have made -- so neither can be recycled while the entry lives
-            keep += [cost, zn, zf, v["K"], v["c2w"], v["cost"], v.get("z_mvs"), v.get("z_near"), v.get("z_far")]
             copied = copied or cost.data_ptr() != v["cost"].data_ptr()
             cost_p.append(cost); near_p.append(zn); far_p.append(zf)
             dims[3 * j], dims[3 * j + 1], dims[3 * j + 2] = cost.shape
-        if len(_LOOKUP_CONSTS) >= 4:
-            _LOOKUP_CONSTS.clear()
-        hit = (vp, dims, _ptr_array(cost_p), _ptr_array(near_p), _ptr_array(far_p), keep)
-        if not copied:
-            # (a volume or a depth-range plane _f32 had to convert -- not float32 or not contiguous -- is looked up from a
-            # private copy: the original may change without its address changing, so such a call is not cached)
-            _LOOKUP_CONSTS[key] = hit
-    vp, dims, cost_arr, near_arr, far_arr, _ = hit
+        return vp, dims, _ptr_array(cost_p), _ptr_array(near_p), _ptr_array(far_p), (cost_p, near_p, far_p, cams), copied
+
+    # (a volume or a depth-range plane _f32 had to convert -- not float32 or not contiguous -- is looked up from a private
+    # copy: the original may change without its address changing, so such a call is not cached; `owned` lives through the launch)
+    vp, dims, cost_arr, near_arr, far_arr, owned, _ = _LOOKUP_CONSTS.get(volumes, make, tag=tuple(map(ver, cams)),
+                                                                         cacheable=lambda made: not made[-1])
     pj = torch.empty(R, S, device=dev)
     pi = torch.empty(R, S, device=dev)
     valid = torch.empty(R, S, dtype=torch.uint8, device=dev)

@@ -22,6 +22,14 @@ def _dev(module):
     return next(module.parameters()).device
 
 
+def _layer_tensors(net):
+    """(weight_v, weight_g, bias) of a network's layers as lists; (weight, None, bias) without weight-norm"""
+    lins = [getattr(net, f"lin{l}") for l in range(net.num_layers - 1)]
+    if net.weight_norm:
+        return [m.weight_v for m in lins], [m.weight_g for m in lins], [m.bias for m in lins]
+    return [m.weight for m in lins], None, [m.bias for m in lins]
+
+
 class ImplicitNetwork(nn.Module):
     """SDF MLP, network.py:10-131.  Parameters are created exactly as the reference creates them (nn.Linear +
     geometric initialisation + weight_norm), so seeds and checkpoints carry over; evaluation is the fused
@@ -61,27 +69,17 @@ class ImplicitNetwork(nn.Module):
             if weight_norm:
                 lin = nn.utils.weight_norm(lin)
             setattr(self, "lin" + str(l), lin)
-        self._packed, self._packed_key = None, None
+        self._packed = None
 
     # ---- packed weights ----------------------------------------------------------------------------
-    def _layer_tensors(self):
-        n = self.num_layers - 1
-        lins = [getattr(self, f"lin{l}") for l in range(n)]
-        if self.weight_norm:
-            return [m.weight_v for m in lins], [m.weight_g for m in lins], [m.bias for m in lins]
-        return [m.weight for m in lins], None, [m.bias for m in lins]
-
     def packed(self, owner=None):
         if not self._supported:
             raise NotImplementedError("the fused SDF kernel is built for d_in=3, 8x256, skip_in=[4], multires=6, 256 features")
-        v, g, b = self._layer_tensors()
-        key = tuple((t.data_ptr(), t._version) for t in v + (g or []) + b)
+        v, g, b = _layer_tensors(self)
         pk = owner if owner is not None else self._packed
         if pk is None:
             pk = self._packed = ops.PackedMlp(v[0].device)
-        if self._packed_key != key or getattr(pk, "_sdf_key", None) != key:
-            pk.pack_sdf(v, g, b)
-            pk._sdf_key = self._packed_key = key
+        pk.sdf_slot(v + (g or []) + b, lambda: pk.pack_sdf(v, g, b))
         return pk
 
     # ---- reference call surface (inference; gradients w.r.t. parameters arrive with the backward kernels) ----
@@ -123,20 +121,12 @@ class RenderingNetwork(nn.Module):
             if weight_norm:
                 lin = nn.utils.weight_norm(lin)
             setattr(self, "lin" + str(l), lin)
-        self._packed_key = None
 
     def pack_into(self, pk):
         if not self._supported:
             raise NotImplementedError("the fused radiance kernel is built for mode='idr', 271->4x256->3")
-        lins = [getattr(self, f"lin{l}") for l in range(self.num_layers - 1)]
-        if self.weight_norm:
-            v, g, b = [m.weight_v for m in lins], [m.weight_g for m in lins], [m.bias for m in lins]
-        else:
-            v, g, b = [m.weight for m in lins], None, [m.bias for m in lins]
-        key = tuple((t.data_ptr(), t._version) for t in v + (g or []) + b)
-        if getattr(pk, "_rgb_key", None) != key:
-            pk.pack_rgb(v, g, b)
-            pk._rgb_key = key
+        v, g, b = _layer_tensors(self)
+        pk.rgb_slot(v + (g or []) + b, lambda: pk.pack_rgb(v, g, b))
         return pk
 
 
@@ -158,12 +148,7 @@ class VolSDFBase(nn.Module):
     # ---- parameters in a fixed order (shared by the autograd bridge and the fused trainer) -----------------
     def mlp_params(self):
         """((sdf weight_v, weight_g, bias), (rgb weight_v, weight_g, bias)) of the foreground networks, as lists per layer."""
-        def grab(net, n):
-            lins = [getattr(net, f"lin{l}") for l in range(n)]
-            if net.weight_norm:
-                return [m.weight_v for m in lins], [m.weight_g for m in lins], [m.bias for m in lins]
-            return [m.weight for m in lins], None, [m.bias for m in lins]
-        return grab(self.implicit_network, 9), grab(self.rendering_network, 5)
+        return _layer_tensors(self.implicit_network), _layer_tensors(self.rendering_network)
 
     def _flat_param_list(self):
         out = []
@@ -174,9 +159,10 @@ class VolSDFBase(nn.Module):
 
     def invalidate_packed(self):
         """Call after parameters were changed outside torch's version counter (fused optimiser kernel)."""
-        self.implicit_network._packed_key = None
-        if self._pk is not None:
-            self._pk._sdf_key = self._pk._rgb_key = None
+        for pk in (self._pk, self.implicit_network._packed):
+            if pk is not None:
+                pk.sdf_slot.invalidate()
+                pk.rgb_slot.invalidate()
 
     # ---- batch geometry -------------------------------------------------------------------------------------
     def samples_per_ray(self):

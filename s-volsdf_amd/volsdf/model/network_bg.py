@@ -38,7 +38,6 @@ class VolSDFNetworkBG(VolSDFBase):
             raise NotImplementedError("the background kernels are built for bmvs.yaml's bg_network (4-D PE-10 8x256 "
                                       "skip-4 implicit network, 283->128->3 'nerf' radiance network, no weight-norm)")
         self._pk_bg = None
-        self._bg_key = None
         self._bg_streams = {}              # per calling stream: the stream the background networks' forward runs on
 
     # ---- packed weights -------------------------------------------------------------------------------------
@@ -50,12 +49,9 @@ class VolSDFNetworkBG(VolSDFBase):
 
     def packed_bg(self):
         if self._pk_bg is None or self._pk_bg.device != _dev(self):
-            self._pk_bg, self._bg_key = ops.PackedBg(_dev(self)), None
+            self._pk_bg = ops.PackedBg(_dev(self))
         sw, rw = self.bg_params()
-        key = tuple((t.data_ptr(), t._version) for t in sw[0] + sw[1] + rw[0] + rw[1])
-        if key != self._bg_key:
-            self._pk_bg.pack(sw, rw)
-            self._bg_key = key
+        self._pk_bg.slot(sw[0] + sw[1] + rw[0] + rw[1], lambda: self._pk_bg.pack(sw, rw))
         return self._pk_bg
 
     def _flat_param_list(self):
@@ -67,7 +63,8 @@ class VolSDFNetworkBG(VolSDFBase):
 
     def invalidate_packed(self):
         super().invalidate_packed()
-        self._bg_key = None
+        if self._pk_bg is not None:
+            self._pk_bg.slot.invalidate()
 
     # ---- forward --------------------------------------------------------------------------------------------
     def forward(self, input, fast=-1):

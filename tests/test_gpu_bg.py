@@ -44,6 +44,27 @@ def _model(dev, beta):
     return m.to(dev)
 
 
+def test_packed_bg_follows_invalidate_packed(dev):
+    """packed_bg() like the foreground's streams (test_gpu_parity.py::test_packed_streams_follow_invalidate_packed): a write
+    torch does not see leaves the streams as they are, invalidate_packed() repacks them from the current parameters."""
+    from svs_hip import ops
+    m = _model(dev, 0.1)
+    pkb = m.packed_bg()
+    bits = lambda p: [p.sdf_stream.view(torch.int32), p.rgb_stream.view(torch.int32)]
+    before = [t.clone() for t in bits(pkb)]
+    for bias in (m.bg_implicit_network.lin3.bias, m.bg_rendering_network.lin0.bias):
+        version = bias._version
+        bias.data.add_(1.0)
+        assert bias._version == version
+    assert m.packed_bg() is pkb and all(torch.equal(a, b) for a, b in zip(before, bits(pkb)))
+    m.invalidate_packed()
+    assert m.packed_bg() is pkb
+    fresh = ops.PackedBg(dev)
+    fresh.pack(*m.bg_params())
+    for a, b, old in zip(bits(fresh), bits(pkb), before):
+        assert torch.equal(a, b) and not torch.equal(b, old)
+
+
 @pytest.mark.parametrize("precision", [None, "f32"])
 @pytest.mark.parametrize("tag", ["eval_b0.1", "train"])
 def test_bg_pieces(dev, golden_dir, tag, precision, monkeypatch):

@@ -453,6 +453,45 @@ def _model(dev, beta, wset="w0"):
     return m.to(dev), params
 
 
+def test_packed_streams_follow_invalidate_packed(dev, ops):
+    """A write torch does not see (`bias.data.add_`, like the fused optimiser kernel: no version bump) leaves the packed
+    streams as they are -- the documented limit of svs_hip/tensor_cache.py, asserted so that it is a decision --, and
+    invalidate_packed() repacks BOTH PackedMlp objects: the model's and the SDF network's own (mesh.py's net.packed())."""
+    m, _ = _model(dev, 0.1)
+    net = m.implicit_network
+    own, pk = net.packed(), m.packed_mlp()
+    assert own is not pk
+    bits = lambda *streams: [t.view(torch.int32) for t in streams]     # (fp16 pairs: compared as bits, not as floats)
+    before = [t.clone() for t in bits(own.sdf_stream, pk.sdf_stream, pk.rgb_stream)]
+    for bias in (net.lin3.bias, m.rendering_network.lin2.bias):
+        version = bias._version
+        bias.data.add_(1.0)
+        assert bias._version == version
+    assert net.packed() is own and m.packed_mlp() is pk
+    for a, b in zip(before, bits(own.sdf_stream, pk.sdf_stream, pk.rgb_stream)):
+        assert torch.equal(a, b)
+    m.invalidate_packed()
+    assert net.packed() is own and m.packed_mlp() is pk
+    fresh = ops.PackedMlp(dev)
+    sdf_p, rgb_p = m.mlp_params()
+    fresh.pack_sdf(*sdf_p)
+    fresh.pack_rgb(*rgb_p)
+    for a, b, old in zip(bits(fresh.sdf_stream, fresh.sdf_stream, fresh.rgb_stream),
+                         bits(own.sdf_stream, pk.sdf_stream, pk.rgb_stream), before):
+        assert torch.equal(a, b) and not torch.equal(b, old)
+
+
+def test_host_copy_of_a_recycled_device_address(dev, ops):
+    """_host_f32 of a (4,4) device tensor allocated into the block a freed one left (torch's caching allocator hands it
+    straight back; a fresh tensor's version is 0 again) is the second tensor's values, not the first one's cached copy"""
+    ops.clear_lookup_caches()
+    first = torch.arange(16, dtype=torch.float32, device=dev).reshape(4, 4)
+    assert torch.equal(ops._host_f32(first), torch.arange(16, dtype=torch.float32).reshape(4, 4))
+    del first
+    second = torch.full((4, 4), 7.0, device=dev)
+    assert torch.equal(ops._host_f32(second), torch.full((4, 4), 7.0))
+
+
 @pytest.mark.parametrize("tag", ["eval_b0.1", "eval_b0.01", "eval_b0.01_f1", "train", "w1_eval", "w1_train"])
 def test_model_forward_golden(dev, golden_dir, tag):
     """VolSDFNetwork.forward (HIP) against the reference's outputs (fixtures; w1_*: the trained-scale weight set):

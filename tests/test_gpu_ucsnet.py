@@ -167,7 +167,7 @@ def test_feature_extractor_golden_and_in_place_concatenation(dev, g):
     with pytest.raises(Exception):
         fe(torch.zeros(1, 3, 30, 40, device=dev))                      # H, W multiples of 4
     costvol.clear_caches()
-    assert fe._unet._tables is None and fe._unet._ws is None
+    assert fe._unet._tables.value is None and fe._unet._ws is None
     with torch.no_grad():
         assert torch.equal(fe(img[None])["stage3"][0], out["stage3"][0])
 
