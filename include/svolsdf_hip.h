@@ -1134,6 +1134,58 @@ int svs_mesh_paint_finish(const double* acc, int n_verts, int flags, uint8_t* rg
 int svs_mesh_paint_spread(const int* faces, int n_faces, int n_verts, int round, uint8_t* rgb, int* painted, int* work,
                           int* changed, void* hip_stream);
 
+/* ---- a mesh made smaller: vertex clustering with quadric error metrics (svs_hip.meshsimplify; csrc/svs_meshsimplify.hip) --
+ * After Lindstrom, "Out-of-core simplification of large polygonal models" (2000): the vertices of a cell of a uniform grid
+ * become one vertex, placed where the planes of the faces that touch the cell meet best.  The reference has no such step;
+ * the arithmetic below is this project's (tests/meshsimplify_oracle.py restates it in numpy float64).  All arithmetic is
+ * float64 without contraction.  verts DEVICE float[n_verts][3], faces DEVICE int[n_faces][3], colors DEVICE
+ * uint8[n_verts][3] or NULL; origin: HOST double[3], <= every coordinate, (max - origin) / h < 2^21; h > 0: the cell size;
+ * tol in (0,1).  n_faces <= (2^31 - 1) / 3.
+ *
+ * A face is VALID when its three indices lie in [0, n_verts), its corners (float32 widened) are finite, and
+ * n = cross(P1-P0, P2-P0) has L = sqrt(n.x n.x + n.y n.y + n.z n.z) finite and > 0.  Invalid faces contribute nothing, are
+ * never dereferenced past the index check and are absent from the output.
+ *
+ * svs_mesh_cluster_cells: a corner's cell is per axis floor((p - origin) * (1 / h)) clamped to [0, 2^21), its key
+ *   ix | iy << 21 | iz << 42 (csrc/svs_cloud_grid.h).  The occupied cells are those that hold a corner of a valid face;
+ *   they are ranked by ascending key.  vert_cell DEVICE int[n_verts] = the rank of v's cell, -1 when no valid face uses v.
+ *   *n_cells (HOST int) = the number of occupied cells; output vertex r belongs to cell rank r.  Synchronises the stream.
+ *   More than 2^21 occupied cells: SVS_ESHAPE (a face's duplicate key packs three 21-bit ranks).
+ * svs_mesh_cluster_solve: every valid face contributes once per corner to that corner's cell -- a face with two corners in
+ *   one cell contributes TWICE to it: that is the rule.  With c = origin + (cell index + 0.5) h per axis and
+ *   d = -(n.x (P0.x-c.x) + n.y (P0.y-c.y) + n.z (P0.z-c.z)), corner k of face f adds: A_ij += n_i n_j / L (six entries,
+ *   (n_i n_j) / L), b_i += (n_i d) / L, e += (d d) / L, m += P_k - c, count += 1, and the colour codes of vertex faces[f][k]
+ *   to three integer sums.  ORDER of the float64 sums, a function of the input alone: the pairs (f,k) of a cell ascending in
+ *   f, then k, are cut into segments of 64 consecutive pairs; each segment is summed left to right from zero; the segment
+ *   sums are summed left to right from zero.  No float atomics.
+ *   Solve: eigenvalues l_i and eigenvectors v_i of A by cyclic Jacobi (8 sweeps, rotations (0,1), (0,2), (1,2):
+ *   csrc/svs_jacobi3.h, shared with svs_cloud_normals); kept: l_i > tol * max l; mean = m / count;
+ *   g_i = -b_i - (A_i0 mean_0 + A_i1 mean_1 + A_i2 mean_2); x = mean + sum over kept i (in index order) of
+ *   v_i ((v_i . g) / l_i).  If a component of x is not finite or |x_k| > h (farther than one cell size from the cell's
+ *   centre along an axis): x = mean and the fallback bit is set.  out_verts DEVICE float[n_cells][3] = float32(c + x);
+ *   info DEVICE int[n_cells] = kept directions (0..3) | fallback << 2; err DEVICE double[n_cells] = x^T A x + 2 b.x + e;
+ *   out_colors DEVICE uint8[n_cells][3] (given iff colors is) = (2 sum + count) / (2 count) by integer division.
+ *   vert_cell, n_cells: what svs_mesh_cluster_cells gave for the same mesh, origin and h.
+ * svs_mesh_cluster_faces_count: a valid face becomes the three ranks of its corners in its own corner order; it is dropped
+ *   when two ranks are equal; among faces with the same SET of three ranks the one with the lowest input index survives,
+ *   whatever its orientation.  keep DEVICE uint8[n_faces] = 1 for a survivor, offsets DEVICE int[n_faces] = survivors
+ *   before f, *count (DEVICE int) = their number.
+ * svs_mesh_cluster_faces_emit: out_faces DEVICE int[count][3]: the survivors in input order.
+ * workspace: svs_mesh_cluster_workspace_bytes(n_verts, n_faces) bytes serve all three entries that take one; nothing is
+ *   kept in it between calls.  Every check comes before any HIP call: SVS_ESHAPE for a negative count, too many faces or
+ *   cells, SVS_EINVAL for a null required pointer, h <= 0 or not finite, an origin that is not finite, tol outside (0,1),
+ *   colours without their output, with the entry's name in the message.  An empty mesh is not an error. */
+size_t svs_mesh_cluster_workspace_bytes(int n_verts, int n_faces);
+int svs_mesh_cluster_cells(const float* verts, int n_verts, const int* faces, int n_faces, const double SVS_HOST* origin, double h,
+                           void* workspace, int* vert_cell, int SVS_HOST* n_cells, void* hip_stream);
+int svs_mesh_cluster_solve(const float* verts, int n_verts, const int* faces, int n_faces, const uint8_t* colors,
+                           const double SVS_HOST* origin, double h, double tol, const int* vert_cell, int n_cells, void* workspace,
+                           float* out_verts, uint8_t* out_colors, int* info, double* err, void* hip_stream);
+int svs_mesh_cluster_faces_count(const float* verts, int n_verts, const int* faces, int n_faces, const int* vert_cell, int n_cells,
+                                 void* workspace, uint8_t* keep, int* offsets, int* count, void* hip_stream);
+int svs_mesh_cluster_faces_emit(const int* faces, int n_faces, const int* vert_cell, const uint8_t* keep, const int* offsets,
+                                int* out_faces, void* hip_stream);
+
 /* ---- numeric-contract self tests (used by tests/test_gpu_parity.py) --------------------------------------- */
 int svs_selftest_exp(const float* x, float* y_exp, float* y_expm1, int n, void* hip_stream);
 int svs_selftest_arith(const float* a, const float* b, float* quotient, float* sqrt_abs_a, int n, void* hip_stream);

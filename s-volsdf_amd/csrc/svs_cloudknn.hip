@@ -10,6 +10,7 @@
 // largest k and no barrier is needed (a lane touches its own column only).  Latency / gather bound work: no matrix cores.
 #include "svs_cloud_grid.h"
 #include "svs_common.h"
+#include "svs_jacobi3.h"
 
 namespace svs {
 namespace cloud {
@@ -139,35 +140,7 @@ __global__ void outlier_mask_kernel(const double* __restrict__ d, int n, double 
   keep[i] = (finite_f64(v) && v <= threshold) ? 1 : 0;
 }
 
-// ---- normals: the eigenvector of the smallest eigenvalue of the neighbourhood's covariance, by cyclic Jacobi ---------------
-constexpr int kJacobiSweeps = 8;                            // quadratic convergence: a 3x3 matrix settles in 4-5 sweeps
-
-// One rotation that annihilates a[P][Q] (Rutishauser's update, as in Numerical Recipes' jacobi); P < Q are compile-time, so
-// that a and v stay in registers.
-template <int P, int Q>
-__device__ __forceinline__ void jacobi_rotate(double (&a)[3][3], double (&v)[3][3]) {
-  const double apq = a[P][Q];
-  if (apq == 0.0) return;
-  const double theta = (a[Q][Q] - a[P][P]) / (2.0 * apq);
-  const double t = (theta >= 0.0 ? 1.0 : -1.0) / (__builtin_fabs(theta) + __builtin_sqrt(theta * theta + 1.0));
-  // |theta| so large that theta^2 overflows: t = 1 / (2 theta)
-  const double tt = __builtin_fabs(theta) > 1e150 ? 0.5 / theta : t;
-  const double c = 1.0 / __builtin_sqrt(tt * tt + 1.0), s = tt * c;
-  constexpr int R = 3 - P - Q;                              // the third index
-  const double app = a[P][P], aqq = a[Q][Q], arp = a[R][P], arq = a[R][Q];
-  a[P][P] = app - tt * apq;
-  a[Q][Q] = aqq + tt * apq;
-  a[P][Q] = a[Q][P] = 0.0;
-  a[R][P] = a[P][R] = c * arp - s * arq;
-  a[R][Q] = a[Q][R] = s * arp + c * arq;
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const double vip = v[i][P], viq = v[i][Q];
-    v[i][P] = c * vip - s * viq;
-    v[i][Q] = s * vip + c * viq;
-  }
-}
-
+// ---- normals: the eigenvector of the smallest eigenvalue of the neighbourhood's covariance, by cyclic Jacobi (svs_jacobi3.h) ----
 __global__ __launch_bounds__(256) void normals_kernel(const double* __restrict__ pts, int n, const int* __restrict__ idx, int k,
                                                       int include_self, const int* __restrict__ view_index,
                                                       const double* __restrict__ centres, int n_views, float* __restrict__ normals,
@@ -203,12 +176,7 @@ __global__ __launch_bounds__(256) void normals_kernel(const double* __restrict__
     }
     double a[3][3] = {{cxx * inv_m, cxy * inv_m, cxz * inv_m}, {cxy * inv_m, cyy * inv_m, cyz * inv_m}, {cxz * inv_m, cyz * inv_m, czz * inv_m}};
     double v[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
-#pragma unroll 1
-    for (int sweep = 0; sweep < kJacobiSweeps; ++sweep) {
-      jacobi_rotate<0, 1>(a, v);
-      jacobi_rotate<0, 2>(a, v);
-      jacobi_rotate<1, 2>(a, v);
-    }
+    jacobi_sweeps(a, v);
     const double l0 = a[0][0], l1 = a[1][1], l2 = a[2][2];
     // the smallest eigenvalue's column, the lowest index on a tie (selected, not indexed)
     const bool pick1 = l1 < l0 && l1 <= l2, pick2 = l2 < l0 && l2 < l1;

@@ -17,6 +17,9 @@ filter_depth_folder`) -> {outdir}/mvsnet{scan:03}_l3.ply.
                              {outdir}/tsdf/mvsnet{scan:03}_l3.ply (`python -m evals.eval_dtu --datadir {outdir}/tsdf --mode mesh`)
     +tsdf_views=true         with +tsdf_voxel: every scan's TSDF mesh rendered into its training views by `svs_hip.meshview`,
                              {outdir}/tsdf/scanNNN/mesh_depth/{id:08}.pfm and mesh_shade/{id:08}.png
+    +tsdf_simplify=R         with +tsdf_voxel: every scan's TSDF mesh also simplified to at most R (in (0,1)) of its faces by
+                             `svs_hip.meshsimplify`, {outdir}/tsdf_simple/mvsnet{scan:03}_l3.ply
+                             (`python -m evals.eval_dtu --datadir {outdir}/tsdf_simple --mode mesh`)
     +cloud_clean=true [+cloud_k=20 +cloud_std_ratio=2.0 +cloud_normal_k=16]   after the point clouds, every scan's cloud
                              without its statistical outliers and with oriented normals (`svs_hip.cloudclean`), in
                              {outdir}/clean/mvsnet{scan:03}_l3.ply (`python -m evals.eval_dtu --datadir {outdir}/clean`)
@@ -138,6 +141,16 @@ def _require(ok, key, why):
         raise ValueError(f"{key}: {why}")
 
 
+def check_tsdf_simplify(args):
+    """+tsdf_simplify=R: a ratio in (0,1), and only together with +tsdf_voxel (ValueError naming the key) -> R or None"""
+    r = args.get("tsdf_simplify")
+    if r is None:
+        return None
+    _require(isinstance(r, (int, float)) and not isinstance(r, bool) and 0 < r < 1, "tsdf_simplify", f"a ratio in (0,1), got {r!r}")
+    _require(bool(args.get("tsdf_voxel")), "tsdf_simplify", "simplifies the TSDF meshes: give +tsdf_voxel=V as well")
+    return float(r)
+
+
 def save_yaml(path, args):
     import yaml
     with open(path, "w") as f:
@@ -148,6 +161,7 @@ def run_help(args, select_device=True):
     """helpers/help.py::run_help on the plain dict, in place: the device, the derived values, the six assertions
     (:48-53, as ValueError naming the key), outdir and all_scans.yaml (unless filter_only).  -> args"""
     a = attr_view(args)
+    check_tsdf_simplify(args)
     if select_device and args["gpu"] != "auto":
         import torch
         torch.cuda.set_device(int(args["gpu"]))
@@ -410,6 +424,27 @@ def tsdf_views(args, testlist):
     return out
 
 
+def tsdf_simple_ply_name(outdir, scan):
+    """the simplified TSDF mesh of a scan, where `evals.eval_dtu --datadir {outdir}/tsdf_simple --mode mesh` finds it"""
+    return ply_name(os.path.join(outdir, "tsdf_simple"), scan)
+
+
+def tsdf_simplified(args, testlist):
+    """+tsdf_simplify=R: every scan's TSDF mesh (`tsdf_meshes`) simplified by `meshsimplify.simplify_ply` to at most R of its
+    faces, into {outdir}/tsdf_simple/mvsnet{scan:03}_l3.ply; one time line per scan.  -> {scene: simplify_ply's stats}"""
+    from . import meshsimplify
+    ratio = check_tsdf_simplify(args)
+    out = OrderedDict()
+    for scan in testlist:
+        ply = tsdf_simple_ply_name(args["outdir"], scan)
+        os.makedirs(os.path.dirname(ply), exist_ok=True)
+        stats = meshsimplify.simplify_ply(tsdf_ply_name(args["outdir"], scan), ply, ratio=ratio)[3]
+        info(f"saving the simplified TSDF mesh to {ply} ({stats['faces_out']} of {stats['faces_in']} faces, cell {stats['cell']:.6g})")
+        info(f"{scan} tsdf simplify seconds: " + ", ".join(f"{k} {v:.3f}" for k, v in stats["seconds"].items()))
+        out[scan] = stats
+    return out
+
+
 def clean_ply_name(outdir, scan):
     """the cleaned cloud of a scan: the point cloud's name one folder down, where `evals.eval_dtu --datadir` finds it"""
     return ply_name(os.path.join(outdir, "clean"), scan)
@@ -484,6 +519,8 @@ def main(argv=None, scan_fn=None):
         result["meshes"] = tsdf_meshes(args, testlist)
         if args.get("tsdf_views"):
             result["mesh_views"] = tsdf_views(args, testlist)
+        if args.get("tsdf_simplify") is not None:
+            result["simple_meshes"] = tsdf_simplified(args, testlist)
     if args.get("cloud_clean"):
         result["clean"] = clean_clouds(args, testlist)
     return result
