@@ -138,12 +138,13 @@ def depth_hypotheses(stage_idx, depth_values_1d, img_hw, ndepth, stage_scale, in
     return resize_linear(vol, (ndepth, H // int(stage_scale), W // int(stage_scale)))
 
 
-def cost_reg_net_torch(params, x):
-    """CostRegNet.forward (:441-472) as a plain torch float32 reference (floating-point kernel).
-    params: dict from synth.make_costreg_params; x (C,D,H,W) numpy -> (D,H,W) numpy."""
+def costreg_blocks_torch(params, dtype=None):
+    """The Conv3d / Deconv3d blocks (:107-186: convolution, BatchNorm in eval form, ReLU) over a state dict, as plain torch
+    functions in `dtype` (None: float32) -> T(key), conv(y, name, stride), deconv(y, name) on (1,C,D,H,W) tensors."""
     import torch
     import torch.nn.functional as Fn
-    T = lambda k: torch.from_numpy(np.asarray(params[k]))
+    dtype = torch.float32 if dtype is None else dtype
+    T = lambda k: torch.from_numpy(np.asarray(params[k])).to(dtype)
 
     def bn_relu(y, name):
         y = Fn.batch_norm(y, T(f"{name}.bn.running_mean"), T(f"{name}.bn.running_var"), T(f"{name}.bn.weight"),
@@ -156,8 +157,20 @@ def cost_reg_net_torch(params, x):
     def deconv(y, name):
         return bn_relu(Fn.conv_transpose3d(y, T(f"{name}.conv.weight"), stride=2, padding=1, output_padding=1), name)
 
+    return T, conv, deconv
+
+
+def cost_reg_net_torch(params, x, dtype=None):
+    """CostRegNet.forward (:441-472) as a plain torch reference (floating-point kernel), float32 unless `dtype` (a torch
+    dtype: torch.float64 for the high-precision form) says otherwise.
+    params: dict from synth.make_costreg_params; x (C,D,H,W) numpy -> (D,H,W) numpy of that type."""
+    import torch
+    import torch.nn.functional as Fn
+    dtype = torch.float32 if dtype is None else dtype
+    T, conv, deconv = costreg_blocks_torch(params, dtype)
+
     with torch.no_grad():
-        x = torch.from_numpy(np.asarray(x, F32))[None]
+        x = torch.from_numpy(np.asarray(x, F32)).to(dtype)[None]
         c0 = conv(x, "conv0", 1)
         c2 = conv(conv(c0, "conv1", 2), "conv2", 1)
         c4 = conv(conv(c2, "conv3", 2), "conv4", 1)

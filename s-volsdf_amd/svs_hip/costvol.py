@@ -655,8 +655,11 @@ def rows_supported(Cin, Cout):
 
 def conv3d(x, weight, bias=None, skip=None, stride=1, transposed=False, relu=True, split_out=False):
     """x (Cin,D,H,W); weight [Cin][27][Cout] folded; -> (Cout,Do,Ho,Wo).  split_out: return the result as a SplitVolume (the
-    stride-2 convolution from 8 to 16 channels only: conv1 feeding conv2)."""
+    stride-2 convolution from 8 to 16 channels only: conv1 feeding conv2).  bias [Cout] and skip (Cout,Do,Ho,Wo) may be views
+    (a slice of a larger volume): the kernels read contiguous float32 copies of them."""
     L = _lib.load()
+    bias = _f32(bias) if bias is not None else None
+    skip = _f32(skip) if skip is not None else None
     if isinstance(x, SplitVolume):
         Cout = weight.shape[2]
         rows = x.C == 16 and Cout > 8                # conv2 (channel rows); otherwise conv0 (x-pair rows, Cout <= 8)
