@@ -192,21 +192,30 @@ constexpr int kWarpDz = 4;
 //     an active wave issues exactly two stores per stored plane, and waves without a voxel inside the image leave the pass);
 //   * corner tables source-major (a wave's entries belong to one source: its camera block comes from SGPRs), the four corners
 //     without branches, the four IEEE divisions as the compiler's own sequence without its scaling / fix-up instructions where
-//     no operand needs them, the refined reciprocal shared (bit-identical quotients);
+//     no operand needs them, the refined reciprocal shared (bit-identical quotients in the operand range div2_ieee checks,
+//     the ordinary division outside it);
 //   * CPL = 4 channels per lane (round 5's shape, 16 waves per CU; eight per lane halved the per-lane overhead but needed
 //     176-190 VGPRs, one 5-wave workgroup per CU, and measured slower: NOTES/r06.md).
 // ~1060 lane-instructions per (voxel, plane).  Measured (NOTES/r06.md): -4 % / -11 % / -6 % at the three stage
 // shapes against round 5's kernel -- a third fewer instructions buy a twentieth of the time, so the kernel is NOT bound by
 // instruction issue (this round's hypothesis), nor by where its gathers hit (below).
-// Same arithmetic per channel in the same order as warp_variance_kernel: the values are the float32 kernel's bit for bit
-// (tests/test_gpu_costvol.py::test_warp_variance_split_volume).
+// Same arithmetic per channel in the same order as warp_variance_kernel.  The values are the float32 kernel's bit for bit
+// wherever the four quotients of a table entry are (below); that is what the tests hold it to, on benign geometry
+// (tests/test_gpu_costvol.py::test_warp_variance_split_volume) and on samples that cross the borders, leave and enter the
+// image inside a four-plane run, project with q.z <= 0 and take the fall-back below, for all twelve (C, NS) instances
+// (tests/test_gpu_warp_edges.py::test_split_producer_vs_float64).
 // IEEE float32 quotients n0 / d and n1 / d as the compiler's own division sequence computes them (v_div_scale, v_rcp, the
 // two Newton steps on the reciprocal and the quotient, v_div_fmas, v_div_fixup: LLVM's AMDGPU f32 fdiv lowering), with the
-// scaling and fix-up instructions left out and the refined reciprocal shared by both quotients: when neither operand is
-// scaled (|d| and |n| well inside the normal range: v_div_scale returns them unchanged, v_div_fmas is a plain fma,
-// v_div_fixup passes the quotient through) these ARE that sequence's operations, operation by operation, so the quotients
-// are the correctly rounded ones bit for bit.  Outside that range the ordinary division runs.  (A projection divides two
-// coordinates by one depth and the two results by two constants: four divisions of ~12 instructions per table entry.)
+// scaling and fix-up instructions left out and the refined reciprocal shared by both quotients.  Where v_div_scale would
+// leave both operands unchanged, v_div_fmas is a plain fma and v_div_fixup passes the quotient through, so these ARE that
+// sequence's operations, operation by operation, and the quotients are the correctly rounded ones bit for bit.  The range
+// checked here is 2^-40 < |d| < 2^40 and |n| < 2^40 -- NOT all of that: v_div_scale also scales a numerator of very small
+// magnitude and operands whose quotient would come out denormal (a non-zero |n| below ~2^-86 at the largest |d| admitted),
+// and no lower bound on |n| excludes those here.  There the unscaled sequence rounds residuals in the denormal range and a
+// quotient of magnitude < 2^-100 may differ from the compiler's division in its last bits: the same sample position to far
+// below any pixel fraction that matters, harmless for grid coordinates, but not `bit for bit'.  Outside the checked range
+// the ordinary division runs.  (A projection divides two coordinates by one depth and the two results by two constants:
+// four divisions of ~12 instructions per table entry.)
 __device__ __forceinline__ void div2_ieee(float n0, float n1, float d, float& q0, float& q1) {
   const float ad = __builtin_fabsf(d);
   if (ad > 0x1p-40f && ad < 0x1p40f && __builtin_fabsf(n0) < 0x1p40f && __builtin_fabsf(n1) < 0x1p40f) {

@@ -3,7 +3,11 @@ the reference-generated fixtures.  Tolerances: 2e-4 abs on warped features / var
 |coordinate| ~ 1e2 px), 2e-3 abs / 5e-5 mean on the 11-layer 3-D U-Net output, exact regression index.
 The tail of the cost volume (softmax / depth / confidence, the depth hypotheses) and the prior look-up it feeds are held to
 float64 references at their dispatch edges in tests/test_gpu_costvol_tail.py (references: tests/costvol_tail_ref.py, inputs:
-tests/costvol_tail_cases.py, their CPU-side checks: tests/test_costvol_tail_cpu.py)."""
+tests/costvol_tail_cases.py, their CPU-side checks: tests/test_costvol_tail_cpu.py).
+The warp + variance builders themselves are held to a float64 reference off the image -- samples on every border, entering and
+leaving between the planes of a four-plane run, q.z <= 0, the division fall-back, hypotheses of 0, < 0, inf and NaN, all twelve
+(C, NS) instances of both kernels and the raw warp -- in tests/test_gpu_warp_edges.py (reference, inputs and cases:
+tests/warp_cases.py, their CPU-side checks: tests/test_warp_cases_cpu.py)."""
 import os
 
 import numpy as np
