@@ -1186,6 +1186,63 @@ int svs_mesh_cluster_faces_count(const float* verts, int n_verts, const int* fac
 int svs_mesh_cluster_faces_emit(const int* faces, int n_faces, const int* vert_cell, const uint8_t* keep, const int* offsets,
                                 int* out_faces, void* hip_stream);
 
+/* ---- a surface from an oriented point cloud: Poisson reconstruction on one dense grid (svs_hip.poisson; csrc/svs_poisson.hip)
+ * After Kazhdan, Bolitho and Hoppe, "Poisson surface reconstruction" (2006), on one dense grid and without screening.  The
+ * reference has no such step; the arithmetic below is this project's (tests/poisson_oracle.py restates it in numpy float64).
+ * The grid is node-centred with shape (n0,n1,n2), last axis contiguous, node (i,j,k) at origin + (i,j,k) h; origin: HOST
+ * double[3], finite; h > 0.  Two nodes along every axis, fewer than 2^31 nodes.  Volumes are float32; every per-element
+ * computation is float64 without contraction, rounded once on store.
+ *
+ * A point COUNTS when its three coordinates and (in the splat) its three normal components are finite and, per axis,
+ * g = (p - origin) / h, b = floor(g) has 0 <= b <= n - 2; t = g - b.  Corner c = 4 di + 2 dj + dk of its cell (b0,b1,b2) is
+ * node (b0+di, b1+dj, b2+dk) and has weight (wx * wy) * wz with w = t for d = 1 and 1 - t for d = 0.
+ *
+ * svs_poisson_splat: pts DEVICE double[n][3], normals DEVICE float[n][3] (used as given, never renormalised) -> field DEVICE
+ *   float planar (4,n0,n1,n2): Vx, Vy, Vz, W.  Corner c of a counted point's cell receives w (nx, ny, nz, 1) (products
+ *   w * nx ...).  ORDER of the float64 sums, a function of the input alone: the counted points of a cell ascending by
+ *   index are cut into segments of 64; each segment is summed left to right from zero, per corner and component; the
+ *   segment sums are summed left to right from zero; a node adds, from zero and in ascending corner order, corner c's sum of
+ *   cell (node - (di,dj,dk)) over the cells that exist and hold a point; float32 once.  No float atomics.  counts HOST int[2]
+ *   = counted, skipped.  Synchronises the stream.  n >= 1.
+ * svs_poisson_divergence: rhs = -(((Vx[i+1] - Vx[i-1]) + (Vy[j+1] - Vy[j-1])) + (Vz[k+1] - Vz[k-1])) / (2 h), values beyond the
+ *   grid 0: the solution is smaller inside, like the SDFs svs_mc_classify takes.
+ * svs_poisson_apply: y = A x, A x = (6 x - s) / (h h), s = (((((x[i-1] + x[i+1]) + x[j-1]) + x[j+1]) + x[k-1]) + x[k+1]),
+ *   0 beyond the grid (Dirichlet).  x and y may not be the same array.  16-byte accesses when n2 % 4 == 0 and both bases
+ *   are 16-byte aligned, scalar ones otherwise; the same values either way.  svs_poisson_tile: tile HOST int[3] = the
+ *   stencil workgroup's extent along axes 0, 1, 2.
+ * svs_poisson_cg: conjugate gradients for A x = rhs from x = 0: r = rhs, p = r, rr = bb = r.r; repeat: q = A p;
+ *   alpha = rr / p.q; x += alpha p; r -= alpha q; rn = r.r; beta = rn / rr; rr = rn; p = r + beta p (alpha = 0 when p.q <= 0,
+ *   beta = 0 when rr <= 0).  Vectors float32 (x + alpha p etc. in float64, rounded once); dot products float64 over the
+ *   stored float32 values: per-workgroup partial sums, then one pass over the partials, one fixed order (the same bytes in
+ *   every run).  alpha, beta, rr stay on the device; every check_every iterations and at max_iter the host downloads rn
+ *   (8 bytes) and stops when rn <= tol^2 bb.  iterations, residual = sqrt(rn / bb), converged: HOST.  bb == 0 (or not finite):
+ *   SVS_EINVAL, "no normal field".  tol in (0,1), max_iter >= 1, check_every >= 1.  Synchronises the stream.
+ * svs_poisson_sample: vals DEVICE double[n] = sum over the corners, ascending from zero, of weight * x[node], NaN for a point
+ *   that does not count; level HOST = the mean over the counted points (sums per workgroup of 256 points by a binary tree,
+ *   thread t of the last pass adding the partials t, t + 256, ... from zero, then the same tree), 0 when none counts;
+ *   counted HOST.  Synchronises the stream.  n >= 1.
+ * svs_poisson_face_keep: cells[f] = the node index (i*n1 + j)*n2 + k of the cell face f came from (svs_mc_emit's active
+ *   node); keep[f] = 1 iff the float64 sum, in corner order from zero, of W over the cell's eight nodes is >= min_density
+ *   (a node on an upper face or an index out of range: 0).  Not svs_tsdf_face_keep's rule: a trilinear splat leaves the
+ *   far nodes of a surface cell nearly empty.
+ * Every check comes before any HIP call: SVS_ESHAPE for a grid with fewer than two nodes along an axis or 2^31 nodes or
+ * more, n < 1, a negative face count; SVS_EINVAL for a null required pointer, h <= 0 or not finite, an origin that is not
+ * finite, with the entry's name in the message. */
+int svs_poisson_tile(int SVS_HOST* tile);
+size_t svs_poisson_splat_workspace_bytes(int n, int n0, int n1, int n2);
+int svs_poisson_splat(const double* pts, const float* normals, int n, int n0, int n1, int n2, const double SVS_HOST* origin, double h,
+                      void* workspace, float* field, int SVS_HOST* counts, void* hip_stream);
+int svs_poisson_divergence(const float* field, int n0, int n1, int n2, double h, float* rhs, void* hip_stream);
+int svs_poisson_apply(const float* x, int n0, int n1, int n2, double h, float* y, void* hip_stream);
+size_t svs_poisson_cg_workspace_bytes(int n0, int n1, int n2);
+int svs_poisson_cg(const float* rhs, int n0, int n1, int n2, double h, double tol, int max_iter, int check_every, void* workspace,
+                   float* x, int SVS_HOST* iterations, double SVS_HOST* residual, int SVS_HOST* converged, void* hip_stream);
+size_t svs_poisson_sample_workspace_bytes(int n);
+int svs_poisson_sample(const float* x, int n0, int n1, int n2, const double SVS_HOST* origin, double h, const double* pts, int n,
+                       void* workspace, double* vals, double SVS_HOST* level, int SVS_HOST* counted, void* hip_stream);
+int svs_poisson_face_keep(const float* W, int n0, int n1, int n2, const int* cells, int n_faces, double min_density, uint8_t* keep,
+                          void* hip_stream);
+
 /* ---- numeric-contract self tests (used by tests/test_gpu_parity.py) --------------------------------------- */
 int svs_selftest_exp(const float* x, float* y_exp, float* y_expm1, int n, void* hip_stream);
 int svs_selftest_arith(const float* a, const float* b, float* quotient, float* sqrt_abs_a, int n, void* hip_stream);

@@ -23,6 +23,9 @@ filter_depth_folder`) -> {outdir}/mvsnet{scan:03}_l3.ply.
     +cloud_clean=true [+cloud_k=20 +cloud_std_ratio=2.0 +cloud_normal_k=16]   after the point clouds, every scan's cloud
                              without its statistical outliers and with oriented normals (`svs_hip.cloudclean`), in
                              {outdir}/clean/mvsnet{scan:03}_l3.ply (`python -m evals.eval_dtu --datadir {outdir}/clean`)
+    +cloud_poisson=V         with +cloud_clean=true: every scan's cleaned cloud meshed by `svs_hip.poisson` on a grid of node
+                             spacing V, {outdir}/poisson/mvsnet{scan:03}_l3.ply
+                             (`python -m evals.eval_dtu --datadir {outdir}/poisson --mode mesh`)
 
 Differences from the reference, all deliberate: `gpu: auto` keeps the current device (there is no GPUtil probe) and an
 integer selects it with torch.cuda.set_device; `prevent_oom` is taken as given; the five-second sleep before the first
@@ -151,6 +154,17 @@ def check_tsdf_simplify(args):
     return float(r)
 
 
+def check_cloud_poisson(args):
+    """+cloud_poisson=V: a positive node spacing, and only together with +cloud_clean=true, whose normals it meshes (ValueError
+    naming the key) -> V or None"""
+    v = args.get("cloud_poisson")
+    if v is None:
+        return None
+    _require(isinstance(v, (int, float)) and not isinstance(v, bool) and v > 0, "cloud_poisson", f"a positive node spacing, got {v!r}")
+    _require(bool(args.get("cloud_clean")), "cloud_poisson", "meshes the cleaned clouds: give +cloud_clean=true as well")
+    return float(v)
+
+
 def save_yaml(path, args):
     import yaml
     with open(path, "w") as f:
@@ -162,6 +176,7 @@ def run_help(args, select_device=True):
     (:48-53, as ValueError naming the key), outdir and all_scans.yaml (unless filter_only).  -> args"""
     a = attr_view(args)
     check_tsdf_simplify(args)
+    check_cloud_poisson(args)
     if select_device and args["gpu"] != "auto":
         import torch
         torch.cuda.set_device(int(args["gpu"]))
@@ -474,6 +489,28 @@ def clean_clouds(args, testlist):
     return out
 
 
+def poisson_ply_name(outdir, scan):
+    """the Poisson mesh of a scan's cleaned cloud, where `evals.eval_dtu --datadir {outdir}/poisson --mode mesh` finds it"""
+    return ply_name(os.path.join(outdir, "poisson"), scan)
+
+
+def poisson_meshes(args, testlist):
+    """+cloud_poisson=V: every scan's cleaned cloud (`clean_clouds`) meshed by `poisson.reconstruct_ply` on a grid of node
+    spacing V into {outdir}/poisson/mvsnet{scan:03}_l3.ply; one time line per scan.  -> {scene: reconstruct_ply's stats}"""
+    from . import poisson
+    voxel = check_cloud_poisson(args)
+    out = OrderedDict()
+    for scan in testlist:
+        ply = poisson_ply_name(args["outdir"], scan)
+        stats = poisson.reconstruct_ply(clean_ply_name(args["outdir"], scan), ply, voxel)["stats"]
+        g = stats["grid"]
+        info(f"saving the Poisson mesh to {ply} ({stats['n_verts']} vertices, {stats['faces_after']} of {stats['faces_before']} faces, "
+             f"grid {g[0]} x {g[1]} x {g[2]}, {stats['iterations']} iterations)")
+        info(f"{scan} cloud poisson seconds: " + ", ".join(f"{k} {v:.3f}" for k, v in stats["seconds"].items()))
+        out[scan] = stats
+    return out
+
+
 def create_scenes(args, testlist):
     """runner.py:74-108, 447-452: the folder of cameras and images that image-based rendering reads, per scan"""
     from . import mvsdata
@@ -523,6 +560,8 @@ def main(argv=None, scan_fn=None):
             result["simple_meshes"] = tsdf_simplified(args, testlist)
     if args.get("cloud_clean"):
         result["clean"] = clean_clouds(args, testlist)
+        if args.get("cloud_poisson") is not None:
+            result["poisson"] = poisson_meshes(args, testlist)
     return result
 
 
