@@ -628,7 +628,8 @@ int svs_fuse_points(const double* depth_avg, const uint8_t* final_mask, const fl
  * One reference (evaluation) view, n_src in 1..16 source (training) views, H and W positive multiples of 8 (the
  * reference's pyrUp(g_i) must match g_(i-1)'s shape).  float32 throughout; workspace: svs_ibr_workspace_bytes(), shared
  * by both entries (stream-ordered).  Both entries check every argument before their first launch: a rejected call
- * (SVS_EINVAL: null pointer or n_src out of range; SVS_ESHAPE: H or W) writes nothing.
+ * (SVS_EINVAL: null pointer or n_src out of range; SVS_ESHAPE: H or W) writes nothing, and the size query answers 0
+ * for every n_src, H, W that they reject.
  * svs_ibr_weights: simple_ibr.py:171-214 -- per source, cv2.remap(INTER_CUBIC, BORDER_CONSTANT 0) of the image and of
  *   the direction field at map_x / map_y (5-bit fixed point, OpenCV's A = -0.75 cubic), the sampled direction
  *   normalised, cos_dir = dot with ref_dir, nan_to_num, times geo_mask; the constant 0.2 of the render appended;

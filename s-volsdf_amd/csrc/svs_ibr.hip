@@ -409,7 +409,8 @@ using namespace svs::ibr;
 extern "C" {
 
 size_t svs_ibr_workspace_bytes(int n_src, int H, int W) {
-  if (n_src < 1 || n_src > kMaxSrc || H < 8 || W < 8) return 0;
+  // 0 for every size the two entries reject (check_sizes, without its error text)
+  if (n_src < 1 || n_src > kMaxSrc || H < 8 || W < 8 || (H & 7) || (W & 7) || (long long)H * W > kMaxPixels) return 0;
   return Layout(n_src, H, W).total;
 }
 

@@ -14,12 +14,10 @@ import torch
 
 import ibr_oracle as io_
 import synth
+from ibr_cases import REACH, TOL, dilate, near_threshold, run_blend, run_weights
 from make_ibr_fixture import digest
 
 pytestmark = pytest.mark.gpu
-F32 = np.float32
-TOL = 1e-5
-REACH = 32
 SVS_EINVAL, SVS_ESHAPE = -1, -2
 
 
@@ -45,48 +43,6 @@ def views(golden, tmp_path_factory):
         assert digest(o["blend"]) == str(golden[f"sha_blend_{vid}"])
         res[vid] = (ref, srcs, pred, o)
     return scan, out, res
-
-
-def dilate(mask, r):
-    """Chebyshev dilation of a boolean (H,W) mask by r pixels."""
-    m = np.asarray(mask, bool)
-    for ax in (0, 1):
-        c = np.cumsum(np.pad(m, [(r + 1, r) if a == ax else (0, 0) for a in (0, 1)]).astype(np.int32), axis=ax)
-        hi = np.take(c, np.arange(2 * r + 1, c.shape[ax]), axis=ax)
-        lo = np.take(c, np.arange(0, c.shape[ax] - 2 * r - 1), axis=ax)
-        m = (hi - lo) > 0
-    return m
-
-
-def near_threshold(weights):
-    """pixels whose weight of some source lies within 1e-6 of 0.2"""
-    return (np.abs(weights[:-1].astype(np.float64) - 0.2) < 1e-6).any(0)
-
-
-def run_weights(L, srcs_img, src_dirs, ref_dir, pred, geo, x2d, y2d, dev):
-    from svs_hip.ops import _ptr, _ptr_array, _stream
-    n, H, W = geo.shape
-    t = lambda a, dt=torch.float32: torch.from_numpy(np.ascontiguousarray(a)).to(dev, dt)   # noqa: E731
-    imgs, dirs = [t(a) for a in srcs_img], [t(a) for a in src_dirs]
-    rd, pr, g, mx, my = t(ref_dir), t(pred), t(np.asarray(geo, np.uint8), torch.uint8), t(x2d), t(y2d)
-    ws = torch.empty(int(L.svs_ibr_workspace_bytes(n, H, W)), dtype=torch.uint8, device=dev)
-    fill = torch.empty(n + 1, H, W, 3, device=dev)
-    masks = torch.empty(n + 1, H, W, device=dev)
-    rc = L.svs_ibr_weights(_ptr_array(imgs), _ptr_array(dirs), _ptr(rd), _ptr(pr), _ptr(g), _ptr(mx), _ptr(my), n, H, W,
-                           _ptr(ws), _ptr(fill), _ptr(masks), _stream())
-    assert rc == 0
-    return fill.cpu().numpy(), masks.cpu().numpy()
-
-
-def run_blend(L, fill, masks, dev):
-    from svs_hip.ops import _ptr, _stream
-    n1, H, W = masks.shape
-    f = torch.from_numpy(np.ascontiguousarray(fill, F32)).to(dev)
-    m = torch.from_numpy(np.ascontiguousarray(masks, F32)).to(dev)
-    ws = torch.empty(int(L.svs_ibr_workspace_bytes(n1 - 1, H, W)), dtype=torch.uint8, device=dev)
-    out = torch.empty(H, W, 3, device=dev)
-    assert L.svs_ibr_laplacian_blend(_ptr(f), _ptr(m), n1 - 1, H, W, _ptr(ws), _ptr(out), _stream()) == 0
-    return out.cpu().numpy()
 
 
 def test_blend_stage_matches_reference(dev, views):
