@@ -1283,6 +1283,73 @@ int svs_plan_info(void* plan, int* counts);
 int svs_plan_describe(void* plan, char* text, size_t capacity);
 int svs_plan_destroy(void* plan);
 
+/* ---- a mesh made smoother: connectivity, Taubin smoothing, bilateral normal filtering (svs_hip.meshsmooth;
+ * csrc/svs_meshsmooth.hip) ---------------------------------------------------------------------------------------------------
+ * Taubin, "A signal processing approach to fair surface design" (1995); Zheng et al., "Bilateral normal filtering for mesh
+ * denoising" (2011, local scheme) with the vertex update of Sun et al., "Fast and effective feature-preserving mesh
+ * denoising" (2007), Tukey biweights in place of the Gaussians.  The reference has no such step; the arithmetic below is
+ * this project's (tests/meshsmooth_oracle.py restates it in numpy float64).  All arithmetic is float64 without contraction,
+ * IEEE division and sqrt, no library function.  No float atomics: every sum has one order that depends on the input alone.
+ * verts DEVICE float[n_verts][3], faces DEVICE int[n_faces][3].  n_faces <= (2^31 - 1) / 6.
+ *
+ * A face is VALID exactly as in the svs_mesh_cluster_* section (indices in [0, n_verts), corners finite, cross(P1-P0, P2-P0)
+ * of finite length > 0), so it has three different indices.  Invalid faces contribute nothing and are never dereferenced
+ * past the index check.  An EDGE is an unordered pair {a, b} of a valid face; its use = the number of (valid face, side)
+ * pairs that name it (a face listed twice counts twice); BOUNDARY: use == 1; NON-MANIFOLD: use > 2.
+ *
+ * svs_mesh_adjacency: flags DEVICE int[n_verts] = SVS_MESH_USED (a corner of a valid face) | SVS_MESH_BOUNDARY (an end of a
+ *   boundary edge) | SVS_MESH_NONMANIFOLD (an end of a non-manifold edge).  nbr_start DEVICE int[n_verts + 1], nbr DEVICE
+ *   int[6 n_faces] (nbr_start[n_verts] entries written): each distinct neighbour of a vertex once, ascending by index;
+ *   nbr_boundary DEVICE uint8, parallel to nbr: 1 where that edge is a boundary edge.  face_start DEVICE int[n_verts + 1],
+ *   vert_face DEVICE int[3 n_faces] (face_start[n_verts] entries written): the valid faces of a vertex, ascending by face
+ *   index.  face_valid DEVICE uint8[n_faces].  counts HOST int[4] = edges, boundary edges, non-manifold edges, valid faces.
+ *   Built from a radix sort of the directed pairs keyed a << 32 | b, run-length passes and scans; integer atomics only
+ *   (flags, counts).  Synchronises the stream.  workspace: svs_mesh_smooth_workspace_bytes(n_verts, n_faces) bytes; nothing
+ *   is kept in it between calls.
+ * svs_mesh_taubin: x DEVICE double[n_verts][3] in and out (the result is in x whatever the parity of the pass count), tmp
+ *   DEVICE double[n_verts][3].  iters >= 0, lambda in (0,1], mu in [-2,0], boundary one of SVS_SMOOTH_FIXED / CURVE / FREE.
+ *   One iteration = a pass with factor lambda, then a pass with factor mu (skipped when mu == 0: plain Laplacian).  A pass
+ *   with factor s is Jacobi (it reads only the previous positions), one lane per vertex i: not USED: y = x; a BOUNDARY vertex
+ *   under FIXED: y = x; a BOUNDARY vertex under CURVE: N = its neighbours across boundary edges; FREE or an interior vertex:
+ *   N = all neighbours; N empty: y = x; else per component m = the sum of x[j] over N in ascending j, left to right from
+ *   zero, and y = x + s * (m / count - x).
+ * svs_mesh_face_frames: per valid face from x DEVICE double[n_verts][3]: n = cross(P1-P0, P2-P0), L = sqrt(n.x n.x + n.y n.y
+ *   + n.z n.z), normals DEVICE double[n_faces][3] = n / L per component, areas DEVICE double[n_faces] = 0.5 L, centroids
+ *   DEVICE double[n_faces][3] = ((P0 + P1) + P2) / 3; zeros for an invalid face.
+ * svs_mesh_normal_filter: iters Jacobi passes over normals (in and out; tmp DEVICE double[n_faces][3]); areas and centroids
+ *   stay as given.  Per valid face f: s = area_f * n_f; for corner k = 0, 1, 2 each face g of vert_face of that corner,
+ *   ascending, g != f: d2 = dx dx + dy dy + dz dz of the centroids, q2 the same of n_f - n_g, a = 1 - d2 / (rs rs),
+ *   b = 1 - q2 / (rn rn); skipped unless a > 0 and b > 0; w = (area_g * (a a)) * (b b); s += w * n_g per component.  A face
+ *   that shares an edge with f is met at two corners and COUNTS TWICE: that is the rule.  Ls = sqrt(s.s); the new normal is
+ *   s / Ls when Ls is finite and > 0, else the old one.  rs > 0 (the spatial support), rn in (0,2] (the support on |n_f - n_g|).
+ * svs_mesh_vertex_update: iters Jacobi passes over x (x, tmp as in svs_mesh_taubin) with the normals as given; centroids are
+ *   those of the pass's input positions (the expression above).  Per USED vertex i that is not a BOUNDARY vertex under
+ *   FIXED, its faces f ascending: d = c_f - x_i, t = (n.x d.x + n.y d.y) + n.z d.z, acc += n_f * t per component;
+ *   y = x + acc / count.  SVS_SMOOTH_FIXED or SVS_SMOOTH_FREE only.
+ * The arrays nbr_start .. flags are those svs_mesh_adjacency wrote for the same mesh; they are trusted.  nbr, nbr_boundary and
+ * vert_face may be null for a mesh without a valid face: they are then never read.
+ * Every check comes before any HIP call: SVS_ESHAPE for a negative count or too many faces, SVS_EINVAL for a null required
+ * pointer, iters < 0 or a parameter outside its range, with the entry's name in the message.  An empty mesh is not an error. */
+#define SVS_MESH_USED 1
+#define SVS_MESH_BOUNDARY 2
+#define SVS_MESH_NONMANIFOLD 4
+#define SVS_SMOOTH_FIXED 0
+#define SVS_SMOOTH_CURVE 1
+#define SVS_SMOOTH_FREE 2
+size_t svs_mesh_smooth_workspace_bytes(int n_verts, int n_faces);
+int svs_mesh_adjacency(const float* verts, int n_verts, const int* faces, int n_faces, void* workspace, int* nbr_start, int* nbr,
+                       uint8_t* nbr_boundary, int* face_start, int* vert_face, uint8_t* face_valid, int* flags, int SVS_HOST* counts,
+                       void* hip_stream);
+int svs_mesh_taubin(double* x, double* tmp, int n_verts, const int* nbr_start, const int* nbr, const uint8_t* nbr_boundary,
+                    const int* flags, int iters, double lambda, double mu, int boundary, void* hip_stream);
+int svs_mesh_face_frames(const double* x, int n_verts, const int* faces, const uint8_t* face_valid, int n_faces, double* normals,
+                         double* areas, double* centroids, void* hip_stream);
+int svs_mesh_normal_filter(const int* faces, const uint8_t* face_valid, int n_faces, int n_verts, const int* face_start,
+                           const int* vert_face, const double* areas, const double* centroids, double* normals, double* tmp, int iters,
+                           double rs, double rn, void* hip_stream);
+int svs_mesh_vertex_update(double* x, double* tmp, int n_verts, const int* faces, int n_faces, const int* face_start,
+                           const int* vert_face, const int* flags, const double* normals, int iters, int boundary, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

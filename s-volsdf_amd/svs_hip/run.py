@@ -20,6 +20,9 @@ filter_depth_folder`) -> {outdir}/mvsnet{scan:03}_l3.ply.
     +tsdf_simplify=R         with +tsdf_voxel: every scan's TSDF mesh also simplified to at most R (in (0,1)) of its faces by
                              `svs_hip.meshsimplify`, {outdir}/tsdf_simple/mvsnet{scan:03}_l3.ply
                              (`python -m evals.eval_dtu --datadir {outdir}/tsdf_simple --mode mesh`)
+    +tsdf_smooth=N [+tsdf_smooth_method=taubin|denoise]   with +tsdf_voxel: every scan's TSDF mesh also smoothed by
+                             `svs_hip.meshsmooth` (N iterations, boundary fixed), {outdir}/tsdf_smooth/mvsnet{scan:03}_l3.ply;
+                             +tsdf_simplify then simplifies the smoothed mesh
     +cloud_clean=true [+cloud_k=20 +cloud_std_ratio=2.0 +cloud_normal_k=16]   after the point clouds, every scan's cloud
                              without its statistical outliers and with oriented normals (`svs_hip.cloudclean`), in
                              {outdir}/clean/mvsnet{scan:03}_l3.ply (`python -m evals.eval_dtu --datadir {outdir}/clean`)
@@ -154,6 +157,20 @@ def check_tsdf_simplify(args):
     return float(r)
 
 
+def check_tsdf_smooth(args):
+    """+tsdf_smooth=N [+tsdf_smooth_method=taubin|denoise]: a positive integer and one of the two names, and only together
+    with +tsdf_voxel (ValueError naming the key) -> (N, method) or None"""
+    n, method = args.get("tsdf_smooth"), args.get("tsdf_smooth_method")
+    if n is None:
+        _require(method is None, "tsdf_smooth_method", "names the method of +tsdf_smooth=N: give that as well")
+        return None
+    _require(isinstance(n, int) and not isinstance(n, bool) and n > 0, "tsdf_smooth", f"a positive number of iterations, got {n!r}")
+    method = "taubin" if method is None else method
+    _require(method in ("taubin", "denoise"), "tsdf_smooth_method", f"taubin or denoise, got {method!r}")
+    _require(bool(args.get("tsdf_voxel")), "tsdf_smooth", "smooths the TSDF meshes: give +tsdf_voxel=V as well")
+    return int(n), method
+
+
 def check_cloud_poisson(args):
     """+cloud_poisson=V: a positive node spacing, and only together with +cloud_clean=true, whose normals it meshes (ValueError
     naming the key) -> V or None"""
@@ -176,6 +193,7 @@ def run_help(args, select_device=True):
     (:48-53, as ValueError naming the key), outdir and all_scans.yaml (unless filter_only).  -> args"""
     a = attr_view(args)
     check_tsdf_simplify(args)
+    check_tsdf_smooth(args)
     check_cloud_poisson(args)
     if select_device and args["gpu"] != "auto":
         import torch
@@ -444,16 +462,43 @@ def tsdf_simple_ply_name(outdir, scan):
     return ply_name(os.path.join(outdir, "tsdf_simple"), scan)
 
 
+def tsdf_smooth_ply_name(outdir, scan):
+    """the smoothed TSDF mesh of a scan, where `evals.eval_dtu --datadir {outdir}/tsdf_smooth --mode mesh` finds it"""
+    return ply_name(os.path.join(outdir, "tsdf_smooth"), scan)
+
+
+def tsdf_smoothed(args, testlist):
+    """+tsdf_smooth=N [+tsdf_smooth_method=M]: every scan's TSDF mesh (`tsdf_meshes`) smoothed by `meshsmooth.smooth_ply` into
+    {outdir}/tsdf_smooth/mvsnet{scan:03}_l3.ply -- taubin: N iterations; denoise: N vertex and max(1, N // 2) normal
+    iterations; the boundary fixed, because TSDF meshes are open surfaces; one time line per scan.
+    -> {scene: smooth_ply's stats}"""
+    from . import meshsmooth
+    n, method = check_tsdf_smooth(args)
+    out = OrderedDict()
+    for scan in testlist:
+        ply = tsdf_smooth_ply_name(args["outdir"], scan)
+        os.makedirs(os.path.dirname(ply), exist_ok=True)
+        stats = meshsmooth.smooth_ply(tsdf_ply_name(args["outdir"], scan), ply, method, iters=n, vertex_iters=n,
+                                      normal_iters=max(1, n // 2), boundary="fixed")[3]
+        info(f"saving the smoothed TSDF mesh to {ply} ({method}, {n} iterations, {stats['faces']} faces, "
+             f"{stats['counts']['boundary_edges']} boundary edges)")
+        info(f"{scan} tsdf smooth seconds: " + ", ".join(f"{k} {v:.3f}" for k, v in stats["seconds"].items()))
+        out[scan] = stats
+    return out
+
+
 def tsdf_simplified(args, testlist):
-    """+tsdf_simplify=R: every scan's TSDF mesh (`tsdf_meshes`) simplified by `meshsimplify.simplify_ply` to at most R of its
-    faces, into {outdir}/tsdf_simple/mvsnet{scan:03}_l3.ply; one time line per scan.  -> {scene: simplify_ply's stats}"""
+    """+tsdf_simplify=R: every scan's TSDF mesh (`tsdf_meshes`; with +tsdf_smooth the smoothed one, `tsdf_smoothed`) simplified
+    by `meshsimplify.simplify_ply` to at most R of its faces, into {outdir}/tsdf_simple/mvsnet{scan:03}_l3.ply; one time line
+    per scan.  -> {scene: simplify_ply's stats}"""
     from . import meshsimplify
     ratio = check_tsdf_simplify(args)
+    source = tsdf_smooth_ply_name if args.get("tsdf_smooth") is not None else tsdf_ply_name
     out = OrderedDict()
     for scan in testlist:
         ply = tsdf_simple_ply_name(args["outdir"], scan)
         os.makedirs(os.path.dirname(ply), exist_ok=True)
-        stats = meshsimplify.simplify_ply(tsdf_ply_name(args["outdir"], scan), ply, ratio=ratio)[3]
+        stats = meshsimplify.simplify_ply(source(args["outdir"], scan), ply, ratio=ratio)[3]
         info(f"saving the simplified TSDF mesh to {ply} ({stats['faces_out']} of {stats['faces_in']} faces, cell {stats['cell']:.6g})")
         info(f"{scan} tsdf simplify seconds: " + ", ".join(f"{k} {v:.3f}" for k, v in stats["seconds"].items()))
         out[scan] = stats
@@ -556,6 +601,8 @@ def main(argv=None, scan_fn=None):
         result["meshes"] = tsdf_meshes(args, testlist)
         if args.get("tsdf_views"):
             result["mesh_views"] = tsdf_views(args, testlist)
+        if args.get("tsdf_smooth") is not None:
+            result["smooth_meshes"] = tsdf_smoothed(args, testlist)
         if args.get("tsdf_simplify") is not None:
             result["simple_meshes"] = tsdf_simplified(args, testlist)
     if args.get("cloud_clean"):
