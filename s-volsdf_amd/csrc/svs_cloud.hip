@@ -5,16 +5,15 @@
 // STL -> data completeness) that the reference runs through sklearn's kd-tree on the CPU.
 //
 // Here both neighbour problems use one structure (svs_cloud_grid.h, shared with svs_cloudknn.hip; built here): points
-// sorted by the key of their cell in a uniform grid
-// (rocPRIM radix sort -- the only library call) plus an open-addressing hash from cell key to the [begin, end) run
-// in the sorted order.  Neighbour candidates are the runs of the cells around the query, scanned in float64 with
-// the kd-tree's arithmetic (dx*dx + dy*dy + dz*dz, no fused multiply-add), so distances agree with sklearn's to the
-// last bit.  This is latency / HBM-bound gather work: no matrix cores.
-#include <hipcub/hipcub.hpp>
-
+// sorted by the key of their cell in a uniform grid (hipcub's DeviceRadixSort through svs_sorted_runs.h -- the only
+// library call) plus an open-addressing hash from cell key to the [begin, end) run in the sorted order.  Neighbour
+// candidates are the runs of the cells around the query, scanned in float64 with the kd-tree's arithmetic
+// (dx*dx + dy*dy + dz*dz, no fused multiply-add), so distances agree with sklearn's to the last bit.  This is latency /
+// HBM-bound gather work: no matrix cores.
 #include "svs_cloud_grid.h"
 #include "svs_common.h"
 #include "svs_scan.h"
+#include "svs_sorted_runs.h"
 
 namespace svs {
 namespace cloud {
@@ -209,10 +208,11 @@ __global__ void mean_final_kernel(const double* __restrict__ part, double* __res
 
 using namespace svs;
 using namespace svs::cloud;
+using namespace svs::ws;
 
 namespace {
 
-struct GridLayout {            // carve-up of the caller's workspace
+struct GridLayout {            // carve-up of the caller's workspace (svs_workspace.h)
   size_t keys, skeys, idx, sidx, spts, hkey, hrun, sort_tmp, total;
   unsigned cap;
   size_t sort_bytes;
@@ -222,25 +222,19 @@ unsigned pow2_at_least(size_t v) { unsigned c = 16; while (c < v) c <<= 1; retur
 
 GridLayout grid_layout(int n) {
   GridLayout L;
-  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  L.cap = pow2_at_least(2 * (size_t)(n > 0 ? n : 1));
-  L.sort_bytes = 0;
-  hipError_t e = hipcub::DeviceRadixSort::SortPairs(nullptr, L.sort_bytes, (const u64*)nullptr, (u64*)nullptr, (const unsigned*)nullptr,
-                                                    (unsigned*)nullptr, n > 0 ? n : 1, 0, 3 * kCellBits, (hipStream_t)0);
-  if (e != hipSuccess) { (void)hipGetLastError(); L.sort_bytes = 0; }
-  // never below a double buffer of the pairs: the size query needs a device, this bound does not
-  const size_t floor_bytes = 16 * (size_t)(n > 0 ? n : 1) + ((size_t)1 << 20);
-  if (L.sort_bytes < floor_bytes) L.sort_bytes = floor_bytes;
-  size_t o = 0;
-  L.keys = o; o += al(sizeof(u64) * (size_t)n);
-  L.skeys = o; o += al(sizeof(u64) * (size_t)n);
-  L.idx = o; o += al(sizeof(unsigned) * (size_t)n);
-  L.sidx = o; o += al(sizeof(unsigned) * (size_t)n);
-  L.spts = o; o += al(sizeof(double) * 3 * (size_t)n);
-  L.hkey = o; o += al(sizeof(u64) * (size_t)L.cap);
-  L.hrun = o; o += al(sizeof(uint2) * (size_t)L.cap);
-  L.sort_tmp = o; o += al(L.sort_bytes);
-  L.total = o + 256;
+  Bump b;
+  const size_t np = (size_t)n, m = (size_t)(n > 0 ? n : 1);
+  L.cap = pow2_at_least(2 * m);
+  L.keys = b.take(sizeof(u64) * np); L.skeys = b.take(sizeof(u64) * np);
+  L.idx = b.take(sizeof(unsigned) * np); L.sidx = b.take(sizeof(unsigned) * np);
+  L.spts = b.take(sizeof(double) * 3 * np);
+  L.hkey = b.take(sizeof(u64) * (size_t)L.cap); L.hrun = b.take(sizeof(uint2) * (size_t)L.cap);
+  // 16 bytes a point where the shared floor has 12: svs_cloud_grid_bytes has answered with 16 since before the floor was
+  // shared (on a device too: hipcub asks for less), and callers hold workspaces of that size
+  const size_t shared = runs::sort_scratch_bytes<u64, true>(m), own = 16 * m + ((size_t)1 << 20);
+  L.sort_bytes = shared > own ? shared : own;
+  L.sort_tmp = b.take(L.sort_bytes);
+  L.total = b.o + 256;
   return L;
 }
 
@@ -322,7 +316,7 @@ __global__ __launch_bounds__(256) void mesh_sample_kernel(const double* __restri
 // Builds the grid of `pts` in `ws`; returns the device-side view (declared in svs_cloud_grid.h).
 int svs::cloud::build_grid(const double* pts, int n, const double* origin, double h, void* ws, hipStream_t s, Grid* g) {
   const GridLayout L = grid_layout(n);
-  char* base = (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+  char* base = aligned(ws);
   u64* keys = (u64*)(base + L.keys); u64* skeys = (u64*)(base + L.skeys);
   unsigned* idx = (unsigned*)(base + L.idx); unsigned* sidx = (unsigned*)(base + L.sidx);
   double* spts = (double*)(base + L.spts);
@@ -331,9 +325,8 @@ int svs::cloud::build_grid(const double* pts, int n, const double* origin, doubl
   clear_hash_kernel<<<(L.cap + 255) / 256, 256, 0, s>>>(hkey, L.cap);
   if (n > 0) {
     keys_kernel<<<nb, 256, 0, s>>>(pts, n, origin[0], origin[1], origin[2], 1.0 / h, keys, idx);
-    size_t tmp = L.sort_bytes;
-    hipError_t e = hipcub::DeviceRadixSort::SortPairs(base + L.sort_tmp, tmp, keys, skeys, idx, sidx, n, 0, 3 * kCellBits, s);
-    if (e != hipSuccess) { set_error("cell sort: %s", hipGetErrorString(e)); return (int)e; }
+    const int rc = runs::sort_pairs("cell sort", base + L.sort_tmp, L.sort_bytes, keys, skeys, idx, sidx, n, 3 * kCellBits, s);
+    if (rc) return rc;
     heads_kernel<<<nb, 256, 0, s>>>(skeys, sidx, pts, n, hkey, hrun, L.cap - 1, spts);
     tails_kernel<<<nb, 256, 0, s>>>(skeys, n, hkey, hrun, L.cap - 1);
   }
@@ -377,7 +370,7 @@ int svs_cloud_downsample_round(const double* origin, int n, double radius, void*
   if (!origin || !grid_ws || !state || !undecided || n < 0) { set_error("svs_cloud_downsample_round: bad argument"); return SVS_EINVAL; }
   hipStream_t s = (hipStream_t)hip_stream;
   const GridLayout L = grid_layout(n);
-  char* base = (char*)(((uintptr_t)grid_ws + 255) & ~(uintptr_t)255);
+  char* base = aligned(grid_ws);
   Grid g;
   g.ox = origin[0]; g.oy = origin[1]; g.oz = origin[2]; g.inv_h = 1.0 / radius; g.h = radius;
   g.pts = (const double*)(base + L.spts); g.perm = (const unsigned*)(base + L.sidx);

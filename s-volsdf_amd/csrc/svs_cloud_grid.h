@@ -1,6 +1,6 @@
 // The uniform grid over a point cloud that the cloud kernels search (csrc/svs_cloud.hip builds it; svs_cloud.hip and
-// svs_cloudknn.hip read it): points sorted by the key of their cell (rocPRIM radix sort) plus an open-addressing hash from
-// cell key to the [begin, end) run of the cell in the sorted order.
+// svs_cloudknn.hip read it): points sorted by the key of their cell (hipcub's DeviceRadixSort, called through
+// svs_sorted_runs.h) plus an open-addressing hash from cell key to the [begin, end) run of the cell in the sorted order.
 #pragma once
 #include "svs_common.h"
 

@@ -100,7 +100,6 @@ __global__ __launch_bounds__(kKnnLanes) void knn_kernel(Grid g, const double* __
 
 // ---- statistics of the finite mean distances: one fixed two-level order, no atomics (the pattern of mean_partial_kernel) ----
 constexpr int kStatBlocks = 256;
-__device__ __forceinline__ bool finite_f64(double v) { return v - v == 0.0; }
 
 // SECOND == false: per block (sum, count) of the finite entries; SECOND: (sum of squared deviations from *mean, count)
 template <bool SECOND>

@@ -44,6 +44,9 @@ __device__ __forceinline__ unsigned xcd_chunked(unsigned i, unsigned n) {
 
 __host__ __device__ constexpr int rho(int r) { return (r & 3) + 8 * (r >> 2); }
 
+// neither NaN nor an infinity: v - v is 0 for every other float64
+__host__ __device__ __forceinline__ bool finite_f64(double v) { return v - v == 0.0; }
+
 // ------------------------------------------------------------------------------------------
 // exp / expm1 of the numeric contract: the float32 routines torch-CPU evaluates, restated
 // operation by operation -- Sleef 3.x `Sleef_expf8_u10` (xexpf) and `Sleef_expm1f8_u10` (xexpm1f = expk2f(a) - 1 in

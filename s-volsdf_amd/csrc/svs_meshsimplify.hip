@@ -10,12 +10,12 @@
 // duplicates (the same set of three cells) removed by a sort of the packed triple: the first face in input order stays.
 // All float64, compiled with -ffp-contract=off.  Plain wave64 kernels of 256 threads, sums in registers; the work is bound
 // by the bytes the sorts and the gathers move, not by arithmetic: no matrix cores.
-#include <hipcub/hipcub.hpp>
-
 #include "svs_cloud_grid.h"
 #include "svs_common.h"
 #include "svs_jacobi3.h"
+#include "svs_mesh_face.h"
 #include "svs_scan.h"
+#include "svs_sorted_runs.h"
 
 namespace svs {
 namespace simplify {
@@ -25,43 +25,14 @@ using cloud::cell_key;
 using cloud::kCellBits;
 using cloud::kEmpty;
 using cloud::u64;
+using meshface::Face;
+using meshface::load_face;
 
 constexpr int kSegment = 64;                                // pairs per segment of a cell's run
 constexpr int kMaxCells = 1 << kCellBits;                   // occupied cells per call: three ranks pack into one key
 constexpr int kMaxFaces = 0x7fffffff / 3;                   // 3 * n_faces pairs are indexed by int
 
 struct Cells { double ox, oy, oz, inv_h, h; };
-
-__device__ __forceinline__ bool finite_f64(double v) { return v - v == 0.0; }
-
-struct Face {
-  int i[3];
-  double p[3][3];                                           // corners, float32 widened
-  double n[3], L;                                           // cross(P1 - P0, P2 - P0) and its length
-};
-
-// face f -> t; false when it is not valid (nothing is read through an index outside [0, n_verts))
-__device__ __forceinline__ bool load_face(const float* __restrict__ verts, int n_verts, const int* __restrict__ faces, int f, Face& t) {
-#pragma unroll
-  for (int k = 0; k < 3; ++k) t.i[k] = faces[3 * (size_t)f + k];
-  if ((unsigned)t.i[0] >= (unsigned)n_verts || (unsigned)t.i[1] >= (unsigned)n_verts || (unsigned)t.i[2] >= (unsigned)n_verts) return false;
-  bool ok = true;
-#pragma unroll
-  for (int k = 0; k < 3; ++k)
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      t.p[k][a] = (double)verts[3 * (size_t)t.i[k] + a];
-      ok = ok && finite_f64(t.p[k][a]);
-    }
-  if (!ok) return false;
-  const double ux = t.p[1][0] - t.p[0][0], uy = t.p[1][1] - t.p[0][1], uz = t.p[1][2] - t.p[0][2];
-  const double vx = t.p[2][0] - t.p[0][0], vy = t.p[2][1] - t.p[0][1], vz = t.p[2][2] - t.p[0][2];
-  t.n[0] = uy * vz - uz * vy;
-  t.n[1] = uz * vx - ux * vz;
-  t.n[2] = ux * vy - uy * vx;
-  t.L = __builtin_sqrt(t.n[0] * t.n[0] + t.n[1] * t.n[1] + t.n[2] * t.n[2]);
-  return finite_f64(t.L) && t.L > 0.0;
-}
 
 // ---- cells ---------------------------------------------------------------------------------------------------------------
 // every lane that marks a vertex stores the same byte: the races are between equal values
@@ -84,13 +55,6 @@ __global__ __launch_bounds__(256) void vert_keys_kernel(const float* __restrict_
                  cell_coord((double)verts[3 * (size_t)v + 2], g.oz, g.inv_h));
   keys[v] = k;
   idx[v] = (unsigned)v;
-}
-
-__global__ __launch_bounds__(256) void cell_heads_kernel(const u64* __restrict__ skeys, int n, uint8_t* __restrict__ head) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const u64 k = skeys[i];
-  head[i] = (k != kEmpty && (i == 0 || skeys[i - 1] != k)) ? 1 : 0;
 }
 
 // offset[i] = heads before sorted position i: the rank of i's cell is offset[i] + head[i] - 1
@@ -123,32 +87,13 @@ __global__ __launch_bounds__(256) void pair_keys_kernel(const float* __restrict_
   }
 }
 
-// begin[r] = the first sorted position whose key is >= r, r = 0 .. n_cells: cell r's run is [begin[r], begin[r + 1])
-__global__ __launch_bounds__(256) void cell_begin_kernel(const unsigned* __restrict__ skeys, int n_pairs, int n_cells, int* __restrict__ begin) {
-  const int r = blockIdx.x * 256 + threadIdx.x;
-  if (r > n_cells) return;
-  int lo = 0, hi = n_pairs;
-  while (lo < hi) {
-    const int mid = lo + ((hi - lo) >> 1);
-    if (skeys[mid] < (unsigned)r) lo = mid + 1; else hi = mid;
-  }
-  begin[r] = lo;
-}
-
+// begin[r], r = 0 .. n_cells, from runs::lower_bound_kernel: cell r's run is [begin[r], begin[r + 1])
 __global__ __launch_bounds__(256) void seg_flags_kernel(const unsigned* __restrict__ skeys, int n_pairs, int n_cells,
                                                         const int* __restrict__ begin, uint8_t* __restrict__ flag) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n_pairs) return;
   const unsigned k = skeys[i];
   flag[i] = (k < (unsigned)n_cells && ((i - begin[k]) & (kSegment - 1)) == 0) ? 1 : 0;
-}
-
-__global__ __launch_bounds__(256) void seg_start_kernel(const uint8_t* __restrict__ flag, const int* __restrict__ offset, int n_pairs,
-                                                        int max_segs, int* __restrict__ seg_start) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n_pairs || !flag[i]) return;
-  const int s = offset[i];
-  if (s < max_segs) seg_start[s] = i;
 }
 
 struct Partial {                                            // 128 bytes
@@ -324,25 +269,9 @@ __global__ __launch_bounds__(256) void face_emit_kernel(const int* __restrict__ 
 
 using namespace svs;
 using namespace svs::simplify;
+using namespace svs::ws;
 
 namespace {
-
-struct Bump {                                               // carve-up of the caller's workspace, 256-byte slabs
-  size_t o = 0;
-  size_t take(size_t bytes) { const size_t at = o; o += (bytes + 255) & ~(size_t)255; return at; }
-};
-
-template <typename K>
-size_t sort_bytes(size_t n) {
-  size_t bytes = 0;
-  const int m = (int)(n > 0 ? n : 1);
-  hipError_t e = hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, (const K*)nullptr, (K*)nullptr, (const unsigned*)nullptr,
-                                                    (unsigned*)nullptr, m, 0, (int)(8 * sizeof(K)), (hipStream_t)0);
-  if (e != hipSuccess) { (void)hipGetLastError(); bytes = 0; }
-  // never below a double buffer of the pairs: the size query needs a device, this bound does not
-  const size_t floor_bytes = (sizeof(K) + sizeof(unsigned)) * (size_t)m + ((size_t)1 << 20);
-  return bytes < floor_bytes ? floor_bytes : bytes;
-}
 
 int cell_bound(int n_verts) { return n_verts < kMaxCells ? n_verts : kMaxCells; }
 
@@ -353,7 +282,7 @@ CellsLayout cells_layout(int n_verts) {
   const size_t n = (size_t)n_verts;
   L.used = b.take(n); L.keys = b.take(8 * n); L.skeys = b.take(8 * n); L.idx = b.take(4 * n); L.sidx = b.take(4 * n);
   L.head = b.take(n); L.offset = b.take(4 * n); L.count = b.take(sizeof(int));
-  L.sort_size = sort_bytes<u64>(n); L.sort_tmp = b.take(L.sort_size);
+  L.sort_size = runs::sort_scratch_bytes<u64, true>(n); L.sort_tmp = b.take(L.sort_size);
   L.total = b.o;
   return L;
 }
@@ -369,7 +298,7 @@ SolveLayout solve_layout(int n_verts, int n_faces) {
   L.keys = b.take(4 * np); L.skeys = b.take(4 * np); L.vals = b.take(4 * np); L.svals = b.take(4 * np);
   L.begin = b.take(4 * (nc + 2)); L.flag = b.take(np); L.offset = b.take(4 * np); L.count = b.take(sizeof(int));
   L.seg_start = b.take(4 * segs); L.part = b.take(sizeof(Partial) * segs);
-  L.sort_size = sort_bytes<unsigned>(np); L.sort_tmp = b.take(L.sort_size);
+  L.sort_size = runs::sort_scratch_bytes<unsigned, true>(np); L.sort_tmp = b.take(L.sort_size);
   L.total = b.o;
   return L;
 }
@@ -380,30 +309,17 @@ FacesLayout faces_layout(int n_faces) {
   Bump b;
   const size_t n = (size_t)n_faces;
   L.keys = b.take(8 * n); L.skeys = b.take(8 * n); L.idx = b.take(4 * n); L.sidx = b.take(4 * n);
-  L.sort_size = sort_bytes<u64>(n); L.sort_tmp = b.take(L.sort_size);
+  L.sort_size = runs::sort_scratch_bytes<u64, true>(n); L.sort_tmp = b.take(L.sort_size);
   L.total = b.o;
   return L;
 }
 
-char* aligned(void* ws) { return (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255); }
-
-int bit_length(unsigned v) { int b = 0; while (v) { ++b; v >>= 1; } return b; }
-
-// the checks every entry shares: counts, then the cell size
-int check_counts(const char* name, int n_verts, int n_faces) {
-  if (n_verts < 0 || n_faces < 0) { set_error("%s: negative count", name); return SVS_ESHAPE; }
-  if (n_faces > kMaxFaces) { set_error("%s: more than %d faces", name, kMaxFaces); return SVS_ESHAPE; }
-  return SVS_OK;
-}
+// the cell of every entry: the origin's pointer, then the cell size, then the origin's values
 int check_cell(const char* name, const double* origin, double h) {
-  if (!origin) { set_error("%s: bad argument (null pointer)", name); return SVS_EINVAL; }
-  if (!(h > 0.0) || !(h - h == 0.0)) { set_error("%s: the cell size must be positive and finite", name); return SVS_EINVAL; }
-  if (!(origin[0] - origin[0] == 0.0) || !(origin[1] - origin[1] == 0.0) || !(origin[2] - origin[2] == 0.0)) {
-    set_error("%s: the origin must be finite", name); return SVS_EINVAL;
-  }
-  return SVS_OK;
+  if (!origin) return null_pointer(name);
+  const int rc = check_spacing(name, h, "cell size");
+  return rc ? rc : check_origin(name, origin);
 }
-int hip_fail(const char* name, hipError_t e) { set_error("%s: %s", name, hipGetErrorString(e)); return (int)e; }
 
 }  // namespace
 
@@ -423,11 +339,9 @@ size_t svs_mesh_cluster_workspace_bytes(int n_verts, int n_faces) {
 int svs_mesh_cluster_cells(const float* verts, int n_verts, const int* faces, int n_faces, const double* origin, double h,
                            void* workspace, int* vert_cell, int* n_cells, void* hip_stream) {
   const char* name = "svs_mesh_cluster_cells";
-  int rc = check_counts(name, n_verts, n_faces);
+  int rc = check_counts(name, n_verts, n_faces, kMaxFaces);
   if (rc) return rc;
-  if (!n_cells || (n_verts > 0 && (!verts || !vert_cell || !workspace)) || (n_faces > 0 && !faces)) {
-    set_error("%s: bad argument (null pointer)", name); return SVS_EINVAL;
-  }
+  if (!n_cells || (n_verts > 0 && (!verts || !vert_cell || !workspace)) || (n_faces > 0 && !faces)) return null_pointer(name);
   rc = check_cell(name, origin, h);
   if (rc) return rc;
   *n_cells = 0;
@@ -450,18 +364,16 @@ int svs_mesh_cluster_cells(const float* verts, int n_verts, const int* faces, in
   if (e != hipSuccess) return hip_fail(name, e);
   mark_used_kernel<<<(n_faces + 255) / 256, 256, 0, s>>>(verts, n_verts, faces, n_faces, used);
   vert_keys_kernel<<<nb, 256, 0, s>>>(verts, n_verts, used, g, keys, idx);
-  size_t tmp = L.sort_size;
-  e = hipcub::DeviceRadixSort::SortPairs(base + L.sort_tmp, tmp, keys, skeys, idx, sidx, n_verts, 0, 64, s);
-  if (e != hipSuccess) return hip_fail(name, e);
-  cell_heads_kernel<<<nb, 256, 0, s>>>(skeys, n_verts, head);
+  rc = runs::sort_pairs(name, base + L.sort_tmp, L.sort_size, keys, skeys, idx, sidx, n_verts, 64, s);
+  if (rc) return rc;
+  runs::run_heads_kernel<u64><<<nb, 256, 0, s>>>(skeys, n_verts, kEmpty, head);
   scan::mask_offsets(head, n_verts, offset, count, s);
   vert_rank_kernel<<<nb, 256, 0, s>>>(skeys, sidx, head, offset, n_verts, vert_cell);
   rc = check_launch(name);
   if (rc) return rc;
   int cells = 0;
-  e = hipMemcpyAsync(&cells, count, sizeof(int), hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess) return hip_fail(name, e);
+  rc = download(name, count, 1, &cells, s);
+  if (rc) return rc;
   *n_cells = cells;
   if (cells > kMaxCells) {
     set_error("%s: %d occupied cells, at most %d in one call (use a larger cell)", name, cells, kMaxCells); return SVS_ESHAPE;
@@ -473,7 +385,7 @@ int svs_mesh_cluster_solve(const float* verts, int n_verts, const int* faces, in
                            const double* origin, double h, double tol, const int* vert_cell, int n_cells, void* workspace,
                            float* out_verts, uint8_t* out_colors, int* info, double* err, void* hip_stream) {
   const char* name = "svs_mesh_cluster_solve";
-  int rc = check_counts(name, n_verts, n_faces);
+  int rc = check_counts(name, n_verts, n_faces, kMaxFaces);
   if (rc) return rc;
   if (n_cells < 0) { set_error("%s: negative count", name); return SVS_ESHAPE; }
   if (n_cells > kMaxCells || n_cells > n_verts) {
@@ -501,14 +413,12 @@ int svs_mesh_cluster_solve(const float* verts, int n_verts, const int* faces, in
   const long long seg_cap = (long long)n_pairs / kSegment + n_cells;
   const int max_segs = (int)(seg_cap < L.max_segs ? seg_cap : L.max_segs);
   pair_keys_kernel<<<(n_faces + 255) / 256, 256, 0, s>>>(verts, n_verts, faces, n_faces, vert_cell, n_cells, keys, vals);
-  size_t tmp = L.sort_size;
-  hipError_t e = hipcub::DeviceRadixSort::SortPairs(base + L.sort_tmp, tmp, keys, skeys, vals, svals, n_pairs, 0,
-                                                    bit_length((unsigned)n_cells), s);
-  if (e != hipSuccess) return hip_fail(name, e);
-  cell_begin_kernel<<<(n_cells + 1 + 255) / 256, 256, 0, s>>>(skeys, n_pairs, n_cells, begin);
+  rc = runs::sort_pairs(name, base + L.sort_tmp, L.sort_size, keys, skeys, vals, svals, n_pairs, runs::bit_length((unsigned)n_cells), s);
+  if (rc) return rc;
+  runs::lower_bound_kernel<unsigned><<<(n_cells + 1 + 255) / 256, 256, 0, s>>>(skeys, n_pairs, n_cells, begin);
   seg_flags_kernel<<<pb, 256, 0, s>>>(skeys, n_pairs, n_cells, begin, flag);
   scan::mask_offsets(flag, n_pairs, offset, count, s);
-  seg_start_kernel<<<pb, 256, 0, s>>>(flag, offset, n_pairs, max_segs, seg_start);
+  runs::seg_start_kernel<256><<<pb, 256, 0, s>>>(flag, offset, n_pairs, max_segs, seg_start);
   seg_sum_kernel<<<(max_segs + 255) / 256, 256, 0, s>>>(verts, n_verts, faces, colors, g, skeys, svals, begin, seg_start, count, max_segs, part);
   cell_solve_kernel<<<(n_cells + 255) / 256, 256, 0, s>>>(verts, faces, g, tol, svals, begin, offset, n_cells, max_segs, part, out_verts,
                                                           out_colors, info, err);
@@ -518,15 +428,14 @@ int svs_mesh_cluster_solve(const float* verts, int n_verts, const int* faces, in
 int svs_mesh_cluster_faces_count(const float* verts, int n_verts, const int* faces, int n_faces, const int* vert_cell, int n_cells,
                                  void* workspace, uint8_t* keep, int* offsets, int* count, void* hip_stream) {
   const char* name = "svs_mesh_cluster_faces_count";
-  int rc = check_counts(name, n_verts, n_faces);
+  int rc = check_counts(name, n_verts, n_faces, kMaxFaces);
   if (rc) return rc;
   if (n_cells < 0) { set_error("%s: negative count", name); return SVS_ESHAPE; }
   if (n_cells > kMaxCells) {
     set_error("%s: %d cells, at most %d in one call: three ranks of 21 bits make a face's key", name, n_cells, kMaxCells); return SVS_ESHAPE;
   }
-  if (!count || (n_faces > 0 && (!faces || !workspace || !keep || !offsets || (n_verts > 0 && (!verts || !vert_cell))))) {
-    set_error("%s: bad argument (null pointer)", name); return SVS_EINVAL;
-  }
+  if (!count || (n_faces > 0 && (!faces || !workspace || !keep || !offsets || (n_verts > 0 && (!verts || !vert_cell)))))
+    return null_pointer(name);
   hipStream_t s = (hipStream_t)hip_stream;
   if (n_faces == 0) {
     hipError_t e = hipMemsetAsync(count, 0, sizeof(int), s);
@@ -538,10 +447,9 @@ int svs_mesh_cluster_faces_count(const float* verts, int n_verts, const int* fac
   unsigned* idx = (unsigned*)(base + L.idx); unsigned* sidx = (unsigned*)(base + L.sidx);
   const int nb = (n_faces + 255) / 256;
   face_keys_kernel<<<nb, 256, 0, s>>>(verts, n_verts, faces, n_faces, vert_cell, n_cells, keys, idx);
-  size_t tmp = L.sort_size;
-  hipError_t e = hipcub::DeviceRadixSort::SortPairs(base + L.sort_tmp, tmp, keys, skeys, idx, sidx, n_faces, 0,
-                                                    2 * kCellBits + bit_length((unsigned)n_cells), s);
-  if (e != hipSuccess) return hip_fail(name, e);
+  rc = runs::sort_pairs(name, base + L.sort_tmp, L.sort_size, keys, skeys, idx, sidx, n_faces,
+                        2 * kCellBits + runs::bit_length((unsigned)n_cells), s);
+  if (rc) return rc;
   face_keep_kernel<<<nb, 256, 0, s>>>(skeys, sidx, n_faces, (u64)n_cells << (2 * kCellBits), keep);
   scan::mask_offsets(keep, n_faces, offsets, count, s);
   return check_launch(name);
@@ -551,9 +459,7 @@ int svs_mesh_cluster_faces_emit(const int* faces, int n_faces, const int* vert_c
                                 int* out_faces, void* hip_stream) {
   const char* name = "svs_mesh_cluster_faces_emit";
   if (n_faces < 0) { set_error("%s: negative count", name); return SVS_ESHAPE; }
-  if (n_faces > 0 && (!faces || !vert_cell || !keep || !offsets || !out_faces)) {
-    set_error("%s: bad argument (null pointer)", name); return SVS_EINVAL;
-  }
+  if (n_faces > 0 && (!faces || !vert_cell || !keep || !offsets || !out_faces)) return null_pointer(name);
   if (n_faces == 0) return SVS_OK;
   face_emit_kernel<<<(n_faces + 255) / 256, 256, 0, (hipStream_t)hip_stream>>>(faces, n_faces, vert_cell, keep, offsets, out_faces);
   return check_launch(name);

@@ -5,14 +5,15 @@
 // Connectivity: the six directed pairs of every valid face are sorted by a << 32 | b (hipcub radix sort over the bits the
 // vertex count needs); a run of equal keys is one neighbour and its length the edge's use; a scan of the run heads
 // (svs_scan.h) gives the compressed rows.  The (vertex, face) pairs are sorted by vertex alone: the sort is stable, so a
-// vertex's faces stay in ascending order.  Row starts are binary searches in the sorted keys.
+// vertex's faces stay in ascending order.  Row starts are binary searches in the sorted keys.  The sorts, the run heads and
+// the plain lower bound are svs_sorted_runs.h's, shared with the other geometry units; which face is valid, svs_mesh_face.h.
 // Smoothing: gathers, one lane per vertex (or face) walking its own list left to right, 256-lane workgroups.  No float
 // atomics and no cooperative path for long lists: either would change the order of the sums.  All float64, compiled with
 // -ffp-contract=off.  Bound by the bytes of the positions, the rows and the frames: no matrix cores.
-#include <hipcub/hipcub.hpp>
-
 #include "svs_common.h"
+#include "svs_mesh_face.h"
 #include "svs_scan.h"
+#include "svs_sorted_runs.h"
 
 namespace svs {
 namespace smooth {
@@ -20,30 +21,6 @@ namespace smooth {
 typedef unsigned long long u64;
 
 constexpr int kMaxFaces = 0x7fffffff / 6;                   // 6 * n_faces directed pairs are indexed by int
-
-__device__ __forceinline__ bool finite_f64(double v) { return v - v == 0.0; }
-
-// the validity test of svs_meshsimplify.hip's load_face: nothing is read through an index outside [0, n_verts)
-__device__ __forceinline__ bool valid_face(const float* __restrict__ verts, int n_verts, const int* __restrict__ faces, int f, int (&i)[3]) {
-#pragma unroll
-  for (int k = 0; k < 3; ++k) i[k] = faces[3 * (size_t)f + k];
-  if ((unsigned)i[0] >= (unsigned)n_verts || (unsigned)i[1] >= (unsigned)n_verts || (unsigned)i[2] >= (unsigned)n_verts) return false;
-  double p[3][3];
-  bool ok = true;
-#pragma unroll
-  for (int k = 0; k < 3; ++k)
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      p[k][a] = (double)verts[3 * (size_t)i[k] + a];
-      ok = ok && finite_f64(p[k][a]);
-    }
-  if (!ok) return false;
-  const double ux = p[1][0] - p[0][0], uy = p[1][1] - p[0][1], uz = p[1][2] - p[0][2];
-  const double vx = p[2][0] - p[0][0], vy = p[2][1] - p[0][1], vz = p[2][2] - p[0][2];
-  const double nx = uy * vz - uz * vy, ny = uz * vx - ux * vz, nz = ux * vy - uy * vx;
-  const double L = __builtin_sqrt(nx * nx + ny * ny + nz * nz);
-  return finite_f64(L) && L > 0.0;
-}
 
 // ---- connectivity --------------------------------------------------------------------------------------------------------
 // pair 6 f + 2 side + direction; a pair of an invalid face gets the key n_verts << 32, behind every valid one.
@@ -54,8 +31,9 @@ __global__ __launch_bounds__(256) void pair_keys_kernel(const float* __restrict_
                                                         int* __restrict__ flags, int* __restrict__ cnt) {
   const int f = blockIdx.x * 256 + threadIdx.x;
   if (f >= n_faces) return;
-  int i[3];
-  const bool ok = valid_face(verts, n_verts, faces, f, i);
+  meshface::Face t;
+  const bool ok = meshface::load_face(verts, n_verts, faces, f, t);
+  const int (&i)[3] = t.i;
   face_valid[f] = ok ? 1 : 0;
   const u64 none = (u64)(unsigned)n_verts << 32;
 #pragma unroll
@@ -68,13 +46,6 @@ __global__ __launch_bounds__(256) void pair_keys_kernel(const float* __restrict_
     if (ok) atomicOr(&flags[a], SVS_MESH_USED);
   }
   if (ok) atomicAdd(&cnt[3], 1);
-}
-
-__global__ __launch_bounds__(256) void pair_heads_kernel(const u64* __restrict__ skeys, int n, u64 none, uint8_t* __restrict__ head) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const u64 k = skeys[i];
-  head[i] = (k != none && (i == 0 || skeys[i - 1] != k)) ? 1 : 0;
 }
 
 // one lane per run head: the neighbour, whether its edge is a boundary edge, the flags of the edge's ends, and (where a < b,
@@ -112,18 +83,6 @@ __global__ __launch_bounds__(256) void nbr_start_kernel(const u64* __restrict__ 
     if (skeys[mid] < key) lo = mid + 1; else hi = mid;
   }
   nbr_start[v] = lo < n ? offset[lo] : *n_heads;
-}
-
-// face_start[v] = the first sorted (vertex, face) pair whose vertex is >= v; v = 0 .. n_verts
-__global__ __launch_bounds__(256) void face_start_kernel(const unsigned* __restrict__ skeys, int n, int n_verts, int* __restrict__ face_start) {
-  const int v = blockIdx.x * 256 + threadIdx.x;
-  if (v > n_verts) return;
-  int lo = 0, hi = n;
-  while (lo < hi) {
-    const int mid = lo + ((hi - lo) >> 1);
-    if (skeys[mid] < (unsigned)v) lo = mid + 1; else hi = mid;
-  }
-  face_start[v] = lo;
 }
 
 // ---- Taubin ----------------------------------------------------------------------------------------------------------------
@@ -253,18 +212,9 @@ __global__ __launch_bounds__(256) void vertex_pass_kernel(const double* __restri
 
 using namespace svs;
 using namespace svs::smooth;
+using namespace svs::ws;
 
 namespace {
-
-struct Bump {                                               // carve-up of the caller's workspace, 256-byte slabs
-  size_t o = 0;
-  size_t take(size_t bytes) { const size_t at = o; o += (bytes + 255) & ~(size_t)255; return at; }
-};
-
-template <typename K>
-size_t sort_floor(size_t n) {                               // a bound that needs no device: a double buffer and a margin
-  return 2 * (sizeof(K) + sizeof(unsigned)) * (n > 0 ? n : 1) + ((size_t)1 << 20);
-}
 
 struct Layout { size_t pkeys, spkeys, head, offset, ckeys, sckeys, cvals, cnt, sort_tmp, sort_size, total; };
 Layout layout(int n_faces) {
@@ -273,31 +223,13 @@ Layout layout(int n_faces) {
   const size_t np = 6 * (size_t)n_faces, nc = 3 * (size_t)n_faces;
   L.pkeys = b.take(8 * np); L.spkeys = b.take(8 * np); L.head = b.take(np); L.offset = b.take(4 * np);
   L.ckeys = b.take(4 * nc); L.sckeys = b.take(4 * nc); L.cvals = b.take(4 * nc); L.cnt = b.take(8 * sizeof(int));
-  const int m = (int)(np > 0 ? np : 1);
-  size_t keys_bytes = 0, pairs_bytes = 0;
-  hipError_t e = hipcub::DeviceRadixSort::SortKeys(nullptr, keys_bytes, (const u64*)nullptr, (u64*)nullptr, m, 0, 64, (hipStream_t)0);
-  if (e != hipSuccess) { (void)hipGetLastError(); keys_bytes = 0; }
-  e = hipcub::DeviceRadixSort::SortPairs(nullptr, pairs_bytes, (const unsigned*)nullptr, (unsigned*)nullptr, (const unsigned*)nullptr,
-                                         (unsigned*)nullptr, (int)(nc > 0 ? nc : 1), 0, 32, (hipStream_t)0);
-  if (e != hipSuccess) { (void)hipGetLastError(); pairs_bytes = 0; }
-  size_t s = keys_bytes > pairs_bytes ? keys_bytes : pairs_bytes;
-  const size_t f = sort_floor<u64>(np);
-  L.sort_size = s < f ? f : s;
+  // one scratch serves both sorts: the directed pairs (keys alone) and the corners (with their faces)
+  const size_t pairs = runs::sort_scratch_bytes<u64, false>(np), corners = runs::sort_scratch_bytes<unsigned, true>(nc);
+  L.sort_size = pairs > corners ? pairs : corners;
   L.sort_tmp = b.take(L.sort_size);
   L.total = b.o;
   return L;
 }
-
-char* aligned(void* ws) { return (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255); }
-int bit_length(unsigned v) { int b = 0; while (v) { ++b; v >>= 1; } return b; }
-
-int check_counts(const char* name, int n_verts, int n_faces) {
-  if (n_verts < 0 || n_faces < 0) { set_error("%s: negative count", name); return SVS_ESHAPE; }
-  if (n_faces > kMaxFaces) { set_error("%s: more than %d faces", name, kMaxFaces); return SVS_ESHAPE; }
-  return SVS_OK;
-}
-int null_pointer(const char* name) { set_error("%s: bad argument (null pointer)", name); return SVS_EINVAL; }
-int hip_fail(const char* name, hipError_t e) { set_error("%s: %s", name, hipGetErrorString(e)); return (int)e; }
 
 // the result of an odd number of passes lies in tmp: bring it home
 int settle(const char* name, double* x, const double* cur, size_t doubles, hipStream_t s) {
@@ -323,7 +255,7 @@ int svs_mesh_adjacency(const float* verts, int n_verts, const int* faces, int n_
                        uint8_t* nbr_boundary, int* face_start, int* vert_face, uint8_t* face_valid, int* flags, int* counts,
                        void* hip_stream) {
   const char* name = "svs_mesh_adjacency";
-  int rc = check_counts(name, n_verts, n_faces);
+  int rc = check_counts(name, n_verts, n_faces, kMaxFaces);
   if (rc) return rc;
   if (!counts || !nbr_start || !face_start || (n_verts > 0 && (!verts || !flags)) ||
       (n_faces > 0 && (!faces || !workspace || !nbr || !nbr_boundary || !vert_face || !face_valid)))
@@ -346,28 +278,25 @@ int svs_mesh_adjacency(const float* verts, int n_verts, const int* faces, int n_
   unsigned* ckeys = (unsigned*)(base + L.ckeys); unsigned* sckeys = (unsigned*)(base + L.sckeys); unsigned* cvals = (unsigned*)(base + L.cvals);
   int* cnt = (int*)(base + L.cnt);                           // edges, boundary, non-manifold, valid faces, run heads
   const int n_pairs = 6 * n_faces, n_corners = 3 * n_faces;
-  const int bits = bit_length((unsigned)n_verts);
+  const int bits = runs::bit_length((unsigned)n_verts);
   const u64 none = (u64)(unsigned)n_verts << 32;
   e = hipMemsetAsync(cnt, 0, 8 * sizeof(int), s);
   if (e != hipSuccess) return hip_fail(name, e);
   pair_keys_kernel<<<(n_faces + 255) / 256, 256, 0, s>>>(verts, n_verts, faces, n_faces, pkeys, ckeys, cvals, face_valid, flags, cnt);
-  size_t tmp = L.sort_size;
-  e = hipcub::DeviceRadixSort::SortKeys(base + L.sort_tmp, tmp, pkeys, spkeys, n_pairs, 0, 32 + bits, s);
-  if (e != hipSuccess) return hip_fail(name, e);
-  tmp = L.sort_size;
-  e = hipcub::DeviceRadixSort::SortPairs(base + L.sort_tmp, tmp, ckeys, sckeys, cvals, (unsigned*)vert_face, n_corners, 0, bits, s);
-  if (e != hipSuccess) return hip_fail(name, e);
-  pair_heads_kernel<<<(n_pairs + 255) / 256, 256, 0, s>>>(spkeys, n_pairs, none, head);
+  rc = runs::sort_keys(name, base + L.sort_tmp, L.sort_size, pkeys, spkeys, n_pairs, 32 + bits, s);
+  if (rc) return rc;
+  rc = runs::sort_pairs(name, base + L.sort_tmp, L.sort_size, ckeys, sckeys, cvals, (unsigned*)vert_face, n_corners, bits, s);
+  if (rc) return rc;
+  runs::run_heads_kernel<u64><<<(n_pairs + 255) / 256, 256, 0, s>>>(spkeys, n_pairs, none, head);
   scan::mask_offsets(head, n_pairs, offset, cnt + 4, s);
   emit_nbr_kernel<<<(n_pairs + 255) / 256, 256, 0, s>>>(spkeys, head, offset, n_pairs, nbr, nbr_boundary, flags, cnt);
   nbr_start_kernel<<<(n_verts + 1 + 255) / 256, 256, 0, s>>>(spkeys, offset, cnt + 4, n_pairs, n_verts, nbr_start);
-  face_start_kernel<<<(n_verts + 1 + 255) / 256, 256, 0, s>>>(sckeys, n_corners, n_verts, face_start);
+  runs::lower_bound_kernel<unsigned><<<(n_verts + 1 + 255) / 256, 256, 0, s>>>(sckeys, n_corners, n_verts, face_start);
   rc = check_launch(name);
   if (rc) return rc;
   int host[4] = {0, 0, 0, 0};
-  e = hipMemcpyAsync(host, cnt, sizeof(host), hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess) return hip_fail(name, e);
+  rc = download(name, cnt, 4, host, s);
+  if (rc) return rc;
   for (int k = 0; k < 4; ++k) counts[k] = host[k];
   return SVS_OK;
 }
@@ -401,7 +330,7 @@ int svs_mesh_taubin(double* x, double* tmp, int n_verts, const int* nbr_start, c
 int svs_mesh_face_frames(const double* x, int n_verts, const int* faces, const uint8_t* face_valid, int n_faces, double* normals,
                          double* areas, double* centroids, void* hip_stream) {
   const char* name = "svs_mesh_face_frames";
-  int rc = check_counts(name, n_verts, n_faces);
+  int rc = check_counts(name, n_verts, n_faces, kMaxFaces);
   if (rc) return rc;
   if (n_faces > 0 && (!faces || !face_valid || !normals || !areas || !centroids || (n_verts > 0 && !x))) return null_pointer(name);
   if (n_faces == 0) return SVS_OK;
@@ -420,12 +349,12 @@ int svs_mesh_normal_filter(const int* faces, const uint8_t* face_valid, int n_fa
                            const int* vert_face, const double* areas, const double* centroids, double* normals, double* tmp, int iters,
                            double rs, double rn, void* hip_stream) {
   const char* name = "svs_mesh_normal_filter";
-  int rc = check_counts(name, n_verts, n_faces);
+  int rc = check_counts(name, n_verts, n_faces, kMaxFaces);
   if (rc) return rc;
   // vert_face may be null for a mesh without a valid face: it is then never read
   if (n_faces > 0 && (!faces || !face_valid || !face_start || !areas || !centroids || !normals || !tmp)) return null_pointer(name);
   if (iters < 0) { set_error("%s: iters must not be negative", name); return SVS_EINVAL; }
-  if (!(rs > 0.0) || !(rs - rs == 0.0)) { set_error("%s: rs must be positive and finite", name); return SVS_EINVAL; }
+  if (!(rs > 0.0) || !finite_f64(rs)) { set_error("%s: rs must be positive and finite", name); return SVS_EINVAL; }
   if (!(rn > 0.0 && rn <= 2.0)) { set_error("%s: rn must lie in (0,2]", name); return SVS_EINVAL; }
   if (n_faces == 0 || iters == 0) return SVS_OK;
   hipStream_t s = (hipStream_t)hip_stream;
@@ -442,7 +371,7 @@ int svs_mesh_normal_filter(const int* faces, const uint8_t* face_valid, int n_fa
 int svs_mesh_vertex_update(double* x, double* tmp, int n_verts, const int* faces, int n_faces, const int* face_start,
                            const int* vert_face, const int* flags, const double* normals, int iters, int boundary, void* hip_stream) {
   const char* name = "svs_mesh_vertex_update";
-  int rc = check_counts(name, n_verts, n_faces);
+  int rc = check_counts(name, n_verts, n_faces, kMaxFaces);
   if (rc) return rc;
   // vert_face may be null for a mesh without a valid face: it is then never read
   if (n_verts > 0 && (!x || !tmp || !face_start || !flags || (n_faces > 0 && (!faces || !normals)))) return null_pointer(name);

@@ -19,10 +19,9 @@
 // the halo (1.16 in the plane, 1.125 along the march).  16-byte accesses when n2 % 4 == 0 and the bases are aligned,
 // scalar ones otherwise; both walk the nodes in the same order, so both give the same sums.
 // All float64 arithmetic is compiled with -ffp-contract=off.
-#include <hipcub/hipcub.hpp>
-
 #include "svs_common.h"
 #include "svs_scan.h"
+#include "svs_sorted_runs.h"
 
 namespace svs {
 namespace poisson {
@@ -36,8 +35,6 @@ constexpr int kLdsStride = kTileK + 8;                      // interior at colum
 enum { kRR = 0, kBB = 1, kAlpha = 2, kBeta = 3, kRN = 4, kScalars = 8 };
 
 struct Grid { double ox, oy, oz, h; long long n0, n1, n2; };
-
-__device__ __forceinline__ bool finite_f64(double v) { return v - v == 0.0; }
 
 // the cell of a point and its position in it; false when the point does not count
 __device__ __forceinline__ bool locate(const Grid& g, double px, double py, double pz, long long (&b)[3], double (&t)[3]) {
@@ -118,14 +115,6 @@ __global__ __launch_bounds__(256) void seg_flags_kernel(const unsigned* __restri
   if (i >= n) return;
   const int r = hoff[i] + (int)head[i] - 1;
   flag[i] = (skeys[i] < n_cells && ((i - run_first[r]) & (kSegment - 1)) == 0) ? 1 : 0;
-}
-
-__global__ __launch_bounds__(256) void seg_start_kernel(const uint8_t* __restrict__ flag, const int* __restrict__ soff, int n, int max_segs,
-                                                        int* __restrict__ seg_start) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n || !flag[i]) return;
-  const int s = soff[i];
-  if (s < max_segs) seg_start[s] = i;
 }
 
 struct Partial { double s[8][4]; };                         // corner c: Vx, Vy, Vz, W; 256 bytes
@@ -479,28 +468,9 @@ __global__ __launch_bounds__(256) void face_keep_kernel(const float* __restrict_
 
 using namespace svs;
 using namespace svs::poisson;
+using namespace svs::ws;
 
 namespace {
-
-struct Bump {                                               // carve-up of the caller's workspace, 256-byte slabs
-  size_t o = 0;
-  size_t take(size_t bytes) { const size_t at = o; o += (bytes + 255) & ~(size_t)255; return at; }
-};
-
-size_t sort_bytes(size_t n) {
-  size_t bytes = 0;
-  const int m = (int)(n > 0 ? n : 1);
-  hipError_t e = hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, (const unsigned*)nullptr, (unsigned*)nullptr, (const unsigned*)nullptr,
-                                                    (unsigned*)nullptr, m, 0, 32, (hipStream_t)0);
-  if (e != hipSuccess) { (void)hipGetLastError(); bytes = 0; }
-  // never below a double buffer of the pairs: the size query needs a device, this bound does not
-  const size_t floor_bytes = 8 * (size_t)m + ((size_t)1 << 20);
-  return bytes < floor_bytes ? floor_bytes : bytes;
-}
-
-char* aligned(void* ws) { return (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255); }
-int bit_length(unsigned v) { int b = 0; while (v) { ++b; v >>= 1; } return b; }
-int hip_fail(const char* name, hipError_t e) { set_error("%s: %s", name, hipGetErrorString(e)); return (int)e; }
 
 // cells of a grid; 0 when a size is below 2
 long long cell_count(int n0, int n1, int n2) {
@@ -523,7 +493,7 @@ SplatLayout splat_layout(int n, long long cells) {
   L.head = b.take(np); L.hoff = b.take(4 * np); L.flag = b.take(np); L.soff = b.take(4 * np);
   L.run_first = b.take(4 * (np + 2)); L.seg_start = b.take(4 * segs); L.part = b.take(sizeof(Partial) * segs);
   L.cell_seg = b.take(4 * (size_t)cells); L.counts = b.take(4 * sizeof(int));
-  L.sort_size = sort_bytes(np); L.sort_tmp = b.take(L.sort_size);
+  L.sort_size = runs::sort_scratch_bytes<unsigned, true>(np); L.sort_tmp = b.take(L.sort_size);
   L.total = b.o;
   return L;
 }
@@ -557,17 +527,7 @@ int check_grid(const char* name, int n0, int n1, int n2) {
   if ((long long)n0 * n1 * n2 > 0x7fffffffLL) { set_error("%s: more than 2^31 - 1 nodes", name); return SVS_ESHAPE; }
   return SVS_OK;
 }
-int check_h(const char* name, double h) {
-  if (!(h > 0.0) || !(h - h == 0.0)) { set_error("%s: the node spacing must be positive and finite", name); return SVS_EINVAL; }
-  return SVS_OK;
-}
-int check_origin(const char* name, const double* origin) {
-  if (!origin) { set_error("%s: bad argument (null pointer)", name); return SVS_EINVAL; }
-  if (!(origin[0] - origin[0] == 0.0) || !(origin[1] - origin[1] == 0.0) || !(origin[2] - origin[2] == 0.0)) {
-    set_error("%s: the origin must be finite", name); return SVS_EINVAL;
-  }
-  return SVS_OK;
-}
+int check_h(const char* name, double h) { return check_spacing(name, h, "node spacing"); }
 
 void launch_stencil(const float* p, float* q, int n0, int n1, int n2, double h, double* partial, hipStream_t s) {
   dim3 grid;
@@ -584,7 +544,7 @@ void launch_stencil(const float* p, float* q, int n0, int n1, int n2, double h, 
 extern "C" {
 
 int svs_poisson_tile(int* tile) {
-  if (!tile) { set_error("svs_poisson_tile: bad argument (null pointer)"); return SVS_EINVAL; }
+  if (!tile) return null_pointer("svs_poisson_tile");
   tile[0] = kTileI; tile[1] = kTileJ; tile[2] = kTileK;
   return SVS_OK;
 }
@@ -600,7 +560,7 @@ int svs_poisson_splat(const double* pts, const float* normals, int n, int n0, in
   int rc = check_grid(name, n0, n1, n2);
   if (rc) return rc;
   if (n <= 0) { set_error("%s: no points (n = %d)", name, n); return SVS_ESHAPE; }
-  if (!pts || !normals || !workspace || !field || !counts) { set_error("%s: bad argument (null pointer)", name); return SVS_EINVAL; }
+  if (!pts || !normals || !workspace || !field || !counts) return null_pointer(name);
   rc = check_origin(name, origin);
   if (rc) return rc;
   rc = check_h(name, h);
@@ -621,24 +581,22 @@ int svs_poisson_splat(const double* pts, const float* normals, int n, int n0, in
   hipError_t e = hipMemsetAsync(cell_seg, 0xff, sizeof(int) * (size_t)cells, s);
   if (e != hipSuccess) return hip_fail(name, e);
   point_keys_kernel<<<nb, 256, 0, s>>>(pts, normals, n, g, (unsigned)cells, keys, vals, dcounts);
-  size_t tmp = L.sort_size;
-  e = hipcub::DeviceRadixSort::SortPairs(base + L.sort_tmp, tmp, keys, skeys, vals, svals, n, 0, bit_length((unsigned)cells), s);
-  if (e != hipSuccess) return hip_fail(name, e);
+  rc = runs::sort_pairs(name, base + L.sort_tmp, L.sort_size, keys, skeys, vals, svals, n, runs::bit_length((unsigned)cells), s);
+  if (rc) return rc;
   run_heads_kernel<<<nb, 256, 0, s>>>(skeys, n, (unsigned)cells, head, dcounts);
   scan::mask_offsets(head, n, hoff, dcounts + 1, s);
   run_first_kernel<<<nb, 256, 0, s>>>(head, hoff, n, run_first);
   seg_flags_kernel<<<nb, 256, 0, s>>>(skeys, n, (unsigned)cells, head, hoff, run_first, flag);
   scan::mask_offsets(flag, n, soff, dcounts + 2, s);
-  seg_start_kernel<<<nb, 256, 0, s>>>(flag, soff, n, L.max_segs, seg_start);
+  runs::seg_start_kernel<256><<<nb, 256, 0, s>>>(flag, soff, n, L.max_segs, seg_start);
   seg_sum_kernel<<<(L.max_segs + 255) / 256, 256, 0, s>>>(pts, normals, g, svals, head, hoff, run_first, seg_start, dcounts + 2, L.max_segs, part);
   cell_sum_kernel<<<nb, 256, 0, s>>>(skeys, (unsigned)cells, run_first, soff, dcounts + 1, n, L.max_segs, part, cell_seg);
   node_gather_kernel<<<(unsigned)((total + 255) / 256), 256, 0, s>>>(g, cell_seg, part, field);
   rc = check_launch(name);
   if (rc) return rc;
   int counted = 0;
-  e = hipMemcpyAsync(&counted, dcounts, sizeof(int), hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess) return hip_fail(name, e);
+  rc = download(name, dcounts, 1, &counted, s);
+  if (rc) return rc;
   counts[0] = counted; counts[1] = n - counted;
   return SVS_OK;
 }
@@ -647,7 +605,7 @@ int svs_poisson_divergence(const float* field, int n0, int n1, int n2, double h,
   const char* name = "svs_poisson_divergence";
   int rc = check_grid(name, n0, n1, n2);
   if (rc) return rc;
-  if (!field || !rhs) { set_error("%s: bad argument (null pointer)", name); return SVS_EINVAL; }
+  if (!field || !rhs) return null_pointer(name);
   rc = check_h(name, h);
   if (rc) return rc;
   const long long total = (long long)n0 * n1 * n2;
@@ -659,7 +617,7 @@ int svs_poisson_apply(const float* x, int n0, int n1, int n2, double h, float* y
   const char* name = "svs_poisson_apply";
   int rc = check_grid(name, n0, n1, n2);
   if (rc) return rc;
-  if (!x || !y) { set_error("%s: bad argument (null pointer)", name); return SVS_EINVAL; }
+  if (!x || !y) return null_pointer(name);
   if (x == y) { set_error("%s: bad argument (x and y are the same array)", name); return SVS_EINVAL; }
   rc = check_h(name, h);
   if (rc) return rc;
@@ -677,7 +635,7 @@ int svs_poisson_cg(const float* rhs, int n0, int n1, int n2, double h, double to
   const char* name = "svs_poisson_cg";
   int rc = check_grid(name, n0, n1, n2);
   if (rc) return rc;
-  if (!rhs || !workspace || !x || !iterations || !residual || !converged) { set_error("%s: bad argument (null pointer)", name); return SVS_EINVAL; }
+  if (!rhs || !workspace || !x || !iterations || !residual || !converged) return null_pointer(name);
   rc = check_h(name, h);
   if (rc) return rc;
   if (!(tol > 0.0) || !(tol < 1.0)) { set_error("%s: tol must lie in (0,1)", name); return SVS_EINVAL; }
@@ -696,10 +654,9 @@ int svs_poisson_cg(const float* rhs, int n0, int n1, int n2, double h, double to
   rc = check_launch(name);
   if (rc) return rc;
   double bb = 0.0, rn = 0.0;
-  hipError_t e = hipMemcpyAsync(&bb, scal + kBB, sizeof(double), hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess) return hip_fail(name, e);
-  if (!(bb > 0.0) || !(bb - bb == 0.0)) {
+  rc = download(name, scal + kBB, 1, &bb, s);
+  if (rc) return rc;
+  if (!(bb > 0.0) || !finite_f64(bb)) {
     set_error("%s: no normal field (the right-hand side is zero or not finite: |rhs|^2 = %g)", name, bb); return SVS_EINVAL;
   }
   rn = bb;
@@ -714,11 +671,10 @@ int svs_poisson_cg(const float* rhs, int n0, int n1, int n2, double h, double to
     if (it % check_every == 0 || it == max_iter) {
       rc = check_launch(name);
       if (rc) return rc;
-      e = hipMemcpyAsync(&rn, scal + kRN, sizeof(double), hipMemcpyDeviceToHost, s);
-      if (e == hipSuccess) e = hipStreamSynchronize(s);
-      if (e != hipSuccess) return hip_fail(name, e);
+      rc = download(name, scal + kRN, 1, &rn, s);
+      if (rc) return rc;
       if (rn <= tol * tol * bb) { *converged = 1; break; }
-      if (!(rn - rn == 0.0)) break;                          // not finite: more iterations change nothing
+      if (!finite_f64(rn)) break;                            // not finite: more iterations change nothing
     }
   }
   *iterations = it;
@@ -737,7 +693,7 @@ int svs_poisson_sample(const float* x, int n0, int n1, int n2, const double* ori
   int rc = check_grid(name, n0, n1, n2);
   if (rc) return rc;
   if (n <= 0) { set_error("%s: no points (n = %d)", name, n); return SVS_ESHAPE; }
-  if (!x || !pts || !workspace || !vals || !level || !counted) { set_error("%s: bad argument (null pointer)", name); return SVS_EINVAL; }
+  if (!x || !pts || !workspace || !vals || !level || !counted) return null_pointer(name);
   rc = check_origin(name, origin);
   if (rc) return rc;
   rc = check_h(name, h);
@@ -753,9 +709,8 @@ int svs_poisson_sample(const float* x, int n0, int n1, int n2, const double* ori
   rc = check_launch(name);
   if (rc) return rc;
   double host[2] = {0.0, 0.0};
-  hipError_t e = hipMemcpyAsync(host, out, sizeof(host), hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess) return hip_fail(name, e);
+  rc = download(name, out, 2, host, s);
+  if (rc) return rc;
   *level = host[0]; *counted = (int)host[1];
   return SVS_OK;
 }
@@ -767,7 +722,7 @@ int svs_poisson_face_keep(const float* W, int n0, int n1, int n2, const int* cel
   if (rc) return rc;
   if (n_faces < 0) { set_error("%s: negative count", name); return SVS_ESHAPE; }
   if (n_faces == 0) return SVS_OK;
-  if (!W || !cells || !keep) { set_error("%s: bad argument (null pointer)", name); return SVS_EINVAL; }
+  if (!W || !cells || !keep) return null_pointer(name);
   face_keep_kernel<<<(n_faces + 255) / 256, 256, 0, (hipStream_t)hip_stream>>>(W, n0, n1, n2, cells, n_faces, min_density, keep);
   return check_launch(name);
 }

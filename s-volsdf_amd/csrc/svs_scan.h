@@ -2,7 +2,9 @@
 // Three launches over blocks of 4096 bytes (256 threads x 16): per-block counts, one workgroup turning them into bases,
 // per-block offsets.  The per-block counts / bases live in offset[4096 b] (the block's own first slot, which the third
 // launch overwrites last), so no workspace beyond the n ints of `offset` is needed.  Used by the depth-fusion point list
-// (svs_fusion.hip, runner.py:377-386) and the evaluator's compaction (svs_cloud.hip): both keep the row-major order.
+// (svs_fusion.hip, runner.py:377-386) and the evaluator's compaction (svs_cloud.hip), which keep the row-major order, and
+// over the head and segment flags of sorted runs (svs_sorted_runs.h) by svs_meshsimplify.hip (cells, segments, kept faces),
+// svs_poisson.hip (runs, segments) and svs_meshsmooth.hip (neighbour rows).
 // (A single workgroup walking the whole mask -- the first version -- took 3.5 ms for a 1200 x 1600 mask.)
 #pragma once
 #include "svs_common.h"

@@ -303,6 +303,7 @@ SMALL = {
     "face_twice": ([[0, 0, 0], [1, 0, 0], [0, 1, 0], [1, 1, 0]], [[0, 1, 2], [2, 1, 3], [0, 1, 2]]),
     "unused_vertex": ([[0, 0, 0], [1, 0, 0], [0, 1, 0], [5, 5, 5]], [[0, 1, 2]]),
     "bad_faces": ([[0, 0, 0], [1, 0, 0], [0, 1, 0], [np.nan, 0, 0], [2, 0, 0]], [[0, 1, 2], [0, 1, 5], [0, 1, 3], [0, 1, 4], [-1, 0, 1], [1, 1, 2]]),
+    "no_valid_face": ([[0, 0, 0], [1, 0, 0], [0, 1, 0]], [[0, 0, 1], [0, 1, 7]]),      # every sorted key is the sentinel
 }
 
 

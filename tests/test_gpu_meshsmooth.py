@@ -76,8 +76,8 @@ def _adjacency_equal(got, want, what):
 
 # ---- adjacency -----------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", ["empty", "triangle", "two_triangles", "tetrahedron", "three_on_an_edge", "face_twice", "unused_vertex",
-                                  "bad_faces", "fin", "cube", "sphere", "patch", "sphere_shuffled", "bad", "bipyramid_63", "bipyramid_64",
-                                  "bipyramid_65", "bipyramid_4097"])
+                                  "bad_faces", "no_valid_face", "fin", "cube", "sphere", "patch", "sphere_shuffled", "bad", "bipyramid_63",
+                                  "bipyramid_64", "bipyramid_65", "bipyramid_4097"])
 def test_adjacency(name):
     v, f, want = case(name)
     got = sm.adjacency(v, f)
