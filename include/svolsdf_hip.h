@@ -615,7 +615,10 @@ int svs_prob_wta(const float* reg, const float* depth_values, int D, int H, int 
  * Optional per-source outputs (all four or none, (n_src,H,W)): the tuple check_geometric_consistency returns.
  * svs_fuse_points: the surviving pixels in row-major order -> world xyz float32 (count,3) and, if ref_img (H,W,3
  * float32 in [0,1]) is given, uint8 colours (count,3) = trunc(img * 255).  mats: inv(K_ref) (9), inv(E_ref) (16).
- * offset_ws: H*W ints; xyz / rgb sized for H*W points; *count (device int) receives the number written. */
+ * offset_ws: H*W ints; xyz / rgb sized for H*W points; *count (device int) receives the number written.
+ * Both entries check every argument before their first launch: a rejected call (SVS_EINVAL: a null pointer, a null entry
+ * of src_depths, an incomplete set of per-source outputs; SVS_ESHAPE: n_src outside 0..16, H or W below 1, or H * W above
+ * 2^31 - 256, the range of the kernels' int pixel index and grid size) writes nothing. */
 int svs_fuse_mats_per_src(void);
 int svs_fuse_view(const float* ref_depth, const float* confidence, const float* const SVS_HOST* src_depths,
                   const double* mats, int n_src, int H, int W, float conf, double filter_dist, float filter_diff, int thres_view,

@@ -16,6 +16,8 @@ namespace fusion {
 
 constexpr int kMaxSrc = 16;
 constexpr int kMatsPerSrc = 68;      // Kri(9) Trs(16) Ks(9) Ksi(9) Tsr(16) Kr(9), row-major float64
+// both kernels index pixels and size their grid in int: H * W + 255 must not wrap
+constexpr long long kMaxPixels = 2147483647LL - 255;
 
 struct FuseArgs {
   const float* ref_depth;            // (H,W)
@@ -165,6 +167,7 @@ int svs_fuse_view(const float* ref_depth, const float* confidence, const float* 
     set_error("svs_fuse_view: null argument"); return SVS_EINVAL;
   }
   if (n_src < 0 || n_src > kMaxSrc || H < 1 || W < 1) { set_error("svs_fuse_view: bad sizes (n_src <= %d)", kMaxSrc); return SVS_ESHAPE; }
+  if ((long long)H * W > kMaxPixels) { set_error("svs_fuse_view: H * W = %lld exceeds %lld pixels", (long long)H * W, kMaxPixels); return SVS_ESHAPE; }
   if (src_mask && (!src_depth_reproj || !src_x || !src_y)) { set_error("svs_fuse_view: per-source outputs come as a set"); return SVS_EINVAL; }
   FuseArgs a;
   a.ref_depth = ref_depth; a.confidence = confidence; a.mats = mats; a.extra_mask = extra_mask;
@@ -186,6 +189,7 @@ int svs_fuse_points(const double* depth_avg, const uint8_t* final_mask, const fl
     set_error("svs_fuse_points: null argument"); return SVS_EINVAL;
   }
   if (H < 1 || W < 1) { set_error("svs_fuse_points: bad sizes"); return SVS_ESHAPE; }
+  if ((long long)H * W > kMaxPixels) { set_error("svs_fuse_points: H * W = %lld exceeds %lld pixels", (long long)H * W, kMaxPixels); return SVS_ESHAPE; }
   hipStream_t s = (hipStream_t)hip_stream;
   scan::mask_offsets(final_mask, (long long)H * W, offset_ws, count, s);
   int rc = check_launch("svs_fuse_points(scan)");
