@@ -931,7 +931,10 @@ int svs_mesh_sample_points(const double* tri, int n_tri, const long long* offset
  * svs_cloud_normals: for point i the set S = {pts[j] : j = idx[i, s], 0 <= j < n} (idx (n,k) int32, 1 <= k <= 32: what
  *   svs_cloud_knn wrote, -1 = no neighbour) plus pts[i] itself when include_self != 0.  The float64 covariance of S about
  *   its centroid, its eigenvectors by cyclic Jacobi (8 sweeps, rotations in the order (0,1), (0,2), (1,2)); the normal is
- *   the eigenvector of the smallest eigenvalue l0, curvature = l0 / (l0 + l1 + l2) (0 for a zero trace).
+ *   the eigenvector of the smallest eigenvalue l0, curvature = l0 / (l0 + l1 + l2) (0 for a zero trace; an l0 that
+ *   rounding left below 0 counts as 0, so 0 <= curvature <= 1/3).  Of equal smallest entries of the rotated diagonal the
+ *   lowest index is taken; a covariance that is diagonal as summed is not rotated, so its normal is the positive axis of
+ *   its smallest diagonal entry, the lowest axis among equal ones (all points coincident: (1,0,0), curvature 0).
  *   centres (n_views,3) float64 DEVICE or NULL: NULL leaves the normal as the solver gave it; otherwise it is negated when
  *   n . (c - p) < 0, c = centres[view_index[i]] (view_index (n) int32, clamped to [0, n_views)) or, with view_index NULL,
  *   the centre nearest to the point (the lowest index on a tie).  normals (n,3) float32, unit length; curvature (n)

@@ -67,26 +67,33 @@ def clean_scores(pts, k, max_radius, std_ratio):
 # ---- normals -------------------------------------------------------------------------------------------------------------
 def normals(pts, idx, include_self=True, view_index=None, centres=None):
     """-> (normals (n,3) float64 unit, curvature (n,), eigenvalues (n,3) ascending, facing (n,) = n . (c - p) / |c - p| BEFORE
-    the flip, nan without centres).  The covariance of the neighbours idx[i] >= 0 (and the point) about their centroid,
-    np.linalg.eigh; the normal is negated when n . (c - p) < 0, c = centres[view_index[i]] or the nearest centre (lowest
-    index on a tie).  Fewer than three points: zeros."""
+    the flip, nan without centres).  The covariance of the neighbours 0 <= idx[i] < n (and the point) about their centroid,
+    np.linalg.eigh; the normal is negated when n . (c - p) < 0, c = centres[view_index[i]] (clamped to [0, n_views)) or the
+    nearest centre (lowest index on a tie).  Fewer than three points: zeros.
+    A covariance that is diagonal as summed is not rotated by the kernel's Jacobi: the normal is then the POSITIVE axis of
+    its smallest diagonal entry, the lowest axis among equal ones (include/svolsdf_hip.h, f4c) -- eigh's choice inside an
+    eigenspace of equal eigenvalues is LAPACK's, not the contract's."""
     pts = np.asarray(pts, np.float64).reshape(-1, 3)
     n = len(pts)
     out, curv, lam, facing = np.zeros((n, 3)), np.zeros(n), np.zeros((n, 3)), np.full(n, np.nan)
     for i in range(n):
-        sel = [j for j in idx[i] if j >= 0]
+        sel = [j for j in idx[i] if 0 <= j < n]
         S = pts[([i] if include_self else []) + sel]
         if len(S) < 3:
             continue
         d = S - S.mean(0)
-        w, v = np.linalg.eigh(d.T @ d / len(S))
-        nrm = v[:, 0] / np.linalg.norm(v[:, 0])
+        cov = d.T @ d / len(S)
+        if not (cov - np.diag(np.diag(cov))).any():
+            w, nrm = np.sort(np.diag(cov)), np.eye(3)[int(np.argmin(np.diag(cov)))]
+        else:
+            w, v = np.linalg.eigh(cov)
+            nrm = v[:, 0] / np.linalg.norm(v[:, 0])
         lam[i] = w
         curv[i] = max(w[0], 0.0) / w.sum() if w.sum() > 0 else 0.0
         if centres is not None:
             C = np.asarray(centres, np.float64).reshape(-1, 3)
             if view_index is not None:
-                c = C[int(view_index[i])]
+                c = C[min(max(int(view_index[i]), 0), len(C) - 1)]
             else:
                 e = C - pts[i]
                 c = C[int(np.argmin(e[:, 0] * e[:, 0] + e[:, 1] * e[:, 1] + e[:, 2] * e[:, 2]))]
