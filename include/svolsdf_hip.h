@@ -1356,6 +1356,75 @@ int svs_mesh_normal_filter(const int* faces, const uint8_t* face_valid, int n_fa
 int svs_mesh_vertex_update(double* x, double* tmp, int n_verts, const int* faces, int n_faces, const int* face_start,
                            const int* vert_face, const int* flags, const double* normals, int iters, int boundary, void* hip_stream);
 
+/* ---- a texture atlas baked from a scan's photographs (svs_hip.meshtexture; csrc/svs_meshtexture.hip) ----------------------
+ * One chart per valid face, two charts per square cell of the atlas: no unwrapping, no seam pass (the meshes this is for are
+ * marching-cubes meshes and their clustered simplifications, whose faces are near-uniform in size).  The reference has no
+ * such step; the arithmetic below is this project's (tests/meshtexture_oracle.py restates it in numpy float64).  Cameras,
+ * projection, pixel convention and the 16 views per call are those of svs_mesh_paint; all arithmetic is float64 without
+ * contraction.  verts DEVICE float[n_verts][3], faces DEVICE int[n_faces][3].
+ *
+ * THE ATLAS is S x S texels, c <= S <= 32768; texel (i, j) has its centre at x = i, y = j and row 0 is the top row of the
+ * picture.  A cell is c x c texels, c >= 6; n = S / c (integer division) cells fit per row; columns and rows from n c on
+ * are an unused margin.  Slot s lies in cell q = s >> 1, half h = s & 1, with the cell's origin at (ox, oy) =
+ * ((q % n) c, (q / n) c).  Chart corners in the cell's local texel coordinates:
+ *   lower (h = 0): A0 = (1, 1), A1 = (c-4, 1), A2 = (1, c-4);    upper (h = 1): A0 = (c-2, c-2), A1 = (2, c-2), A2 = (c-2, 2).
+ * Local texel (i, j) BELONGS to the lower chart iff i + j <= c - 2, otherwise to the upper one.  At every point of a
+ * chart's closed triangle every bilinear tap with a non-zero weight (step 6 of svs_mesh_paint) is a texel of the same cell
+ * that belongs to the same chart (tests/test_meshtexture_cpu.py checks it in exact rationals for c = 6 .. 40).
+ *
+ * svs_mesh_atlas_slots: a face is VALID exactly as in the svs_mesh_cluster_* section.  Its slot is its rank among the valid
+ *   faces in index order (an exclusive scan of the flags, csrc/svs_scan.h).  Its rotation r puts the longest edge on the
+ *   chart's hypotenuse: with d_k = dx dx + dy dy + dz dz of P_((k+2)%3) - P_((k+1)%3) in float64, r = 0, then r = 1 if
+ *   d_1 > d_r, then r = 2 if d_2 > d_r (strict: the first corner wins a tie).  chart DEVICE int[n_faces] = slot * 4 + r,
+ *   -1 for a face that is not valid.  counts DEVICE int[2] = valid faces, the others.  work DEVICE uint8[n_faces]: scratch.
+ *   Does not depend on S or c.  n_faces <= (2^31 - 1) / 4.
+ * svs_mesh_atlas_uv: n_slots = counts[0].  Face corner (r + k) % 3 sits at A_k.  uv DEVICE float[n_faces][3][2] per face
+ *   corner in the OBJ convention, with (x, y) the corner's texel: u = float32((x + 0.5) / S), v = float32(1 - (y + 0.5) / S),
+ *   computed in float64; zeros for a face with chart -1.  slot_face DEVICE int[n_slots]: the face of every slot.
+ * svs_mesh_atlas_bake: acc DEVICE double[rows][S][4] = (r, g, b, w) per texel, ACCUMULATED as in svs_mesh_paint (the caller
+ *   zeroes it; more than 16 views: several calls); rows = ceil(ceil(n_slots / 2) / n) c: only the rows that hold charts.
+ *   normals DEVICE float[n_verts][3] (what svs_mesh_vertex_normals gives) or NULL.  Per texel (i, j): its cell, its half by
+ *   the ownership rule, its slot; a slot >= n_slots or a column >= n c: not touched.  Else f = slot_face[slot], r from
+ *   chart[f], and with (li, lj) the local texel the barycentrics of its centre against A0, A1, A2:
+ *     lower: b1 = (li - 1) / (c - 5), b2 = (lj - 1) / (c - 5);   upper: b1 = ((c-2) - li) / (c - 4), b2 = ((c-2) - lj) / (c - 4);
+ *     b0 = 1 - b1 - b2.  Gutter texels (outside the triangle; bilinear sampling reads them) are clamped onto it:
+ *     b_k = max(b_k, 0), s = b0 + b1 + b2 (left to right), b_k = b_k / s.
+ *   p = b0 P_r + b1 P_(r+1) + b2 P_(r+2) per component (corner indices mod 3, float32 widened, summed left to right).  With
+ *   normals: m = the same combination of the three vertex normals, L = sqrt(m.x m.x + m.y m.y + m.z m.z), n = m / L; a
+ *   texel whose m is not finite or whose L is zero or not finite is skipped in every view.  Then steps 1 to 7 of
+ *   svs_mesh_paint for the point p and the normal n, the views in index order (one lane per texel: no atomics, one fixed
+ *   order, the same bytes in every run).  near .. flags: as in svs_mesh_paint; SVS_ATLAS_CELL_MAJOR may be added to flags:
+ *   lanes then walk the atlas cell by cell instead of row by row (for measurements: the bytes written are the same).
+ * svs_mesh_atlas_finish: atlas DEVICE uint8[S][S][3], which the CALLER fills with the fill colour first; covered DEVICE
+ *   uint8[S][S], zeroed by the caller.  acc as baked, or NULL; vert_rgb DEVICE uint8[n_verts][3] or NULL.  Per texel that
+ *   has a face: acc.w > 0: the code of svs_mesh_paint_finish (blend or SVS_PAINT_BEST), covered = 1; else with vert_rgb:
+ *   floor(b0 C_r + b1 C_(r+1) + b2 C_(r+2) + 0.5) per channel, clamped to [0,255], with the clamped b of the bake and C the
+ *   codes of the three vertices, covered = 2; else left as filled.  A texel without a face is left as filled.  acc NULL:
+ *   every texel takes the vertex-colour branch.
+ * svs_mesh_atlas_render: face DEVICE int (n_views,H,W) as svs_mesh_raster_resolve wrote it; rgb DEVICE uint8 (n_views,H,W,3),
+ *   which the CALLER fills first.  Per pixel whose id lies in [face_base, face_base + n_faces) with chart >= 0: the three
+ *   corners projected, b_k and zc at the pixel as the resolve step takes them, w_k = b_k / z_k * zc; the atlas position
+ *   X = w_0 T_0 + w_1 T_1 + w_2 T_2 per axis (left to right), T_k the texel of face corner k recomputed from chart, S and c
+ *   in integers; X clamped to [0, S-1] (NaN: 0); then the bilinear formula of step 6 of svs_mesh_paint on the atlas codes,
+ *   in that order, and floor(. + 0.5) clamped to [0,255].  No shading factor.  Other pixels are left untouched.
+ * SVS_ESHAPE with the entry's name for 2 n n < n_slots, c < 6, S < c, S > 32768, more than 16 views, H * W == 0 or a negative
+ * count; SVS_EINVAL as in svs_mesh_paint; every check comes before any HIP call.  An empty mesh and zero views touch nothing
+ * (svs_mesh_atlas_slots still writes counts).  Bad input (indices out of range, NaN vertices) is skipped, never dereferenced. */
+#define SVS_ATLAS_CELL_MAJOR 256
+int svs_mesh_atlas_slots(const float* verts, int n_verts, const int* faces, int n_faces, uint8_t* work, int* chart, int* counts,
+                         void* hip_stream);
+int svs_mesh_atlas_uv(const int* chart, int n_faces, int n_slots, int S, int c, float* uv, int* slot_face, void* hip_stream);
+int svs_mesh_atlas_bake(const float* verts, int n_verts, const float* normals, const int* faces, int n_faces, const int* chart,
+                        const int* slot_face, int n_slots, int S, int c, const double* mats, int n_views, int H, int W, double near,
+                        const float* depth, const uint8_t* const SVS_HOST* images, const uint8_t* const SVS_HOST* masks, double rel,
+                        double abs_tol, double cos_min, int power, int flags, double* acc, void* hip_stream);
+int svs_mesh_atlas_finish(const double* acc, const int* faces, int n_faces, int n_verts, const int* chart, const int* slot_face,
+                          int n_slots, int S, int c, const uint8_t* vert_rgb, int flags, uint8_t* atlas, uint8_t* covered,
+                          void* hip_stream);
+int svs_mesh_atlas_render(const int* face, const float* verts, int n_verts, const int* faces, int n_faces, int face_base,
+                          const int* chart, const double* mats, int n_views, int H, int W, const uint8_t* atlas, int S, int c,
+                          uint8_t* rgb, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

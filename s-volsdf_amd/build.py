@@ -60,6 +60,7 @@ UNITS = {
     "svs_meshsimplify.hip": ["-ffp-contract=off"],
     "svs_poisson.hip": ["-ffp-contract=off"],
     "svs_meshsmooth.hip": ["-ffp-contract=off"],
+    "svs_meshtexture.hip": ["-ffp-contract=off"],
     "svs_plan.hip": [],
 }
 BASE_FLAGS = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function", "-x", "hip"]

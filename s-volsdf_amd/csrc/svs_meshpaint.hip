@@ -3,20 +3,20 @@
 // the conversion to codes, and the hole filling over the mesh's edges.  The reference has no such step; the arithmetic is
 // this project's, fixed in include/svolsdf_hip.h and restated in tests/meshpaint_oracle.py.
 //
-// paint_kernel is a gather: one lane per vertex walks the launch's views in index order with its four accumulators in
-// registers, so the sum has one fixed order and needs no atomics; two runs give the same bits.  The per-view eye
-// (-R^T t) is worked out once per workgroup into LDS.  The normals are a scatter of float64 atomic adds (their last bits
+// paint_kernel is a gather (svs_paint_gather.h, shared with svs_meshtexture.hip): one lane per vertex walks the launch's
+// views in index order with its four accumulators in registers, so the sum has one fixed order and needs no atomics; two
+// runs give the same bits.  The per-view eye (-R^T t) is worked out once per workgroup into LDS.  The normals are a scatter of float64 atomic adds (their last bits
 // depend on arrival order: they only weight the views); the hole filling is a scatter of integer atomic adds, which is exact
 // in any order.  All camera arithmetic is float64 without contraction; its rules are those of svs_views.h.
 #include "svs_common.h"
+#include "svs_paint_gather.h"
 #include "svs_views.h"
 
 namespace svs {
 namespace meshpaint {
 
 using namespace views;
-
-constexpr int kMaxPower = 8;
+using namespace paintgather;
 
 // ---- normals ---------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void normal_accumulate_kernel(const float* __restrict__ verts, int n_verts,
@@ -55,25 +55,16 @@ __global__ __launch_bounds__(256) void normal_finish_kernel(const double* __rest
 
 // ---- paint -----------------------------------------------------------------------------------------------------------
 struct PaintArgs {
+  GatherArgs g;
   const float* verts;
   const float* normals;
-  const double* mats;
-  const float* depth;
-  const uint8_t* image[kMaxViews];
-  const uint8_t* mask[kMaxViews];
   double* acc;
-  double near, rel, abs_tol, cos_min;
-  int n_verts, n_views, H, W, power, flags;
+  int n_verts;
 };
 
 __global__ __launch_bounds__(256) void paint_kernel(PaintArgs a) {
   __shared__ double eye[kMaxViews][3];
-  if (threadIdx.x < (unsigned)a.n_views) {                   // eye = -R^T t, once per view
-    const double* __restrict__ E = a.mats + (size_t)threadIdx.x * kMatsPerView + 9;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) eye[threadIdx.x][k] = -(E[k] * E[3] + E[4 + k] * E[7] + E[8 + k] * E[11]);
-  }
-  __syncthreads();
+  load_eyes(a.g.mats, a.g.n_views, eye);
   const int v = blockIdx.x * blockDim.x + threadIdx.x;
   if (v >= a.n_verts) return;
   const float* __restrict__ p = a.verts + (size_t)v * 3;
@@ -85,42 +76,7 @@ __global__ __launch_bounds__(256) void paint_kernel(PaintArgs a) {
     lit = finite3(n[0], n[1], n[2]) && !(n[0] == 0.0 && n[1] == 0.0 && n[2] == 0.0);
   }
   double r = a.acc[(size_t)v * 4], g = a.acc[(size_t)v * 4 + 1], b = a.acc[(size_t)v * 4 + 2], wsum = a.acc[(size_t)v * 4 + 3];
-  const bool best = a.flags & SVS_PAINT_BEST;
-  const size_t hw = (size_t)a.H * (size_t)a.W;
-  for (int view = 0; lit && view < a.n_views; ++view) {
-    Corner c; size_t pix;
-    if (!project(a.mats + (size_t)view * kMatsPerView, p, a.near, c)) continue;                      // 1
-    if (!(c.x >= 0.0 && c.x <= (double)(a.W - 1) && c.y >= 0.0 && c.y <= (double)(a.H - 1))) continue;   // 2
-    if (!nearest_pixel(c, a.H, a.W, pix, true) || masked_out(a.mask[view], pix)) continue;           // 3 (inside after 2)
-    if (!not_hidden((double)a.depth[(size_t)view * hw + pix], c.cz, a.rel, a.abs_tol)) continue;     // 4
-    double w = 1.0;
-    if (a.normals) {                                                                                 // 5
-      const double tx = eye[view][0] - (double)p[0], ty = eye[view][1] - (double)p[1], tz = eye[view][2] - (double)p[2];
-      double cs = (n[0] * tx + n[1] * ty + n[2] * tz) / __builtin_sqrt(tx * tx + ty * ty + tz * tz);
-      if (!(a.flags & SVS_PAINT_ONE_SIDED)) cs = __builtin_fabs(cs);
-      if (!(cs >= a.cos_min)) continue;                      // NaN too
-      for (int k = 0; k < a.power; ++k) w = w * cs;
-    }
-    const double x0 = __builtin_floor(c.x), y0 = __builtin_floor(c.y);                               // 6
-    const double fx = c.x - x0, fy = c.y - y0;
-    const int ix0 = (int)x0, iy0 = (int)y0;
-    const int ix1 = ix0 + 1 < a.W ? ix0 + 1 : a.W - 1, iy1 = iy0 + 1 < a.H ? iy0 + 1 : a.H - 1;
-    const uint8_t* __restrict__ img = a.image[view];
-    const uint8_t* __restrict__ t00 = img + ((size_t)iy0 * a.W + ix0) * 3;
-    const uint8_t* __restrict__ t01 = img + ((size_t)iy0 * a.W + ix1) * 3;
-    const uint8_t* __restrict__ t10 = img + ((size_t)iy1 * a.W + ix0) * 3;
-    const uint8_t* __restrict__ t11 = img + ((size_t)iy1 * a.W + ix1) * 3;
-    double col[3];
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch)
-      col[ch] = ((1.0 - fx) * (double)t00[ch] + fx * (double)t01[ch]) * (1.0 - fy) +
-                ((1.0 - fx) * (double)t10[ch] + fx * (double)t11[ch]) * fy;
-    if (best) {                                                                                      // 7
-      if (w > wsum) { r = col[0]; g = col[1]; b = col[2]; wsum = w; }
-    } else {
-      r = r + w * col[0]; g = g + w * col[1]; b = b + w * col[2]; wsum = wsum + w;
-    }
-  }
+  if (lit) gather(a.g, eye, (double)p[0], (double)p[1], (double)p[2], n, a.normals != nullptr, r, g, b, wsum);   // steps 1 to 7
   a.acc[(size_t)v * 4] = r; a.acc[(size_t)v * 4 + 1] = g; a.acc[(size_t)v * 4 + 2] = b; a.acc[(size_t)v * 4 + 3] = wsum;
 }
 
@@ -198,26 +154,15 @@ int svs_mesh_vertex_normals(const float* verts, int n_verts, const int* faces, i
 int svs_mesh_paint(const float* verts, int n_verts, const float* normals, const double* mats, int n_views, int H, int W,
                    double near, const float* depth, const uint8_t* const* images, const uint8_t* const* masks, double rel,
                    double abs_tol, double cos_min, int power, int flags, double* acc, void* hip_stream) {
-  if (int rc = check_views("svs_mesh_paint", n_views, H, W)) return rc;
-  if (!(near > 0.0) || !(rel >= 0.0) || !(abs_tol >= 0.0)) {
-    set_error("svs_mesh_paint: near must be positive, rel and abs_tol not negative"); return SVS_EINVAL;
-  }
-  if (!(cos_min >= 0.0 && cos_min <= 1.0) || power < 0 || power > kMaxPower) {
-    set_error("svs_mesh_paint: cos_min in [0,1] and power in [0,%d], got %g and %d", kMaxPower, cos_min, power); return SVS_EINVAL;
-  }
-  if (flags & ~(SVS_PAINT_BEST | SVS_PAINT_ONE_SIDED)) { set_error("svs_mesh_paint: unknown flags %d", flags); return SVS_EINVAL; }
+  if (int rc = check_rules("svs_mesh_paint", n_views, H, W, near, rel, abs_tol, cos_min, power, flags)) return rc;
   if (n_verts < 0) { set_error("svs_mesh_paint: negative count"); return SVS_ESHAPE; }
   if (!images) { set_error("svs_mesh_paint: null argument (images)"); return SVS_EINVAL; }
   if (n_verts == 0 || n_views == 0) return SVS_OK;
   if (!verts || !mats || !depth || !acc) { set_error("svs_mesh_paint: null argument"); return SVS_EINVAL; }
   PaintArgs a;
-  view_pointers(images, n_views, a.image);
-  view_pointers(masks, n_views, a.mask);
-  for (int v = 0; v < n_views; ++v)
-    if (!a.image[v]) { set_error("svs_mesh_paint: view %d has no image", v); return SVS_EINVAL; }
-  a.verts = verts; a.normals = normals; a.mats = mats; a.depth = depth; a.acc = acc;
-  a.near = near; a.rel = rel; a.abs_tol = abs_tol; a.cos_min = cos_min;
-  a.n_verts = n_verts; a.n_views = n_views; a.H = H; a.W = W; a.power = power; a.flags = flags;
+  if (int rc = fill_gather_args("svs_mesh_paint", a.g, mats, n_views, H, W, near, depth, images, masks, rel, abs_tol, cos_min,
+                                power, flags)) return rc;
+  a.verts = verts; a.normals = normals; a.acc = acc; a.n_verts = n_verts;
   paint_kernel<<<(n_verts + 255) / 256, 256, 0, (hipStream_t)hip_stream>>>(a);
   return check_launch("svs_mesh_paint");
 }

@@ -131,6 +131,7 @@ try:
     EINVAL, ESHAPE, ENOCONV, EOVERFLOW = (_CONSTANTS["SVS_E" + n] for n in ("INVAL", "SHAPE", "NOCONV", "OVERFLOW"))
     MMA_F32, MMA_F16X2, MMA_F16X2_HALF = (_CONSTANTS["SVS_MMA_" + n] for n in ("F32", "F16X2", "F16X2_HALF"))
     PAINT_BEST, PAINT_ONE_SIDED = (_CONSTANTS["SVS_PAINT_" + n] for n in ("BEST", "ONE_SIDED"))
+    ATLAS_CELL_MAJOR = _CONSTANTS["SVS_ATLAS_CELL_MAJOR"]
     MESH_USED, MESH_BOUNDARY, MESH_NONMANIFOLD = (_CONSTANTS["SVS_MESH_" + n] for n in ("USED", "BOUNDARY", "NONMANIFOLD"))
     SMOOTH_FIXED, SMOOTH_CURVE, SMOOTH_FREE = (_CONSTANTS["SVS_SMOOTH_" + n] for n in ("FIXED", "CURVE", "FREE"))
 except (OSError, KeyError) as _e:

@@ -23,6 +23,9 @@ filter_depth_folder`) -> {outdir}/mvsnet{scan:03}_l3.ply.
     +tsdf_smooth=N [+tsdf_smooth_method=taubin|denoise]   with +tsdf_voxel: every scan's TSDF mesh also smoothed by
                              `svs_hip.meshsmooth` (N iterations, boundary fixed), {outdir}/tsdf_smooth/mvsnet{scan:03}_l3.ply;
                              +tsdf_simplify then simplifies the smoothed mesh
+    +tsdf_texture=S          with +tsdf_voxel: a texture atlas of S x S texels (S in [64, 16384]) baked by `svs_hip.meshtexture`
+                             from every scan's training views for its simplified (+tsdf_simplify), else smoothed (+tsdf_smooth),
+                             else plain TSDF mesh, {outdir}/tsdf_texture/mvsnet{scan:03}_l3.{obj,mtl,png}
     +cloud_clean=true [+cloud_k=20 +cloud_std_ratio=2.0 +cloud_normal_k=16]   after the point clouds, every scan's cloud
                              without its statistical outliers and with oriented normals (`svs_hip.cloudclean`), in
                              {outdir}/clean/mvsnet{scan:03}_l3.ply (`python -m evals.eval_dtu --datadir {outdir}/clean`)
@@ -171,6 +174,17 @@ def check_tsdf_smooth(args):
     return int(n), method
 
 
+def check_tsdf_texture(args):
+    """+tsdf_texture=S: an atlas size in [64, 16384], and only together with +tsdf_voxel (ValueError naming the key) -> S or None"""
+    size = args.get("tsdf_texture")
+    if size is None:
+        return None
+    _require(isinstance(size, int) and not isinstance(size, bool) and 64 <= size <= 16384, "tsdf_texture",
+             f"an atlas size in [64, 16384], got {size!r}")
+    _require(bool(args.get("tsdf_voxel")), "tsdf_texture", "textures the TSDF meshes: give +tsdf_voxel=V as well")
+    return int(size)
+
+
 def check_cloud_poisson(args):
     """+cloud_poisson=V: a positive node spacing, and only together with +cloud_clean=true, whose normals it meshes (ValueError
     naming the key) -> V or None"""
@@ -194,6 +208,7 @@ def run_help(args, select_device=True):
     a = attr_view(args)
     check_tsdf_simplify(args)
     check_tsdf_smooth(args)
+    check_tsdf_texture(args)
     check_cloud_poisson(args)
     if select_device and args["gpu"] != "auto":
         import torch
@@ -505,6 +520,33 @@ def tsdf_simplified(args, testlist):
     return out
 
 
+def tsdf_texture_obj_name(outdir, scan):
+    """the textured TSDF mesh of a scan: the point cloud's name in {outdir}/tsdf_texture, as an OBJ beside its MTL and PNG"""
+    return ply_name(os.path.join(outdir, "tsdf_texture"), scan)[:-4] + ".obj"
+
+
+def tsdf_textured(args, testlist):
+    """+tsdf_texture=S: every scan's TSDF mesh -- the simplified one with +tsdf_simplify, else the smoothed one with
+    +tsdf_smooth, else `tsdf_meshes`' -- textured from the scan's training views by `meshtexture.texture_folder` into
+    {outdir}/tsdf_texture/mvsnet{scan:03}_l3.{obj,mtl,png}; one time line per scan.  -> {scene: texture_folder's stats}"""
+    from . import meshtexture
+    from .scans import get_trains_ids
+    size = check_tsdf_texture(args)
+    data_dir = args["vol"]["dataset"]["data_dir"]
+    source = (tsdf_simple_ply_name if args.get("tsdf_simplify") is not None else
+              tsdf_smooth_ply_name if args.get("tsdf_smooth") is not None else tsdf_ply_name)
+    out = OrderedDict()
+    for scan in testlist:
+        obj = tsdf_texture_obj_name(args["outdir"], scan)
+        stats = meshtexture.texture_folder(source(args["outdir"], scan), os.path.join(args["outdir"], scan),
+                                           get_trains_ids(data_dir, scan, args["num_view"]), obj, size=size)[1]
+        info(f"saving the textured TSDF mesh to {obj} ({stats['faces_written']} faces, atlas {size} x {size}, cell {stats['cell']}, "
+             f"{stats['texels_baked']} texels baked, {stats['texels_from_vertices']} from vertex colours)")
+        info(f"{scan} tsdf texture seconds: " + ", ".join(f"{k} {v:.3f}" for k, v in stats["seconds"].items()))
+        out[scan] = stats
+    return out
+
+
 def clean_ply_name(outdir, scan):
     """the cleaned cloud of a scan: the point cloud's name one folder down, where `evals.eval_dtu --datadir` finds it"""
     return ply_name(os.path.join(outdir, "clean"), scan)
@@ -605,6 +647,8 @@ def main(argv=None, scan_fn=None):
             result["smooth_meshes"] = tsdf_smoothed(args, testlist)
         if args.get("tsdf_simplify") is not None:
             result["simple_meshes"] = tsdf_simplified(args, testlist)
+        if args.get("tsdf_texture") is not None:
+            result["textured_meshes"] = tsdf_textured(args, testlist)
     if args.get("cloud_clean"):
         result["clean"] = clean_clouds(args, testlist)
         if args.get("cloud_poisson") is not None:
