@@ -3,7 +3,7 @@
 // the conversion to codes, and the hole filling over the mesh's edges.  The reference has no such step; the arithmetic is
 // this project's, fixed in include/svolsdf_hip.h and restated in tests/meshpaint_oracle.py.
 //
-// paint_kernel is a gather (svs_paint_gather.h, shared with svs_meshtexture.hip): one lane per vertex walks the launch's
+// paint_kernel is a gather (svs_paint_gather.h, shared with svs_meshtexture.hip, with the tap and the code rule): one lane per vertex walks the launch's
 // views in index order with its four accumulators in registers, so the sum has one fixed order and needs no atomics; two
 // runs give the same bits.  The per-view eye (-R^T t) is worked out once per workgroup into LDS.  The normals are a scatter of float64 atomic adds (their last bits
 // depend on arrival order: they only weight the views); the hole filling is a scatter of integer atomic adds, which is exact
@@ -86,11 +86,7 @@ __global__ __launch_bounds__(256) void paint_finish_kernel(const double* __restr
   if (v >= n_verts) return;
   const double w = acc[(size_t)v * 4 + 3];
   if (!(w > 0.0)) { painted[v] = 0; return; }
-#pragma unroll
-  for (int ch = 0; ch < 3; ++ch) {
-    const double c = acc[(size_t)v * 4 + ch];
-    rgb[(size_t)v * 3 + ch] = code_u8((flags & SVS_PAINT_BEST) ? c : c / w);
-  }
+  acc_codes(acc[(size_t)v * 4], acc[(size_t)v * 4 + 1], acc[(size_t)v * 4 + 2], w, flags, rgb + (size_t)v * 3);
   painted[v] = 1;
 }
 

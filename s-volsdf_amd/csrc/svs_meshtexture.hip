@@ -184,11 +184,7 @@ __global__ __launch_bounds__(256) void finish_kernel(AtlasArgs a, const double* 
   if (!texel_face(a, i, j, t)) return;
   const double w = acc ? acc[(size_t)at * 4 + 3] : 0.0;
   if (w > 0.0) {
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-      const double c = acc[(size_t)at * 4 + ch];
-      atlas[(size_t)at * 3 + ch] = code_u8((flags & SVS_PAINT_BEST) ? c : c / w);
-    }
+    acc_codes(acc[(size_t)at * 4], acc[(size_t)at * 4 + 1], acc[(size_t)at * 4 + 2], w, flags, atlas + (size_t)at * 3);
     covered[at] = 1;
   } else if (vert_rgb) {
 #pragma unroll
@@ -253,18 +249,10 @@ __global__ __launch_bounds__(256) void render_kernel(RenderArgs a) {
   const double top = (double)(a.S - 1);
   X = X >= 0.0 ? X : 0.0; X = X > top ? top : X;             // NaN to 0
   Y = Y >= 0.0 ? Y : 0.0; Y = Y > top ? top : Y;
-  const double x0 = __builtin_floor(X), y0 = __builtin_floor(Y);
-  const double fx = X - x0, fy = Y - y0;
-  const int ix0 = (int)x0, iy0 = (int)y0;
-  const int ix1 = ix0 + 1 < a.S ? ix0 + 1 : a.S - 1, iy1 = iy0 + 1 < a.S ? iy0 + 1 : a.S - 1;
-  const uint8_t* __restrict__ t00 = a.atlas + ((size_t)iy0 * a.S + ix0) * 3;
-  const uint8_t* __restrict__ t01 = a.atlas + ((size_t)iy0 * a.S + ix1) * 3;
-  const uint8_t* __restrict__ t10 = a.atlas + ((size_t)iy1 * a.S + ix0) * 3;
-  const uint8_t* __restrict__ t11 = a.atlas + ((size_t)iy1 * a.S + ix1) * 3;
+  double col[3];
+  bilinear_rgb(a.atlas, a.S, a.S, X, Y, col);
 #pragma unroll
-  for (int k = 0; k < 3; ++k)
-    a.rgb[p * 3 + k] = code_u8(((1.0 - fx) * (double)t00[k] + fx * (double)t01[k]) * (1.0 - fy) +
-                               ((1.0 - fx) * (double)t10[k] + fx * (double)t11[k]) * fy);
+  for (int k = 0; k < 3; ++k) a.rgb[p * 3 + k] = code_u8(col[k]);
 }
 
 // S, c and the slots they must hold; SVS_OK or SVS_ESHAPE with the error set

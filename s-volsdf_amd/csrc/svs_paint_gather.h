@@ -1,7 +1,9 @@
 // Steps 1 to 7 of svs_mesh_paint (include/svolsdf_hip.h) for one world-space point: what the photographs of a launch's views
 // add to the point's four accumulators.  svs_meshpaint.hip calls it per vertex, svs_meshtexture.hip per texel of an atlas:
 // one definition, one order of operations, the same bits in both.  The point and its normal are float64 (a vertex's are its
-// float32 values widened).  The units that include this are compiled with -ffp-contract=off.
+// float32 values widened).  Also here, for the same reason: the bilinear RGB tap (step 6, and the atlas renderer's) and the
+// rule that turns four accumulators into codes (both finish kernels).  The units that include this are compiled with
+// -ffp-contract=off.
 #pragma once
 #include "svs_common.h"
 #include "svs_views.h"
@@ -32,6 +34,29 @@ __device__ __forceinline__ void load_eyes(const double* __restrict__ mats, int n
   __syncthreads();
 }
 
+// the bilinear tap of an (H, W, 3) image at (x, y), 0 <= x <= W - 1 and 0 <= y <= H - 1; the taps past the last column and
+// row are the last column and row (their weight is 0 there)
+__device__ __forceinline__ void bilinear_rgb(const uint8_t* __restrict__ img, int W, int H, double x, double y, double (&col)[3]) {
+  const double x0 = __builtin_floor(x), y0 = __builtin_floor(y);
+  const double fx = x - x0, fy = y - y0;
+  const int ix0 = (int)x0, iy0 = (int)y0;
+  const int ix1 = ix0 + 1 < W ? ix0 + 1 : W - 1, iy1 = iy0 + 1 < H ? iy0 + 1 : H - 1;
+  const uint8_t* __restrict__ t00 = img + ((size_t)iy0 * W + ix0) * 3;
+  const uint8_t* __restrict__ t01 = img + ((size_t)iy0 * W + ix1) * 3;
+  const uint8_t* __restrict__ t10 = img + ((size_t)iy1 * W + ix0) * 3;
+  const uint8_t* __restrict__ t11 = img + ((size_t)iy1 * W + ix1) * 3;
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch)
+    col[ch] = ((1.0 - fx) * (double)t00[ch] + fx * (double)t01[ch]) * (1.0 - fy) +
+              ((1.0 - fx) * (double)t10[ch] + fx * (double)t11[ch]) * fy;
+}
+
+// accumulators with w > 0 -> codes: the best view's colour as it is, the blend's sum over its weight
+__device__ __forceinline__ void acc_codes(double r, double g, double b, double w, int flags, uint8_t* __restrict__ code) {
+  const bool best = flags & SVS_PAINT_BEST;
+  code[0] = code_u8(best ? r : r / w); code[1] = code_u8(best ? g : g / w); code[2] = code_u8(best ? b : b / w);
+}
+
 // n: the point's normal when use_normals (the caller has shown it finite and not zero); (r, g, b, wsum): the accumulators
 __device__ __forceinline__ void gather(const GatherArgs& a, const double (*eye)[3], double px, double py, double pz, const double* n,
                                        bool use_normals, double& r, double& g, double& b, double& wsum) {
@@ -51,20 +76,8 @@ __device__ __forceinline__ void gather(const GatherArgs& a, const double (*eye)[
       if (!(cs >= a.cos_min)) continue;                      // NaN too
       for (int k = 0; k < a.power; ++k) w = w * cs;
     }
-    const double x0 = __builtin_floor(c.x), y0 = __builtin_floor(c.y);                               // 6
-    const double fx = c.x - x0, fy = c.y - y0;
-    const int ix0 = (int)x0, iy0 = (int)y0;
-    const int ix1 = ix0 + 1 < a.W ? ix0 + 1 : a.W - 1, iy1 = iy0 + 1 < a.H ? iy0 + 1 : a.H - 1;
-    const uint8_t* __restrict__ img = a.image[view];
-    const uint8_t* __restrict__ t00 = img + ((size_t)iy0 * a.W + ix0) * 3;
-    const uint8_t* __restrict__ t01 = img + ((size_t)iy0 * a.W + ix1) * 3;
-    const uint8_t* __restrict__ t10 = img + ((size_t)iy1 * a.W + ix0) * 3;
-    const uint8_t* __restrict__ t11 = img + ((size_t)iy1 * a.W + ix1) * 3;
     double col[3];
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch)
-      col[ch] = ((1.0 - fx) * (double)t00[ch] + fx * (double)t01[ch]) * (1.0 - fy) +
-                ((1.0 - fx) * (double)t10[ch] + fx * (double)t11[ch]) * fy;
+    bilinear_rgb(a.image[view], a.W, a.H, c.x, c.y, col);                                            // 6
     if (best) {                                                                                      // 7
       if (w > wsum) { r = col[0]; g = col[1]; b = col[2]; wsum = w; }
     } else {

@@ -14,7 +14,9 @@ include/svolsdf_hip.h and restated in float64 in tests/meshpaint_oracle.py.  SET
 `mode` (blend: the weighted mean of all views; best: the view with the largest weight), `cos_min` (default 0.1), `power`
 (default 2: weight = cos^2), `one_sided` (a normal that points away from the camera does not count), `use_normals`, the
 visibility tolerances `rel` (default 0.01) and `abs_tol` of `meshview.visibility`, `near`, `spread_rounds` (default: until
-nothing changes), `fill` (the colour of what is never reached).
+nothing changes), `fill` (the colour of what is never reached).  `svs_hip.meshtexture` takes from here what the two share:
+`check_rules`, `view_inputs`, `view_chunks` (not in `svs_hip.views`, which launches nothing), `filled`, `agreement`, and the command
+lines' `add_painter_args`, `check_painter_args`, `painter_rules`; both read a scan folder through `views.scan_folder_inputs`.
 """
 import argparse
 import os
@@ -29,18 +31,33 @@ from . import meshview as _mv
 from . import ply as _ply
 from .images import seconds_line, tick, to_device
 from .ops import _ptr, _ptr_array, _stream
-from .views import (MAX_VIEWS, add_eval_mask_args, check_eval_mask_args, chunks, device_masks, folder_cameras, folder_images,
-                    folder_masks, launches_since, mesh_args)
+from .views import (MAX_VIEWS, add_eval_mask_args, check_eval_mask_args, chunks, device_masks, folder_images, launches_since,
+                    mesh_args, scan_folder_inputs)
 
 FACE_CHUNK = 1 << 24                 # faces per call of svs_mesh_vertex_normals
 ENTRY_CALLS = {"normals": 0, "paint": 0, "finish": 0, "spread": 0}  # C entry points called, not kernels
 RULES = dict(cos_min=0.1, power=2, one_sided=False, use_normals=True, rel=0.01, abs_tol=0.0, near=1e-6)
 
 
-def flags_of(mode="blend", one_sided=False):
+def check_rules(rules, name="svs_mesh_paint"):
+    """The caller's rules over RULES and mode="blend", for the painter and for `svs_hip.meshtexture`: TypeError in `name` for a
+    rule that is not known, ValueError for a mode or a range that is not allowed -> (the rules without mode, flags)"""
+    unknown = sorted(set(rules) - set(RULES) - {"mode"})
+    if unknown:
+        raise TypeError(f"{name}: unknown rules {unknown} (known: {sorted(list(RULES) + ['mode'])})")
+    r = dict(RULES, **rules)
+    mode = r.pop("mode", "blend")
     if mode not in ("blend", "best"):
         raise ValueError(f"svs_mesh_paint: mode 'blend' or 'best', got {mode!r}")
-    return (_lib.PAINT_BEST if mode == "best" else 0) | (_lib.PAINT_ONE_SIDED if one_sided else 0)
+    if not (0 <= r["cos_min"] <= 1) or int(r["power"]) != r["power"] or not (0 <= r["power"] <= 8):
+        raise ValueError(f"svs_mesh_paint: cos_min in [0,1] and power an integer in [0,8], got {r['cos_min']} and {r['power']}")
+    if r["rel"] < 0 or r["abs_tol"] < 0 or not (r["near"] > 0):
+        raise ValueError(f"svs_mesh_paint: near must be positive, rel and abs_tol not negative, got {r['near']}, {r['rel']}, {r['abs_tol']}")
+    return r, (_lib.PAINT_BEST if mode == "best" else 0) | (_lib.PAINT_ONE_SIDED if r["one_sided"] else 0)
+
+
+def flags_of(mode="blend", one_sided=False):
+    return check_rules(dict(mode=mode, one_sided=one_sided))[1]
 
 
 def normals_raw(verts, faces, accum, normals):
@@ -78,10 +95,7 @@ def paint_raw(verts, normals, mats, n_views, H, W, depth, images, masks, acc, ne
 
 
 def _check_rules(cos_min, power, rel, abs_tol, near):
-    if not (0 <= cos_min <= 1) or int(power) != power or not (0 <= power <= 8):
-        raise ValueError(f"svs_mesh_paint: cos_min in [0,1] and power an integer in [0,8], got {cos_min} and {power}")
-    if rel < 0 or abs_tol < 0 or not (near > 0):
-        raise ValueError(f"svs_mesh_paint: near must be positive, rel and abs_tol not negative, got {near}, {rel}, {abs_tol}")
+    check_rules(dict(cos_min=cos_min, power=power, rel=rel, abs_tol=abs_tol, near=near))
 
 
 def _images(images, n_views):
@@ -94,49 +108,66 @@ def _images(images, n_views):
     return out
 
 
-def accumulate(verts, faces, views, images, masks=None, *, normals=None, flags=0, cos_min=0.1, power=2, rel=0.01, abs_tol=0.0,
-               near=1e-6, depth=None, seen=None, timers=None):
-    """The views in chunks of MAX_VIEWS: each chunk is rasterised (`meshview.rasterize`, unless depth (n_views,H,W) is
-    given) and painted before the next, so the device holds MAX_VIEWS z-buffers at a time.  normals: (V,3) float32 or
-    None (every view weighs 1).  seen: a zeroed (V,) int32 tensor that gets `meshview.visibility`'s count of the views
-    that pass the mask and the depth test.  -> acc (V,4) float64: (r, g, b, w) as svs_mesh_paint leaves them."""
-    verts, faces, _ = mesh_args(verts, faces)
+def view_inputs(name, verts, views, images, masks, depth, normals):
+    """What `accumulate` and `meshtexture.bake` are given per view, checked in the name of the entry `name` and on the device
+    -> views (a list), images, masks, depth (n_views,H,W) or None, normals (V,3) or None, H, W"""
     views = list(views)
-    _check_rules(cos_min, power, rel, abs_tol, near)
     if not views:
-        raise ValueError("svs_mesh_paint: no views")
-    dev = verts.device
+        raise ValueError(f"{name}: no views")
     images = _images(images, len(views))
     H, W = int(images[0].shape[0]), int(images[0].shape[1])
-    masks = device_masks(masks, len(views), H, W, dev, "svs_mesh_paint")
+    masks = device_masks(masks, len(views), H, W, verts.device, name)
     if depth is not None:
         depth = to_device(depth, torch.float32, "meshpaint", "depth", ndim=(3,))
         if tuple(depth.shape) != (len(views), H, W):
-            raise ValueError(f"svs_mesh_paint: depth maps of {tuple(depth.shape)} for {len(views)} views of {(H, W)}")
+            raise ValueError(f"{name}: depth maps of {tuple(depth.shape)} for {len(views)} views of {(H, W)}")
     if normals is not None:
         normals = to_device(normals, torch.float32, "meshpaint", "normals")
         if tuple(normals.shape) != tuple(verts.shape):
-            raise ValueError(f"svs_mesh_paint: normals of {tuple(normals.shape)} for {verts.shape[0]} vertices")
-    acc = torch.zeros((verts.shape[0], 4), dtype=torch.float64, device=dev)
+            raise ValueError(f"{name}: normals of {tuple(normals.shape)} for {verts.shape[0]} vertices")
+    return views, images, masks, depth, normals, H, W
+
+
+def view_chunks(verts, faces, views, H, W, masks, depth, near, timers, phase):
+    """yields (at, to, mats, depth maps, masks or None) of views[at:to] per chunk of MAX_VIEWS.  A chunk is rasterised when it is
+    asked for (`meshview.rasterize`, unless depth has the maps; ticks "raster"), so the device holds MAX_VIEWS z-buffers at a
+    time; what the caller does with it ticks `phase`."""
     t0 = time.perf_counter()
-    for at, to, mats in chunks(views, dev):
+    for at, to, mats in chunks(views, verts.device):
         part = depth[at:to] if depth is not None else _mv.rasterize(verts, faces, views[at:to], H, W, near=near)["depth"]
         t0 = tick(timers, "raster", t0)
-        part_masks = masks[at:to] if masks is not None else None
+        yield at, to, mats, part, masks[at:to] if masks is not None else None
+        t0 = tick(timers, phase, t0)
+
+
+def accumulate(verts, faces, views, images, masks=None, *, normals=None, flags=0, cos_min=0.1, power=2, rel=0.01, abs_tol=0.0,
+               near=1e-6, depth=None, seen=None, timers=None):
+    """The views painted chunk by chunk (`view_chunks`; depth: (n_views,H,W) when the caller has the maps).  normals: (V,3)
+    float32 or None (every view weighs 1).  seen: a zeroed (V,) int32 tensor that gets `meshview.visibility`'s count of the
+    views that pass the mask and the depth test.  -> acc (V,4) float64: (r, g, b, w) as svs_mesh_paint leaves them."""
+    verts, faces, _ = mesh_args(verts, faces)
+    _check_rules(cos_min, power, rel, abs_tol, near)
+    views, images, masks, depth, normals, H, W = view_inputs("svs_mesh_paint", verts, views, images, masks, depth, normals)
+    acc = torch.zeros((verts.shape[0], 4), dtype=torch.float64, device=verts.device)
+    for at, to, mats, part, part_masks in view_chunks(verts, faces, views, H, W, masks, depth, near, timers, "paint"):
         _lib.check(paint_raw(verts, normals, mats, to - at, H, W, part, images[at:to], part_masks, acc, near, rel, abs_tol,
                              cos_min, power, flags), "svs_mesh_paint")
         if seen is not None:
             off = torch.zeros_like(seen)
             _lib.check(_mv.visibility_raw(verts, mats, to - at, H, W, part, part_masks, rel, abs_tol, seen, off, near),
                        "svs_mesh_vertex_visibility")
-        t0 = tick(timers, "paint", t0)
     return acc
+
+
+def filled(fill, shape, dev):
+    """a uint8 tensor of shape + (3,) on dev that holds the colour `fill` everywhere"""
+    return torch.tensor([int(c) for c in fill], dtype=torch.uint8, device=dev).repeat(*shape, 1).contiguous()
 
 
 def finish(acc, flags=0, fill=(128, 128, 128)):
     """svs_mesh_paint_finish -> colors (V,3) uint8 (`fill` where acc.w is 0), painted (V,) int32 (1 or 0)"""
     n = int(acc.shape[0])
-    colors = torch.tensor([int(c) for c in fill], dtype=torch.uint8, device=acc.device).repeat(n, 1).contiguous()
+    colors = filled(fill, (n,), acc.device)
     painted = torch.zeros(n, dtype=torch.int32, device=acc.device)
     rc = _lib.load().svs_mesh_paint_finish(_ptr(acc), n, int(flags), _ptr(colors), _ptr(painted), _stream())
     ENTRY_CALLS["finish"] += 1
@@ -174,8 +205,7 @@ def paint(verts, faces, views, images, masks=None, *, mode="blend", cos_min=0.1,
     stats: a dict that gets acc (V,4) float64, normals, seen (V,) int32 (views that pass the mask and depth test),
     rounds, and seconds per phase (which makes every phase wait for the device)."""
     verts, faces, _ = mesh_args(verts, faces)
-    flags = flags_of(mode, one_sided)
-    _check_rules(cos_min, power, rel, abs_tol, near)
+    flags = check_rules(dict(mode=mode, cos_min=cos_min, power=power, one_sided=one_sided, rel=rel, abs_tol=abs_tol, near=near))[1]
     timers = None
     if stats is not None:
         timers = stats.setdefault("seconds", OrderedDict())
@@ -209,12 +239,15 @@ def consistency(verts, faces, colors, views, images, masks=None, *, cos_min=0.1,
     acc = accumulate(verts, faces, views, images, masks, normals=normals, flags=flags_of("blend", one_sided), cos_min=cos_min,
                      power=power, rel=rel, abs_tol=abs_tol, near=near, depth=depth)
     at = acc[:, 3] > 0
-    n = int(at.sum())
-    if n == 0:
+    return agreement(colors[at].to(torch.float64) - acc[at, :3] / acc[at, 3:4])
+
+
+def agreement(diff):
+    """diff (n,3) float64, channels pooled -> dict(n, mad = mean |diff|, psnr = 10 log10(255^2 / mean square)), NaN for n = 0"""
+    if not len(diff):
         return dict(n=0, mad=float("nan"), psnr=float("nan"))
-    diff = colors[at].to(torch.float64) - acc[at, :3] / acc[at, 3:4]
     mse = float((diff * diff).mean())
-    return dict(n=n, mad=float(diff.abs().mean()), psnr=float("inf") if mse == 0 else float(10.0 * np.log10(255.0 ** 2 / mse)))
+    return dict(n=len(diff), mad=float(diff.abs().mean()), psnr=float("inf") if mse == 0 else float(10.0 * np.log10(255.0 ** 2 / mse)))
 
 
 def paint_folder(ply, scan_folder, view_ids, ply_out, holdout=(), *, mode="blend", cos_min=0.1, power=2, one_sided=False,
@@ -231,12 +264,8 @@ def paint_folder(ply, scan_folder, view_ids, ply_out, holdout=(), *, mode="blend
     view_ids, holdout = list(view_ids), list(holdout)
     rules = dict(cos_min=cos_min, power=power, one_sided=one_sided, use_normals=use_normals, rel=rel, abs_tol=abs_tol, near=near)
     t0 = time.perf_counter()
-    verts, faces = _ply.read_mesh(ply)
-    views = folder_cameras(scan_folder, view_ids + holdout)
-    images = folder_images(scan_folder, view_ids + holdout)
-    H, W = images[0].shape[:2]
-    masks = folder_masks(eval_mask_root, dataset, os.path.normpath(scan_folder).split(os.sep)[-1], view_ids + holdout,
-                         H, W, eval_mask_radius)
+    verts, faces, _, views, images, masks, (H, W) = scan_folder_inputs(ply, scan_folder, view_ids + holdout, eval_mask_root, dataset,
+                                                                       eval_mask_radius)
     t0 = tick(sec, "read", t0)
     verts_d, faces_d, _ = mesh_args(verts, faces)
     images_d = [to_device(im, torch.uint8, "meshpaint", "image") for im in images]
@@ -272,30 +301,50 @@ def paint_folder(ply, scan_folder, view_ids, ply_out, holdout=(), *, mode="blend
     return colors, painted, stats
 
 
+def add_painter_args(p, verb, point, holdout_use):
+    """the options `svs_hip.meshpaint` and `svs_hip.meshtexture` share: the views and the rules"""
+    p.add_argument("--views", type=int, nargs="+", required=True, help=f"view ids to {verb} from, e.g. 25 22 28")
+    p.add_argument("--holdout", type=int, nargs="*", default=[], help=f"view ids kept back: {holdout_use}")
+    p.add_argument("--mode", default="blend", choices=("blend", "best"), help="the weighted mean of all views, or the best view alone")
+    p.add_argument("--cos-min", type=float, default=RULES["cos_min"], help="a view counts from this cosine between normal and viewing direction")
+    p.add_argument("--power", type=int, default=RULES["power"], help="weight = cosine ** power, 0..8")
+    p.add_argument("--one-sided", action="store_true", help="a normal that points away from the camera does not count")
+    p.add_argument("--no-normals", action="store_true", help=f"every view that sees a {point} weighs 1")
+    p.add_argument("--rel", type=float, default=RULES["rel"], help="relative depth tolerance of the visibility test")
+    p.add_argument("--abs-tol", type=float, default=RULES["abs_tol"], help="absolute depth tolerance of the visibility test")
+    p.add_argument("--fill", type=int, nargs=3, default=[128, 128, 128], metavar=("R", "G", "B"), help="the colour of what is never reached")
+    add_eval_mask_args(p, "the evaluation masks cut the photographs")
+
+
+def check_painter_args(p, a, also, also_ok=True):
+    """`check_rules`' ranges in the parsers' words; also, also_ok: the module's own options that the second message names"""
+    check_eval_mask_args(p, a)
+    rest_ok = also_ok and all(0 <= c <= 255 for c in a.fill)
+    for names, ok, text in ((("cos_min", "power"), True, "--cos-min lies in [0,1] and --power in [0,8]"),
+                            (("rel", "abs_tol"), rest_ok, f"{also} are not negative, --fill holds codes in [0,255]")):
+        try:
+            check_rules({k: getattr(a, k) for k in names})
+        except ValueError:
+            ok = False
+        if not ok:
+            p.error(text)
+
+
+def painter_rules(a):
+    return dict(mode=a.mode, cos_min=a.cos_min, power=a.power, one_sided=a.one_sided, use_normals=not a.no_normals, rel=a.rel,
+                abs_tol=a.abs_tol)
+
+
 def parse_args(argv=None):
     p = argparse.ArgumentParser(description="Colours a mesh's vertices from a scan's photographs on the GPU and scores the result "
                                             "against held-out views")
     p.add_argument("--ply", required=True, help="the mesh (a PLY with faces; colours it has are ignored)")
     p.add_argument("--scan-folder", required=True, help="holds cams/{id:08}_cam.txt and images/{id:08}.jpg; its last component names the scan")
-    p.add_argument("--views", type=int, nargs="+", required=True, help="view ids to paint from, e.g. 25 22 28")
     p.add_argument("--ply-out", required=True, help="the coloured mesh")
-    p.add_argument("--holdout", type=int, nargs="*", default=[], help="view ids kept back: the photo-consistency score is taken against them")
-    p.add_argument("--mode", default="blend", choices=("blend", "best"), help="the weighted mean of all views, or the best view alone")
-    p.add_argument("--cos-min", type=float, default=RULES["cos_min"], help="a view counts from this cosine between normal and viewing direction")
-    p.add_argument("--power", type=int, default=RULES["power"], help="weight = cosine ** power, 0..8")
-    p.add_argument("--one-sided", action="store_true", help="a normal that points away from the camera does not count")
-    p.add_argument("--no-normals", action="store_true", help="every view that sees a vertex weighs 1")
-    p.add_argument("--rel", type=float, default=RULES["rel"], help="relative depth tolerance of the visibility test")
-    p.add_argument("--abs-tol", type=float, default=RULES["abs_tol"], help="absolute depth tolerance of the visibility test")
+    add_painter_args(p, "paint", "vertex", "the photo-consistency score is taken against them")
     p.add_argument("--spread-rounds", type=int, default=None, help="rounds of hole filling (default: until nothing changes; 0: none)")
-    p.add_argument("--fill", type=int, nargs=3, default=[128, 128, 128], metavar=("R", "G", "B"), help="the colour of what is never reached")
-    add_eval_mask_args(p, "the evaluation masks cut the photographs")
     a = p.parse_args(argv)
-    check_eval_mask_args(p, a)
-    if not (0 <= a.cos_min <= 1) or not (0 <= a.power <= 8):
-        p.error("--cos-min lies in [0,1] and --power in [0,8]")
-    if a.rel < 0 or a.abs_tol < 0 or (a.spread_rounds is not None and a.spread_rounds < 0) or not all(0 <= c <= 255 for c in a.fill):
-        p.error("--rel, --abs-tol and --spread-rounds are not negative, --fill holds codes in [0,255]")
+    check_painter_args(p, a, "--rel, --abs-tol and --spread-rounds", a.spread_rounds is None or a.spread_rounds >= 0)
     if set(a.views) & set(a.holdout):
         p.error("--holdout names views that --views paints from")
     return a
@@ -303,9 +352,8 @@ def parse_args(argv=None):
 
 def main(argv=None):
     a = parse_args(argv)
-    return paint_folder(a.ply, a.scan_folder, a.views, a.ply_out, a.holdout, mode=a.mode, cos_min=a.cos_min, power=a.power,
-                        one_sided=a.one_sided, use_normals=not a.no_normals, rel=a.rel, abs_tol=a.abs_tol,
-                        spread_rounds=a.spread_rounds, fill=tuple(a.fill), eval_mask_root=a.data_dir_root, dataset=a.dataset, log=print)
+    return paint_folder(a.ply, a.scan_folder, a.views, a.ply_out, a.holdout, spread_rounds=a.spread_rounds, fill=tuple(a.fill),
+                        eval_mask_root=a.data_dir_root, dataset=a.dataset, log=print, **painter_rules(a))
 
 
 if __name__ == "__main__":

@@ -250,12 +250,6 @@ def distance(verts_a, faces_a, verts_b, faces_b, thresh):
     return out
 
 
-def read_mesh_colors(ply_in):
-    """-> (verts (V,3) float64, faces (F,3) int64, colors (V,3) uint8 or None) of a PLY mesh"""
-    verts, faces = _ply.read_mesh(ply_in)
-    return verts, faces, _ply.read_points(ply_in)[1]
-
-
 def simplify_ply(ply_in, ply_out, *, cell=None, target_faces=None, ratio=None, tol=1e-3, tries=16, report=False, report_thresh=None,
                  log=None):
     """The mesh file ply_in (`ply.read_mesh`; its colours are kept when it has them) simplified into ply_out (`ply.write`).
@@ -265,7 +259,7 @@ def simplify_ply(ply_in, ply_out, *, cell=None, target_faces=None, ratio=None, t
     sec = OrderedDict((k, 0.0) for k in PHASES)
     calls = dict(ENTRY_CALLS)
     t0 = time.perf_counter()
-    verts, faces, colors = read_mesh_colors(ply_in)
+    verts, faces, colors = _ply.read_mesh_colors(ply_in)
     t0 = tick(sec, "read", t0)
     verts_d, faces_d, colors_d = mesh_args(verts, faces, colors)
     tick(sec, "upload", t0)

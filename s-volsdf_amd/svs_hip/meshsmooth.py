@@ -232,7 +232,7 @@ def smooth_ply(ply_in, ply_out, method="taubin", *, iters=10, lam=0.5, mu=-0.53,
     sec = OrderedDict((k, 0.0) for k in PHASES)
     calls = dict(ENTRY_CALLS)
     t0 = time.perf_counter()
-    verts, faces, colors = meshsimplify.read_mesh_colors(ply_in)
+    verts, faces, colors = _ply.read_mesh_colors(ply_in)
     t0 = tick(sec, "read", t0)
     verts_d, faces_d, _ = mesh_args(verts, faces)
     t0 = tick(sec, "upload", t0)

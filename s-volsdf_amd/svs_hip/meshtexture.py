@@ -10,26 +10,23 @@ every texel gathers the photographs exactly as `svs_hip.meshpaint` gathers them 
 both); texels no view sees take the interpolated vertex colours.  `svs_hip.obj` writes the OBJ, MTL and PNG.
 
 OURS throughout: the reference has no such step.  The arithmetic is fixed in include/svolsdf_hip.h and restated in float64 in
-tests/meshtexture_oracle.py.  SETTINGS: `size` (the atlas is size x size texels), `cell` (texels per cell side, >= 6; default:
-`cell_for`), and the painter's `mode`, `cos_min`, `power`, `one_sided`, `use_normals`, `rel`, `abs_tol`, `near`, `fill`.
+tests/meshtexture_oracle.py (the gather: tests/meshpaint_oracle.py).  SETTINGS: `size` (the atlas is size x size texels), `cell`
+(texels per cell side, >= 6; default: `cell_for`), and the painter's `mode`, `cos_min`, `power`, `one_sided`, `use_normals`, `rel`,
+`abs_tol`, `near`, `fill`; its rules record, checked view inputs, loop over launches and command-line options are `svs_hip.meshpaint`'s.
 """
 import argparse
-import os
 import time
 from collections import OrderedDict
 
-import numpy as np
 import torch
 
 from . import lib as _lib
 from . import meshpaint as _mp
 from . import meshview as _mv
 from . import obj as _obj
-from . import ply as _ply
 from .images import seconds_line, tick, to_device
 from .ops import _ptr, _ptr_array, _stream
-from .views import (add_eval_mask_args, check_eval_mask_args, chunks, device_masks, folder_cameras, folder_images, folder_masks,
-                    launches_since, mesh_args)
+from .views import chunks, launches_since, mesh_args, scan_folder_inputs
 
 MIN_CELL = 6
 MAX_SIZE = 32768
@@ -39,14 +36,8 @@ LANE_ORDER = "cell"                  # how svs_mesh_atlas_bake's lanes walk the 
 
 
 def _rules(rules):
-    """the caller's rules over the defaults, checked as `meshpaint.paint` checks them -> (rules without mode, flags)"""
-    unknown = sorted(set(rules) - set(RULES))
-    if unknown:
-        raise TypeError(f"svs_mesh_atlas_bake: unknown rules {unknown} (known: {sorted(RULES)})")
-    r = dict(RULES, **rules)
-    flags = _mp.flags_of(r.pop("mode"), r["one_sided"])
-    _mp._check_rules(r["cos_min"], r["power"], r["rel"], r["abs_tol"], r["near"])
-    return r, flags
+    """`meshpaint.check_rules` -> (rules without mode, flags)"""
+    return _mp.check_rules(rules, "svs_mesh_atlas_bake")
 
 
 def slots(verts, faces):
@@ -106,49 +97,28 @@ def bake_raw(verts, normals, faces, chart, slot_face, size, cell, mats, n_views,
 
 def bake(verts, faces, chart, slot_face, size, cell, views, images, masks=None, *, normals=None, flags=0, cos_min=0.1, power=2,
          rel=0.01, abs_tol=0.0, near=1e-6, depth=None, timers=None, order=None):
-    """The views in chunks of MAX_VIEWS, rasterised (unless depth (n_views,H,W) is given) and baked chunk by chunk, as
-    `meshpaint.accumulate` paints them.  order: "row" or "cell" (default: LANE_ORDER).
-    -> acc (rows,size,4) float64: (r, g, b, w) per texel of the rows that hold charts"""
+    """The views baked chunk by chunk, as `meshpaint.accumulate` paints them (`meshpaint.view_chunks`).  order: "row" or "cell"
+    (default: LANE_ORDER).  -> acc (rows,size,4) float64: (r, g, b, w) per texel of the rows that hold charts"""
     verts, faces, _ = mesh_args(verts, faces)
-    views = list(views)
     order = LANE_ORDER if order is None else order
     if order not in ("row", "cell"):
         raise ValueError(f"svs_mesh_atlas_bake: order 'row' or 'cell', got {order!r}")
     flags = int(flags) | (_lib.ATLAS_CELL_MAJOR if order == "cell" else 0)
     _mp._check_rules(cos_min, power, rel, abs_tol, near)
-    if not views:
-        raise ValueError("svs_mesh_atlas_bake: no views")
-    dev = verts.device
-    images = _mp._images(images, len(views))
-    H, W = int(images[0].shape[0]), int(images[0].shape[1])
-    masks = device_masks(masks, len(views), H, W, dev, "svs_mesh_atlas_bake")
-    if depth is not None:
-        depth = to_device(depth, torch.float32, "meshtexture", "depth", ndim=(3,))
-        if tuple(depth.shape) != (len(views), H, W):
-            raise ValueError(f"svs_mesh_atlas_bake: depth maps of {tuple(depth.shape)} for {len(views)} views of {(H, W)}")
-    if normals is not None:
-        normals = to_device(normals, torch.float32, "meshtexture", "normals")
-        if tuple(normals.shape) != tuple(verts.shape):
-            raise ValueError(f"svs_mesh_atlas_bake: normals of {tuple(normals.shape)} for {verts.shape[0]} vertices")
-    acc = torch.zeros((rows_for(slot_face.shape[0], size, cell), int(size), 4), dtype=torch.float64, device=dev)
-    t0 = time.perf_counter()
-    for at, to, mats in chunks(views, dev):
-        part = depth[at:to] if depth is not None else _mv.rasterize(verts, faces, views[at:to], H, W, near=near)["depth"]
-        t0 = tick(timers, "raster", t0)
-        _lib.check(bake_raw(verts, normals, faces, chart, slot_face, size, cell, mats, to - at, H, W, part, images[at:to],
-                            masks[at:to] if masks is not None else None, acc, near, rel, abs_tol, cos_min, power, flags),
-                   "svs_mesh_atlas_bake")
-        t0 = tick(timers, "bake", t0)
+    views, images, masks, depth, normals, H, W = _mp.view_inputs("svs_mesh_atlas_bake", verts, views, images, masks, depth, normals)
+    acc = torch.zeros((rows_for(slot_face.shape[0], size, cell), int(size), 4), dtype=torch.float64, device=verts.device)
+    for at, to, mats, part, part_masks in _mp.view_chunks(verts, faces, views, H, W, masks, depth, near, timers, "bake"):
+        _lib.check(bake_raw(verts, normals, faces, chart, slot_face, size, cell, mats, to - at, H, W, part, images[at:to], part_masks,
+                            acc, near, rel, abs_tol, cos_min, power, flags), "svs_mesh_atlas_bake")
     return acc
 
 
 def finish(acc, faces, n_verts, chart, slot_face, size, cell, vert_colors=None, flags=0, fill=(128, 128, 128)):
     """svs_mesh_atlas_finish -> atlas (size,size,3) uint8 (`fill` where nothing was written), covered (size,size) uint8: 1 =
     baked from a view, 2 = from the vertex colours, 0 = left as filled.  acc None: the vertex-colour atlas"""
-    dev = chart.device
     size = int(size)
-    atlas = torch.tensor([int(c) for c in fill], dtype=torch.uint8, device=dev).repeat(size, size, 1).contiguous()
-    covered = torch.zeros((size, size), dtype=torch.uint8, device=dev)
+    atlas = _mp.filled(fill, (size, size), chart.device)
+    covered = torch.zeros((size, size), dtype=torch.uint8, device=chart.device)
     if acc is not None and tuple(acc.shape) != (rows_for(slot_face.shape[0], size, cell), size, 4):
         raise ValueError(f"svs_mesh_atlas_finish: acc of {tuple(acc.shape)} for {rows_for(slot_face.shape[0], size, cell)} rows of {size}")
     rc = _lib.load().svs_mesh_atlas_finish(_ptr(acc), _ptr(faces), int(faces.shape[0]), int(n_verts), _ptr(chart), _ptr(slot_face),
@@ -177,11 +147,10 @@ def render(verts, faces, chart, atlas, cell, views, H, W, fill=(255, 255, 255), 
     views = list(views)
     if not views:
         raise ValueError("svs_mesh_atlas_render: no views")
-    dev = verts.device
     if face is None:
         face = _mv.rasterize(verts, faces, views, H, W, near=near)["face"]
-    rgb = torch.tensor([int(c) for c in fill], dtype=torch.uint8, device=dev).repeat(len(views), int(H), int(W), 1).contiguous()
-    for at, to, mats in chunks(views, dev):
+    rgb = _mp.filled(fill, (len(views), int(H), int(W)), verts.device)
+    for at, to, mats in chunks(views, verts.device):
         _lib.check(render_raw(face[at:to], verts, faces, chart, mats, atlas, cell, rgb[at:to]), "svs_mesh_atlas_render")
     return rgb, face
 
@@ -207,9 +176,8 @@ def texture(verts, faces, views, images, masks=None, *, size=4096, cell=None, ve
     cell = cell_for(n_slots, size) if cell is None else int(cell)
     uv, slot_face = layout(chart, n_slots, size, cell)
     t0 = tick(timers, "slots", t0)
-    use_normals = r.pop("use_normals")
     r.pop("one_sided")
-    normals = _mp.vertex_normals(verts, faces) if use_normals else None
+    normals = _mp.vertex_normals(verts, faces) if r.pop("use_normals") else None
     t0 = tick(timers, "normals", t0)
     acc = bake(verts, faces, chart, slot_face, size, cell, views, images, masks, normals=normals, flags=flags, depth=depth,
                timers=timers, **r)
@@ -237,12 +205,7 @@ def score(rgb, face, chart, images, masks=None):
         for v, m in enumerate(masks):
             if m is not None:
                 at[v] &= torch.as_tensor(m).to(at.device) != 0
-    n = int(at.sum())
-    if n == 0:
-        return dict(n=0, mad=float("nan"), psnr=float("nan"))
-    diff = rgb[at].to(torch.float64) - photo[at].to(torch.float64)
-    mse = float((diff * diff).mean())
-    return dict(n=n, mad=float(diff.abs().mean()), psnr=float("inf") if mse == 0 else float(10.0 * np.log10(255.0 ** 2 / mse)))
+    return _mp.agreement(rgb[at].to(torch.float64) - photo[at].to(torch.float64))
 
 
 def consistency(verts, faces, tex, vert_colors, views, images, masks=None, near=1e-6):
@@ -277,13 +240,8 @@ def texture_folder(ply, scan_folder, view_ids, obj_out, holdout=(), *, size=4096
     view_ids, holdout = list(view_ids), list(holdout)
     _rules(rules)
     t0 = time.perf_counter()
-    verts, faces = _ply.read_mesh(ply)
-    colors = _ply.read_points(ply)[1]
-    views = folder_cameras(scan_folder, view_ids + holdout)
-    images = folder_images(scan_folder, view_ids + holdout)
-    H, W = images[0].shape[:2]
-    masks = folder_masks(eval_mask_root, dataset, os.path.normpath(scan_folder).split(os.sep)[-1], view_ids + holdout,
-                         H, W, eval_mask_radius)
+    verts, faces, colors, views, images, masks, (H, W) = scan_folder_inputs(ply, scan_folder, view_ids + holdout, eval_mask_root,
+                                                                            dataset, eval_mask_radius)
     t0 = tick(sec, "read", t0)
     verts_d, faces_d, colors_d = mesh_args(verts, faces, colors)
     images_d = [to_device(im, torch.uint8, "meshtexture", "image") for im in images]
@@ -330,26 +288,12 @@ def parse_args(argv=None):
                                             "and PNG, and scores the result against held-out views")
     p.add_argument("--ply", required=True, help="the mesh (a PLY with faces; its vertex colours fill what no view sees)")
     p.add_argument("--scan-folder", required=True, help="holds cams/{id:08}_cam.txt and images/{id:08}.jpg; its last component names the scan")
-    p.add_argument("--views", type=int, nargs="+", required=True, help="view ids to bake from, e.g. 25 22 28")
     p.add_argument("--obj-out", required=True, help="the textured mesh; the .mtl and .png go beside it")
     p.add_argument("--size", type=int, default=4096, help="the atlas is size x size texels")
     p.add_argument("--cell", type=int, default=None, help="texels per cell side, at least 6 (default: the largest that holds every face)")
-    p.add_argument("--holdout", type=int, nargs="*", default=[], help="view ids kept back: the rendered mesh is scored against them")
-    p.add_argument("--mode", default="blend", choices=("blend", "best"), help="the weighted mean of all views, or the best view alone")
-    p.add_argument("--cos-min", type=float, default=RULES["cos_min"], help="a view counts from this cosine between normal and viewing direction")
-    p.add_argument("--power", type=int, default=RULES["power"], help="weight = cosine ** power, 0..8")
-    p.add_argument("--one-sided", action="store_true", help="a normal that points away from the camera does not count")
-    p.add_argument("--no-normals", action="store_true", help="every view that sees a texel weighs 1")
-    p.add_argument("--rel", type=float, default=RULES["rel"], help="relative depth tolerance of the visibility test")
-    p.add_argument("--abs-tol", type=float, default=RULES["abs_tol"], help="absolute depth tolerance of the visibility test")
-    p.add_argument("--fill", type=int, nargs=3, default=[128, 128, 128], metavar=("R", "G", "B"), help="the colour of what is never reached")
-    add_eval_mask_args(p, "the evaluation masks cut the photographs")
+    _mp.add_painter_args(p, "bake", "texel", "the rendered mesh is scored against them")
     a = p.parse_args(argv)
-    check_eval_mask_args(p, a)
-    if not (0 <= a.cos_min <= 1) or not (0 <= a.power <= 8):
-        p.error("--cos-min lies in [0,1] and --power in [0,8]")
-    if a.rel < 0 or a.abs_tol < 0 or not all(0 <= c <= 255 for c in a.fill):
-        p.error("--rel and --abs-tol are not negative, --fill holds codes in [0,255]")
+    _mp.check_painter_args(p, a, "--rel and --abs-tol")
     if not (MIN_CELL <= a.size <= MAX_SIZE) or (a.cell is not None and not (MIN_CELL <= a.cell <= a.size)):
         p.error(f"--size lies in [{MIN_CELL}, {MAX_SIZE}] and --cell in [{MIN_CELL}, size]")
     if not a.obj_out.lower().endswith(".obj"):
@@ -362,8 +306,7 @@ def parse_args(argv=None):
 def main(argv=None):
     a = parse_args(argv)
     return texture_folder(a.ply, a.scan_folder, a.views, a.obj_out, a.holdout, size=a.size, cell=a.cell, fill=tuple(a.fill),
-                          eval_mask_root=a.data_dir_root, dataset=a.dataset, log=print, mode=a.mode, cos_min=a.cos_min,
-                          power=a.power, one_sided=a.one_sided, use_normals=not a.no_normals, rel=a.rel, abs_tol=a.abs_tol)
+                          eval_mask_root=a.data_dir_root, dataset=a.dataset, log=print, **_mp.painter_rules(a))
 
 
 if __name__ == "__main__":

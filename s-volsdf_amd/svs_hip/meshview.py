@@ -184,8 +184,7 @@ def view_folder(ply, scan_folder, out_folder, view_ids, size=None, cull=False, m
     calls = dict(ENTRY_CALLS)
     view_ids = list(view_ids)
     t0 = time.perf_counter()
-    verts, faces = _ply.read_mesh(ply)
-    colors = _ply.read_points(ply)[1]
+    verts, faces, colors = _ply.read_mesh_colors(ply)
     views = folder_cameras(scan_folder, view_ids)
     if size is None:
         size = folder_size(scan_folder, view_ids, "svs_mesh_raster")

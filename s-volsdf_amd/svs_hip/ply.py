@@ -125,6 +125,11 @@ def read_mesh(filename):
     return vertices, np.asarray(tris, np.int64).reshape(-1, 3)
 
 
+def read_mesh_colors(filename):
+    """-> `read_mesh`'s vertices and triangles, and `read_points`' rgb (n,3) uint8 or None"""
+    return read_mesh(filename) + (read_points(filename)[1],)
+
+
 def _host(a, dtype):
     return np.asarray(a.detach().cpu() if torch.is_tensor(a) else a, dtype).reshape(-1, 3)
 

@@ -1,11 +1,12 @@
-"""The shared parts of `tsdf`, `meshview` and `meshpaint`: a view's matrices as the kernels of csrc/svs_views.h read them, the
-launch chunks, the checked upload of masks and of a mesh, a scan folder's cameras, photographs and evaluation masks, the
-command lines' evaluation-mask options.  Host code only; nothing here launches a kernel."""
+"""The shared parts of `tsdf`, `meshview`, `meshpaint` and `meshtexture`: a view's matrices as the kernels of csrc/svs_views.h read
+them, the launch chunks, the checked upload of masks and of a mesh, a scan folder's cameras, photographs and evaluation masks (all of
+them with the mesh file: `scan_folder_inputs`), the command lines' evaluation-mask options.  Host code only; nothing here launches a kernel."""
 import os
 
 import numpy as np
 import torch
 
+from . import ply
 from .images import read_rgb8, to_device
 
 MAX_VIEWS = 16                       # views per launch (csrc/svs_views.h kMaxViews)
@@ -91,6 +92,16 @@ def folder_masks(eval_mask_root, dataset, scan_name, view_ids, H, W, radius):
     from . import mvsout
     by_view = mvsout.folder_eval_masks(eval_mask_root, dataset, scan_name, view_ids, {v: (H, W) for v in view_ids}, radius=radius)
     return [by_view[v] for v in view_ids]
+
+
+def scan_folder_inputs(ply_file, scan_folder, view_ids, eval_mask_root, dataset, eval_mask_radius):
+    """The mesh file (`ply.read_mesh_colors`), the cameras and photographs of view_ids and their evaluation masks under the scan's
+    name, the last component of scan_folder -> verts, faces, colors or None, views, images, masks or None, (H, W): host arrays"""
+    verts, faces, colors = ply.read_mesh_colors(ply_file)
+    views, images = folder_cameras(scan_folder, view_ids), folder_images(scan_folder, view_ids)
+    H, W = images[0].shape[:2]
+    masks = folder_masks(eval_mask_root, dataset, os.path.normpath(scan_folder).split(os.sep)[-1], view_ids, H, W, eval_mask_radius)
+    return verts, faces, colors, views, images, masks, (H, W)
 
 
 def add_eval_mask_args(parser, effect):

@@ -4,7 +4,7 @@ hole filling and the photo-consistency score.  numpy only; every expression is w
 that float64 without contraction gives the same bits on both sides."""
 import numpy as np
 
-from meshview_oracle import FRAGILE, project
+from meshview_oracle import FRAGILE, project_points
 
 DEGENERATE = 1e-6                    # |sum| < this * sum of |cross|: a normal that cancellation decides
 
@@ -40,30 +40,39 @@ def _near_int(a):
     return np.abs(a - np.rint(a)) <= FRAGILE
 
 
-def paint(verts, normals, views, depth, images, masks=None, mode="blend", cos_min=0.1, power=2, one_sided=False, rel=0.01,
-          abs_tol=0.0, near=1e-6, acc=None):
-    """svs_mesh_paint over all views in index order (what several calls of at most 16 views accumulate).  normals: (V,3)
-    float32 as the device gets them, or None; depth: (n_views,H,W) float32; images: per view (H,W,3) uint8; masks: None or
-    per view None / (H,W).  -> acc (V,4) float64, fragile (V,) bool: a vertex where, in some view, z is within 1e-9 of near,
-    x or y within 1e-9 of the image bounds, x + 0.5 or y + 0.5 within 1e-9 of an integer, |z - (d (1 + rel) + abs_tol)|
-    <= 1e-9 z, or c within 1e-9 of cos_min; in best mode where the two largest weights are within 1e-9 relative (an exact
-    tie of weights that are 1 by construction is not fragile: the earlier view wins it); and where a channel's mean is
-    within 1e-9 of a rounding boundary."""
-    p = np.asarray(verts, np.float32).astype(np.float64).reshape(-1, 3)
+def paint(verts, normals, views, depth, images, masks=None, **rules):
+    """svs_mesh_paint over all views in index order (what several calls of at most 16 views accumulate): `gather` on the
+    vertices and normals (V,3) as the device gets them, float32 widened (normals None: every view weighs 1); a vertex whose
+    normal is zero or not finite is not lit.  -> acc (V,4) float64, fragile (V,) bool"""
+    n, lit = None, None
+    if normals is not None:
+        n = np.asarray(normals, np.float32).astype(np.float64).reshape(-1, 3)
+        lit = np.isfinite(n).all(1) & ~(n == 0).all(1)
+    return gather(np.asarray(verts, np.float32).astype(np.float64), n, lit, views, depth, images, masks, **rules)
+
+
+def gather(p, n, lit, views, depth, images, masks=None, mode="blend", cos_min=0.1, power=2, one_sided=False, rel=0.01,
+           abs_tol=0.0, near=1e-6, acc=None):
+    """Steps 1 to 7 of svs_mesh_paint for float64 points p (N,3) with float64 normals n (N,3) or None and lit (N,) bool or
+    None (a point that is not lit is skipped in every view), the one restatement of csrc/svs_paint_gather.h: `paint` calls
+    it per vertex, `meshtexture_oracle.bake` per texel.  depth: (n_views,H,W) float32; images: per view (H,W,3) uint8; masks:
+    None or per view None / (H,W); acc: what earlier calls left.  -> acc (N,4) float64, fragile (N,) bool: a point where, in
+    some view, z is within 1e-9 of near, x or y within 1e-9 of the image bounds, x + 0.5 or y + 0.5 within 1e-9 of an
+    integer, |z - (d (1 + rel) + abs_tol)| <= 1e-9 z, or c within 1e-9 of cos_min; in best mode where the two largest weights
+    are within 1e-9 relative (an exact tie of weights that are 1 by construction is not fragile: the earlier view wins it);
+    and where a channel's mean is within 1e-9 of a rounding boundary."""
+    p = np.asarray(p, np.float64).reshape(-1, 3)
     n_verts = len(p)
     acc = np.zeros((n_verts, 4)) if acc is None else np.array(acc, np.float64)
     fragile = np.zeros(n_verts, bool)
     best = mode == "best"
-    lit = np.ones(n_verts, bool)
-    if normals is not None:
-        n = np.asarray(normals, np.float32).astype(np.float64).reshape(-1, 3)
-        lit = np.isfinite(n).all(1) & ~(n == 0).all(1)
+    lit = np.ones(n_verts, bool) if lit is None else np.asarray(lit, bool)
     top = np.stack([acc[:, 3], np.zeros(n_verts)], 1)          # the two largest weights met so far
     for v, view in enumerate(views):
         d32 = np.asarray(depth[v], np.float32)
         img = np.asarray(images[v], np.uint8).astype(np.float64)
         H, W = d32.shape
-        cam, x, y, ok = project(p.astype(np.float32), view["K"], view["E"], near)
+        cam, x, y, ok = project_points(p, view["K"], view["E"], near)
         z = cam[2]
         with np.errstate(all="ignore"):
             fragile |= lit & np.isfinite(z) & (np.abs(z - near) <= FRAGILE)
@@ -83,7 +92,7 @@ def paint(verts, normals, views, depth, images, masks=None, mode="blend", cos_mi
             fragile |= ok & (d != 0) & (np.abs(z - lim) <= FRAGILE * z)
             ok = ok & ((d == 0) | (z <= lim))
         w = np.ones(n_verts)
-        if normals is not None:
+        if n is not None:
             E = np.asarray(view["E"], np.float64)
             eye = [-(E[0, k] * E[0, 3] + E[1, k] * E[1, 3] + E[2, k] * E[2, 3]) for k in range(3)]
             t = [eye[k] - p[:, k] for k in range(3)]
@@ -111,7 +120,7 @@ def paint(verts, normals, views, depth, images, masks=None, mode="blend", cos_mi
             acc[ok, :3] = acc[ok, :3] + w[ok, None] * col[ok]
             acc[ok, 3] = acc[ok, 3] + w[ok]
     if best:
-        by_construction = normals is None or int(power) == 0
+        by_construction = n is None or int(power) == 0
         close = (top[:, 1] > 0) & (top[:, 0] - top[:, 1] <= FRAGILE * top[:, 0])
         if by_construction:
             close &= top[:, 0] != top[:, 1]
@@ -123,16 +132,28 @@ def paint(verts, normals, views, depth, images, masks=None, mode="blend", cos_mi
     return acc, fragile
 
 
+def codes(acc, mode="blend"):
+    """accumulators (...,4) -> codes (...,3) uint8: the rule both finish kernels share (meaningless where acc.w is 0)"""
+    with np.errstate(all="ignore"):
+        mean = acc[..., :3] if mode == "best" else acc[..., :3] / acc[..., 3:4]
+        code = np.floor(mean + 0.5)
+    return np.clip(np.where(np.isnan(code), 0.0, code), 0, 255).astype(np.uint8)
+
+
+def agreement(diff):
+    """differences (n,3) float64, channels pooled -> dict(n, mad, psnr); NaN for n = 0"""
+    if not len(diff):
+        return dict(n=0, mad=float("nan"), psnr=float("nan"))
+    mse = float((diff * diff).mean())
+    return dict(n=len(diff), mad=float(np.abs(diff).mean()), psnr=float("inf") if mse == 0 else float(10.0 * np.log10(255.0 ** 2 / mse)))
+
+
 def finish(acc, mode="blend", fill=(128, 128, 128)):
     """svs_mesh_paint_finish -> rgb (V,3) uint8, painted (V,) int32"""
     acc = np.asarray(acc, np.float64)
     rgb = np.tile(np.asarray(fill, np.uint8), (len(acc), 1))
     seen = acc[:, 3] > 0
-    with np.errstate(all="ignore"):
-        mean = acc[:, :3] if mode == "best" else acc[:, :3] / acc[:, 3:4]
-        code = np.floor(mean + 0.5)
-    code = np.clip(np.where(np.isnan(code), 0.0, code), 0, 255).astype(np.uint8)
-    rgb[seen] = code[seen]
+    rgb[seen] = codes(acc, mode)[seen]
     return rgb, seen.astype(np.int32)
 
 
@@ -173,8 +194,4 @@ def consistency(colors, acc):
     -> dict(n, mad, psnr)"""
     acc = np.asarray(acc, np.float64)
     at = acc[:, 3] > 0
-    if not at.any():
-        return dict(n=0, mad=float("nan"), psnr=float("nan"))
-    diff = np.asarray(colors, np.uint8)[at].astype(np.float64) - acc[at, :3] / acc[at, 3:4]
-    mse = float((diff * diff).mean())
-    return dict(n=int(at.sum()), mad=float(np.abs(diff).mean()), psnr=float("inf") if mse == 0 else float(10.0 * np.log10(255.0 ** 2 / mse)))
+    return agreement(np.asarray(colors, np.uint8)[at].astype(np.float64) - acc[at, :3] / acc[at, 3:4])

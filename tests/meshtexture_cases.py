@@ -99,7 +99,7 @@ def pattern(p):
 def surface_points(face, verts, faces, view):
     """the world point under every pixel centre of one view: the perspective-correct combination of the winner's corners"""
     p = np.asarray(verts, np.float32).astype(np.float64)
-    cam, x, y, _ = mt.project64(p, view["K"], view["E"], 0.0)
+    cam, x, y, _ = mv.project_points(p, view["K"], view["E"], 0.0)
     tri = np.asarray(faces, np.int64)[np.maximum(face, 0)]
     h, w = face.shape
     iy, ix = np.meshgrid(np.arange(h, dtype=np.float64), np.arange(w, dtype=np.float64), indexing="ij")

@@ -3,14 +3,14 @@ from a scan's photographs): slots and rotations, the layout, the per-texel baryc
 the conversion to codes with its vertex-colour branch, and the renderer with its fragile pixels.  numpy only; every
 expression is written in the order the header gives, so that float64 without contraction gives the same bits on both sides.
 
-The gather.  `meshpaint_oracle.paint` rounds the points and normals it is given to float32, as the device's vertices are;
-a texel's point and normal are float64 combinations that no float32 holds, so `gather` below is `paint`'s loop over the
-views on float64 points, statement for statement.  tests/test_meshtexture_cpu.py holds the two together: on points that
-float32 holds, `gather` returns `paint`'s accumulators and fragile flags bit for bit."""
+The gather.  A texel's point and normal are float64 combinations that no float32 holds; `bake` hands them to
+`meshpaint_oracle.gather`, the one restatement of the device's gather, which `meshpaint_oracle.paint` calls on widened
+float32 vertices.  tests/test_meshtexture_cpu.py checks that widening: on points that float32 holds, `gather` returns `paint`'s
+accumulators and fragile flags bit for bit; tests/test_paint_gather_golden.py holds both to what they returned as two loops."""
 import numpy as np
 
-from meshpaint_oracle import _near_int
-from meshview_oracle import FRAGILE, _edges
+from meshpaint_oracle import _near_int, agreement, codes, gather
+from meshview_oracle import _edges, project_points
 
 MIN_CELL = 6
 
@@ -129,95 +129,6 @@ def texels(faces, n_verts, chart, slot_face, S, c):
     return has, idx, np.stack([b0 / s, b1 / s, b2 / s], -1)
 
 
-# ---- the gather ------------------------------------------------------------------------------------------------------------
-def project64(p, K, E, near):
-    """meshview_oracle.project on float64 points"""
-    K, E = np.asarray(K, np.float64), np.asarray(E, np.float64)
-    px, py, pz = p[:, 0], p[:, 1], p[:, 2]
-    with np.errstate(all="ignore"):
-        cam = [E[r, 0] * px + E[r, 1] * py + E[r, 2] * pz + E[r, 3] for r in range(3)]
-        q = [K[r, 0] * cam[0] + K[r, 1] * cam[1] + K[r, 2] * cam[2] for r in range(3)]
-        x, y = q[0] / q[2], q[1] / q[2]
-        ok = (cam[2] > near) & np.isfinite(cam[2]) & np.isfinite(x) & np.isfinite(y)
-    return cam, x, y, ok
-
-
-def gather(p, n, lit, views, depth, images, masks=None, mode="blend", cos_min=0.1, power=2, one_sided=False, rel=0.01,
-           abs_tol=0.0, near=1e-6, acc=None):
-    """steps 1 to 7 of svs_mesh_paint for float64 points p (N,3) with float64 normals n (N,3) or None and lit (N,) bool (a
-    point that is not lit is skipped in every view) -> acc (N,4), fragile (N,): `meshpaint_oracle.paint`'s, statement for
-    statement"""
-    p = np.asarray(p, np.float64).reshape(-1, 3)
-    n_pts = len(p)
-    acc = np.zeros((n_pts, 4)) if acc is None else np.array(acc, np.float64)
-    fragile = np.zeros(n_pts, bool)
-    best = mode == "best"
-    lit = np.ones(n_pts, bool) if lit is None else np.asarray(lit, bool)
-    top = np.stack([acc[:, 3], np.zeros(n_pts)], 1)
-    for v, view in enumerate(views):
-        d32 = np.asarray(depth[v], np.float32)
-        img = np.asarray(images[v], np.uint8).astype(np.float64)
-        H, W = d32.shape
-        cam, x, y, ok = project64(p, view["K"], view["E"], near)
-        z = cam[2]
-        with np.errstate(all="ignore"):
-            fragile |= lit & np.isfinite(z) & (np.abs(z - near) <= FRAGILE)
-            ok = ok & lit
-            inside = (x >= 0) & (x <= W - 1) & (y >= 0) & (y <= H - 1)
-            fragile |= ok & ((np.abs(x) <= FRAGILE) | (np.abs(x - (W - 1)) <= FRAGILE)) & (y >= -FRAGILE) & (y <= H - 1 + FRAGILE)
-            fragile |= ok & ((np.abs(y) <= FRAGILE) | (np.abs(y - (H - 1)) <= FRAGILE)) & (x >= -FRAGILE) & (x <= W - 1 + FRAGILE)
-            ok = ok & inside
-            fragile |= ok & (_near_int(x + 0.5) | _near_int(y + 0.5))
-        xs, ys = np.where(ok, x, 0.0), np.where(ok, y, 0.0)
-        iu, iv = np.floor(xs + 0.5).astype(np.int64), np.floor(ys + 0.5).astype(np.int64)
-        if masks is not None and masks[v] is not None:
-            ok = ok & (np.asarray(masks[v])[iv, iu] != 0)
-        d = d32[iv, iu].astype(np.float64)
-        lim = d * (1.0 + rel) + abs_tol
-        with np.errstate(all="ignore"):
-            fragile |= ok & (d != 0) & (np.abs(z - lim) <= FRAGILE * z)
-            ok = ok & ((d == 0) | (z <= lim))
-        w = np.ones(n_pts)
-        if n is not None:
-            E = np.asarray(view["E"], np.float64)
-            eye = [-(E[0, k] * E[0, 3] + E[1, k] * E[1, 3] + E[2, k] * E[2, 3]) for k in range(3)]
-            t = [eye[k] - p[:, k] for k in range(3)]
-            with np.errstate(all="ignore"):
-                c = (n[:, 0] * t[0] + n[:, 1] * t[1] + n[:, 2] * t[2]) / np.sqrt(t[0] * t[0] + t[1] * t[1] + t[2] * t[2])
-                if not one_sided:
-                    c = np.abs(c)
-                fragile |= ok & (np.abs(c - cos_min) <= FRAGILE)
-                ok = ok & (c >= cos_min)
-                for _ in range(int(power)):
-                    w = w * c
-        x0, y0 = np.floor(xs), np.floor(ys)
-        fx, fy = xs - x0, ys - y0
-        ix0, iy0 = x0.astype(np.int64), y0.astype(np.int64)
-        ix1, iy1 = np.minimum(ix0 + 1, W - 1), np.minimum(iy0 + 1, H - 1)
-        col = ((1.0 - fx)[:, None] * img[iy0, ix0] + fx[:, None] * img[iy0, ix1]) * (1.0 - fy)[:, None] + \
-              ((1.0 - fx)[:, None] * img[iy1, ix0] + fx[:, None] * img[iy1, ix1]) * fy[:, None]
-        if best:
-            take = ok & (w > acc[:, 3])
-            acc[take, :3] = col[take]
-            acc[take, 3] = w[take]
-            both = np.sort(np.stack([top[:, 0], top[:, 1], np.where(ok, w, 0.0)], 1), 1)[:, ::-1]
-            top = both[:, :2]
-        else:
-            acc[ok, :3] = acc[ok, :3] + w[ok, None] * col[ok]
-            acc[ok, 3] = acc[ok, 3] + w[ok]
-    if best:
-        by_construction = n is None or int(power) == 0
-        close = (top[:, 1] > 0) & (top[:, 0] - top[:, 1] <= FRAGILE * top[:, 0])
-        if by_construction:
-            close &= top[:, 0] != top[:, 1]
-        fragile |= close
-    seen = acc[:, 3] > 0
-    with np.errstate(all="ignore"):
-        mean = acc[:, :3] if best else acc[:, :3] / acc[:, 3:4]
-        fragile |= seen & _near_int(mean + 0.5).any(1)
-    return acc, fragile
-
-
 # ---- bake, finish ------------------------------------------------------------------------------------------------------------
 def bake(verts, normals, faces, chart, slot_face, S, c, views, depth, images, masks=None, **rules):
     """svs_mesh_atlas_bake over all views in index order.  normals: (V,3) float32 as the device gets them, or None; depth:
@@ -252,11 +163,7 @@ def finish(acc, faces, n_verts, chart, slot_face, S, c, vert_rgb=None, mode="ble
     covered = np.zeros((S, S), np.uint8)
     acc = np.zeros((rows, S, 4)) if acc is None else np.asarray(acc, np.float64)
     seen = has & (acc[..., 3] > 0)
-    with np.errstate(all="ignore"):
-        mean = acc[..., :3] if mode == "best" else acc[..., :3] / acc[..., 3:4]
-        code = np.floor(mean + 0.5)
-    code = np.clip(np.where(np.isnan(code), 0.0, code), 0, 255).astype(np.uint8)
-    atlas[:rows][seen] = code[seen]
+    atlas[:rows][seen] = codes(acc, mode)[seen]
     covered[:rows][seen] = 1
     if vert_rgb is not None:
         col = np.asarray(vert_rgb, np.uint8).astype(np.float64).reshape(-1, 3)
@@ -287,7 +194,7 @@ def render(face, verts, faces, chart, views, atlas, c, fill=(255, 255, 255), fac
     T = corner_texels(chart, S, c).astype(np.float64)
     iy, ix = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing="ij")
     for v, view in enumerate(views):
-        cam, x, y, _ = project64(p, view["K"], view["E"], 0.0)
+        cam, x, y, _ = project_points(p, view["K"], view["E"], 0.0)
         local = face[v] - face_base
         own = (face[v] >= 0) & (local >= 0) & (local < len(faces))
         local = np.where(own, local, 0)
@@ -328,8 +235,4 @@ def score(rgb, face, chart, images, masks=None):
     for v in range(len(face)):
         if masks is not None and masks[v] is not None:
             at[v] &= np.asarray(masks[v]) != 0
-    if not at.any():
-        return dict(n=0, mad=float("nan"), psnr=float("nan"))
-    diff = np.asarray(rgb, np.uint8)[at].astype(np.float64) - np.stack([np.asarray(im, np.uint8) for im in images])[at].astype(np.float64)
-    mse = float((diff * diff).mean())
-    return dict(n=int(at.sum()), mad=float(np.abs(diff).mean()), psnr=float("inf") if mse == 0 else float(10.0 * np.log10(255.0 ** 2 / mse)))
+    return agreement(np.asarray(rgb, np.uint8)[at].astype(np.float64) - np.stack([np.asarray(im, np.uint8) for im in images])[at].astype(np.float64))

@@ -12,9 +12,13 @@ EMPTY = np.uint64(0xFFFFFFFFFFFFFFFF)
 
 
 def project(verts, K, E, near):
-    """-> cam (3 arrays), x, y, ok: cam = E (p,1), pix = K cam, x = pix.x / pix.z, y = pix.y / pix.z; ok: z > near and z, x,
-    y finite"""
-    p = np.asarray(verts, np.float32).astype(np.float64).reshape(-1, 3)
+    """`project_points` of the vertices as the device has them: float32, widened"""
+    return project_points(np.asarray(verts, np.float32).astype(np.float64).reshape(-1, 3), K, E, near)
+
+
+def project_points(p, K, E, near):
+    """float64 points p (N,3) -> cam (3 arrays), x, y, ok: cam = E (p,1), pix = K cam, x = pix.x / pix.z, y = pix.y / pix.z; ok:
+    z > near and z, x, y finite"""
     K, E = np.asarray(K, np.float64), np.asarray(E, np.float64)
     px, py, pz = p[:, 0], p[:, 1], p[:, 2]
     with np.errstate(all="ignore"):

@@ -290,6 +290,51 @@ def test_symbols_unit_and_command_line():
     assert meshpaint.flags_of("best", True) == 3 and meshpaint.flags_of() == 0
 
 
+def test_one_rules_record_serves_the_painter_the_atlas_and_both_command_lines(capsys):
+    """`meshpaint.check_rules` is the one place that knows the rules: `flags_of`, `_check_rules` and `meshtexture._rules` are
+    calls of it, with the messages they always had; both parsers take their shared options and range checks from meshpaint,
+    and give the namespaces recorded below before they did."""
+    from svs_hip import meshpaint, meshtexture
+    r, flags = meshpaint.check_rules(dict(mode="best", one_sided=True))
+    assert flags == 3 == meshpaint.flags_of("best", True) and r == dict(meshpaint.RULES, one_sided=True) and "mode" not in r
+    assert meshpaint.check_rules({}) == (meshpaint.RULES, 0) and meshtexture._rules(dict(power=0, near=0.5))[0]["near"] == 0.5
+    for call in (meshpaint.check_rules, meshtexture._rules):
+        with pytest.raises(ValueError, match=r"svs_mesh_paint: cos_min in \[0,1\] and power an integer in \[0,8\], got 0.1 and 9"):
+            call(dict(power=9))
+        with pytest.raises(ValueError, match="svs_mesh_paint: mode 'blend' or 'best', got 'mean'"):
+            call(dict(mode="mean"))
+        with pytest.raises(ValueError, match="svs_mesh_paint: near must be positive, rel and abs_tol not negative, got 0.0, 0.01, 0.0"):
+            call(dict(near=0.0))
+    with pytest.raises(TypeError, match=r"svs_mesh_paint: unknown rules \['spread_rounds'\] \(known: \['abs_tol', 'cos_min', 'mode', 'near'"):
+        meshpaint.check_rules(dict(spread_rounds=3))
+    with pytest.raises(TypeError, match=r"svs_mesh_atlas_bake: unknown rules \['spread_rounds'\]"):
+        meshtexture._rules(dict(spread_rounds=3, power=9))     # the unknown name is refused first
+    with pytest.raises(ValueError, match="mode"):
+        meshpaint.check_rules(dict(mode="mean", power=9))      # then the mode, then the ranges
+    with pytest.raises(ValueError, match="svs_mesh_paint: cos_min"):
+        meshpaint._check_rules(0.1, 2.5, 0.01, 0.0, 1e-6)
+    shared = ["--views", "25", "22", "28", "--holdout", "23", "24", "--mode", "best", "--cos-min", "0.3", "--power", "3", "--one-sided",
+              "--no-normals", "--rel", "0.02", "--abs-tol", "0.5", "--fill", "1", "2", "3"]
+    want = dict(abs_tol=0.5, cos_min=0.3, data_dir_root=None, dataset=None, fill=[1, 2, 3], holdout=[23, 24], mode="best", no_normals=True,
+                one_sided=True, ply="m.ply", power=3, rel=0.02, scan_folder="s", views=[25, 22, 28])
+    a = meshpaint.parse_args(["--ply", "m.ply", "--scan-folder", "s", "--ply-out", "p.ply", "--spread-rounds", "4"] + shared)
+    assert vars(a) == dict(want, ply_out="p.ply", spread_rounds=4)
+    b = meshtexture.parse_args(["--ply", "m.ply", "--scan-folder", "s", "--obj-out", "o.obj", "--size", "512", "--cell", "9"] + shared)
+    assert vars(b) == dict(want, obj_out="o.obj", size=512, cell=9)
+    rules = dict(mode="best", cos_min=0.3, power=3, one_sided=True, use_normals=False, rel=0.02, abs_tol=0.5)
+    assert meshpaint.painter_rules(a) == meshpaint.painter_rules(b) == rules and meshtexture._rules(rules)[1] == 3
+    paint_base = ["--ply", "m.ply", "--scan-folder", "s", "--views", "25", "--ply-out", "p.ply"]
+    bake_base = ["--ply", "m.ply", "--scan-folder", "s", "--views", "25", "--obj-out", "o.obj"]
+    for parse, base, second in ((meshpaint.parse_args, paint_base, "--rel, --abs-tol and --spread-rounds are not negative, --fill holds codes in [0,255]"),
+                                (meshtexture.parse_args, bake_base, "--rel and --abs-tol are not negative, --fill holds codes in [0,255]")):
+        for bad, text in ((["--power", "9"], "--cos-min lies in [0,1] and --power in [0,8]"), (["--cos-min", "-0.1"], "--cos-min lies in [0,1] and --power in [0,8]"),
+                          (["--abs-tol", "-1"], second), (["--fill", "0", "-1", "0"], second), (["--power", "9", "--rel", "-1"], "--cos-min lies"),
+                          (["--dataset", "DTU", "--power", "9"], "--data-dir-root and --dataset come together")):
+            with pytest.raises(SystemExit):
+                parse(base + bad)
+            assert text in capsys.readouterr().err, (bad, text)
+
+
 def test_argument_errors_name_the_entry():
     """the checks come before any device work: no GPU needed"""
     from svs_hip import lib
