@@ -1194,7 +1194,7 @@ int svs_mesh_cluster_faces_emit(const int* faces, int n_faces, const int* vert_c
                                 int* out_faces, void* hip_stream);
 
 /* ---- a surface from an oriented point cloud: Poisson reconstruction on one dense grid (svs_hip.poisson; csrc/svs_poisson.hip)
- * After Kazhdan, Bolitho and Hoppe, "Poisson surface reconstruction" (2006), on one dense grid and without screening.  The
+ * After Kazhdan, Bolitho and Hoppe, "Poisson surface reconstruction" (2006), on one dense grid; screening is opt-in (below).  The
  * reference has no such step; the arithmetic below is this project's (tests/poisson_oracle.py restates it in numpy float64).
  * The grid is node-centred with shape (n0,n1,n2), last axis contiguous, node (i,j,k) at origin + (i,j,k) h; origin: HOST
  * double[3], finite; h > 0.  Two nodes along every axis, fewer than 2^31 nodes.  Volumes are float32; every per-element
@@ -1232,6 +1232,28 @@ int svs_mesh_cluster_faces_emit(const int* faces, int n_faces, const int* vert_c
  *   node); keep[f] = 1 iff the float64 sum, in corner order from zero, of W over the cell's eight nodes is >= min_density
  *   (a node on an upper face or an index out of range: 0).  Not svs_tsdf_face_keep's rule: a trilinear splat leaves the
  *   far nodes of a surface cell nearly empty.
+ *
+ * SCREENING (opt-in; after Kazhdan and Hoppe, "Screened Poisson surface reconstruction", 2013, with the point term lumped):
+ * the system A + diag(weight W), W the splat's weight plane field[3] (the row sums of S^T S for the trilinear sampling
+ * matrix S), used as given and never read back: values that are not negative keep the operator positive definite.
+ * tests/poisson_screen_oracle.py restates what follows in numpy float64.
+ * svs_screened_apply: a = (6 x - s) / (h h) with s exactly as svs_poisson_apply sums it and 0 beyond the grid,
+ *   b = (weight * W) * x, y = float32(a + b).  The operator's diagonal is d = 6 / (h h) + weight * W.  x and y may not be the
+ *   same array.  16-byte accesses when n2 % 4 == 0 and x, y and W are 16-byte aligned (field[3] lies 3 n0 n1 n2 floats into
+ *   its buffer and need not be), scalar ones otherwise; the same values either way.
+ * svs_screened_pcg: conjugate gradients preconditioned by that diagonal for (A + diag(weight W)) x = rhs from x = 0:
+ *   r = rhs, p = float32(r / d), rz = sum r (r / d), bb = rn = sum r r; repeat: q = float32(A_s p); alpha = rz / p.q (0 when
+ *   p.q <= 0); x = float32(x + alpha p); r = float32(r - alpha q); rn = r.r; rzn = sum r (r / d); beta = rzn / rz (0 when
+ *   rz <= 0); rz = rzn; p = float32(r / d + beta p).  z = r / d is never stored: it is formed from W where it is needed.
+ *   Dot products float64 over the stored float32 values in svs_poisson_cg's order (per-workgroup partials, then one
+ *   workgroup over the partials: a function of the shape alone, the same bytes in every run); the scalars stay on the
+ *   device.  The stopping rule, check_every, the three HOST outputs and the 8-byte download are svs_poisson_cg's:
+ *   rn <= tol^2 bb; bb == 0 (or not finite): SVS_EINVAL, "no normal field".  Synchronises the stream.
+ *   At weight == 0 svs_screened_apply gives svs_poisson_apply's bytes; svs_screened_pcg is then svs_poisson_cg with every
+ *   direction scaled by h h / 6: the same iterates up to rounding, not the same bytes.
+ * Their checks are svs_poisson_apply's and svs_poisson_cg's, and: weight finite and >= 0 (SVS_EINVAL, "weight" in the
+ * message), W not null.
+ *
  * Every check comes before any HIP call: SVS_ESHAPE for a grid with fewer than two nodes along an axis or 2^31 nodes or
  * more, n < 1, a negative face count; SVS_EINVAL for a null required pointer, h <= 0 or not finite, an origin that is not
  * finite, with the entry's name in the message. */
@@ -1249,6 +1271,11 @@ int svs_poisson_sample(const float* x, int n0, int n1, int n2, const double SVS_
                        void* workspace, double* vals, double SVS_HOST* level, int SVS_HOST* counted, void* hip_stream);
 int svs_poisson_face_keep(const float* W, int n0, int n1, int n2, const int* cells, int n_faces, double min_density, uint8_t* keep,
                           void* hip_stream);
+int svs_screened_apply(const float* x, const float* W, int n0, int n1, int n2, double h, double weight, float* y, void* hip_stream);
+size_t svs_screened_pcg_workspace_bytes(int n0, int n1, int n2);
+int svs_screened_pcg(const float* rhs, const float* W, int n0, int n1, int n2, double h, double weight, double tol, int max_iter,
+                     int check_every, void* workspace, float* x, int SVS_HOST* iterations, double SVS_HOST* residual,
+                     int SVS_HOST* converged, void* hip_stream);
 
 /* ---- numeric-contract self tests (used by tests/test_gpu_parity.py) --------------------------------------- */
 int svs_selftest_exp(const float* x, float* y_exp, float* y_expm1, int n, void* hip_stream);

@@ -1,6 +1,7 @@
 // A surface from an oriented point cloud on gfx950 (svs_hip/poisson.py): Poisson reconstruction on one dense grid, after
-// Kazhdan, Bolitho and Hoppe, "Poisson surface reconstruction" (2006), without octree and without screening.  The rule is
-// stated in include/svolsdf_hip.h and restated in float64 numpy by tests/poisson_oracle.py.
+// Kazhdan, Bolitho and Hoppe, "Poisson surface reconstruction" (2006), without octree; screening (Kazhdan and Hoppe 2013, the
+// point term lumped into the diagonal weight * W) is opt-in through the svs_screened_* entries.  The rule is stated in
+// include/svolsdf_hip.h and restated in float64 numpy by tests/poisson_oracle.py and tests/poisson_screen_oracle.py.
 //
 // Splat: the counted points are sorted by the index of their cell (a stable radix sort of the bits the cell count needs),
 // the eight corner sums of a cell are formed in one fixed order -- segments of 64 consecutive points, one lane per segment,
@@ -11,7 +12,9 @@
 // is five launches and moves 44 bytes per node: the 7-point stencil fused with p.q (read p, write q), a one-workgroup pass
 // over the partial sums that leaves alpha in device memory, the two axpys fused with r.r (read x p r q, write x r), the pass
 // that leaves beta, and the direction update (read r p, write p).  The host never waits inside an iteration; every
-// check_every iterations it downloads the 8 bytes of r.r.
+// check_every iterations it downloads the 8 bytes of r.r.  The screened solve is the same five launches with the diagonal
+// d = 6 / h^2 + weight * W as preconditioner: each of the three passes over the volume reads W once more (56 bytes per node),
+// the axpy pass leaves r.r and r.(r / d) together, and r / d is never stored.
 //
 // The stencil kernel: a workgroup owns kTileJ x kTileK nodes of a plane and marches over kTileI planes.  A lane holds four
 // consecutive nodes of the contiguous axis in registers for the planes i-1, i, i+1 and i+2 (the last one a prefetch); the
@@ -232,10 +235,11 @@ __device__ __forceinline__ float load_node(const float* __restrict__ p, const Vo
 }
 
 // q = A p with A p = (6 p - ((((((i-1) + (i+1)) + (j-1)) + (j+1)) + (k-1)) + (k+1))) / h^2, 0 beyond the grid; partial[workgroup] =
-// the workgroup's share of p.q (products of the stored float32 values, in float64)
-template <bool kVec>
+// the workgroup's share of p.q (products of the stored float32 values, in float64).  kScreen: q = A p + (weight * W) * p, the
+// lane's own four W values of a plane fetched one plane ahead like the halo (the other instantiations never touch W or weight)
+template <bool kVec, bool kScreen>
 __global__ __launch_bounds__(kThreads) void stencil_kernel(const float* __restrict__ p, float* __restrict__ q, Vol v, double h2,
-                                                           double* __restrict__ partial) {
+                                                           double* __restrict__ partial, const float* __restrict__ W, double weight) {
   __shared__ __attribute__((aligned(16))) float plane[kTileJ + 2][kLdsStride];
   __shared__ double red[kThreads];
   const int tid = threadIdx.x, tj = tid / (kTileK / kGroup), tk = (tid % (kTileK / kGroup)) * kGroup;
@@ -254,14 +258,18 @@ __global__ __launch_bounds__(kThreads) void stencil_kernel(const float* __restri
   float hcol = 0.0f;
   if (halo_row) hrow = load_row4<kVec>(p, v, i0, hrow_j, k);
   if (halo_col) hcol = load_node(p, v, i0, j0 + hc_row, hcol_k);
+  f32x4 wcur = {0.0f, 0.0f, 0.0f, 0.0f};
+  if (kScreen) wcur = load_row4<kVec>(W, v, i0, j, k);
   double acc = 0.0;
   for (long long i = i0; i < i1; ++i) {
     const f32x4 next2 = load_row4<kVec>(p, v, i + 2 < i1 + 1 ? i + 2 : v.n0, j, k);       // prefetch; nothing past plane i1
     f32x4 hrow_next = {0.0f, 0.0f, 0.0f, 0.0f};
     float hcol_next = 0.0f;
+    f32x4 wnext = {0.0f, 0.0f, 0.0f, 0.0f};
     if (i + 1 < i1) {
       if (halo_row) hrow_next = load_row4<kVec>(p, v, i + 1, hrow_j, k);
       if (halo_col) hcol_next = load_node(p, v, i + 1, j0 + hc_row, hcol_k);
+      if (kScreen) wnext = load_row4<kVec>(W, v, i + 1, j, k);
     }
     __syncthreads();                                         // the reads of the previous plane are done
     *reinterpret_cast<f32x4*>(&plane[tj + 1][4 + tk]) = cur;
@@ -275,12 +283,14 @@ __global__ __launch_bounds__(kThreads) void stencil_kernel(const float* __restri
       const float c[6] = {left, cur.x, cur.y, cur.z, cur.w, right};
       const float pm[4] = {prev.x, prev.y, prev.z, prev.w}, pp[4] = {next.x, next.y, next.z, next.w};
       const float bm[4] = {below.x, below.y, below.z, below.w}, bp[4] = {above.x, above.y, above.z, above.w};
+      const float wv[4] = {wcur.x, wcur.y, wcur.z, wcur.w};
       float out[4];
 #pragma unroll
       for (int e = 0; e < kGroup; ++e) {
         // beyond the row's end the right neighbour is 0 (the loads gave 0 there)
         const double sum = (((((double)pm[e] + (double)pp[e]) + (double)bm[e]) + (double)bp[e]) + (double)c[e]) + (double)c[e + 2];
-        out[e] = (float)((6.0 * (double)c[e + 1] - sum) / h2);
+        if (kScreen) out[e] = (float)((6.0 * (double)c[e + 1] - sum) / h2 + (weight * (double)wv[e]) * (double)c[e + 1]);
+        else out[e] = (float)((6.0 * (double)c[e + 1] - sum) / h2);
         if (k + e < v.n2) acc += (double)c[e + 1] * (double)out[e];
       }
       float* at = q + (i * v.n1 + j) * v.n2 + k;
@@ -293,7 +303,7 @@ __global__ __launch_bounds__(kThreads) void stencil_kernel(const float* __restri
           if (k + e < v.n2) at[e] = out[e];
       }
     }
-    prev = cur; cur = next; next = next2; hrow = hrow_next; hcol = hcol_next;
+    prev = cur; cur = next; next = next2; hrow = hrow_next; hcol = hcol_next; wcur = wnext;
   }
   const double total = block_sum(acc, red);
   if (partial && tid == 0) partial[((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = total;
@@ -403,6 +413,113 @@ __global__ __launch_bounds__(kThreads) void cg_scalars_kernel(const double* __re
   }
 }
 
+// ---- the screened system: A + diag(weight W), Jacobi-preconditioned conjugate gradients ------------------------------------
+// d = 6 / h^2 + weight * W is the operator's diagonal; z = r / d is formed in float64 where it is needed and never stored.
+enum { kRZ = 5 };                                           // r.z beside kRR .. kRN (svs_poisson_cg leaves the slot alone)
+
+__device__ __forceinline__ double screened_diagonal(double six_h2, double weight, float w) { return six_h2 + weight * (double)w; }
+
+// x = 0, r = rhs, p = r / d, partial = r.r, partial_z = r.(r / d)
+__global__ __launch_bounds__(kThreads) void pcg_init_kernel(const float* __restrict__ rhs, const float* __restrict__ W, long long total,
+                                                            int vec_rhs, int vec_w, int vec_x, double six_h2, double weight,
+                                                            float* __restrict__ x, float* __restrict__ r, float* __restrict__ p,
+                                                            double* __restrict__ partial, double* __restrict__ partial_z) {
+  __shared__ double red[kThreads];
+  const long long groups = (total + kGroup - 1) / kGroup;
+  const float zero[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+  double acc = 0.0, acc_z = 0.0;
+  for (long long g = (long long)blockIdx.x * kThreads + threadIdx.x; g < groups; g += (long long)gridDim.x * kThreads) {
+    float b[4], wv[4], pv[4];
+    load4(rhs, g * kGroup, total, vec_rhs, b);
+    load4(W, g * kGroup, total, vec_w, wv);
+#pragma unroll
+    for (int e = 0; e < kGroup; ++e) {
+      const double z = (double)b[e] / screened_diagonal(six_h2, weight, wv[e]);
+      pv[e] = (float)z;
+      acc += (double)b[e] * (double)b[e];                    // (elements past the end are 0, and their d is 6 / h^2 > 0)
+      acc_z += (double)b[e] * z;
+    }
+    store4(x, g * kGroup, total, vec_x, zero);
+    store4(r, g * kGroup, total, true, b);
+    store4(p, g * kGroup, total, true, pv);
+  }
+  const double sum = block_sum(acc, red);
+  const double sum_z = block_sum(acc_z, red);
+  if (threadIdx.x == 0) { partial[blockIdx.x] = sum; partial_z[blockIdx.x] = sum_z; }
+}
+
+// x += alpha p, r -= alpha q, partial = r.r and partial_z = r.(r / d) of the stored r, both in the one pass
+__global__ __launch_bounds__(kThreads) void pcg_axpy_kernel(long long total, int vec_x, int vec_w, double six_h2, double weight,
+                                                            const double* __restrict__ scal, const float* __restrict__ W,
+                                                            float* __restrict__ x, float* __restrict__ r, const float* __restrict__ p,
+                                                            const float* __restrict__ q, double* __restrict__ partial,
+                                                            double* __restrict__ partial_z) {
+  __shared__ double red[kThreads];
+  const long long groups = (total + kGroup - 1) / kGroup;
+  const double alpha = scal[kAlpha];
+  double acc = 0.0, acc_z = 0.0;
+  for (long long g = (long long)blockIdx.x * kThreads + threadIdx.x; g < groups; g += (long long)gridDim.x * kThreads) {
+    float xv[4], rv[4], pv[4], qv[4], wv[4];
+    load4(x, g * kGroup, total, vec_x, xv);
+    load4(r, g * kGroup, total, true, rv);
+    load4(p, g * kGroup, total, true, pv);
+    load4(q, g * kGroup, total, true, qv);
+    load4(W, g * kGroup, total, vec_w, wv);
+#pragma unroll
+    for (int e = 0; e < kGroup; ++e) {
+      xv[e] = (float)((double)xv[e] + alpha * (double)pv[e]);
+      rv[e] = (float)((double)rv[e] - alpha * (double)qv[e]);
+      acc += (double)rv[e] * (double)rv[e];                  // (elements past the end are 0)
+      acc_z += (double)rv[e] * ((double)rv[e] / screened_diagonal(six_h2, weight, wv[e]));
+    }
+    store4(x, g * kGroup, total, vec_x, xv);
+    store4(r, g * kGroup, total, true, rv);
+  }
+  const double sum = block_sum(acc, red);
+  const double sum_z = block_sum(acc_z, red);
+  if (threadIdx.x == 0) { partial[blockIdx.x] = sum; partial_z[blockIdx.x] = sum_z; }
+}
+
+// p = r / d + beta p
+__global__ __launch_bounds__(kThreads) void pcg_direction_kernel(long long total, int vec_w, double six_h2, double weight,
+                                                                 const double* __restrict__ scal, const float* __restrict__ W,
+                                                                 const float* __restrict__ r, float* __restrict__ p) {
+  const long long groups = (total + kGroup - 1) / kGroup;
+  const double beta = scal[kBeta];
+  for (long long g = (long long)blockIdx.x * kThreads + threadIdx.x; g < groups; g += (long long)gridDim.x * kThreads) {
+    float rv[4], pv[4], wv[4];
+    load4(r, g * kGroup, total, true, rv);
+    load4(p, g * kGroup, total, true, pv);
+    load4(W, g * kGroup, total, vec_w, wv);
+#pragma unroll
+    for (int e = 0; e < kGroup; ++e) pv[e] = (float)((double)rv[e] / screened_diagonal(six_h2, weight, wv[e]) + beta * (double)pv[e]);
+    store4(p, g * kGroup, total, true, pv);
+  }
+}
+
+// cg_scalars_kernel's order over two rows of partials (partial_z is not read in kModePQ); thread 0 updates the scalars
+__global__ __launch_bounds__(kThreads) void pcg_scalars_kernel(const double* __restrict__ partial, const double* __restrict__ partial_z,
+                                                               int n_partials, int mode, double* __restrict__ scal) {
+  __shared__ double red[kThreads];
+  double acc = 0.0, acc_z = 0.0;
+  for (int b = threadIdx.x; b < n_partials; b += kThreads) {
+    acc += partial[b];
+    if (mode != kModePQ) acc_z += partial_z[b];
+  }
+  const double sum = block_sum(acc, red);
+  const double sum_z = block_sum(acc_z, red);
+  if (threadIdx.x != 0) return;
+  if (mode == kModeInit) {
+    scal[kRR] = sum; scal[kBB] = sum; scal[kRN] = sum; scal[kRZ] = sum_z; scal[kAlpha] = 0.0; scal[kBeta] = 0.0;
+  } else if (mode == kModePQ) {
+    scal[kAlpha] = sum > 0.0 ? scal[kRZ] / sum : 0.0;        // p = 0 (r = 0 exactly): nothing moves any more
+  } else {
+    const double rz = scal[kRZ];
+    scal[kBeta] = rz > 0.0 ? sum_z / rz : 0.0;
+    scal[kRR] = sum; scal[kRN] = sum; scal[kRZ] = sum_z;
+  }
+}
+
 // ---- sample, level, trim -------------------------------------------------------------------------------------------------
 // vals[i] = the trilinear value of x at point i (NaN for a point that does not count); partial[workgroup] = the sum over
 // the workgroup's counted points, cpartial[workgroup] = their number
@@ -504,14 +621,15 @@ int stencil_blocks(int n0, int n1, int n2, dim3* grid) {
   if (grid) *grid = dim3((unsigned)gx, (unsigned)gy, (unsigned)gz);
   return (int)(gx * gy * gz);                                // <= 2^31 / 2^14 workgroups for a volume of int32 sizes below 2^31 nodes
 }
-CgLayout cg_layout(int n0, int n1, int n2) {
+// rows: the dot products a flat pass leaves partials of (the preconditioned solve's r.r and r.z: row 1 lies n_partials behind row 0)
+CgLayout cg_layout(int n0, int n1, int n2, int rows = 1) {
   CgLayout L;
   Bump b;
   const size_t total = (size_t)n0 * n1 * n2;
   const int sb = stencil_blocks(n0, n1, n2, nullptr);
   L.n_partials = sb > kFlatBlocks ? sb : kFlatBlocks;
   L.r = b.take(4 * total); L.p = b.take(4 * total); L.q = b.take(4 * total);
-  L.partial = b.take(sizeof(double) * (size_t)L.n_partials); L.scal = b.take(sizeof(double) * kScalars);
+  L.partial = b.take(sizeof(double) * (size_t)L.n_partials * (size_t)rows); L.scal = b.take(sizeof(double) * kScalars);
   L.total = b.o;
   return L;
 }
@@ -535,8 +653,65 @@ void launch_stencil(const float* p, float* q, int n0, int n1, int n2, double h, 
   const Vol v = {n0, n1, n2};
   const double h2 = h * h;
   const bool vec = (n2 % kGroup) == 0 && (((uintptr_t)p | (uintptr_t)q) & 15u) == 0;
-  if (vec) stencil_kernel<true><<<grid, kThreads, 0, s>>>(p, q, v, h2, partial);
-  else stencil_kernel<false><<<grid, kThreads, 0, s>>>(p, q, v, h2, partial);
+  if (vec) stencil_kernel<true, false><<<grid, kThreads, 0, s>>>(p, q, v, h2, partial, nullptr, 0.0);
+  else stencil_kernel<false, false><<<grid, kThreads, 0, s>>>(p, q, v, h2, partial, nullptr, 0.0);
+}
+
+// the screened instantiations: the 16-byte path needs W aligned as well
+void launch_screened_stencil(const float* p, const float* W, float* q, int n0, int n1, int n2, double h, double weight, double* partial,
+                             hipStream_t s) {
+  dim3 grid;
+  stencil_blocks(n0, n1, n2, &grid);
+  const Vol v = {n0, n1, n2};
+  const double h2 = h * h;
+  const bool vec = (n2 % kGroup) == 0 && (((uintptr_t)p | (uintptr_t)q | (uintptr_t)W) & 15u) == 0;
+  if (vec) stencil_kernel<true, true><<<grid, kThreads, 0, s>>>(p, q, v, h2, partial, W, weight);
+  else stencil_kernel<false, true><<<grid, kThreads, 0, s>>>(p, q, v, h2, partial, W, weight);
+}
+
+int check_stopping(const char* name, double tol, int max_iter, int check_every) {
+  if (!(tol > 0.0) || !(tol < 1.0)) { set_error("%s: tol must lie in (0,1)", name); return SVS_EINVAL; }
+  if (max_iter < 1 || check_every < 1) { set_error("%s: max_iter and check_every must be at least 1", name); return SVS_EINVAL; }
+  return SVS_OK;
+}
+
+// the host side of both solves: start() enqueues the first pass and the scalars, step() one iteration; every check_every
+// iterations and at max_iter the 8 bytes of rn come down and the solve stops when rn <= tol^2 bb
+template <typename Start, typename Step>
+int cg_drive(const char* name, const double* scal, double tol, int max_iter, int check_every, hipStream_t s, int* iterations,
+             double* residual, int* converged, Start start, Step step) {
+  *iterations = 0; *residual = 0.0; *converged = 0;
+  start();
+  int rc = check_launch(name);
+  if (rc) return rc;
+  double bb = 0.0, rn = 0.0;
+  rc = download(name, scal + kBB, 1, &bb, s);
+  if (rc) return rc;
+  if (!(bb > 0.0) || !finite_f64(bb)) {
+    set_error("%s: no normal field (the right-hand side is zero or not finite: |rhs|^2 = %g)", name, bb); return SVS_EINVAL;
+  }
+  rn = bb;
+  int it = 0;
+  while (it < max_iter) {
+    step();
+    ++it;
+    if (it % check_every == 0 || it == max_iter) {
+      rc = check_launch(name);
+      if (rc) return rc;
+      rc = download(name, scal + kRN, 1, &rn, s);
+      if (rc) return rc;
+      if (rn <= tol * tol * bb) { *converged = 1; break; }
+      if (!finite_f64(rn)) break;                            // not finite: more iterations change nothing
+    }
+  }
+  *iterations = it;
+  *residual = __builtin_sqrt(rn / bb);
+  return SVS_OK;
+}
+
+int check_weight(const char* name, double weight) {
+  if (!(weight >= 0.0) || !finite_f64(weight)) { set_error("%s: the screening weight must be finite and not negative, got %g", name, weight); return SVS_EINVAL; }
+  return SVS_OK;
 }
 
 }  // namespace
@@ -638,8 +813,8 @@ int svs_poisson_cg(const float* rhs, int n0, int n1, int n2, double h, double to
   if (!rhs || !workspace || !x || !iterations || !residual || !converged) return null_pointer(name);
   rc = check_h(name, h);
   if (rc) return rc;
-  if (!(tol > 0.0) || !(tol < 1.0)) { set_error("%s: tol must lie in (0,1)", name); return SVS_EINVAL; }
-  if (max_iter < 1 || check_every < 1) { set_error("%s: max_iter and check_every must be at least 1", name); return SVS_EINVAL; }
+  rc = check_stopping(name, tol, max_iter, check_every);
+  if (rc) return rc;
   hipStream_t s = (hipStream_t)hip_stream;
   const long long total = (long long)n0 * n1 * n2;
   const CgLayout L = cg_layout(n0, n1, n2);
@@ -648,38 +823,72 @@ int svs_poisson_cg(const float* rhs, int n0, int n1, int n2, double h, double to
   double* partial = (double*)(base + L.partial); double* scal = (double*)(base + L.scal);
   const int fb = flat_blocks(total), sb = stencil_blocks(n0, n1, n2, nullptr);
   const int vec_rhs = ((uintptr_t)rhs & 15u) == 0, vec_x = ((uintptr_t)x & 15u) == 0;
-  *iterations = 0; *residual = 0.0; *converged = 0;
-  cg_init_kernel<<<fb, kThreads, 0, s>>>(rhs, total, vec_rhs, vec_x, x, r, p, partial);
-  cg_scalars_kernel<<<1, kThreads, 0, s>>>(partial, fb, kModeInit, scal);
-  rc = check_launch(name);
+  return cg_drive(name, scal, tol, max_iter, check_every, s, iterations, residual, converged,
+                  [&] {
+                    cg_init_kernel<<<fb, kThreads, 0, s>>>(rhs, total, vec_rhs, vec_x, x, r, p, partial);
+                    cg_scalars_kernel<<<1, kThreads, 0, s>>>(partial, fb, kModeInit, scal);
+                  },
+                  [&] {
+                    launch_stencil(p, q, n0, n1, n2, h, partial, s);
+                    cg_scalars_kernel<<<1, kThreads, 0, s>>>(partial, sb, kModePQ, scal);
+                    cg_axpy_kernel<<<fb, kThreads, 0, s>>>(total, vec_x, scal, x, r, p, q, partial);
+                    cg_scalars_kernel<<<1, kThreads, 0, s>>>(partial, fb, kModeRR, scal);
+                    cg_direction_kernel<<<fb, kThreads, 0, s>>>(total, scal, r, p);
+                  });
+}
+
+int svs_screened_apply(const float* x, const float* W, int n0, int n1, int n2, double h, double weight, float* y, void* hip_stream) {
+  const char* name = "svs_screened_apply";
+  int rc = check_grid(name, n0, n1, n2);
   if (rc) return rc;
-  double bb = 0.0, rn = 0.0;
-  rc = download(name, scal + kBB, 1, &bb, s);
+  if (!x || !W || !y) return null_pointer(name);
+  if (x == y) { set_error("%s: bad argument (x and y are the same array)", name); return SVS_EINVAL; }
+  rc = check_h(name, h);
   if (rc) return rc;
-  if (!(bb > 0.0) || !finite_f64(bb)) {
-    set_error("%s: no normal field (the right-hand side is zero or not finite: |rhs|^2 = %g)", name, bb); return SVS_EINVAL;
-  }
-  rn = bb;
-  int it = 0;
-  while (it < max_iter) {
-    launch_stencil(p, q, n0, n1, n2, h, partial, s);
-    cg_scalars_kernel<<<1, kThreads, 0, s>>>(partial, sb, kModePQ, scal);
-    cg_axpy_kernel<<<fb, kThreads, 0, s>>>(total, vec_x, scal, x, r, p, q, partial);
-    cg_scalars_kernel<<<1, kThreads, 0, s>>>(partial, fb, kModeRR, scal);
-    cg_direction_kernel<<<fb, kThreads, 0, s>>>(total, scal, r, p);
-    ++it;
-    if (it % check_every == 0 || it == max_iter) {
-      rc = check_launch(name);
-      if (rc) return rc;
-      rc = download(name, scal + kRN, 1, &rn, s);
-      if (rc) return rc;
-      if (rn <= tol * tol * bb) { *converged = 1; break; }
-      if (!finite_f64(rn)) break;                            // not finite: more iterations change nothing
-    }
-  }
-  *iterations = it;
-  *residual = __builtin_sqrt(rn / bb);
-  return SVS_OK;
+  rc = check_weight(name, weight);
+  if (rc) return rc;
+  launch_screened_stencil(x, W, y, n0, n1, n2, h, weight, nullptr, (hipStream_t)hip_stream);
+  return check_launch(name);
+}
+
+size_t svs_screened_pcg_workspace_bytes(int n0, int n1, int n2) {
+  if (n0 < 2 || n1 < 2 || n2 < 2 || (long long)n0 * n1 * n2 > 0x7fffffffLL) return 0;
+  return cg_layout(n0, n1, n2, 2).total + 256;
+}
+
+int svs_screened_pcg(const float* rhs, const float* W, int n0, int n1, int n2, double h, double weight, double tol, int max_iter,
+                     int check_every, void* workspace, float* x, int* iterations, double* residual, int* converged, void* hip_stream) {
+  const char* name = "svs_screened_pcg";
+  int rc = check_grid(name, n0, n1, n2);
+  if (rc) return rc;
+  if (!rhs || !W || !workspace || !x || !iterations || !residual || !converged) return null_pointer(name);
+  rc = check_h(name, h);
+  if (rc) return rc;
+  rc = check_weight(name, weight);
+  if (rc) return rc;
+  rc = check_stopping(name, tol, max_iter, check_every);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)hip_stream;
+  const long long total = (long long)n0 * n1 * n2;
+  const CgLayout L = cg_layout(n0, n1, n2, 2);
+  char* base = aligned(workspace);
+  float* r = (float*)(base + L.r); float* p = (float*)(base + L.p); float* q = (float*)(base + L.q);
+  double* partial = (double*)(base + L.partial); double* partial_z = partial + L.n_partials; double* scal = (double*)(base + L.scal);
+  const int fb = flat_blocks(total), sb = stencil_blocks(n0, n1, n2, nullptr);
+  const int vec_rhs = ((uintptr_t)rhs & 15u) == 0, vec_x = ((uintptr_t)x & 15u) == 0, vec_w = ((uintptr_t)W & 15u) == 0;
+  const double six_h2 = 6.0 / (h * h);
+  return cg_drive(name, scal, tol, max_iter, check_every, s, iterations, residual, converged,
+                  [&] {
+                    pcg_init_kernel<<<fb, kThreads, 0, s>>>(rhs, W, total, vec_rhs, vec_w, vec_x, six_h2, weight, x, r, p, partial, partial_z);
+                    pcg_scalars_kernel<<<1, kThreads, 0, s>>>(partial, partial_z, fb, kModeInit, scal);
+                  },
+                  [&] {
+                    launch_screened_stencil(p, W, q, n0, n1, n2, h, weight, partial, s);
+                    pcg_scalars_kernel<<<1, kThreads, 0, s>>>(partial, partial_z, sb, kModePQ, scal);
+                    pcg_axpy_kernel<<<fb, kThreads, 0, s>>>(total, vec_x, vec_w, six_h2, weight, scal, W, x, r, p, q, partial, partial_z);
+                    pcg_scalars_kernel<<<1, kThreads, 0, s>>>(partial, partial_z, fb, kModeRR, scal);
+                    pcg_direction_kernel<<<fb, kThreads, 0, s>>>(total, vec_w, six_h2, weight, scal, W, r, p);
+                  });
 }
 
 size_t svs_poisson_sample_workspace_bytes(int n) {

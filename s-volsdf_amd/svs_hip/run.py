@@ -32,6 +32,8 @@ filter_depth_folder`) -> {outdir}/mvsnet{scan:03}_l3.ply.
     +cloud_poisson=V         with +cloud_clean=true: every scan's cleaned cloud meshed by `svs_hip.poisson` on a grid of node
                              spacing V, {outdir}/poisson/mvsnet{scan:03}_l3.ply
                              (`python -m evals.eval_dtu --datadir {outdir}/poisson --mode mesh`)
+    +cloud_poisson_screen=S  with +cloud_poisson: the screened reconstruction (`poisson.reconstruct(screen=S)`, S positive).
+                             It has no default value: 1, 4 and 16 were tried on a synthetic sphere of uneven density only
 
 Differences from the reference, all deliberate: `gpu: auto` keeps the current device (there is no GPUtil probe) and an
 integer selects it with torch.cuda.set_device; `prevent_oom` is taken as given; the five-second sleep before the first
@@ -196,6 +198,18 @@ def check_cloud_poisson(args):
     return float(v)
 
 
+def check_cloud_poisson_screen(args):
+    """+cloud_poisson_screen=S: a positive finite screen value, and only together with +cloud_poisson=V (ValueError naming
+    the key) -> S or None"""
+    s = args.get("cloud_poisson_screen")
+    if s is None:
+        return None
+    _require(isinstance(s, (int, float)) and not isinstance(s, bool) and 0 < s < float("inf"), "cloud_poisson_screen",
+             f"a positive finite screen value, got {s!r}")
+    _require(args.get("cloud_poisson") is not None, "cloud_poisson_screen", "screens the Poisson meshes: give +cloud_poisson=V as well")
+    return float(s)
+
+
 def save_yaml(path, args):
     import yaml
     with open(path, "w") as f:
@@ -210,6 +224,7 @@ def run_help(args, select_device=True):
     check_tsdf_smooth(args)
     check_tsdf_texture(args)
     check_cloud_poisson(args)
+    check_cloud_poisson_screen(args)
     if select_device and args["gpu"] != "auto":
         import torch
         torch.cuda.set_device(int(args["gpu"]))
@@ -583,16 +598,17 @@ def poisson_ply_name(outdir, scan):
 
 def poisson_meshes(args, testlist):
     """+cloud_poisson=V: every scan's cleaned cloud (`clean_clouds`) meshed by `poisson.reconstruct_ply` on a grid of node
-    spacing V into {outdir}/poisson/mvsnet{scan:03}_l3.ply; one time line per scan.  -> {scene: reconstruct_ply's stats}"""
+    spacing V into {outdir}/poisson/mvsnet{scan:03}_l3.ply, screened with +cloud_poisson_screen=S; one time line per scan.
+    -> {scene: reconstruct_ply's stats}"""
     from . import poisson
-    voxel = check_cloud_poisson(args)
+    voxel, screen = check_cloud_poisson(args), check_cloud_poisson_screen(args)
     out = OrderedDict()
     for scan in testlist:
         ply = poisson_ply_name(args["outdir"], scan)
-        stats = poisson.reconstruct_ply(clean_ply_name(args["outdir"], scan), ply, voxel)["stats"]
+        stats = poisson.reconstruct_ply(clean_ply_name(args["outdir"], scan), ply, voxel, screen=screen)["stats"]
         g = stats["grid"]
         info(f"saving the Poisson mesh to {ply} ({stats['n_verts']} vertices, {stats['faces_after']} of {stats['faces_before']} faces, "
-             f"grid {g[0]} x {g[1]} x {g[2]}, {stats['iterations']} iterations)")
+             f"grid {g[0]} x {g[1]} x {g[2]}, {stats['iterations']} iterations" + ("" if screen is None else f", screen {screen:g}") + ")")
         info(f"{scan} cloud poisson seconds: " + ", ".join(f"{k} {v:.3f}" for k, v in stats["seconds"].items()))
         out[scan] = stats
     return out

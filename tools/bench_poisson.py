@@ -3,13 +3,16 @@
 normals, meshed on a --resolution^3 grid.
 
     python tools/bench_poisson.py [--resolution 256 [512 ...]] [--points 5000000] [--repeats 7] [--out profiles/poisson_bench.txt]
+    python tools/bench_poisson.py --resolution 256 --screen 4 --out profiles/poisson_screen_bench.txt
 
 Per phase the milliseconds (after one untimed call, the median and the spread of --repeats host-clock intervals that end in a
 device synchronise, as tools/bench_meshsimplify.py takes them): the sort alone (torch.sort of the same cell keys: the splat's
 own sort is inside its entry point), the splat, divergence, the solve, sample, marching cubes, the trim, the colours and the
 download.  For the solve: iterations, ms per iteration, the bytes an iteration moves as counted from csrc/svs_poisson.hip, and
 that rate against a float4 copy measured in the same run; beside it the same recurrence written with torch slicing ops on
-the device.  Needs the GPU.
+the device.  --screen S: after that the screened solve (`solve_screened`, W passed as field[3]) on the same right-hand side:
+its iterations and ms per iteration beside the unscreened ones, its counted 56 B per node against the same copy, and its
+recurrence in torch ops.  Needs the GPU.
 """
 import argparse
 import os
@@ -66,13 +69,62 @@ def torch_cg(torch, rhs, h, iterations):
     return x
 
 
+def torch_pcg(torch, rhs, W, weight, h, iterations):
+    """the recurrence of svs_screened_pcg in torch ops, as `torch_cg` does svs_poisson_cg's; z = r / d is a temporary -> x"""
+    inv_h2 = 1.0 / (h * h)
+    d = 6.0 * inv_h2 + weight * W
+    x = torch.zeros_like(rhs)
+    r = rhs.clone()
+    p = r / d
+    rz = (r.double() * p.double()).sum()
+    for _ in range(iterations):
+        q = torch_apply(torch, p, inv_h2) + (weight * W) * p
+        alpha = rz / (p.double() * q.double()).sum()
+        x += alpha.float() * p
+        r -= alpha.float() * q
+        z = r / d
+        rzn = (r.double() * z.double()).sum()
+        p = z + (rzn / rz).float() * p
+        rz = rzn
+    return x
+
+
+def screened_lines(a, torch, timed_ms, ps, field, rhs, counted, h, nodes, per, copy_rate):
+    """--screen S: the screened solve beside the unscreened one of the same run (per: its ms per iteration) -> lines"""
+    box = {}
+    weight, density = ps.screen_weight(field[3], counted, a.screen, h)
+
+    def solve():
+        box["x"], box["info"] = ps.solve_screened(rhs, field[3], weight, h)
+    ms = timed_ms(torch, solve, a.repeats)
+    info = box["info"]
+    per_s = ms[0] / max(info["iterations"], 1)
+
+    def in_torch():
+        box["xt"] = torch_pcg(torch, rhs, field[3], weight, h, TORCH_ITERATIONS)
+    per_torch = timed_ms(torch, in_torch, max(1, a.repeats // 2))[0] / TORCH_ITERATIONS
+    ideal = 56 * nodes
+    return [f"  screened solve, screen {a.screen:g} (weight {weight:.6g}, {density:.3f} points per touched node, W as field[3], "
+            f"{'16-byte aligned' if field[3].data_ptr() % 16 == 0 else 'not 16-byte aligned'}): {ms[0]:10.3f} ms ({ms[1]:.3f} .. {ms[2]:.3f})",
+            f"  screened: {info['iterations']} iterations to a recursive residual of {info['residual']:.3e} (converged: {info['converged']}), "
+            f"{per_s:.4f} ms per iteration against {per:.4f} unscreened = {per_s / per:.3f} times; 56 / 44 of the unscreened time is {per * 56 / 44:.4f} ms",
+            f"  a screened iteration moves {ideal / 1e6:.1f} MB (56 B per node: W once more in each of the three passes) = "
+            f"{ideal / (per_s * 1e-3) / 1e12:.3f} TB/s = {100 * ideal / (per_s * 1e-3) / copy_rate:.1f} % of the float4 copy's rate",
+            f"  the screened recurrence in torch ops: {per_torch:.4f} ms per iteration = {per_torch / per_s:.2f} times ours; its x after "
+            f"{TORCH_ITERATIONS} iterations is finite: {bool(torch.isfinite(box['xt']).all())}"]
+
+
 def main(argv=None):
     p = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     p.add_argument("--resolution", type=int, nargs="+", default=[256], help="one run per grid resolution")
     p.add_argument("--points", type=int, default=5000000)
     p.add_argument("--repeats", type=int, default=7)
     p.add_argument("--out", default=None)
+    p.add_argument("--screen", type=float, default=None, metavar="S", help="also time the screened solve at this screen value, on the "
+                                                                           "same cloud in the same run (no default value)")
     a = p.parse_args(argv)
+    if a.screen is not None and not (a.screen > 0 and a.screen < float("inf")):
+        p.error("--screen must be positive and finite")
     import numpy as np
     import torch
     from bench_meshsimplify import timed_ms
@@ -170,6 +222,8 @@ def bench(a, resolution, np, torch, timed_ms, mesh, ps):
                  f"{copy_rate / 1e12:.3f} TB/s; the solve runs at {100 * ideal / (per * 1e-3) / copy_rate:.1f} % of the copy's rate")
     lines.append(f"  the same recurrence in torch slicing ops (float32 vectors, float64 dots, no host synchronisation): {per_torch:.4f} ms per "
                  f"iteration = {per_torch / per:.2f} times ours; its x after {TORCH_ITERATIONS} iterations is finite: {bool(torch.isfinite(box['xt']).all())}")
+    if a.screen is not None:
+        lines += screened_lines(a, torch, timed_ms, ps, field, rhs, box["counted"], h, nodes, per, copy_rate)
     return "\n".join(lines)
 
 
